@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Co-DINO Swin-L 1920x1280 fp16 inference throughput on N MI355X (one process per GPU).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--res WxH]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--res WxH] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,8 +24,12 @@ codetr/multi_scale_deformable_attention.py:186-191 are in level pixels and unbou
 measured at 0, 4 and 8 px (``roofline_msda_zero_noise`` / ``_4px`` / ``_8px``, with the share of samples that leave the
 staged windows), and the whole model at 8 px (``value_8px``).
 
-Extra objects on that line: ``host_feed`` -- the same K steps with every step's images copied from pinned host memory
-(PCIe) on the sub-batch streams, i.e. the rate including the input transfer (never ``value``); and at N=1 only:
+A plain run sets up, warms up, times the K steps and prints the headline line (``value``, ``ms_per_step``, p50 / p90
+ms per image).  ``--dump-outputs DIR`` then also writes the detections of the last timed step (boxes, scores, labels as
+float32 .npy): same arguments, same seeded inputs, so two builds can be compared output for output.
+
+With ``--full``, extra objects on that line: ``host_feed`` -- the same K steps with every step's images copied from
+pinned host memory (PCIe) on the sub-batch streams, i.e. the rate including the input transfer (never ``value``); and at N=1 only:
 ``latency_batch1`` -- p50 / p90 of single-image forwards (the quantity the
 reference publishes); ``roofline`` -- the dominant kernel group of the forward, the hand-written
 MFMA linears, every launch of one forward timed live with HIP events on its launch stream and priced with
@@ -551,6 +555,29 @@ def cpu_baseline(model, full_hw=(1280, 1920), budget_s=45.0):
             "seconds_for_sample": round(t608, 2)}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, packed):
+    """`--dump-outputs DIR`: the detections of the last timed step as a caller of ``CoDETR.forward`` receives them --
+    boxes [B,300,4], scores [B,300], labels [B,300] (class ids, exact in float32) -- one .npy each.  Past 64 MB in all,
+    a fixed seeded sample of the images is kept (the indices go to images.npy)."""
+    import numpy as np
+    from codetr.sharding import unpack_detections
+
+    os.makedirs(d, exist_ok=True)
+    packed = packed.detach().cpu()
+    n = packed.shape[0]
+    keep = max(1, DUMP_LIMIT_BYTES // (packed[0].numel() * 4))
+    if n > keep:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, keep, replace=False)))
+        packed = packed[idx]
+        np.save(os.path.join(d, "images.npy"), idx.numpy().astype(np.float64))
+    boxes, scores, labels = unpack_detections(packed)
+    for name, t in (("boxes", boxes), ("scores", scores), ("labels", labels)):
+        np.save(os.path.join(d, name + ".npy"), t.float().contiguous().numpy())
+
+
 def _free_port():
     import socket
 
@@ -635,11 +662,18 @@ def main():
     ap.add_argument("--no-fp8-line", action="store_true", help="skip the fp8 (config 5) sub-record of the fp16 run")
     ap.add_argument("--pad", type=float, default=0.9,
                     help="valid fraction per side of the `padded` sub-record's images (1.0 = skip it)")
-    ap.add_argument("--quick", action="store_true", help="headline line only: no sub-records, rooflines or CPU baseline")
+    ap.add_argument("--quick", action="store_true", help="headline line only, even with --full (what a run without --full does)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the sub-records: host feed, fp8, padded images, 8 px offsets, batch-1 latencies, rooflines and "
+                         "the CPU baseline (the --no-* options and --pad still select among them); without it the run times "
+                         "the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the detections of the last one as DIR/boxes.npy, scores.npy and "
+                         "labels.npy (float32)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU / gloo: launcher, sharding, gather, timing and report with stand-in detections, no model")
     a = ap.parse_args()
-    if a.quick:
+    if a.quick or not a.full:
         a.no_cpu_baseline = a.no_roofline = a.no_host_feed = a.no_fp8_line = True
         a.pad = 1.0
 
@@ -702,8 +736,10 @@ def main():
     subs = [(images[bounds[i]:bounds[i + 1]].contiguous(), masks[bounds[i]:bounds[i + 1]].contiguous())
             for i in range(nstreams)]
     static_out = torch.empty(a.batch, 300, 6, device=device, dtype=torch.float32)
-    # host side of the PCIe feed: the same images in pinned memory, one buffer per sub-batch
-    host_subs = [subs[i][0].cpu().pin_memory() for i in range(nstreams)]
+    # host side of the PCIe feed: the same images in pinned memory, one buffer per sub-batch (only for a run that feeds them)
+    host_subs = None
+    if a.feed == "host" or not a.no_host_feed:
+        host_subs = [subs[i][0].cpu().pin_memory() for i in range(nstreams)]
 
     def forward(i):
         with torch.no_grad():
@@ -800,6 +836,9 @@ def main():
 
     elapsed, per_step_ms = timed(a.feed == "host")
     headline_rank_stats = dict(rank_stats)
+    if a.dump_outputs and rank == 0:
+        # before any sub-record replays the graphs again: these are the headline's last timed step
+        dump_outputs(a.dump_outputs, gathered if world > 1 else static_out)
     host_feed = None
     if a.feed == "hbm" and not a.no_host_feed:
         e2, _ = timed(True)

@@ -11,8 +11,8 @@ forward.  Two independent restatements live here:
   cu:52-71), written without looking at the loop structure so the two check each other.
 
 Pinning (see msda_ref.c header): both are checked against outputs of the reference's own
-Python op (codetr/ops.py:129-186) captured into tests/golden/*.npz by make_golden.py, and
-live against the imported reference when /root/reference is present.
+Python op (codetr/ops.py:129-186) captured into tests/golden/*.npz by make_golden.py (seeded
+random float64 cases among them: msda_ref_random.npz).
 
 Only ``tests/``, ``__graft_entry__.smoke()`` and ``bench.py``'s cpu_baseline leg may import
 this module.

@@ -1,9 +1,8 @@
 """Import the reference's Python (read-only tree at /root/reference) in THIS build container.
 
-Test infrastructure only.  Used by ``make_golden.py`` (fixture generation) and by the
-``-m "not gpu"`` tests that cross-check the oracle against the live reference when the
-reference tree is present.  Nothing here travels to the GPU box: the reference does not
-exist there, and every caller skips when ``REFERENCE_ROOT`` is missing.
+Test infrastructure only.  Used by ``make_golden.py`` (fixture generation) alone: the tests
+read what it captured from ``tests/golden/``, so they never need the reference tree, and
+``make_golden.py`` exits when ``REFERENCE_ROOT`` is missing.
 
 The reference cannot be imported as a normal package: ``codetr/__init__.py`` (reference
 codetr/__init__.py:8-19) demands two CUDA ``.so`` files, ``codetr/ops.py`` imports

@@ -338,8 +338,63 @@ def make_key_goldens():
     _save("state_dict_keys", rel_index=s.stages[0].blocks[0].attn.w_msa.relative_position_index, **pack_param_spec(spec))
 
 
+def _jsonable(x):
+    """tuples survive the round trip as {"__tuple__": [...]} (the config sections hold both tuples and lists)"""
+    if isinstance(x, tuple):
+        return {"__tuple__": [_jsonable(v) for v in x]}
+    if isinstance(x, list):
+        return [_jsonable(v) for v in x]
+    if isinstance(x, dict):
+        return {k: _jsonable(v) for k, v in x.items()}
+    return x
+
+
+def make_config_golden():
+    """The inference-relevant model section of the reference's Swin-L config file as the product's own loader
+    (co-detr-tensorrt_amd/codetr/config.py, loaded by path: the reference shim owns the name `codetr`) reads it ->
+    ref_config_swin_l.json (tests/test_host_model.py::test_reference_config_files_load_and_agree)."""
+    import importlib.util
+    import json
+
+    spec = importlib.util.spec_from_file_location(
+        "_codetr_config", os.path.join(HERE, "..", "..", "co-detr-tensorrt_amd", "codetr", "config.py"))
+    cfgmod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cfgmod)
+    m = cfgmod.Config.fromfile(os.path.join(R.REFERENCE_ROOT, "configs", "co_dino_5scale_swin_l_16xb1_16e_o365tococo.py")).model
+    backbone = dict(m.backbone)
+    backbone.pop("init_cfg")   # the pretrained-checkpoint pointer: not part of the inference contract
+    sec = {"backbone": backbone, "neck": m.neck,
+           "query_head": {k: m.query_head[k] for k in ("num_query", "num_classes", "as_two_stage", "transformer",
+                                                       "positional_encoding")},
+           "test_cfg0": m.test_cfg[0], "data_preprocessor_mean": m.data_preprocessor.mean}
+    path = os.path.join(HERE, "ref_config_swin_l.json")
+    with open(path, "w") as f:
+        json.dump(_jsonable(sec), f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote {path}  ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
+def make_msda_random_golden():
+    """Two seeded random float64 cases (the second model-shaped: M=8, D=32, five levels) through the reference's
+    Python op, locations in [-0.15, 1.15) -> msda_ref_random.npz
+    (tests/test_oracle_msda.py::test_live_against_imported_reference)."""
+    f = R.ref("ops").multi_scale_deformable_attention_pytorch
+    torch.manual_seed(7)
+    arrs = {}
+    cases = [(2, 5, 3, 6, [(5, 7), (2, 3)], 3), (1, 9, 8, 32, [(6, 9), (3, 5), (2, 3), (1, 2), (1, 1)], 4)]
+    for c, (B, Nq, M, D, shapes, P) in enumerate(cases):
+        ss = torch.tensor(shapes)
+        S, L = int(ss.prod(1).sum()), len(shapes)
+        v = torch.randn(B, S, M, D, dtype=torch.float64)
+        loc = torch.rand(B, Nq, M, L, P, 2, dtype=torch.float64) * 1.3 - 0.15
+        w = torch.rand(B, Nq, M, L, P, dtype=torch.float64)
+        arrs.update({f"value_{c}": v, f"spatial_shapes_{c}": ss, f"sampling_loc_{c}": loc, f"attn_weight_{c}": w,
+                     f"ref_{c}": f(v, ss, loc, w)})
+    _save("msda_ref_random", **arrs)
+
+
 GROUPS = {"msda": make_msda_goldens, "model": make_model_goldens, "keys": make_key_goldens, "head": make_head_goldens,
-          "grad": make_grad_goldens}
+          "grad": make_grad_goldens, "config": make_config_golden, "msda_random": make_msda_random_golden}
 
 
 if __name__ == "__main__":

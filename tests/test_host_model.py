@@ -1,5 +1,6 @@
 """CPU: host logic of the product package -- config loading, model construction, checkpoint-key
 parity with the reference, loader behaviour.  No compute (the product computes on the GPU only)."""
+import json
 import os
 
 import numpy as np
@@ -33,22 +34,24 @@ def test_config_base_chain_delete_and_base_refs():
     assert r50.test_pipeline[0]["backend_args"] is None                                # `_base_.backend_args`
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference tree not present")
+def _tuples(d):
+    return tuple(d["__tuple__"]) if set(d) == {"__tuple__"} else d
+
+
 def test_reference_config_files_load_and_agree():
-    """The reference's own config files go through the same loader; their inference-relevant model
-    section equals ours."""
+    """The reference's own Swin-L config file, read through the same loader (its inference-relevant model section,
+    captured into tests/golden/ref_config_swin_l.json by make_golden.py), equals ours."""
     from codetr.config import Config
 
-    ref = Config.fromfile("/root/reference/configs/co_dino_5scale_swin_l_16xb1_16e_o365tococo.py")
+    with open(os.path.join(GOLDEN, "ref_config_swin_l.json")) as f:
+        ref = json.load(f, object_hook=_tuples)
     ours = Config.fromfile(SWIN_CFG)
-    rb = dict(ref.model.backbone)
-    rb.pop("init_cfg")
-    assert rb == dict(ours.model.backbone)
-    assert ref.model.neck == ours.model.neck
+    assert ref["backbone"] == dict(ours.model.backbone)
+    assert ref["neck"] == ours.model.neck
     for k in ("num_query", "num_classes", "as_two_stage", "transformer", "positional_encoding"):
-        assert ref.model.query_head[k] == ours.model.query_head[k], k
-    assert ref.model.test_cfg[0] == ours.model.test_cfg[0]
-    assert ref.model.data_preprocessor.mean == ours.model.data_preprocessor.mean
+        assert ref["query_head"][k] == ours.model.query_head[k], k
+    assert ref["test_cfg0"] == ours.model.test_cfg[0]
+    assert ref["data_preprocessor_mean"] == ours.model.data_preprocessor.mean
 
 
 @pytest.fixture(scope="module")

@@ -1,10 +1,7 @@
 """CPU: the oracle (oracle/msda_ref.c + numpy restatement) against the golden vectors captured from
-the reference's own Python (tests/golden/make_golden.py), and live against the imported reference
-when /root/reference is present.  Tolerances are the reference tests' own
-(tests/test_multi_scale_deformable_attention.py:282-283, 319-320, 363-364, 62)."""
+the reference's own Python (tests/golden/make_golden.py), seeded random float64 cases among them.  Tolerances
+are the reference tests' own (tests/test_multi_scale_deformable_attention.py:282-283, 319-320, 363-364, 62)."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -96,29 +93,15 @@ def test_out_of_range_points_contribute_zero():
     np.testing.assert_allclose(out, 0.5)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/codetr"), reason="reference tree not present")
 def test_live_against_imported_reference():
-    """Fresh random cases through the reference's Python (separate process: it owns the module
-    name `codetr`) and through the oracle."""
-    code = r"""
-import sys, numpy as np, torch
-sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[2])
-import _ref_import as R, msda_oracle as O
-f = R.ref('ops').multi_scale_deformable_attention_pytorch
-torch.manual_seed(7)
-worst = 0.0
-for (B, Nq, M, D, shapes, P) in [(2, 5, 3, 6, [(5, 7), (2, 3)], 3), (1, 9, 8, 32, [(6, 9), (3, 5), (2, 3), (1, 2), (1, 1)], 4)]:
-    ss = torch.tensor(shapes); S = int(ss.prod(1).sum()); L = len(shapes)
-    v = torch.randn(B, S, M, D, dtype=torch.float64)
-    loc = torch.rand(B, Nq, M, L, P, 2, dtype=torch.float64) * 1.3 - 0.15
-    w = torch.rand(B, Nq, M, L, P, dtype=torch.float64)
-    ref = f(v, ss, loc, w).numpy()
-    got = O.msda_forward_c(v.numpy(), ss.numpy(), O.level_start_index_from_shapes(ss.numpy()), loc.numpy(), w.numpy(), dtype=np.float64)
-    worst = max(worst, float(np.abs(ref - got).max()))
-print('WORST', worst)
-assert worst < 1e-13
-"""
-    here = os.path.dirname(os.path.abspath(__file__))
-    r = subprocess.run([sys.executable, "-c", code, os.path.join(here, "golden"), os.path.join(here, "..", "oracle")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
+    """Fresh random cases (seed 7; the second model-shaped) through the reference's Python op -- inputs and outputs
+    captured into tests/golden/msda_ref_random.npz by make_golden.py -- and through the oracle, float64."""
+    g = np.load(os.path.join(GOLDEN, "msda_ref_random.npz"))
+    worst = 0.0
+    for c in range(2):
+        ss = g[f"spatial_shapes_{c}"]
+        got = O.msda_forward_c(g[f"value_{c}"], ss, O.level_start_index_from_shapes(ss), g[f"sampling_loc_{c}"],
+                               g[f"attn_weight_{c}"], dtype=np.float64)
+        assert got.shape == g[f"ref_{c}"].shape
+        worst = max(worst, float(np.abs(g[f"ref_{c}"] - got).max()))
+    assert worst < 1e-13

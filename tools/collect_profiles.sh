@@ -6,8 +6,8 @@ tag=${1:-r06}
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 out=gpurun_out/final; mkdir -p $out
 if [ -z "$SKIP_BENCH" ]; then
-timeout 900 python bench.py > $out/${tag}_bench.json 2> $out/bench.err
-timeout 600 python bench.py --dtype fp8 --no-cpu-baseline > $out/${tag}_bench_fp8.json 2>> $out/bench.err
+timeout 900 python bench.py --full > $out/${tag}_bench.json 2> $out/bench.err
+timeout 600 python bench.py --full --dtype fp8 --no-cpu-baseline > $out/${tag}_bench_fp8.json 2>> $out/bench.err
 fi
 # (--no-fp8-line: the default line's fp8 sub-record would put its calibration forward and e4m3 kernels into the fp16 traces)
 common="--no-cpu-baseline --no-graph --no-roofline --no-host-feed --no-fp8-line --pad 1.0"
