@@ -705,6 +705,10 @@ const char* codetr_msda_variant(int elem_bytes, int M, int D, int L, int P) {
   return "scalar";
 }
 
+// the windowed entry of a dtype (csrc/msda_op4.hip), or nullptr where there is none
+typedef int (*Op4Entry)(void*, const void*, const int64_t*, const int64_t*, const void*, const void*, int64_t, int64_t, int,
+                        int, int, int64_t, int, void*);
+
 #define CODETR_MSDA_ENTRY(NAME, TR, ST, AT, CV, EB, OP4)                                                              \
   int NAME(void* stream, const void* value_dev, const int64_t* spatial_shapes_dev, const int64_t* level_start_dev, \
            const void* loc_dev, const void* weight_dev, int64_t B, int64_t S, int M, int D, int L, int64_t Nq,   \
@@ -714,11 +718,12 @@ const char* codetr_msda_variant(int elem_bytes, int M, int D, int L, int P) {
     if (rc) return rc;                                                                                           \
     hipStream_t st = static_cast<hipStream_t>(stream);                                                           \
     const int lanes = tiled_lanes(EB, D, L, P);                                                                  \
-    /* encoder-shaped fp16 calls: the windowed kernel first, this file's kernel behind it with the skip test on */ \
+    /* encoder-shaped 16-bit calls: the windowed kernel first, this file's kernel behind it with the skip test on */ \
     bool behind_op4 = false;                                                                                     \
-    if (OP4 && lanes == 4 && codetr_msda_op4_supported(EB, B, S, M, D, L, Nq, P)) {                               \
-      const int orc = codetr_msda_op4_forward_f16(stream, value_dev, spatial_shapes_dev, level_start_dev, loc_dev, \
-                                                  weight_dev, B, S, M, D, L, Nq, P, out_dev);                     \
+    Op4Entry const op4 = OP4;                                                                                    \
+    if (op4 && lanes == 4 && codetr_msda_op4_supported(EB, B, S, M, D, L, Nq, P)) {                               \
+      const int orc = op4(stream, value_dev, spatial_shapes_dev, level_start_dev, loc_dev, weight_dev, B, S, M, D, \
+                          L, Nq, P, out_dev);                                                                    \
       if (orc == 0) behind_op4 = true;                                                                           \
       else if (orc != CODETR_E_UNSUPPORTED) return orc;                                                          \
     }                                                                                                            \
@@ -731,9 +736,9 @@ const char* codetr_msda_variant(int elem_bytes, int M, int D, int L, int P) {
                                      out_dev, B, S, M, D, L, Nq, P);                                             \
   }
 
-CODETR_MSDA_ENTRY(codetr_msda_forward_f16, F16, _Float16, float, CvF16, 2, true)
-CODETR_MSDA_ENTRY(codetr_msda_forward_bf16, BF16, unsigned short, float, CvBF16, 2, false)
-CODETR_MSDA_ENTRY(codetr_msda_forward_f32, F32, float, float, CvF32, 4, false)
+CODETR_MSDA_ENTRY(codetr_msda_forward_f16, F16, _Float16, float, CvF16, 2, codetr_msda_op4_forward_f16)
+CODETR_MSDA_ENTRY(codetr_msda_forward_bf16, BF16, unsigned short, float, CvBF16, 2, codetr_msda_op4_forward_bf16)
+CODETR_MSDA_ENTRY(codetr_msda_forward_f32, F32, float, float, CvF32, 4, nullptr)
 
 #define CODETR_MSDA_FUSED_ENTRY(NAME, TR, REF32)                                                                 \
   int NAME(void* stream, const void* value_dev, const int64_t* spatial_shapes_dev, const int64_t* level_start_dev, \

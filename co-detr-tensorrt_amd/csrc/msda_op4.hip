@@ -8,7 +8,7 @@
 // for five rounds.  The model's own encoder path got its speed from csrc/msda_encoder4.hip, which needs
 // the producers' cooperation (packed projection, head-major value map, windows from the offset bias).  This kernel carries
 // that kernel's structure to the op's OWN operand layouts, for encoder-shaped calls (Nq == S, 5 levels x 4 points, 32-channel
-// heads, fp16):
+// heads, fp16 or bf16 -- one template over the 16-bit element type, round 7 added the bf16 instantiation):
 //   * a 512-thread workgroup serves one (16 x 16 region of the finest level, head): its queries are the pixels of the region
 //     on all five levels (341 at most on a 2x pyramid); four lanes serve a (query, head) pair, lane p = point p on every level.
 //   * per pass (levels {0}, {1, 2}, {3, 4}) the value rows the region's samples can reach -- the region's footprint on the level
@@ -21,15 +21,16 @@
 //     weights staged in LDS"): a pair's 80 + 40 bytes are fetched with one 16-byte and two 8-byte loads per lane (a quad reads
 //     whole 16-byte pieces of the rows), written to a 144-byte record and read back transposed (lane p: its point's (x, y) on
 //     the five levels, its five weights) -- 3 coalesced loads instead of the ten 2- / 4-byte ones the layout suggests.
-//   * numerics as the general kernel: fp32 corner weights (bilinear x attention), every term added in fp32 with
-//     v_fma_mix_f32 (the fp16 value read in place), one rounding at the end -- the op's tests hold it to one fp16 ulp of the
-//     exactly rounded result (tests/test_msda_gpu.py), which the encoder kernel's packed-half chains do not meet.
+//   * numerics as the general kernel: fp32 corner weights (bilinear x attention), every term added in fp32 -- fp16 with
+//     v_fma_mix_f32 (the value read in place), bf16 widened exactly (16-bit shift / mask) and two v_fma_f32 -- one rounding
+//     to nearest even at the end -- the op's tests hold it to one fp16 / bf16 ulp of the exactly rounded result
+//     (tests/test_msda_gpu.py, tests/test_msda_op4_bf16_gpu.py), which the encoder kernel's packed-half chains do not meet.
 //   * the pyramid's shapes are a DEVICE tensor: the grid is persistent (two workgroups per CU) and every workgroup derives
 //     regions, windows and its tile list from the device-side shapes (msda_op4_plan.h); where the plan does not apply the
 //     workgroups return at once and the general kernel, launched behind this one with the same plan as its skip test, serves
 //     the call.
 // Tested against the fp64 oracle and the reference's golden vectors through the op (tests/test_msda_gpu.py, unchanged, and
-// tests/test_msda_op4_gpu.py).
+// tests/test_msda_op4_gpu.py, tests/test_msda_op4_bf16_gpu.py).
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -58,6 +59,7 @@ constexpr int kAbl = MSDA_OP4_ABL;
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
@@ -97,15 +99,35 @@ __device__ __forceinline__ unsigned quad_bcast_add(unsigned v, int owner, unsign
   return d;
 }
 __device__ __forceinline__ h2 as_h2(unsigned u) { return __builtin_bit_cast(h2, u); }
-__device__ __forceinline__ unsigned pack_h2(float a, float b) {   // v_cvt_pk_f16_f32 (round to nearest even)
-  const h2 v = {(_Float16)a, (_Float16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-// acc += (float)(half of `u`) * w in ONE instruction each: the fp16 value is read in place
-__device__ __forceinline__ void fma_h2(float& lo, float& hi, unsigned u, float w) {
-  asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(u), "v"(w));
-  asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(hi) : "v"(u), "v"(w));
-}
+
+// The op's two 16-bit element types, as (low, high) element pairs of a dword.  Both are 2 bytes wide: staging, operand
+// records, plan and fix-up queue do not depend on which; only widening, the blend and the final rounding do.
+struct OpF16 {
+  __device__ __forceinline__ static float elem(unsigned u, int i) { return (float)as_h2(u)[i]; }
+  // acc += (float)(half of `u`) * w in ONE instruction each: the fp16 value is read in place
+  __device__ __forceinline__ static void fma2(float& lo, float& hi, unsigned u, float w) {
+    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(u), "v"(w));
+    asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(hi) : "v"(u), "v"(w));
+  }
+  __device__ __forceinline__ static unsigned pack2(float a, float b) {   // v_cvt_pk_f16_f32 (round to nearest even)
+    const h2 v = {(_Float16)a, (_Float16)b};
+    return __builtin_bit_cast(unsigned, v);
+  }
+};
+struct OpBF16 {
+  // exact widening: a bf16 value is the top half of the fp32 one (one shift / one mask)
+  __device__ __forceinline__ static float elem(unsigned u, int i) { return __uint_as_float(i ? u & 0xffff0000u : u << 16); }
+  // gfx950 has no mixed-precision FMA that reads bf16: both halves widened, then two fp32 FMAs -- twice the fp16 blend's
+  // vector instructions.  (One v_pk_fma_f32 per pair instead measured 2-5 % slower: profiles/r07_msda_op_bf16.txt)
+  __device__ __forceinline__ static void fma2(float& lo, float& hi, unsigned u, float w) {
+    lo = fmaf(elem(u, 0), w, lo);
+    hi = fmaf(elem(u, 1), w, hi);
+  }
+  __device__ __forceinline__ static unsigned pack2(float a, float b) {   // v_cvt_pk_bf16_f32 (round to nearest even; a NaN stays a NaN)
+    const bf2 v = {(__bf16)a, (__bf16)b};
+    return __builtin_bit_cast(unsigned, v);
+  }
+};
 __device__ __forceinline__ void lds_dma16(const unsigned char* src, unsigned voff, unsigned lds_addr) {
   asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr)
                : "memory", "m0");
@@ -156,12 +178,13 @@ struct Smp {
   float lw, lh;
   int x0, y0;
 };
+template <typename T>
 __device__ __forceinline__ Smp sample_at(const Lv& v, unsigned o2) {
   Smp s;
   // cu:241-247: h_im = loc_h * H - 0.5, w_im = loc_w * W - 0.5 (x first in memory).  fmaxf: a NaN coordinate becomes a huge
   // negative one -> outside every window and outside the gate: the sample is dropped, as by the reference's comparisons
-  const float w_im = fmaxf(fmaf((float)as_h2(o2)[0], v.fW, -0.5f), -3.0e38f);
-  const float h_im = fmaxf(fmaf((float)as_h2(o2)[1], v.fH, -0.5f), -3.0e38f);
+  const float w_im = fmaxf(fmaf(T::elem(o2, 0), v.fW, -0.5f), -3.0e38f);
+  const float h_im = fmaxf(fmaf(T::elem(o2, 1), v.fH, -0.5f), -3.0e38f);
   s.lw = __builtin_amdgcn_fractf(w_im);
   s.lh = __builtin_amdgcn_fractf(h_im);
   s.x0 = floor_i(w_im);
@@ -169,8 +192,9 @@ __device__ __forceinline__ Smp sample_at(const Lv& v, unsigned o2) {
   return s;
 }
 
-// weight of level k out of the lane's five packed halves
-__device__ __forceinline__ float weight_of(const unsigned (&awp)[3], int k) { return (float)as_h2(awp[k >> 1])[k & 1]; }
+// weight of level k out of the lane's five packed 16-bit values
+template <typename T>
+__device__ __forceinline__ float weight_of(const unsigned (&awp)[3], int k) { return T::elem(awp[k >> 1], k & 1); }
 
 // prepared sample: LDS address of its (x0, y0) row, the four corner weights (zero when the sample is not served from LDS)
 struct Prep {
@@ -180,8 +204,9 @@ struct Prep {
 
 // one level's sample of the lane: window test, LDS address, corner weights.  Returns false when the sample is not served
 // from LDS (its weights are then zero and its address a finite staged row)
+template <typename T>
 __device__ __forceinline__ bool prepare(Prep& pp, const Lv& v, const float a, const unsigned o2) {
-  const Smp s = sample_at(v, o2);
+  const Smp s = sample_at<T>(v, o2);
   const unsigned dx = (unsigned)(s.x0 - v.px0), dy = (unsigned)(s.y0 - v.py0);
   const bool ok = dx <= (unsigned)v.xspan && dy <= (unsigned)v.yspan;   // all four corners are staged (or zero border)
   const float wy1 = s.lh * a, wy0 = a - wy1, wx0 = 1.f - s.lw;
@@ -197,6 +222,7 @@ __device__ __forceinline__ bool prepare(Prep& pp, const Lv& v, const float a, co
 // gather of one iteration and one level: the quad's four points, one per step; the rows of step s + 1 are requested before
 // the arithmetic of step s, the step's four weights broadcast when its rows are due (one level's Prep live at a time: the
 // kernel runs at four waves per SIMD, 128 registers)
+template <typename T>
 __device__ __forceinline__ void gather_level(float (&acc)[8], const Prep& pp, const unsigned pitch, const unsigned lds_lane) {
   using LV = const __attribute__((address_space(3))) u32x4*;
   // 16 rows (4 points x 4 corners), a ring of 5 registers sets: row k + 4 is requested right before row k is consumed (a
@@ -222,7 +248,7 @@ __device__ __forceinline__ void gather_level(float (&acc)[8], const Prep& pp, co
     const int o = k >> 2, cr = k & 3;
     const float w = quad_bcast_f(cr == 0 ? pp.w00 : cr == 1 ? pp.w01 : cr == 2 ? pp.w10 : pp.w11, o);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) fma_h2(acc[2 * j], acc[2 * j + 1], rows[k % RING][j], w);
+    for (int j = 0; j < 4; ++j) T::fma2(acc[2 * j], acc[2 * j + 1], rows[k % RING][j], w);
     if (cr == 3) __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -235,9 +261,10 @@ struct FixRec {
   u32x4 ra, rb;
   bool ok, gate;
 };
+template <typename T>
 __device__ __forceinline__ FixRec fix_record(const Lv& v, const float a, const unsigned o2) {
   FixRec f;
-  const Smp s = sample_at(v, o2);
+  const Smp s = sample_at<T>(v, o2);
   const unsigned dx = (unsigned)(s.x0 - v.px0), dy = (unsigned)(s.y0 - v.py0);
   f.ok = dx <= (unsigned)v.xspan && dy <= (unsigned)v.yspan;
   // cu:249: h_im > -1 && w_im > -1 && h_im < H && w_im < W  <=>  floor in [-1, size - 1]
@@ -253,14 +280,14 @@ __device__ __forceinline__ FixRec fix_record(const Lv& v, const float a, const u
 // The rare path: one queued sample per pair and round.  Nothing but the pair's `bad` mask stays live between rounds -- the
 // record of a sample is re-derived when its turn comes (the kernel runs at 128 registers; a path that kept the records and
 // two rounds' rows cost the main path 27 spilled registers).
-template <int LV0, int NLV>
+template <typename T, int LV0, int NLV>
 __device__ __forceinline__ void fixup(float (&acc)[8], const Lv (&lv)[kL], const unsigned (&awp)[3], const unsigned (&o2)[kL],
                                       u32x4* __restrict__ queue, const unsigned char* __restrict__ vhead, const unsigned pix_bytes,
                                       const int sub) {
   unsigned bad = 0;
 #pragma unroll
   for (int i = 0; i < NLV; ++i) {
-    const FixRec f = fix_record(lv[LV0 + i], weight_of(awp, LV0 + i), o2[LV0 + i]);
+    const FixRec f = fix_record<T>(lv[LV0 + i], weight_of<T>(awp, LV0 + i), o2[LV0 + i]);
     bad |= (!f.ok && f.gate) ? 1u << (sub + 4 * i) : 0u;
   }
   bad |= dpp_u<kXor2>(bad);
@@ -271,7 +298,7 @@ __device__ __forceinline__ void fixup(float (&acc)[8], const Lv (&lv)[kL], const
     for (int i = 0; i < NLV; ++i) {
       const int pt = sub + 4 * i;
       if (((bad >> pt) & 1u) && __builtin_popcount(bad & ((1u << pt) - 1u)) == base) {
-        const FixRec f = fix_record(lv[LV0 + i], weight_of(awp, LV0 + i), o2[LV0 + i]);
+        const FixRec f = fix_record<T>(lv[LV0 + i], weight_of<T>(awp, LV0 + i), o2[LV0 + i]);
         queue[0] = f.ra;
         queue[1] = f.rb;
       }
@@ -285,10 +312,10 @@ __device__ __forceinline__ void fixup(float (&acc)[8], const Lv (&lv)[kL], const
       const u32x4 r2 = *reinterpret_cast<const u32x4*>(p + ys), r3 = *reinterpret_cast<const u32x4*>(p + ys + xs);
 #pragma unroll
       for (int jj = 0; jj < 4; ++jj) {
-        fma_h2(acc[2 * jj], acc[2 * jj + 1], r0[jj], __uint_as_float(wts[0]));
-        fma_h2(acc[2 * jj], acc[2 * jj + 1], r1[jj], __uint_as_float(wts[1]));
-        fma_h2(acc[2 * jj], acc[2 * jj + 1], r2[jj], __uint_as_float(wts[2]));
-        fma_h2(acc[2 * jj], acc[2 * jj + 1], r3[jj], __uint_as_float(wts[3]));
+        T::fma2(acc[2 * jj], acc[2 * jj + 1], r0[jj], __uint_as_float(wts[0]));
+        T::fma2(acc[2 * jj], acc[2 * jj + 1], r1[jj], __uint_as_float(wts[1]));
+        T::fma2(acc[2 * jj], acc[2 * jj + 1], r2[jj], __uint_as_float(wts[2]));
+        T::fma2(acc[2 * jj], acc[2 * jj + 1], r3[jj], __uint_as_float(wts[3]));
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -296,8 +323,9 @@ __device__ __forceinline__ void fixup(float (&acc)[8], const Lv (&lv)[kL], const
 }
 
 // LDS: [staged rows of ONE pass (its front doubles as the operand records) | fix-up queues]
+template <typename T>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void msda_op4_kernel(
-    const _Float16* __restrict__ value, const int64_t* __restrict__ spatial_shapes, const int64_t* __restrict__ level_start,
+    const unsigned short* __restrict__ value, const int64_t* __restrict__ spatial_shapes, const int64_t* __restrict__ level_start,
     const unsigned short* __restrict__ loc, const unsigned short* __restrict__ weight, unsigned short* __restrict__ out,
     const int B, const int S, const int M) {
   constexpr unsigned kRow = 64;
@@ -519,11 +547,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
           for (int i = 0; i < NLV; ++i) {
             const Lv& v = lv[LV0 + i];
             Prep pp = Prep{v.base, 0.f, 0.f, 0.f, 0.f};
-            if (!(kAbl & 8)) clean = prepare(pp, v, weight_of(awp[it], LV0 + i), o2[it][LV0 + i]) && clean;
-            gather_level(acc[it], pp, v.pitch, lds_lane);
+            if (!(kAbl & 8)) clean = prepare<T>(pp, v, weight_of<T>(awp[it], LV0 + i), o2[it][LV0 + i]) && clean;
+            gather_level<T>(acc[it], pp, v.pitch, lds_lane);
           }
           clean = __builtin_amdgcn_ballot_w64(!clean) == 0;
-          if (!clean) fixup<LV0, NLV>(acc[it], lv, awp[it], o2[it], queue, vhead, pix_bytes, sub);
+          if (!clean) fixup<T, LV0, NLV>(acc[it], lv, awp[it], o2[it], queue, vhead, pix_bytes, sub);
         }
     };
     run_pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
@@ -535,7 +563,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     for (int it = 0; it < kMaxIt; ++it)
       if (it < n_it && (it * kWaves + wave) * 16 + pl < total) {
         const float (&a)[8] = acc[it];
-        const u32x4 o = {pack_h2(a[0], a[1]), pack_h2(a[2], a[3]), pack_h2(a[4], a[5]), pack_h2(a[6], a[7])};
+        const u32x4 o = {T::pack2(a[0], a[1]), T::pack2(a[2], a[3]), T::pack2(a[4], a[5]), T::pack2(a[6], a[7])};
         if (!(kAbl & 32) || o[0] == 0x12345678u)
           *reinterpret_cast<u32x4*>(orow + (size_t)((unsigned)qs[it] * ((unsigned)M * kRow))) = o;
       }
@@ -554,22 +582,10 @@ int device_cus() {
   return cus[dev];
 }
 
-}  // namespace
-
-extern "C" {
-
-int codetr_msda_op4_supported(int elem_bytes, int64_t B, int64_t S, int M, int D, int L, int64_t Nq, int P) {
-  // the host-visible part of the test; the device-side plan (msda_op4_plan.h) decides on the pyramid itself
-  if (elem_bytes != 2 || D != 32 || L != kL || P != kP || Nq != S || M <= 0 || B <= 0) return 0;
-  if (S < 4096) return 0;                                              // a launch-bound call: the general kernel alone
-  if (S * M * (int64_t)80 > 0xffffffffLL || B * S * M >= (int64_t)1 << 31) return 0;   // 32-bit in-image offsets
-  return 1;
-}
-
-// fp16 only.  Launches the windowed kernel; the caller launches the general kernel behind it with its skip test enabled.
-int codetr_msda_op4_forward_f16(void* stream, const void* value_dev, const int64_t* spatial_shapes_dev, const int64_t* level_start_dev,
-                                const void* loc_dev, const void* weight_dev, int64_t B, int64_t S, int M, int D, int L, int64_t Nq,
-                                int P, void* out_dev) {
+template <typename T>
+int op4_forward(void* stream, const void* value_dev, const int64_t* spatial_shapes_dev, const int64_t* level_start_dev,
+                const void* loc_dev, const void* weight_dev, int64_t B, int64_t S, int M, int D, int L, int64_t Nq, int P,
+                void* out_dev) {
   if (!value_dev || !spatial_shapes_dev || !level_start_dev || !loc_dev || !weight_dev || !out_dev) return CODETR_E_BADARG;
   if (!codetr_msda_op4_supported(2, B, S, M, D, L, Nq, P)) return CODETR_E_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(value_dev) | reinterpret_cast<uintptr_t>(loc_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15)
@@ -580,19 +596,45 @@ int codetr_msda_op4_forward_f16(void* stream, const void* value_dev, const int64
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0, done[0].store(0);
     if (!done[dev].load(std::memory_order_acquire)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(msda_op4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(msda_op4_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                (int)kLdsBytes);
       if (e != hipSuccess) return (int)e;
       done[dev].store(1, std::memory_order_release);
     }
   }
   const int grid = device_cus() / 8 * 8 * 2;   // two workgroups per CU, a multiple of 8
-  hipLaunchKernelGGL(msda_op4_kernel, dim3((unsigned)grid), dim3(kThreads), kLdsBytes, static_cast<hipStream_t>(stream),
-                     static_cast<const _Float16*>(value_dev), spatial_shapes_dev, level_start_dev,
+  hipLaunchKernelGGL(msda_op4_kernel<T>, dim3((unsigned)grid), dim3(kThreads), kLdsBytes, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(value_dev), spatial_shapes_dev, level_start_dev,
                      static_cast<const unsigned short*>(loc_dev), static_cast<const unsigned short*>(weight_dev),
                      static_cast<unsigned short*>(out_dev), (int)B, (int)S, M);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
+}
+
+}  // namespace
+
+extern "C" {
+
+int codetr_msda_op4_supported(int elem_bytes, int64_t B, int64_t S, int M, int D, int L, int64_t Nq, int P) {
+  // the host-visible part of the test; the device-side plan (msda_op4_plan.h) decides on the pyramid itself.  elem_bytes 2:
+  // fp16 and bf16 alike
+  if (elem_bytes != 2 || D != 32 || L != kL || P != kP || Nq != S || M <= 0 || B <= 0) return 0;
+  if (S < 4096) return 0;                                              // a launch-bound call: the general kernel alone
+  if (S * M * (int64_t)80 > 0xffffffffLL || B * S * M >= (int64_t)1 << 31) return 0;   // 32-bit in-image offsets
+  return 1;
+}
+
+// Launch the windowed kernel only; the caller launches the general kernel behind it with its skip test enabled.
+int codetr_msda_op4_forward_f16(void* stream, const void* value_dev, const int64_t* spatial_shapes_dev, const int64_t* level_start_dev,
+                                const void* loc_dev, const void* weight_dev, int64_t B, int64_t S, int M, int D, int L, int64_t Nq,
+                                int P, void* out_dev) {
+  return op4_forward<OpF16>(stream, value_dev, spatial_shapes_dev, level_start_dev, loc_dev, weight_dev, B, S, M, D, L, Nq, P, out_dev);
+}
+
+int codetr_msda_op4_forward_bf16(void* stream, const void* value_dev, const int64_t* spatial_shapes_dev, const int64_t* level_start_dev,
+                                 const void* loc_dev, const void* weight_dev, int64_t B, int64_t S, int M, int D, int L, int64_t Nq,
+                                 int P, void* out_dev) {
+  return op4_forward<OpBF16>(stream, value_dev, spatial_shapes_dev, level_start_dev, loc_dev, weight_dev, B, S, M, D, L, Nq, P, out_dev);
 }
 
 }  // extern "C"
