@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcodetr_hip.so")
-ABI_VERSION = 51
+ABI_VERSION = 52
 
 _i64, _i32, _vp, _cp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p
 
@@ -65,6 +65,10 @@ SIGNATURES = {
     "codetr_linear_xadd_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64]),
     "codetr_linear_xadd_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64]),
     "codetr_im2col_tokens_b16": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
+    "codetr_conv_tokens_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "codetr_conv_tokens_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "codetr_conv_im2col_nchw_b16": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
+    "codetr_maxpool_tokens_b16": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
     "codetr_topk_chunks": (_i64, [_i64, _i32, _i64, _vp]),
     "codetr_topk_chunked_f16": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64]),
     "codetr_topk_chunked_bf16": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64]),
@@ -168,7 +172,9 @@ CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
-         "linear_fp8": 0, "cast_fp8": 0, "layernorm_fp8": 0, "small_ops": 0, "ffn_fp8": 0, "decoder_layer": 0}
+         "linear_fp8": 0, "cast_fp8": 0, "layernorm_fp8": 0, "small_ops": 0, "ffn_fp8": 0, "decoder_layer": 0,
+         # the native ResNet-50 backbone: implicit-GEMM convolution, the stem's window gather, the max pool
+         "conv_tokens": 0, "conv_im2col_nchw": 0, "maxpool_tokens": 0}
 
 
 # Launch recording (codetr/export.py): while RECORDER is a list, every launch-type entry point called through `load()`
@@ -283,7 +289,8 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
     return out
 
 
-_ACT = {None: 0, "relu": 1, "gelu": 2}
+# "relu_res": ReLU applied after the residual add (act 3; codetr_linear_* and codetr_conv_tokens_* only)
+_ACT = {None: 0, "relu": 1, "gelu": 2, "relu_res": 3}
 _LINEAR_BY_DTYPE = {torch.float16: "codetr_linear_f16", torch.bfloat16: "codetr_linear_bf16"}
 
 
@@ -878,6 +885,53 @@ def im2col_tokens(x4d, k, stride, pad, out):
     rc = lib.codetr_im2col_tokens_b16(current_stream_ptr(x4d.device), x4d.data_ptr(), B, H, W, C, k, stride, pad,
                                       out.data_ptr())
     check(rc, "codetr_im2col_tokens_b16")
+    return out
+
+
+_CONV_BY_DTYPE = {torch.float16: "codetr_conv_tokens_f16", torch.bfloat16: "codetr_conv_tokens_bf16"}
+
+
+def conv_tokens_supported(x4d, weight, k, stride, pad) -> bool:
+    """the domain of codetr_conv_tokens_*: 16-bit token-major x [B, H, W, C], C % 64 == 0, Cout % 8 == 0, k in {1, 3},
+    stride in {1, 2}, 0 <= pad < k"""
+    return (x4d.dtype in _CONV_BY_DTYPE and weight.dtype == x4d.dtype and x4d.dim() == 4 and x4d.shape[-1] % 64 == 0
+            and weight.shape[0] % 8 == 0 and k in (1, 3) and stride in (1, 2) and 0 <= pad < k)
+
+
+def conv_tokens(x4d, weight, bias, residual, k, stride, pad, act, out):
+    """x4d [B,H,W,C] -> out [B,Ho,Wo,Cout] = act(conv(x, w) + bias) (+ residual); weight [Cout, k*k*C] in (ky, kx, c)
+    order; all contiguous and 16-byte aligned"""
+    lib = load()
+    CALLS["conv_tokens"] += 1
+    B, H, W, C = x4d.shape
+    name = _CONV_BY_DTYPE[x4d.dtype]
+    rc = getattr(lib, name)(
+        current_stream_ptr(x4d.device), x4d.data_ptr(), weight.data_ptr(),
+        bias.data_ptr() if bias is not None else None, residual.data_ptr() if residual is not None else None,
+        out.data_ptr(), B, H, W, C, weight.shape[0], k, stride, pad, _ACT[act])
+    check(rc, name)
+    return out
+
+
+def conv_im2col_nchw(x, k, stride, pad, kpad, out):
+    """x [B,C,H,W] 16-bit -> out [B*Ho*Wo, kpad] overlapping-window rows in (c, ky, kx) order, zero padded"""
+    lib = load()
+    CALLS["conv_im2col_nchw"] += 1
+    B, C, H, W = x.shape
+    rc = lib.codetr_conv_im2col_nchw_b16(current_stream_ptr(x.device), x.data_ptr(), B, C, H, W, k, stride, pad, kpad,
+                                         out.data_ptr())
+    check(rc, "codetr_conv_im2col_nchw_b16")
+    return out
+
+
+def maxpool_tokens(x4d, out):
+    """x4d [B,H,W,C] 16-bit -> out [B,Ho,Wo,C] = F.max_pool2d(x, 3, 2, 1) in token-major layout"""
+    lib = load()
+    CALLS["maxpool_tokens"] += 1
+    B, H, W, C = x4d.shape
+    rc = lib.codetr_maxpool_tokens_b16(current_stream_ptr(x4d.device), x4d.data_ptr(), B, H, W, C, 3, 2, 1,
+                                       1 if x4d.dtype == torch.bfloat16 else 0, out.data_ptr())
+    check(rc, "codetr_maxpool_tokens_b16")
     return out
 
 

@@ -75,12 +75,13 @@ class CoDETR(nn.Module):
                 capture=None, route=None) -> Tuple[Tensor, Tensor, Tensor]:
         """Reference signature (:66-90) plus three test hooks that do not exist there: `forced_topk_indices` (see
         CoDinoTransformer.forward), `capture` (a dict that receives intermediates; it never changes which kernels
-        run) and `route` ("nchw" forces the generic NCHW backbone -> neck -> head route that ResNet / fp32 models
+        run) and `route` ("nchw" forces the generic NCHW backbone -> neck -> head route that fp32 ResNet models
         take; default: token-major wherever the backbone and neck support it)."""
         if route not in (None, "tokens", "nchw"):
             raise ValueError(f"route must be None, 'tokens' or 'nchw', got {route!r}")
         if (route != "nchw" and hasattr(self.backbone, "forward_tokens") and hasattr(self, "neck")
-                and batch_inputs.is_cuda):
+                and batch_inputs.is_cuda and getattr(self.backbone, "tokens_supported", lambda x: True)(batch_inputs)):
+            # (ResNet: 16-bit inputs only -- fp32 R50 stays on the NCHW parity route)
             # token-major path: backbone stage outputs stay [B, HW, C], the neck's 1x1 convs are linears over
             # tokens, GroupNorm writes straight into the encoder's [B, S, 256] input -- no NCHW round trip
             tokens = self.backbone.forward_tokens(batch_inputs)

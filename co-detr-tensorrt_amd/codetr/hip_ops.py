@@ -30,6 +30,7 @@ NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_win
           "mha_attention(f16/bf16: dense softmax attention, head_dim 32, <= 1024 keys)",
           "topk(f16/bf16 rows, k <= 1024: radix select + bitonic sort)",
           "im2col_tokens(16-bit token-major maps)",
+          "resnet50(f16/bf16: implicit-GEMM conv_tokens, stem window gather + GEMM, maxpool_tokens, BN folded)",
           "small_ops(f16: add, sigmoid, gather_rows, decode_boxes, valid_ratios)",
           "linear_fp8(e4m3 x e4m3, K%128==0) + layer_norm_fp8 + cast_fp8", "ffn_fp8(fused FFN, both products e4m3)"}
 
@@ -73,7 +74,8 @@ def _persistent_ok(mk, head_major, out, x2, w, r2, bias):
 
 
 def linear(x, weight, bias=None, act=None, residual=None, row_mask=None, head_major=None):
-    """y = act(x @ weight.T + bias) (+ residual);  act in {None, 'relu', 'gelu'}.
+    """y = act(x @ weight.T + bias) (+ residual);  act in {None, 'relu', 'gelu', 'relu_res'}.
+    'relu_res': y = relu(x @ weight.T + bias + residual) -- the ReLU after the residual of a ResNet bottleneck.
     row_mask (bool, x.shape[:-1]): rows where it is True come out as zeros (before the residual).
     head_major = head_dim: x must be [B, S, K]; the result is returned as [B, N/head_dim, S, head_dim] (each head's
     map contiguous) instead of [B, S, N] -- the value-map layout of the head-major MSDA kernel (native path only)."""
@@ -105,8 +107,12 @@ def linear(x, weight, bias=None, act=None, residual=None, row_mask=None, head_ma
         out = torch.empty((x2.shape[0], N), dtype=x.dtype, device=x.device)
         if x2.shape[0] > 0:
             with torch.cuda.device(x.device):
-                splits, ws_bytes = (1, 0) if head_major else _cabi.linear_splitk_plan(x2.shape[0], N, K)
-                if splits > 1:
+                # act 'relu_res' exists on codetr_linear_* only: the split-K and persistent GEMMs reject it
+                res_act = act == "relu_res"
+                splits, ws_bytes = (1, 0) if (head_major or res_act) else _cabi.linear_splitk_plan(x2.shape[0], N, K)
+                if res_act:
+                    launch = lambda: _cabi.linear(x2, w, bias, r2, act, out, mk, hm_rows, hm_hd)  # noqa: E731
+                elif splits > 1:
                     # few output tiles, long K (the neck's extra level as a GEMM): two-pass split-K, fp32 partials
                     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
                     launch = lambda: _cabi.linear_splitk(x2, w, bias, r2, act, out, splits, ws, mk)  # noqa: E731
@@ -136,6 +142,10 @@ def linear(x, weight, bias=None, act=None, residual=None, row_mask=None, head_ma
         raise RuntimeError("head_major output exists only on the native linear (f16/bf16, K % 64 == 0)")
     # fp32 / odd-K layers (patch-embed is a conv; fp32 runs are parity runs): ATen library GEMM
     y = F.linear(x, weight, bias)
+    if act == "relu_res":
+        if row_mask is not None:
+            y = y.masked_fill(row_mask[..., None], 0.0)
+        return F.relu(y + residual if residual is not None else y)
     if act == "relu":
         y = F.relu(y, inplace=True)
     elif act == "gelu":
@@ -697,6 +707,59 @@ def im2col_tokens(x4d, k, stride, pad):
                       for ky in range(k) for kx in range(k)], dim=-1).reshape(B, Ho * Wo, -1)
 
 
+# ---- native ResNet-50 backbone (16-bit, token-major; codetr/resnet.py ResNet.forward_tokens) ----
+R50_NATIVE = True        # route switch: False = 16-bit R50 models take the NCHW route (MIOpen / ATen convolutions)
+R50_CONV_IM2COL = False  # A/B baseline: the 3x3 and strided 1x1 convs as codetr_im2col_tokens_b16 + codetr_linear_*
+
+
+def conv_tokens(x4d, weight_kkc, bias, k, stride, pad, act=None, residual=None):
+    """Conv2d(k, stride, pad) on a token-major map: x4d [B,H,W,C] -> [B,Ho,Wo,Cout] = act(conv + bias) (+ residual),
+    weight_kkc [Cout, k*k*C] in (ky, kx, c) order; act as in linear ('relu_res': ReLU after the residual).  Native
+    implicit-GEMM kernel; R50_CONV_IM2COL = True gathers the patches into a buffer and runs the linear instead."""
+    _gpu(x4d, "conv_tokens")
+    B, H, W, C = x4d.shape
+    Cout = weight_kkc.shape[0]
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    if not _cabi.conv_tokens_supported(x4d, weight_kkc, k, stride, pad):
+        raise RuntimeError(f"conv_tokens: no native kernel for x {tuple(x4d.shape)} {x4d.dtype}, k={k}, stride={stride}, "
+                           f"pad={pad}, Cout={Cout} (C % 64 == 0, Cout % 8 == 0, k in (1, 3), stride in (1, 2))")
+    if R50_CONV_IM2COL:
+        cols = im2col_tokens(x4d, k, stride, pad)
+        r = residual.reshape(B, Ho * Wo, Cout) if residual is not None else None
+        return linear(cols, weight_kkc, bias, act=act, residual=r).view(B, Ho, Wo, Cout)
+    x4d = x4d if x4d.is_contiguous() else x4d.contiguous()
+    if residual is not None and not residual.is_contiguous():
+        residual = residual.contiguous()
+    out = torch.empty((B, Ho, Wo, Cout), dtype=x4d.dtype, device=x4d.device)
+    with torch.cuda.device(x4d.device):
+        _timed("conv_tokens", {"M": B * Ho * Wo, "N": Cout, "K": k * k * C},
+               lambda: _cabi.conv_tokens(x4d, weight_kkc, bias, residual, k, stride, pad, act, out), x4d.device)
+    return out
+
+
+def stem_conv_tokens(x, weight_pad, bias, k, stride, pad):
+    """relu(Conv2d(C, Cout, k, stride, pad)(x) + bias) on the NCHW image as window gather + native GEMM:
+    x [B,C,H,W] 16-bit -> [B,Ho,Wo,Cout]; weight_pad [Cout, kpad] = conv.weight.view(Cout, C*k*k) zero-padded"""
+    _gpu(x, "stem_conv_tokens")
+    B, C, H, W = x.shape
+    Cout, kpad = weight_pad.shape
+    Ho, Wo = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+    cols = torch.empty((B * Ho * Wo, kpad), dtype=x.dtype, device=x.device)
+    with torch.cuda.device(x.device):
+        _cabi.conv_im2col_nchw(x if x.is_contiguous() else x.contiguous(), k, stride, pad, kpad, cols)
+    return linear(cols, weight_pad, bias, act="relu").view(B, Ho, Wo, Cout)
+
+
+def maxpool_tokens(x4d):
+    """F.max_pool2d(x, 3, 2, 1) on a 16-bit token-major map [B,H,W,C] (C % 8 == 0) -> [B,Ho,Wo,C]"""
+    _gpu(x4d, "maxpool_tokens")
+    B, H, W, C = x4d.shape
+    out = torch.empty((B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C), dtype=x4d.dtype, device=x4d.device)
+    with torch.cuda.device(x4d.device):
+        _cabi.maxpool_tokens(x4d if x4d.is_contiguous() else x4d.contiguous(), out)
+    return out
+
+
 # (The library routes these three ops can also take -- SDPA, the MIOpen stem convolution, torch.topk -- were measured
 # against the native kernels in rounds 1-2 and are no longer selectable here: tools/ab_library_routes.py times them by
 # patching this module from the outside.  What remains below them is the route for shapes / dtypes the kernels do not
@@ -729,7 +792,8 @@ MSDA_FP32_REF = True    # False = reference points read in the model dtype
 
 
 _SWITCH_DEFAULTS = {"ENC_POSGEN": True, "WINDOW_BIAS_LANE": True, "LINEAR_PP": True, "SWIN_MLP": True, "SWIN_MLP_MIN_ROWS": 32768, "LN_GEMM": True, "XADD": True, "XADD_MIN_ROWS": 0, "MERGE_LN": True, "MSDA_ENCODER": True,
-                    "MSDA_FP32_REF": True, "FP8_MIN_TILES": 96}
+                    "MSDA_FP32_REF": True, "FP8_MIN_TILES": 96,
+                    "R50_NATIVE": True, "R50_CONV_IM2COL": False}
 
 
 def nondefault_switches():

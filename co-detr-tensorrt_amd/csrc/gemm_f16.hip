@@ -110,6 +110,12 @@ __device__ __forceinline__ float gelu_erf(float x) {
   return fmaf(u, fmaf(-(p * t), ez, 0.5f), 0.5f * x);
 }
 
+// act 3 (ReLU after the residual, the ResNet bottleneck's relu(bn3(conv3(x)) + identity)): the accumulator leaves
+// without activation, the ReLU is applied to the sum with the residual (the same two roundings as act 0 + residual,
+// then the exact ReLU); with no residual, act 3 is act 1
+template <bool ON>
+__device__ __forceinline__ float relu_if(float x) { return ON ? (x < 0.f ? 0.f : x) : x; }
+
 // LDS image of one operand tile: [128 rows][CH = BKT/8 chunks of 16 B].  The DMA destination is lane-linear, so
 // the bank swizzle lives on the SOURCE address: LDS position p of row r holds source chunk p ^ sw(r), and the
 // fragment read applies the same XOR.  sw(r) spreads the 16 rows of a ds_read_b128 lane group over distinct
@@ -194,20 +200,69 @@ __device__ __forceinline__ void wait_vmcnt() {
   else static_assert(N < 0, "add the count");
 }
 
-// ACT: 0 none, 1 relu, 2 gelu(erf)
-// ACT: 0 none, 1 relu, 2 gelu(erf).  BKT x STAGES = the K pipeline: STAGES LDS buffers of one (W tile, X tile)
+// ---- implicit im2col operand of codetr_conv_tokens_* ----------------------------------------------------------
+// x [B, H, W, C] token-major, K ordered (ky, kx, c) with C % 64 == 0: a BKT-wide K slice (BKT <= 64) lies inside one
+// tap (ky, kx), so each 16-byte piece of a staged X row is a piece of ONE shifted input pixel's C-vector, or zeros where
+// the tap falls outside the map.  The zeros come from this buffer: LDS-DMA has no "write zeros" form, and one source
+// that is always 128 readable zero bytes keeps the piece a single DMA instruction with the same vmcnt accounting as the
+// dense tile.
+__device__ __attribute__((aligned(16))) unsigned short g_conv_zeros[64];
+
+struct ConvGeom {
+  int H, W, C, Wo, HoWo, k, stride, pad;
+};
+
+// Per-thread state of the BKT/16 pieces a thread stages per X tile (the same piece -> (row, chunk) map as stage_tile):
+// the piece's image base + chunk offset and the top-left input pixel of its output pixel.  Per K tile the tap is
+// uniform, so a piece costs two adds, a bounds test and the DMA.
+template <int BKT>
+struct ConvRows {
+  static constexpr int P = BKT / 16;
+  const unsigned short* src[P];
+  int iy[P], ix[P], chunk8[P];
+  __device__ __forceinline__ void init(const unsigned short* X, const ConvGeom& g, int M, int m0, int tid) {
+    constexpr int CH = BKT / 8;
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      const int u = q * kThreads + tid;
+      const int r = u / CH, pos = u % CH;
+      chunk8[q] = (pos ^ sw<BKT>(r)) * 8;
+      int m = m0 + r;
+      m = m < M ? m : M - 1;  // edge tiles: re-read the last row, results masked later
+      const int b = m / g.HoWo, p = m - b * g.HoWo;
+      const int oy = p / g.Wo, ox = p - oy * g.Wo;
+      src[q] = X + (size_t)b * g.H * g.W * g.C + chunk8[q];
+      iy[q] = oy * g.stride - g.pad;
+      ix[q] = ox * g.stride - g.pad;
+    }
+  }
+  __device__ __forceinline__ void stage(const ConvGeom& g, int k0, unsigned char* lds_tile, int wave) const {
+    const int tap = k0 / g.C, c0 = k0 - tap * g.C;
+    const int ky = tap / g.k, kx = tap - ky * g.k;
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+      const int y = iy[q] + ky, x = ix[q] + kx;
+      const unsigned short* s = ((unsigned)y < (unsigned)g.H && (unsigned)x < (unsigned)g.W)
+                                    ? src[q] + ((size_t)y * g.W + x) * g.C + c0
+                                    : g_conv_zeros + chunk8[q];
+      dma_piece(s, lds_tile, q, wave);
+    }
+  }
+};
+
+// ACT: 0 none, 1 relu, 2 gelu(erf), 3 relu after the residual.  BKT x STAGES = the K pipeline: STAGES LDS buffers of one (W tile, X tile)
 // pair each, STAGES-1 tiles of LDS-DMA in flight across the per-K-step barrier (raw s_barrier + counted
 // s_waitcnt vmcnt: a __syncthreads() would drain the DMA queue, cdna_hip_programming.md section 5).
 // SPLITK: blockIdx.y picks a range of `kps` K tiles; the block's fp32 partial tile goes to Y viewed as
 // float[gridDim.y][M][N] (no bias / activation / residual: splitk_reduce_kernel applies them to the sum).
-template <class T, int ACT, bool HAS_BIAS, bool HAS_RES, int BKT, int STAGES, bool SPLITK = false>
-__global__ __launch_bounds__(kThreads) void linear_kernel(const unsigned short* __restrict__ X,
-                                                          const unsigned short* __restrict__ W,
-                                                          const unsigned short* __restrict__ bias,
-                                                          const unsigned short* __restrict__ R,
-                                                          unsigned short* __restrict__ Y,
-                                                          const unsigned char* __restrict__ row_mask, int M, int N,
-                                                          int K, int tiles_n, int hm_rows, int hm_hd, int kps) {
+// CONV: X is not a dense [M, K] matrix but the implicit im2col matrix of a convolution over a token-major map (ConvRows
+// below); the tile loop, the W side and the epilogue are the same code.
+template <class T, int ACT, bool HAS_BIAS, bool HAS_RES, int BKT, int STAGES, bool SPLITK, bool CONV>
+__device__ __forceinline__ void linear_body(const unsigned short* __restrict__ X, const unsigned short* __restrict__ W,
+                                            const unsigned short* __restrict__ bias,
+                                            const unsigned short* __restrict__ R, unsigned short* __restrict__ Y,
+                                            const unsigned char* __restrict__ row_mask, int M, int N, int K,
+                                            int tiles_n, int hm_rows, int hm_hd, int kps, const ConvGeom& cg) {
   constexpr int kTileBytes = 128 * BKT * 2;        // one operand tile
   constexpr int kStageBytes = 2 * kTileBytes;      // W tile + X tile
   constexpr int LPS = 2 * (BKT / 16);              // LDS-DMA instructions per thread per stage
@@ -255,11 +310,14 @@ __global__ __launch_bounds__(kThreads) void linear_kernel(const unsigned short* 
   const int nk = SPLITK ? (K / BKT - kt0 < kps ? K / BKT - kt0 : kps) : K / BKT;
   const int frow = lane & 15, fchunk = lane >> 4;
   constexpr int KS = BKT / 32;
+  ConvRows<BKT> crows;
+  if (CONV) crows.init(X, cg, M, m0, tid);
   {
   auto issue = [&](int t) {
     unsigned char* buf = lds + (t % STAGES) * kStageBytes;
     stage_tile<BKT>(W, N, K, n0, (kt0 + t) * BKT, buf, tid);
-    stage_tile<BKT>(X, M, K, m0, (kt0 + t) * BKT, buf + kTileBytes, tid);
+    if (CONV) crows.stage(cg, (kt0 + t) * BKT, buf + kTileBytes, wave);
+    else stage_tile<BKT>(X, M, K, m0, (kt0 + t) * BKT, buf + kTileBytes, tid);
   };
 #pragma unroll
   for (int s0 = 0; s0 < STAGES - 1; ++s0)
@@ -345,7 +403,7 @@ __global__ __launch_bounds__(kThreads) void linear_kernel(const unsigned short* 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float x = acc[i][j][r];
-          if (ACT == 1) x = x < 0.f ? 0.f : x;  // NaN-propagating, like torch.relu
+          if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;  // NaN-propagating, like torch.relu
           if (ACT == 2) x = gelu_erf(x);
           v[r] = x;
         }
@@ -380,7 +438,7 @@ __global__ __launch_bounds__(kThreads) void linear_kernel(const unsigned short* 
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
               float x = HAS_BIAS ? T::to_f32(bias[n + e]) : 0.f;
-              if (ACT == 1) x = x < 0.f ? 0.f : x;
+              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
               if (ACT == 2) x = gelu_erf(x);
               v[e] = (short)T::from_f32(x);
             }
@@ -401,7 +459,7 @@ __global__ __launch_bounds__(kThreads) void linear_kernel(const unsigned short* 
           const s16x8 rr = rres[it];
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            v[e] = (short)T::from_f32(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[e]));
+            v[e] = (short)T::from_f32(relu_if<ACT == 3>(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[e])));
         }
         *reinterpret_cast<s16x8*>(Y + off) = v;
       }
@@ -422,24 +480,49 @@ __global__ __launch_bounds__(kThreads) void linear_kernel(const unsigned short* 
       for (int r = 0; r < 4; ++r) {
         if (n + r < N) {
           float v = acc[i][j][r];
-          if (ACT == 1) v = v < 0.f ? 0.f : v;
+          if (ACT == 1 || (ACT == 3 && !HAS_RES)) v = v < 0.f ? 0.f : v;
           if (ACT == 2) v = gelu_erf(v);
           unsigned short h = T::from_f32(v);
           if (row_mask && row_mask[m]) {
             h = 0;
             if (row_mask[m] == 2) {
               float x = HAS_BIAS ? T::to_f32(bias[n + r]) : 0.f;
-              if (ACT == 1) x = x < 0.f ? 0.f : x;
+              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
               if (ACT == 2) x = gelu_erf(x);
               h = T::from_f32(x);
             }
           }
-          if (HAS_RES) h = T::from_f32(T::to_f32(h) + T::to_f32(R[off + r]));
+          if (HAS_RES) h = T::from_f32(relu_if<ACT == 3>(T::to_f32(h) + T::to_f32(R[off + r])));
           Y[off + r] = h;
         }
       }
     }
   }
+}
+
+template <class T, int ACT, bool HAS_BIAS, bool HAS_RES, int BKT, int STAGES, bool SPLITK = false>
+__global__ __launch_bounds__(kThreads) void linear_kernel(const unsigned short* __restrict__ X,
+                                                          const unsigned short* __restrict__ W,
+                                                          const unsigned short* __restrict__ bias,
+                                                          const unsigned short* __restrict__ R,
+                                                          unsigned short* __restrict__ Y,
+                                                          const unsigned char* __restrict__ row_mask, int M, int N,
+                                                          int K, int tiles_n, int hm_rows, int hm_hd, int kps) {
+  linear_body<T, ACT, HAS_BIAS, HAS_RES, BKT, STAGES, SPLITK, false>(X, W, bias, R, Y, row_mask, M, N, K, tiles_n,
+                                                                     hm_rows, hm_hd, kps, ConvGeom{});
+}
+
+// Convolution on a token-major map as an implicit GEMM (codetr_conv_tokens_*): rows m = output pixels (b, oy, ox),
+// K = (ky, kx, c), W = conv.weight permuted to [Cout, k k C]; y [B, Ho, Wo, Cout] is the GEMM's [M, N] result.
+template <class T, int ACT, bool HAS_BIAS, bool HAS_RES, int BKT, int STAGES>
+__global__ __launch_bounds__(kThreads) void conv_tokens_kernel(const unsigned short* __restrict__ X,
+                                                               const unsigned short* __restrict__ W,
+                                                               const unsigned short* __restrict__ bias,
+                                                               const unsigned short* __restrict__ R,
+                                                               unsigned short* __restrict__ Y, int M, int N, int K,
+                                                               int tiles_n, ConvGeom cg) {
+  linear_body<T, ACT, HAS_BIAS, HAS_RES, BKT, STAGES, false, true>(X, W, bias, R, Y, nullptr, M, N, K, tiles_n, 0, 0, 0,
+                                                                   cg);
 }
 
 // Pipeline configuration per problem (A/B on MI355X over the model's 22 layer shapes, tools/bench_linear.py):
@@ -867,7 +950,7 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float x = acc[i][h * 4 + j][r];
-          if (ACT == 1) x = x < 0.f ? 0.f : x;
+          if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
           if (ACT == 2) x = gelu_erf(x);
           v[r] = x;
         }
@@ -897,7 +980,7 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
               float x = HAS_BIAS ? T::to_f32(bias[n + e]) : 0.f;
-              if (ACT == 1) x = x < 0.f ? 0.f : x;
+              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
               if (ACT == 2) x = gelu_erf(x);
               v[e] = (short)T::from_f32(x);
             }
@@ -909,7 +992,7 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
           const s16x8 rr = rres[it];
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            v[e] = (short)T::from_f32(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[e]));
+            v[e] = (short)T::from_f32(relu_if<ACT == 3>(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[e])));
         }
         // uniform 64-bit tile base (SGPRs) + 32-bit lane offset: the store carries half the address bytes
         const unsigned loff = ((unsigned)(wm * 128 + h * 64 + ml) * (unsigned)N + (unsigned)(wn * 64 + schunk * 8)) * 2u;
@@ -1236,7 +1319,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
               float x = bias ? T::to_f32(sBias[n + e]) : 0.f;
-              if (ACT == 1) x = x < 0.f ? 0.f : x;
+              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
               if (ACT == 2) x = gelu_erf(x);
               v[e] = (short)OT::from_f32(x);
             }
@@ -1247,7 +1330,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
         if (HAS_RES) {
 #pragma unroll
           for (int e = 0; e < 8; ++e)
-            v[e] = (short)T::from_f32(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[it][e]));
+            v[e] = (short)T::from_f32(relu_if<ACT == 3>(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[it][e])));
         }
         size_t off = (size_t)m * Ny + n;
         if (hm_hd > 0) {  // column-block-major destination y[b][n / hm_hd][position][n % hm_hd] (hm_hd % 8 == 0: a lane's 8-column chunk lies inside one block)
@@ -1383,7 +1466,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           float x = acc[nt][mt][r];
-          if (ACT == 1) x = x < 0.f ? 0.f : x;
+          if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
           if (ACT == 2) x = gelu_erf(x);
           v[r] = x;
         }
@@ -1455,6 +1538,7 @@ int launch_xs_act(hipStream_t st, const void* X, const void* W, const void* bias
   switch (act) {
     case 0: return launch_xs_res<T, KS, 0>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
     case 1: return launch_xs_res<T, KS, 1>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
+    case 3: return launch_xs_res<T, KS, 3>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
     default: return launch_xs_res<T, KS, 2>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
   }
 }
@@ -1482,9 +1566,10 @@ template <class T>
 int launch(hipStream_t st, const void* X, const void* W, const void* bias, const void* R, void* Y, const void* mask,
            int64_t M, int64_t N, int64_t K, int act, int64_t hm_rows, int hm_hd) {
   if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0) return CODETR_E_BADARG;
-  if (K % 64 != 0 || act < 0 || act > 2) return CODETR_E_UNSUPPORTED;
+  if (K % 64 != 0 || act < 0 || act > 3) return CODETR_E_UNSUPPORTED;
   if (M > 0x7fffffffLL || N > 0x7fffffffLL || K > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
   if (((M + BM - 1) / BM) * ((N + BN - 1) / BN) > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
+  if (act == 3 && !R) act = 1;   // ReLU after a residual that is not there
   if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W)) & 15) return CODETR_E_BADARG;
   if (hm_hd != 0 || hm_rows != 0) {
     if (hm_hd <= 0 || hm_rows <= 0 || hm_hd % 8 != 0 || N % hm_hd != 0 || N % 8 != 0 || M % hm_rows != 0 || R)
@@ -1496,6 +1581,7 @@ int launch(hipStream_t st, const void* X, const void* W, const void* bias, const
     switch (act) {
       case 0: return launch_big<T, 0>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
       case 1: return launch_big<T, 1>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
+      case 3: return launch_big<T, 3>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
       default: return launch_big<T, 2>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
     }
   }
@@ -1504,7 +1590,61 @@ int launch(hipStream_t st, const void* X, const void* W, const void* bias, const
   switch (act) {
     case 0: return launch_act<T, 0>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
     case 1: return launch_act<T, 1>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
+    case 3: return launch_act<T, 3>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
     default: return launch_act<T, 2>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
+  }
+}
+
+template <class T, int ACT, int BKT>
+int launch_conv_cfg(hipStream_t st, const void* X, const void* W, const void* bias, const void* R, void* Y, int M, int N,
+                    int K, const ConvGeom& g) {
+  const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
+  const dim3 grid((unsigned)(tiles_m * tiles_n)), block(kThreads);
+  auto x = static_cast<const unsigned short*>(X);
+  auto w = static_cast<const unsigned short*>(W);
+  auto b = static_cast<const unsigned short*>(bias);
+  auto r = static_cast<const unsigned short*>(R);
+  auto y = static_cast<unsigned short*>(Y);
+  if (bias && R) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, true, true, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
+  else if (bias) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, true, false, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
+  else if (R) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, false, true, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
+  else hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, false, false, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
+template <class T, int ACT>
+int launch_conv_act(hipStream_t st, const void* X, const void* W, const void* bias, const void* R, void* Y, int M, int N,
+                    int K, const ConvGeom& g) {
+  // the linear's pipeline rule (a K slice of 32 or 64 stays inside one tap: C % 64 == 0)
+  if (pipeline_cfg(K, (int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN)) == 322)
+    return launch_conv_cfg<T, ACT, 32>(st, X, W, bias, R, Y, M, N, K, g);
+  return launch_conv_cfg<T, ACT, 64>(st, X, W, bias, R, Y, M, N, K, g);
+}
+
+template <class T>
+int launch_conv(hipStream_t st, const void* X, const void* W, const void* bias, const void* R, void* Y, int64_t B,
+                int64_t H, int64_t Wd, int64_t C, int64_t Cout, int k, int stride, int pad, int act) {
+  if (!X || !W || !Y || B <= 0 || H <= 0 || Wd <= 0 || C <= 0 || Cout <= 0) return CODETR_E_BADARG;
+  if ((k != 1 && k != 3) || (stride != 1 && stride != 2) || pad < 0 || pad >= k || C % 64 != 0 || Cout % 8 != 0 ||
+      act < 0 || act > 3)
+    return CODETR_E_UNSUPPORTED;
+  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(Y) |
+       reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(bias)) & 15)
+    return CODETR_E_BADARG;
+  const int64_t Ho = (H + 2 * pad - k) / stride + 1, Wo = (Wd + 2 * pad - k) / stride + 1;
+  if (Ho <= 0 || Wo <= 0) return CODETR_E_BADARG;
+  const int64_t M = B * Ho * Wo, K = (int64_t)k * k * C;
+  if (M > 0x7fffffffLL || Cout > 0x7fffffffLL || K > 0x7fffffffLL || H > 0xffffLL || Wd > 0xffffLL)
+    return CODETR_E_TOO_LARGE;
+  if (((M + BM - 1) / BM) * ((Cout + BN - 1) / BN) > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
+  if (act == 3 && !R) act = 1;
+  const ConvGeom g{(int)H, (int)Wd, (int)C, (int)Wo, (int)(Ho * Wo), k, stride, pad};
+  switch (act) {
+    case 0: return launch_conv_act<T, 0>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
+    case 1: return launch_conv_act<T, 1>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
+    case 2: return launch_conv_act<T, 2>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
+    default: return launch_conv_act<T, 3>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
   }
 }
 
@@ -1714,6 +1854,20 @@ int codetr_linear_bf16_f16out(void* stream, const void* x_dev, const void* w_dev
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (K == 192) return launch_xs_res<BFloatT, 6, 0, HalfT>(st, x_dev, w_dev, bias_dev, nullptr, y_dev, row_mask_dev, (int)M, (int)N, (int)hm_rows, hm_head_dim);
   return launch_xs_res<BFloatT, 8, 0, HalfT>(st, x_dev, w_dev, bias_dev, nullptr, y_dev, row_mask_dev, (int)M, (int)N, (int)hm_rows, hm_head_dim);
+}
+
+int codetr_conv_tokens_f16(void* stream, const void* x_dev, const void* w_dev, const void* bias_dev,
+                           const void* residual_dev, void* y_dev, int64_t B, int64_t H, int64_t W, int64_t C,
+                           int64_t Cout, int k, int stride, int pad, int act) {
+  return launch_conv<HalfT>(static_cast<hipStream_t>(stream), x_dev, w_dev, bias_dev, residual_dev, y_dev, B, H, W, C,
+                            Cout, k, stride, pad, act);
+}
+
+int codetr_conv_tokens_bf16(void* stream, const void* x_dev, const void* w_dev, const void* bias_dev,
+                            const void* residual_dev, void* y_dev, int64_t B, int64_t H, int64_t W, int64_t C,
+                            int64_t Cout, int k, int stride, int pad, int act) {
+  return launch_conv<BFloatT>(static_cast<hipStream_t>(stream), x_dev, w_dev, bias_dev, residual_dev, y_dev, B, H, W, C,
+                              Cout, k, stride, pad, act);
 }
 
 const char* codetr_linear_variant(int64_t M, int64_t N, int64_t K, int act, int has_residual, int hm_head_dim) {

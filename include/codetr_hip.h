@@ -34,7 +34,7 @@ extern "C" {
 #define CODETR_E_UNSUPPORTED (-4) /* shape outside what the kernel family implements             */
 
 /* ABI version of this header; bumped on any signature change. */
-#define CODETR_HIP_ABI_VERSION 51
+#define CODETR_HIP_ABI_VERSION 52
 int codetr_hip_abi_version(void);
 /* Human-readable message for a code returned by any entry point (static storage). */
 const char *codetr_hip_strerror(int code);
@@ -223,6 +223,48 @@ int codetr_patch_im2col_b16(void *stream, const void *x_dev, int64_t B, int C, i
 int codetr_im2col_tokens_b16(void *stream, const void *x_dev, int64_t B, int64_t H, int64_t W, int64_t C, int k,
                              int stride, int pad, void *out_dev);
 
+/* ------------------------------------------------------------------------------------------
+ * Native ResNet-50 backbone (16-bit, token-major).  Replaces mmdet's ResNet (depth 50, style 'pytorch', frozen BN)
+ * that the R50 config builds, configs/co_dino_5scale_r50_lsj_8xb2_1x_coco.py:22-31: every Conv2d + frozen BatchNorm
+ * (+ ReLU) (+ residual add + ReLU) and the stem's max pool.  The host folds each BN into its conv (weight w gamma /
+ * sqrt(var + eps), bias beta - mean gamma / sqrt(var + eps), in fp32, rounded once to T).
+ *
+ * Convolution on a token-major map as an implicit GEMM (no im2col buffer):
+ *   y[b, oy, ox, n] = act(sum_{ky, kx, c} x[b, oy s + ky - pad, ox s + kx - pad, c] w[n, (ky, kx, c)] + bias[n])
+ *                     (+ residual[b, oy, ox, n]), zero outside the map; act and residual exactly as codetr_linear_*
+ *                     (act 3 = ReLU after the residual)
+ *   x_dev        [B, H, W, C]      T (f16 / bf16), C % 64 == 0
+ *   w_dev        [Cout, k k C]     T, columns ordered (ky, kx, c): conv.weight.permute(0, 2, 3, 1)
+ *   bias_dev     [Cout] or NULL;   residual_dev [B, Ho, Wo, Cout] or NULL;   y_dev [B, Ho, Wo, Cout], Cout % 8 == 0
+ *   Ho = (H + 2 pad - k) / stride + 1 (likewise Wo).  k in {1, 3}, stride in {1, 2}, 0 <= pad < k, act 0..3:
+ *   CODETR_E_UNSUPPORTED otherwise.  Every pointer 16-byte aligned.  fp32 accumulation on the MFMA units, one rounding
+ *   at the store (the residual is added to the rounded result, as in codetr_linear_*).
+ * Serves the bottlenecks' 3x3 convs (stride 1 and 2) and the stride-2 1x1 downsample convs; the stride-1 1x1 convs
+ * are plain GEMMs over tokens (codetr_linear_*).
+ * ------------------------------------------------------------------------------------------ */
+int codetr_conv_tokens_f16(void *stream, const void *x_dev, const void *w_dev, const void *bias_dev,
+                           const void *residual_dev, void *y_dev, int64_t B, int64_t H, int64_t W, int64_t C,
+                           int64_t Cout, int k, int stride, int pad, int act);
+int codetr_conv_tokens_bf16(void *stream, const void *x_dev, const void *w_dev, const void *bias_dev,
+                            const void *residual_dev, void *y_dev, int64_t B, int64_t H, int64_t W, int64_t C,
+                            int64_t Cout, int k, int stride, int pad, int act);
+
+/* Gather of the stem's overlapping-window convolution (Conv2d(3, 64, 7, stride 2, padding 3) on the NCHW image):
+ *   out[(b, oy, ox)][(c, ky, kx)] = x[b, c, oy s + ky - pad, ox s + kx - pad]   (0 outside the image and for columns
+ *   >= C k k), the column order of conv.weight.view(Cout, C k k); codetr_linear_* with the weight padded to kpad columns
+ *   then computes the convolution (the overlapping-window form of codetr_patch_im2col_b16).
+ *   x_dev [B, C, H, W] 16-bit;  out_dev [B Ho Wo, kpad] same type, 16-byte aligned;  kpad % 8 == 0 and kpad >= C k k
+ *   (CODETR_E_UNSUPPORTED otherwise). */
+int codetr_conv_im2col_nchw_b16(void *stream, const void *x_dev, int64_t B, int C, int64_t H, int64_t W, int k,
+                                int stride, int pad, int kpad, void *out_dev);
+
+/* Max pool on a token-major map, F.max_pool2d(x, 3, 2, 1) semantics: padding never wins, a NaN in the window is
+ * returned (torch's rule: the last NaN of the row-major scan), the result is exact (the winner's bits are stored).
+ *   x_dev [B, H, W, C] 16-bit, C % 8 == 0;  y_dev [B, Ho, Wo, C], Ho = (H - 1) / 2 + 1;  is_bf16: 0 = fp16, 1 = bf16.
+ *   k == 3, stride == 2, pad == 1 only (CODETR_E_UNSUPPORTED otherwise); 16-byte aligned bases. */
+int codetr_maxpool_tokens_b16(void *stream, const void *x_dev, int64_t B, int64_t H, int64_t W, int64_t C, int k,
+                              int stride, int pad, int is_bf16, void *y_dev);
+
 /* Row-wise top-k of 16-bit floats: the two selections of the detection head -- the two-stage proposals
  * (torch.topk(enc_outputs_class.max(-1)[0], 900, dim=1), reference codetr/transformer.py:560-561) and the final
  * detections (cls_score.view(B, -1).topk(300), reference codetr/co_dino_head.py:183-186).
@@ -271,7 +313,10 @@ const char *codetr_msda_variant(int elem_bytes, int M, int D, int L, int P);
  *                INPUT row counts as zeros, y = act(bias) -- `memory * keep` of apply_mask_to_proposal_and_memory
  *                (codetr/transformer.py:365-380) folded into enc_output
  *   y_dev        [M, N]  (may alias residual_dev)     T
- *   act          0 = none, 1 = ReLU, 2 = GELU (erf form, nn.GELU default)
+ *   act          0 = none, 1 = ReLU, 2 = GELU (erf form, nn.GELU default), 3 = ReLU applied AFTER the residual:
+ *                y = relu(x . w^T + bias + residual), rounded as act 0 + residual and then clamped (the ResNet
+ *                bottleneck's relu(bn3(conv3(x)) + identity)); with no residual act 3 is act 1.  Act 3 exists on
+ *                codetr_linear_f16 / _bf16 and codetr_conv_tokens_* only: every other linear entry rejects it
  *   hm_rows, hm_head_dim   0, 0: y is row-major [M, N].  Otherwise the rows are (batch, position) with
  *                hm_rows positions per batch and the columns (head, channel) with hm_head_dim channels per
  *                head, and y is written HEAD-MAJOR: y[b][head][position][channel] -- the value-map layout
