@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcodetr_hip.so")
-ABI_VERSION = 52
+ABI_VERSION = 53
 
 _i64, _i32, _vp, _cp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p
 
@@ -102,6 +102,15 @@ SIGNATURES = {
     "codetr_preprocess_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_preprocess_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_batched_nms_f32": (_i32, [_vp, _vp, _vp, _i64, ctypes.c_float, _vp]),
+    "codetr_preprocess_batch_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_preprocess_batch_u8_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_preprocess_batch_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_postprocess_detections_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
+                                                 ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "codetr_postprocess_detections_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
+                                                  ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "codetr_postprocess_detections_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
+                                                 ctypes.c_float, _vp, _vp, _vp, _vp]),
     "codetr_patch_merge_layernorm_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_patch_merge_layernorm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_mask_pyramid": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32]),
@@ -169,6 +178,7 @@ _lib = None
 CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 0, "layernorm": 0, "window_attention": 0, "groupnorm_tokens": 0,
          "sine_pos_tokens": 0, "ffn_fused": 0, "ffn_oproj_fused": 0, "linear_splitk": 0, "linear_sk": 0, "mask_pyramid": 0,
          "query_sine_embed": 0, "encoder_geometry": 0, "row_max": 0, "preprocess": 0, "batched_nms": 0,
+         "preprocess_batch": 0, "postprocess_detections": 0,
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
@@ -511,6 +521,43 @@ def batched_nms_sorted(boxes_sorted, labels_sorted, iou_threshold):
                                        labels_sorted.data_ptr(), N, float(iou_threshold), keep.data_ptr())
     check(rc, "codetr_batched_nms_f32")
     return keep
+
+
+PREPROCESS_BATCH_MAX = 32      # CODETR_PREPROCESS_BATCH_MAX: images per codetr_preprocess_batch_u8_* launch
+POSTPROCESS_MAX_Q = 1024       # CODETR_POSTPROCESS_MAX_Q: detections per image of codetr_postprocess_detections_*
+_PRE_BATCH_BY_DTYPE = {torch.float16: "codetr_preprocess_batch_u8_f16", torch.bfloat16: "codetr_preprocess_batch_u8_bf16",
+                       torch.float32: "codetr_preprocess_batch_u8_f32"}
+_POST_BY_DTYPE = {torch.float16: "codetr_postprocess_detections_f16", torch.bfloat16: "codetr_postprocess_detections_bf16",
+                  torch.float32: "codetr_postprocess_detections_f32"}
+
+
+def preprocess_batch_u8(src, images, batch_hw, mean, std, pad_value, pad_fill, dst, mask):
+    """src: flat uint8 device buffer; images: <= PREPROCESS_BATCH_MAX rows (src_offset, H_src, W_src, H_resized,
+    W_resized, H_pad, W_pad); dst [N,3,H,W] / mask [N,H,W] (or None) contiguous in one of the three dtypes"""
+    CALLS["preprocess_batch"] += 1
+    N = len(images)
+    H, W = batch_hw
+    table = (ctypes.c_int64 * (7 * N))(*[int(v) for row in images for v in row])
+    f3 = ctypes.c_float * 3
+    rc = getattr(load(), _PRE_BATCH_BY_DTYPE[dst.dtype])(
+        current_stream_ptr(src.device), src.data_ptr(), src.numel(), N, table, H, W, f3(*[float(v) for v in mean]),
+        f3(*[float(v) for v in std]), (ctypes.c_int * 3)(*[int(v) for v in pad_value]), float(pad_fill), dst.data_ptr(),
+        mask.data_ptr() if mask is not None else None)
+    check(rc, "codetr_preprocess_batch_u8")
+
+
+def postprocess_detections(boxes, scores, labels, divisors, score_threshold, iou_threshold, boxes_out, scores_out,
+                           labels_out, count):
+    """boxes [N,Q,4] / scores [N,Q] / divisors [N,4] in one dtype, labels [N,Q] int64 -> compacted outputs + count [N]
+    int32 (include/codetr_hip.h); score_threshold None = no threshold, iou_threshold None = no NMS"""
+    CALLS["postprocess_detections"] += 1
+    N, Q = scores.shape
+    rc = getattr(load(), _POST_BY_DTYPE[scores.dtype])(
+        current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), divisors.data_ptr(),
+        N, Q, 0 if score_threshold is None else 1, 0.0 if score_threshold is None else float(score_threshold),
+        0 if iou_threshold is None else 1, 0.0 if iou_threshold is None else float(iou_threshold), boxes_out.data_ptr(),
+        scores_out.data_ptr(), labels_out.data_ptr(), count.data_ptr())
+    check(rc, "codetr_postprocess_detections")
 
 
 def mask_pyramid(img_masks, shapes):

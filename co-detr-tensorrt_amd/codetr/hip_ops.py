@@ -11,6 +11,8 @@ There is no CPU path: a CPU tensor reaching any of these functions is an error (
 formulation of the model lives in oracle/ and is test infrastructure).
 """
 
+import collections
+
 import torch
 import torch.nn.functional as F
 
@@ -24,6 +26,8 @@ NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_win
           "query_sine_embed(f16: sigmoid x valid ratios + sine embedding of the decoder reference boxes)",
           "encoder_geometry(f16: reference points, proposals, keep/drop state)", "row_max(f16)",
           "preprocess_image(u8 -> f16/f32, cv2-exact resize + pad + normalise + mask)", "batched_nms(f32)",
+          "preprocess_batch(u8 -> f16/bf16/f32, <= 32 images of any size per launch, stacked + padded)",
+          "postprocess_detections(f16/bf16/f32: threshold + sort + per-class NMS + rescale, one workgroup per image)",
           "patch_merge_layernorm(f16: Swin 2x2 gather + LayerNorm)",
           "msda_encoder_packed(f16/bf16: LDS-staged gather for the encoder's self-attention, csrc/msda_encoder4.hip)",
           "patch_embed(f16/bf16: 4x4 patch gather + GEMM)",
@@ -499,6 +503,78 @@ def batched_nms(boxes, scores, labels, iou_threshold):
         keep = _cabi.batched_nms_sorted(boxes.float()[order].contiguous(), labels.to(torch.int64)[order].contiguous(),
                                         iou_threshold)
     return order[keep]
+
+
+PREPROCESS_BATCH_MAX = _cabi.PREPROCESS_BATCH_MAX
+
+
+def preprocess_batch(src_u8, images, batch_hw, mean, std, pad_val=(0, 0, 0), pad_value=0.0, dtype=torch.float16,
+                     with_mask=True):
+    """Many uint8 HWC RGB images of different sizes, back to back in ONE flat device buffer -> the stacked
+    (batch_inputs [N, 3, H, W], img_masks [N, H, W] or None), batch_hw = (H, W).  images: one row per image,
+    (src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad).  Per image preprocess_image's arithmetic into its
+    (H_pad, W_pad) Pad region; beyond it `pad_value` as is and mask 1 (DetDataPreprocessor's divisor padding and
+    stack_batch).  One launch per PREPROCESS_BATCH_MAX images (csrc/prepost.hip)."""
+    _gpu(src_u8, "preprocess_batch")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
+        raise ValueError("expected one contiguous flat uint8 buffer")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"preprocess_batch writes f16, bf16 or f32, not {dtype}")
+    N = len(images)
+    H, W = (int(v) for v in batch_hw)
+    x = torch.empty((N, 3, H, W), dtype=dtype, device=src_u8.device)
+    m = torch.empty((N, H, W), dtype=dtype, device=src_u8.device) if with_mask else None
+    with torch.cuda.device(src_u8.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            _cabi.preprocess_batch_u8(src_u8, images[i:j], (H, W), mean, std, pad_val, pad_value, x[i:j],
+                                      m[i:j] if m is not None else None)
+    return x, m
+
+
+# postprocess_detections' result: boxes [N,Q,4] / scores [N,Q] (input dtype), labels [N,Q] int64, count [N] int32 --
+# image i's detections are rows [:count[i]] -- all four views of the one byte buffer `packed`
+Detections = collections.namedtuple("Detections", "boxes scores labels count packed")
+
+
+def _detection_views(packed, N, Q, dtype):
+    es = torch.empty((), dtype=dtype).element_size()
+    o1 = N * Q * 8
+    o2 = o1 + N * 4
+    o3 = o2 + N * Q * 4 * es
+    o4 = o3 + N * Q * es
+    return Detections(packed[o2:o3].view(dtype).view(N, Q, 4), packed[o3:o4].view(dtype).view(N, Q),
+                      packed[:o1].view(torch.int64).view(N, Q), packed[o1:o2].view(torch.int32), packed)
+
+
+def postprocess_detections(boxes, scores, labels, divisors, score_threshold=None, iou_threshold=None):
+    """Inferencer.postprocess_predictions + run_inference's `boxes / scale_factor` for a whole batch in one launch
+    (csrc/prepost.hip): boxes [N,Q,4], scores [N,Q], divisors [N,4] in one of f16 / bf16 / f32, labels [N,Q] int64,
+    Q <= 1024.  score_threshold: keep `scores > score_threshold` (compared in the scores' dtype; None: no threshold);
+    iou_threshold: per-class NMS in descending score order (None: none, index order kept).  -> Detections, compacted
+    per image; `detections_to_host` fetches all of it in one copy."""
+    _gpu(scores, "postprocess_detections")
+    dtype = scores.dtype
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32) or boxes.dtype != dtype or divisors.dtype != dtype:
+        raise ValueError("postprocess_detections: boxes, scores and divisors in one dtype of f16 / bf16 / f32")
+    N, Q = scores.shape
+    if tuple(boxes.shape) != (N, Q, 4) or tuple(labels.shape) != (N, Q) or tuple(divisors.shape) != (N, 4):
+        raise ValueError("postprocess_detections: boxes [N,Q,4], scores [N,Q], labels [N,Q], divisors [N,4]")
+    nbytes = N * Q * 8 + N * 4 + N * Q * 5 * scores.element_size()
+    if N == 0 or Q == 0:   # nothing to launch for: every count is 0
+        return _detection_views(torch.zeros((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
+    out = _detection_views(torch.empty((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
+    with torch.cuda.device(scores.device):
+        _cabi.postprocess_detections(boxes.contiguous(), scores.contiguous(), labels.to(torch.int64).contiguous(),
+                                     divisors.contiguous(), score_threshold, iou_threshold, out.boxes, out.scores,
+                                     out.labels, out.count)
+    return out
+
+
+def detections_to_host(dets):
+    """postprocess_detections' result on the host: one device-to-host copy of the packed buffer"""
+    N, Q = dets.scores.shape
+    return _detection_views(dets.packed.cpu(), N, Q, dets.scores.dtype)
 
 
 def mask_pyramid(img_masks, shapes):

@@ -13,6 +13,12 @@ Same constructor and call signature for the parts that do not need mmengine's vi
 Per image (reference :441-452, :343-378): upload the uint8 image, one kernel for resize + pad + normalise + mask
 (``hip_ops.preprocess_image``), ``model(batch_inputs, img_masks)``, score threshold, per-class NMS
 (``hip_ops.batched_nms``), boxes / scale_factor.
+
+``__call__(..., batch_size=B)`` with B > 1 (and any bf16 call) runs the images in chunks of B instead -- beyond the
+reference, which loops image by image: per chunk one pinned staging buffer and one upload, one launch that resizes,
+pads and stacks them all (``preprocess_batch``: mmdet's ``stack_batch`` shape), one forward, one launch for threshold
++ NMS + rescale of every image (``postprocess_batch``) and one download.  Every image's result is what the per-image
+path returns for it when the model's detections do not depend on the other images of the batch.
 """
 from typing import Dict, List, Optional
 
@@ -94,6 +100,39 @@ class Inferencer:
                     scale_factor=(nw / W, nh / H))
         return x[None], m[None], meta
 
+    def preprocess_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32):
+        """RGB uint8 images [H_i, W_i, 3] -> (batch_inputs [N,3,H,W], img_masks [N,H,W], metas): per image the
+        arithmetic of `preprocess`, stacked as mmdet's DetDataPreprocessor does (H, W = the largest Pad shape rounded
+        up to pad_size_divisor; beyond an image's Pad region pad_value, mask 1).  One host-to-device copy, one launch
+        per 32 images; dtype f16, bf16 or f32."""
+        rows, metas, offset = [], [], 0
+        d = self.pad_size_divisor
+        for image in images:
+            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+                raise ValueError("expected RGB uint8 images of shape (H, W, 3)")
+            H, W = image.shape[:2]
+            nh, nw = rescale_size(H, W, self.scale)
+            Hp, Wp = nh, nw
+            if self.pad_size is not None:
+                Wp, Hp = max(self.pad_size[0], nw), max(self.pad_size[1], nh)
+            rows.append((offset, H, W, nh, nw, Hp, Wp))
+            offset += H * W * 3
+            pad_shape = (-(-Hp // d) * d, -(-Wp // d) * d) if d > 1 else (Hp, Wp)
+            metas.append(dict(ori_shape=(H, W), img_shape=(nh, nw), img_unpadded_shape=(nh, nw), pad_shape=pad_shape,
+                              scale_factor=(nw / W, nh / H)))
+        if not rows:
+            raise ValueError("preprocess_batch: no images")
+        Hb, Wb = max(m["pad_shape"][0] for m in metas), max(m["pad_shape"][1] for m in metas)
+        for m in metas:
+            m["batch_input_shape"] = (Hb, Wb)
+        staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        for image, row in zip(images, rows):
+            host[row[0]:row[0] + image.size] = np.ascontiguousarray(image).reshape(-1)
+        src = staging.to(device, non_blocking=True)
+        x, m = hip_ops.preprocess_batch(src, rows, (Hb, Wb), self.mean, self.std, self.pad_val, self.pad_value, dtype)
+        return x, m, metas
+
     # ---- post -----------------------------------------------------------------------------------------
     def postprocess_predictions(self, batch_boxes, batch_scores, batch_labels):
         """score threshold + per-class NMS per image (reference :380-400)"""
@@ -118,21 +157,55 @@ class Inferencer:
             results.append(dict(bboxes=boxes, scores=scores, labels=labels))
         return results
 
+    def postprocess_batch(self, predictions, metas):
+        """the model's (boxes [N,Q,4], scores [N,Q], labels [N,Q]) -> one result dict per image ({"labels", "scores",
+        "bboxes"} as Python lists, what `__call__` returns): score threshold, per-class NMS and / scale_factor of
+        `run_inference` for the whole batch in one launch, then one device-to-host copy"""
+        boxes, scores, labels = predictions
+        # the rescale divisor exactly as run_inference builds it (boxes.new_tensor of the Python floats)
+        div = torch.tensor([[m["scale_factor"][0], m["scale_factor"][1]] * 2 for m in metas], dtype=boxes.dtype)
+        dets = hip_ops.postprocess_detections(boxes, scores, labels, div.to(boxes.device),
+                                              self.score_threshold if self.score_threshold > 0 else None,
+                                              self.iou_threshold if self.with_nms else None)
+        host = hip_ops.detections_to_host(dets)
+        out = []
+        for i in range(len(metas)):
+            c = int(host.count[i])
+            out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
+                        "bboxes": host.boxes[i, :c].float().tolist()})
+        return out
+
     def __call__(self, images: List[np.ndarray], return_vis: bool = False, show: bool = False, wait_time: int = 0,
                  no_save_vis: bool = False, draw_pred: bool = True, pred_score_thr: float = 0.3,
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
-                 out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32) -> Dict:
+                 out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
+                 batch_size: int = 1) -> Dict:
         if return_vis or show or not no_save_pred or return_datasamples:
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
+        if int(batch_size) != batch_size or batch_size < 1:
+            raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
+        batch_size = int(batch_size)
         results_dict = {"predictions": [], "visualization": []}
-        for image in images:
+        if batch_size == 1 and dtype != torch.bfloat16:
+            for image in images:
+                with torch.no_grad():
+                    x, m, meta = self.preprocess(image, device, dtype)
+                    res = self.run_inference(x, m, [meta])[0]
+                pred = {"labels": res["labels"].tolist(), "scores": res["scores"].float().tolist(),
+                        "bboxes": res["bboxes"].float().tolist()}
+                if print_result:
+                    print(pred)
+                self.num_predicted_imgs += 1
+                results_dict["predictions"].append(pred)
+            return results_dict
+        for start in range(0, len(images), batch_size):
+            chunk = images[start:start + batch_size]
             with torch.no_grad():
-                x, m, meta = self.preprocess(image, device, dtype)
-                res = self.run_inference(x, m, [meta])[0]
-            pred = {"labels": res["labels"].tolist(), "scores": res["scores"].float().tolist(),
-                    "bboxes": res["bboxes"].float().tolist()}
-            if print_result:
-                print(pred)
-            self.num_predicted_imgs += 1
-            results_dict["predictions"].append(pred)
+                x, m, metas = self.preprocess_batch(chunk, device, dtype)
+                preds = self.postprocess_batch(self.model(x, m), metas)
+            for pred in preds:
+                if print_result:
+                    print(pred)
+                self.num_predicted_imgs += 1
+                results_dict["predictions"].append(pred)
         return results_dict

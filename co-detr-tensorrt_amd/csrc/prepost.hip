@@ -10,12 +10,38 @@
 // batched_nms_kernel  replaces torchvision.ops.batched_nms in postprocess_predictions (codetr/inferencer.py:388-398)
 //                     for the <= 300 detections of an image: greedy, per class, candidates in descending score order
 //                     (the caller passes them sorted), IoU > thr suppresses; fp32 arithmetic on the given boxes.
+// preprocess_batch_kernel  the same per-pixel work for up to 32 images of different sizes in one launch, written into
+//                     one stacked batch [N, 3, H, W] whose margin beyond each image's Pad region holds the raw
+//                     DetDataPreprocessor pad_value (mmdet stack_batch); the per-image table travels in the kernargs.
+// postprocess_kernel  postprocess_predictions + the rescale of run_inference (codetr/inferencer.py:343-400) for a
+//                     batch, one workgroup per image: score threshold at the storage precision, stable descending sort
+//                     (bitonic, index tie-break), the NMS of batched_nms_kernel, boxes / scale factor, compacted output.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "codetr_hip.h"
 
 namespace {
+
+// bfloat16 storage (the bf16 model's instantiations); conversions round to nearest even as ATen does, NaN stays NaN
+struct Bf16 {
+  unsigned short bits;
+};
+
+__device__ __forceinline__ float to_f32(float v) { return v; }
+__device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
+__device__ __forceinline__ float to_f32(Bf16 v) { return __uint_as_float(((unsigned)v.bits) << 16); }
+
+template <class T>
+__device__ __forceinline__ T from_f32(float v) {
+  return (T)v;
+}
+template <>
+__device__ __forceinline__ Bf16 from_f32<Bf16>(float v) {
+  const unsigned u = __float_as_uint(v);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return Bf16{(unsigned short)((u >> 16) | 0x40)};
+  return Bf16{(unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};
+}
 
 struct ResizeAxis {
   float scale;  // src / dst
@@ -41,6 +67,29 @@ __device__ __forceinline__ void coeff(int d, ResizeAxis ax, int& s, int& a1) {
   a1 = (int)rintf(f * 2048.0f);  // round half to even, as cvRound
 }
 
+// pixel (y, x) of the cv2-resized image (y < Hr, x < Wr) of a uint8 HWC RGB image [Hs, Ws, 3] -> v[3] in 0..255
+__device__ __forceinline__ void resized_pixel(const unsigned char* __restrict__ src, int Hs, int Ws, int Hr, int Wr,
+                                              int y, int x, int v[3]) {
+  int sy, b1, sx, a1;
+  coeff(y, ResizeAxis{0.f, Hs, Hr}, sy, b1);
+  coeff(x, ResizeAxis{0.f, Ws, Wr}, sx, a1);
+  const int sy1 = min(sy + 1, Hs - 1), sx1 = min(sx + 1, Ws - 1);
+  const int a0 = 2048 - a1, b0 = 2048 - b1;
+  const unsigned char* r0 = src + ((size_t)sy * Ws) * 3;
+  const unsigned char* r1 = src + ((size_t)sy1 * Ws) * 3;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int top = a0 * r0[sx * 3 + c] + a1 * r0[sx1 * 3 + c];
+    const int bot = a0 * r1[sx * 3 + c] + a1 * r1[sx1 * 3 + c];
+    const long long acc = (long long)b0 * top + (long long)b1 * bot + (1 << 21);
+    int q = (int)(acc >> 22);
+    v[c] = q < 0 ? 0 : (q > 255 ? 255 : q);
+  }
+}
+
+// DetDataPreprocessor's (x - mean) / std of a 0..255 value: one fp32 subtract, one IEEE divide
+__device__ __forceinline__ float normalise(int v, float mean, float stdv) { return ((float)v - mean) / stdv; }
+
 template <class OutT>
 __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __restrict__ src, int Hs, int Ws, int Hr,
                                                          int Wr, int Hp, int Wp, float m0, float m1, float m2, float s0,
@@ -52,27 +101,61 @@ __global__ __launch_bounds__(256) void preprocess_kernel(const unsigned char* __
   const float mean[3] = {m0, m1, m2}, stdv[3] = {s0, s1, s2};
   int v[3] = {p0, p1, p2};
   const bool inside = y < Hr && x < Wr;
-  if (inside) {
-    int sy, b1, sx, a1;
-    coeff(y, ResizeAxis{0.f, Hs, Hr}, sy, b1);
-    coeff(x, ResizeAxis{0.f, Ws, Wr}, sx, a1);
-    const int sy1 = min(sy + 1, Hs - 1), sx1 = min(sx + 1, Ws - 1);
-    const int a0 = 2048 - a1, b0 = 2048 - b1;
-    const unsigned char* r0 = src + ((size_t)sy * Ws) * 3;
-    const unsigned char* r1 = src + ((size_t)sy1 * Ws) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int top = a0 * r0[sx * 3 + c] + a1 * r0[sx1 * 3 + c];
-      const int bot = a0 * r1[sx * 3 + c] + a1 * r1[sx1 * 3 + c];
-      const long long acc = (long long)b0 * top + (long long)b1 * bot + (1 << 21);
-      int q = (int)(acc >> 22);
-      v[c] = q < 0 ? 0 : (q > 255 ? 255 : q);
-    }
-  }
+  if (inside) resized_pixel(src, Hs, Ws, Hr, Wr, y, x, v);
   const size_t plane = (size_t)Hp * Wp, o = (size_t)y * Wp + x;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) dst[c * plane + o] = (OutT)(((float)v[c] - mean[c]) / stdv[c]);
+  for (int c = 0; c < 3; ++c) dst[c * plane + o] = (OutT)normalise(v[c], mean[c], stdv[c]);
   if (mask) mask[o] = inside ? (OutT)0.f : (OutT)1.f;
+}
+
+// one image of a batched preprocess launch: its bytes at src + src_offset, resized to (Hr, Wr), Pad region (Hp, Wp)
+struct BatchImage {
+  int64_t src_offset;
+  int Hs, Ws, Hr, Wr, Hp, Wp;
+};
+constexpr int kPreBatchMax = CODETR_PREPROCESS_BATCH_MAX;  // images per launch: the table is a kernel argument (1 KB)
+struct BatchTable {
+  BatchImage img[kPreBatchMax];
+};
+struct BatchNorm {
+  float mean[3], stdv[3];
+  int pad[3];  // the pipeline Pad's pixel value, normalised like the image
+  float fill;  // DetDataPreprocessor's pad_value beyond the Pad region (stored as is, not normalised)
+};
+
+// grid (ceil(W / 256), H, N): one thread per output pixel of the stacked batch [N, 3, H, W] (+ mask [N, H, W])
+template <class OutT>
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char* __restrict__ src, BatchTable tab,
+                                                               BatchNorm nm, int H, int W, OutT* __restrict__ dst,
+                                                               OutT* __restrict__ mask) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  const int y = blockIdx.y;
+  const int n = blockIdx.z;
+  if (x >= W) return;
+  const BatchImage im = tab.img[n];
+  const bool inside = y < im.Hr && x < im.Wr;
+  float o[3] = {nm.fill, nm.fill, nm.fill};
+  if (y < im.Hp && x < im.Wp) {
+    int v[3] = {nm.pad[0], nm.pad[1], nm.pad[2]};
+    if (inside) resized_pixel(src + im.src_offset, im.Hs, im.Ws, im.Hr, im.Wr, y, x, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = normalise(v[c], nm.mean[c], nm.stdv[c]);
+  }
+  const size_t plane = (size_t)H * W, p = (size_t)y * W + x;
+  OutT* d = dst + (size_t)n * 3 * plane;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) d[c * plane + p] = from_f32<OutT>(o[c]);
+  if (mask) mask[(size_t)n * plane + p] = from_f32<OutT>(inside ? 0.f : 1.f);
+}
+
+// torchvision nms's suppression test of candidate j by kept box i (area ia), fp32: IoU > thr
+__device__ __forceinline__ bool iou_above(float ix1, float iy1, float ix2, float iy2, float ia, float jx1, float jy1,
+                                          float jx2, float jy2, float thr) {
+  const float w = fmaxf(0.f, fminf(ix2, jx2) - fmaxf(ix1, jx1));
+  const float h = fmaxf(0.f, fminf(iy2, jy2) - fmaxf(iy1, jy1));
+  const float inter = w * h;
+  const float iou = inter / (ia + (jx2 - jx1) * (jy2 - jy1) - inter);
+  return iou > thr;
 }
 
 // one workgroup; boxes / labels in descending score order.  keep[i] = 1 if i survives.
@@ -89,17 +172,131 @@ __global__ __launch_bounds__(1024) void batched_nms_kernel(const float* __restri
       const int64_t il = labels[i];
       for (int j = i + 1 + threadIdx.x; j < N; j += blockDim.x) {
         if (!s_keep[j] || labels[j] != il) continue;
-        const float jx1 = boxes[4 * j], jy1 = boxes[4 * j + 1], jx2 = boxes[4 * j + 2], jy2 = boxes[4 * j + 3];
-        const float w = fmaxf(0.f, fminf(ix2, jx2) - fmaxf(ix1, jx1));
-        const float h = fmaxf(0.f, fminf(iy2, jy2) - fmaxf(iy1, jy1));
-        const float inter = w * h;
-        const float iou = inter / (ia + (jx2 - jx1) * (jy2 - jy1) - inter);
-        if (iou > thr) s_keep[j] = 0;
+        if (iou_above(ix1, iy1, ix2, iy2, ia, boxes[4 * j], boxes[4 * j + 1], boxes[4 * j + 2], boxes[4 * j + 3], thr))
+          s_keep[j] = 0;
       }
     }
     __syncthreads();
   }
   for (int j = threadIdx.x; j < N; j += blockDim.x) keep[j] = s_keep[j];
+}
+
+constexpr int kPostMaxQ = CODETR_POSTPROCESS_MAX_Q;  // detections per image: one per thread of the workgroup
+
+// descending sort key of a score, the order of the radix sort behind torch.sort of fp32 keys on this platform: the
+// order-preserving image of the bits, so a NaN with the sign bit clear sorts above +inf and one with it set below -inf
+// (the bf16 / f16 NaN of a model is the former); -0 is taken as +0
+__device__ __forceinline__ unsigned score_key(float s) {
+  const unsigned u = __float_as_uint(s == 0.f ? 0.f : s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// grid N, 1024 threads: image n's Q detections -> its kept detections, compacted in output order, count[n] of them.
+// Rows [count, Q) of the outputs are zero.
+template <class T>
+__global__ __launch_bounds__(1024) void postprocess_kernel(const T* __restrict__ boxes, const T* __restrict__ scores,
+                                                           const int64_t* __restrict__ labels,
+                                                           const T* __restrict__ divisors, int Q, int use_thr, float thr,
+                                                           int use_nms, float iou_thr, T* __restrict__ boxes_out,
+                                                           T* __restrict__ scores_out, int64_t* __restrict__ labels_out,
+                                                           int* __restrict__ count) {
+  __shared__ unsigned long long s_key[kPostMaxQ];  // score key << 32 | (2^32 - 1 - index); 0 = dropped
+  __shared__ float4 s_box[kPostMaxQ];              // candidates in output order, fp32
+  __shared__ int64_t s_lab[kPostMaxQ];
+  __shared__ unsigned char s_keep[kPostMaxQ];
+  __shared__ int s_wave[kPostMaxQ / 64];
+  const int tid = threadIdx.x;
+  const size_t n = blockIdx.x;
+  const T* bx = boxes + n * Q * 4;
+  const T* sc = scores + n * Q;
+  const int64_t* lb = labels + n * Q;
+
+  // 1. score threshold, compared at T's precision (`scores > thr` on a T tensor converts the scalar to T)
+  const float thr_t = to_f32(from_f32<T>(thr));
+  unsigned long long key = 0;
+  if (tid < Q) {
+    const float s = to_f32(sc[tid]);
+    if (!use_thr || s > thr_t)
+      key = ((unsigned long long)(use_nms ? score_key(s) : 1u) << 32) | (unsigned long long)(0xffffffffu - (unsigned)tid);
+  }
+  s_key[tid] = key;
+  const int V = __syncthreads_count(key != 0ull);  // candidates; barrier: s_key complete
+
+  // 2. bitonic sort of the 1024 keys, descending: ties (and, without NMS, everything) in ascending index order
+  for (int size = 2; size <= kPostMaxQ; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (tid < kPostMaxQ / 2) {
+        const int lo = 2 * tid - (tid & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long a = s_key[lo], b = s_key[hi];
+        if ((a < b) == desc) {
+          s_key[lo] = b;
+          s_key[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const unsigned src = 0xffffffffu - (unsigned)s_key[tid];  // (meaningful for tid < V)
+  if (tid < V) {
+    s_box[tid] = make_float4(to_f32(bx[4 * src]), to_f32(bx[4 * src + 1]), to_f32(bx[4 * src + 2]),
+                             to_f32(bx[4 * src + 3]));
+    s_lab[tid] = lb[src];
+    s_keep[tid] = 1;
+  }
+  __syncthreads();
+
+  // 3. greedy per-class NMS over the candidates in score order (batched_nms_kernel's visiting order and arithmetic)
+  if (use_nms) {
+    for (int i = 0; i < V; ++i) {
+      if (!s_keep[i]) continue;  // uniform: nothing was written since the last barrier
+      const float4 bi = s_box[i];
+      const float ia = (bi.z - bi.x) * (bi.w - bi.y);
+      if (tid > i && tid < V && s_keep[tid] && s_lab[tid] == s_lab[i]) {
+        const float4 bj = s_box[tid];
+        if (iou_above(bi.x, bi.y, bi.z, bi.w, ia, bj.x, bj.y, bj.z, bj.w, iou_thr)) s_keep[tid] = 0;
+      }
+      __syncthreads();
+    }
+  }
+
+  // 4. compaction (ballot + wave totals) and the rescale: fp32 divide, one rounding to T
+  const bool kept = tid < V && s_keep[tid];
+  const unsigned long long bal = __ballot(kept);
+  const int lane = tid & 63, wave = tid >> 6;
+  if (lane == 0) s_wave[wave] = __popcll(bal);
+  __syncthreads();
+  int pos = __popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+#pragma unroll
+  for (int w = 0; w < kPostMaxQ / 64; ++w) {
+    const int c = s_wave[w];
+    pos += w < wave ? c : 0;
+    total += c;
+  }
+  T* bo = boxes_out + n * Q * 4;
+  T* so = scores_out + n * Q;
+  int64_t* lo = labels_out + n * Q;
+  if (kept) {
+    const T* dv = divisors + n * 4;
+    const float4 b = s_box[tid];
+    bo[4 * pos] = from_f32<T>(b.x / to_f32(dv[0]));
+    bo[4 * pos + 1] = from_f32<T>(b.y / to_f32(dv[1]));
+    bo[4 * pos + 2] = from_f32<T>(b.z / to_f32(dv[2]));
+    bo[4 * pos + 3] = from_f32<T>(b.w / to_f32(dv[3]));
+    so[pos] = sc[src];
+    lo[pos] = s_lab[tid];
+  }
+  if (tid >= total && tid < Q) {  // (kept rows are < total)
+    const T z = from_f32<T>(0.f);
+    bo[4 * tid] = z;
+    bo[4 * tid + 1] = z;
+    bo[4 * tid + 2] = z;
+    bo[4 * tid + 3] = z;
+    so[tid] = z;
+    lo[tid] = 0;
+  }
+  if (tid == 0) count[n] = total;
 }
 
 template <class OutT>
@@ -114,6 +311,55 @@ int launch_pre(void* stream, const void* src, int64_t Hs, int64_t Ws, int64_t Hr
                      static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), (int)Hs, (int)Ws, (int)Hr,
                      (int)Wr, (int)Hp, (int)Wp, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], pad[0], pad[1],
                      pad[2], static_cast<OutT*>(dst), static_cast<OutT*>(mask));
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
+template <class OutT>
+int launch_pre_batch(void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int64_t H,
+                     int64_t W, const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst,
+                     void* mask) {
+  if (!src || !images || !mean || !stdv || !pad || !dst || src_bytes <= 0 || N <= 0 || H <= 0 || W <= 0)
+    return CODETR_E_BADARG;
+  if (N > kPreBatchMax || H > 65535 || W > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
+  BatchNorm nm;
+  for (int c = 0; c < 3; ++c) {
+    if (stdv[c] == 0.f || pad[c] < 0 || pad[c] > 255) return CODETR_E_BADARG;
+    nm.mean[c] = mean[c];
+    nm.stdv[c] = stdv[c];
+    nm.pad[c] = pad[c];
+  }
+  nm.fill = pad_fill;
+  BatchTable tab = {};
+  for (int64_t n = 0; n < N; ++n) {
+    const int64_t* r = images + 7 * n;  // src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad
+    const int64_t off = r[0], Hs = r[1], Ws = r[2], Hr = r[3], Wr = r[4], Hp = r[5], Wp = r[6];
+    if (off < 0 || Hs <= 0 || Ws <= 0 || Hr <= 0 || Wr <= 0 || Hp < Hr || Wp < Wr || Hp > H || Wp > W)
+      return CODETR_E_BADARG;
+    if (Hs > 32767 || Ws > 32767) return CODETR_E_TOO_LARGE;
+    if (off > src_bytes || Hs * Ws * 3 > src_bytes - off) return CODETR_E_BADARG;  // the image must lie in the buffer
+    tab.img[n] = BatchImage{off, (int)Hs, (int)Ws, (int)Hr, (int)Wr, (int)Hp, (int)Wp};
+  }
+  hipLaunchKernelGGL((preprocess_batch_kernel<OutT>), dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N),
+                     dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), tab, nm,
+                     (int)H, (int)W, static_cast<OutT*>(dst), static_cast<OutT*>(mask));
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
+template <class T>
+int launch_post(void* stream, const void* boxes, const void* scores, const int64_t* labels, const void* divisors,
+                int64_t N, int64_t Q, int apply_threshold, float score_threshold, int apply_nms, float iou_threshold,
+                void* boxes_out, void* scores_out, int64_t* labels_out, int* count) {
+  if (!boxes || !scores || !labels || !divisors || !boxes_out || !scores_out || !labels_out || !count || N <= 0 ||
+      Q <= 0)
+    return CODETR_E_BADARG;
+  if (Q > kPostMaxQ || N > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
+  hipLaunchKernelGGL((postprocess_kernel<T>), dim3((unsigned)N), dim3(kPostMaxQ), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const T*>(boxes), static_cast<const T*>(scores), labels,
+                     static_cast<const T*>(divisors), (int)Q, apply_threshold ? 1 : 0, score_threshold,
+                     apply_nms ? 1 : 0, iou_threshold, static_cast<T*>(boxes_out), static_cast<T*>(scores_out),
+                     labels_out, count);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -148,5 +394,28 @@ int codetr_batched_nms_f32(void* stream, const float* boxes_sorted_dev, const in
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
+
+#define CODETR_PRE_BATCH_ENTRY(NAME, OUT_T)                                                                           \
+  int NAME(void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* images_host, int64_t H,    \
+           int64_t W, const float* mean_host, const float* std_host, const int* pad_value_host, float pad_fill,       \
+           void* dst_dev, void* mask_dev) {                                                                           \
+    return launch_pre_batch<OUT_T>(stream, src_dev, src_bytes, N, images_host, H, W, mean_host, std_host,             \
+                                   pad_value_host, pad_fill, dst_dev, mask_dev);                                      \
+  }
+CODETR_PRE_BATCH_ENTRY(codetr_preprocess_batch_u8_f16, _Float16)
+CODETR_PRE_BATCH_ENTRY(codetr_preprocess_batch_u8_bf16, Bf16)
+CODETR_PRE_BATCH_ENTRY(codetr_preprocess_batch_u8_f32, float)
+
+#define CODETR_POST_ENTRY(NAME, T)                                                                                    \
+  int NAME(void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,                    \
+           const void* divisor_dev, int64_t N, int64_t Q, int apply_threshold, float score_threshold, int apply_nms,  \
+           float iou_threshold, void* boxes_out_dev, void* scores_out_dev, int64_t* labels_out_dev, int* count_dev) { \
+    return launch_post<T>(stream, boxes_dev, scores_dev, labels_dev, divisor_dev, N, Q, apply_threshold,              \
+                          score_threshold, apply_nms, iou_threshold, boxes_out_dev, scores_out_dev, labels_out_dev,   \
+                          count_dev);                                                                                 \
+  }
+CODETR_POST_ENTRY(codetr_postprocess_detections_f16, _Float16)
+CODETR_POST_ENTRY(codetr_postprocess_detections_bf16, Bf16)
+CODETR_POST_ENTRY(codetr_postprocess_detections_f32, float)
 
 }  // extern "C"

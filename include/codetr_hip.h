@@ -34,7 +34,7 @@ extern "C" {
 #define CODETR_E_UNSUPPORTED (-4) /* shape outside what the kernel family implements             */
 
 /* ABI version of this header; bumped on any signature change. */
-#define CODETR_HIP_ABI_VERSION 52
+#define CODETR_HIP_ABI_VERSION 53
 int codetr_hip_abi_version(void);
 /* Human-readable message for a code returned by any entry point (static storage). */
 const char *codetr_hip_strerror(int code);
@@ -683,6 +683,67 @@ int codetr_preprocess_u8_f32(void *stream, const void *src_dev, int64_t H_src, i
                              const float *std_host, const int *pad_value_host, void *dst_dev, void *mask_dev);
 int codetr_batched_nms_f32(void *stream, const float *boxes_sorted_dev, const int64_t *labels_sorted_dev, int64_t N,
                            float iou_threshold, void *keep_dev);
+
+/* ------------------------------------------------------------------------------------------
+ * Batched pre- and post-processing: the Inferencer's per-image steps (codetr/inferencer.py:343-400, 439-452) for a
+ * chunk of images in one launch each.
+ *
+ * codetr_preprocess_batch_u8_*: up to CODETR_PREPROCESS_BATCH_MAX uint8 HWC RGB images of different sizes -> the
+ *   stacked batch_inputs [N, 3, H, W] and img_masks [N, H, W] (dtype of the entry).  Per image the arithmetic of
+ *   codetr_preprocess_u8_* (f16 / f32 results are bit-identical to it; bf16 is the f32 value rounded once), then
+ *   DetDataPreprocessor's divisor padding + mmdet stack_batch: beyond the image's Pad region, up to (H, W), every
+ *   value is pad_fill (as given, not normalised) and the mask is 1.
+ *     src_dev            all images' bytes, src_bytes long; image n at byte offset images_host[7n]
+ *     images_host        HOST [N][7] int64: src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad
+ *                        (H_resized <= H_pad <= H, W_resized <= W_pad <= W; the image must lie inside src)
+ *     mean_host/std_host/pad_value_host   as codetr_preprocess_u8_*
+ *     mask_dev           [N, H, W] or NULL
+ *   The table travels in the kernel arguments: no staging copy, capturable.  CODETR_E_BADARG for null pointers,
+ *   N <= 0 and inconsistent rows; CODETR_E_TOO_LARGE for N > CODETR_PREPROCESS_BATCH_MAX (the caller splits),
+ *   H > 65535 or a source side > 32767.
+ *
+ * codetr_postprocess_detections_*: postprocess_predictions + the rescale of run_inference for N images of Q
+ *   detections (boxes_dev [N, Q, 4] xyxy, scores_dev [N, Q] in T; labels_dev [N, Q] int64), one workgroup per image:
+ *     1. apply_threshold: keep score > score_threshold compared at T's precision (the threshold rounded to T first,
+ *        as `scores > thr` on a T tensor does); NaN scores fail it;
+ *     2. apply_nms: stable descending sort of the survivors by score (torch.sort(scores.float(), descending=True,
+ *        stable=True), a radix sort here: ties by ascending index, NaN first -- a NaN with the sign bit set last --,
+ *        -0 equal to +0), then codetr_batched_nms_f32's greedy per-class NMS (same
+ *        fp32 IoU arithmetic, IoU > iou_threshold suppresses); without NMS the survivors keep their index order;
+ *     3. boxes / divisor_dev [N, 4] (T; the host's scale-factor tensor) in fp32, rounded once to T.
+ *   Outputs, compacted per image: boxes_out_dev [N, Q, 4], scores_out_dev [N, Q] (T), labels_out_dev [N, Q] int64,
+ *   count_dev [N] int32 = how many rows of image n are detections; the rows after them are zero.
+ *   CODETR_E_BADARG for null pointers, N <= 0 or Q <= 0; CODETR_E_TOO_LARGE for Q > CODETR_POSTPROCESS_MAX_Q.
+ * ------------------------------------------------------------------------------------------ */
+#define CODETR_PREPROCESS_BATCH_MAX 32
+#define CODETR_POSTPROCESS_MAX_Q 1024
+int codetr_preprocess_batch_u8_f16(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                   const int64_t *images_host, int64_t H, int64_t W, const float *mean_host,
+                                   const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                   void *mask_dev);
+int codetr_preprocess_batch_u8_bf16(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                    const int64_t *images_host, int64_t H, int64_t W, const float *mean_host,
+                                    const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                    void *mask_dev);
+int codetr_preprocess_batch_u8_f32(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                   const int64_t *images_host, int64_t H, int64_t W, const float *mean_host,
+                                   const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                   void *mask_dev);
+int codetr_postprocess_detections_f16(void *stream, const void *boxes_dev, const void *scores_dev,
+                                      const int64_t *labels_dev, const void *divisor_dev, int64_t N, int64_t Q,
+                                      int apply_threshold, float score_threshold, int apply_nms, float iou_threshold,
+                                      void *boxes_out_dev, void *scores_out_dev, int64_t *labels_out_dev,
+                                      int *count_dev);
+int codetr_postprocess_detections_bf16(void *stream, const void *boxes_dev, const void *scores_dev,
+                                       const int64_t *labels_dev, const void *divisor_dev, int64_t N, int64_t Q,
+                                       int apply_threshold, float score_threshold, int apply_nms, float iou_threshold,
+                                       void *boxes_out_dev, void *scores_out_dev, int64_t *labels_out_dev,
+                                       int *count_dev);
+int codetr_postprocess_detections_f32(void *stream, const void *boxes_dev, const void *scores_dev,
+                                      const int64_t *labels_dev, const void *divisor_dev, int64_t N, int64_t Q,
+                                      int apply_threshold, float score_threshold, int apply_nms, float iou_threshold,
+                                      void *boxes_out_dev, void *scores_out_dev, int64_t *labels_out_dev,
+                                      int *count_dev);
 
 /* ------------------------------------------------------------------------------------------
  * Backward of multi-scale deformable attention (training path).

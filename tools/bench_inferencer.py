@@ -1,0 +1,160 @@
+"""Images/s of the user-facing `codetr.Inferencer` (image in, detections out) at batch_size 1, 4 and 8, fp16 and bf16.
+
+Swin-L config (Resize + Pad to 1152x768), seeded random weights (bench.build_model), 32 synthetic RGB uint8 images of
+mixed sizes (640x480, 1280x720, 1920x1080, 800x1333, cycled).  A timed pass is `inf(images, batch_size=B)` over all 32
+images and ends with their detections on the host as Python lists, so the host clock around it is the user's latency;
+each figure is the best of --repeats passes after one warm-up pass.  fp16 at batch_size 1 is the per-image path
+(preprocess_image, F.pad, batched_nms, per-image syncs); every other cell is the batched path (one upload, one
+preprocess_batch launch, one forward, one postprocess_detections launch, one download per chunk).
+
+Kernel times: unless --no-profile, a child process runs the same Inferencer calls (batch 8 over 16 images in fp16 and
+bf16, batch 1 over 4 images in fp16) under `rocprofv3 --kernel-trace --stats`; the per-launch times of the pre- and
+post-processing kernels are read from its kernel statistics.
+
+    python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile]      -> one JSON line
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (ROOT, os.path.join(ROOT, "co-detr-tensorrt_amd"), os.path.join(ROOT, "oracle")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+DEV = "cuda:0"
+SIZES_WH = [(640, 480), (1280, 720), (1920, 1080), (800, 1333)]
+DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
+KERNELS = ("preprocess_batch_kernel", "postprocess_kernel", "preprocess_kernel", "batched_nms_kernel")
+
+
+def synthetic_images(n, seed=0):
+    rng = np.random.default_rng(seed)
+    return [rng.integers(0, 256, (SIZES_WH[i % 4][1], SIZES_WH[i % 4][0], 3), dtype=np.uint8) for i in range(n)]
+
+
+def inferencers():
+    """one Inferencer per dtype over copies of one seeded random-init Swin-L model"""
+    import copy
+
+    import bench
+    import codetr
+    from codetr.inferencer import Inferencer
+
+    torch.manual_seed(42)
+    base = codetr.build_CoDETR(bench.CFG, None, "cpu")
+    base.init_weights()
+    bench.set_offset_noise(base, 2.0, 42)
+    out = {}
+    for name, dt in DTYPES.items():
+        model = copy.deepcopy(base).to(device=DEV, dtype=dt).eval()
+        out[name] = Inferencer(model, bench.CFG, dataset_meta=None)
+    return out
+
+
+def child(n_batch=16, n_single=4):
+    """the workload traced by rocprofv3"""
+    images = synthetic_images(n_batch, seed=1)
+    for name, inf in inferencers().items():
+        inf(images[:8], device=DEV, dtype=DTYPES[name], batch_size=8)   # warm-up
+        inf(images, device=DEV, dtype=DTYPES[name], batch_size=8)
+        if name == "fp16":
+            inf(images[:n_single], device=DEV, dtype=torch.float16, batch_size=1)
+    torch.cuda.synchronize()
+
+
+def _kernel_key(name):
+    """'postprocess_kernel<bf16>' etc. for the kernels of csrc/prepost.hip (demangled or mangled names), else None"""
+    base = next((k for k in KERNELS if k in name), None)   # (KERNELS lists preprocess_batch_kernel first)
+    if base is None or base == "batched_nms_kernel":
+        return base
+    dt = "bf16" if "Bf16" in name else "f16" if ("_Float16" in name or "DF16_" in name) else "f32"
+    return f"{base}<{dt}>"
+
+
+def profile(timeout_s=900):
+    """run `child()` under rocprofv3 and fold its kernel statistics for the four pre / post kernels"""
+    rocprof = shutil.which("rocprofv3")
+    if rocprof is None:
+        return {"error": "rocprofv3 not found"}
+    out_dir = tempfile.mkdtemp(prefix="bench_inferencer_prof_")
+    try:
+        cmd = [rocprof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", out_dir, "--",
+               sys.executable, os.path.abspath(__file__), "--child"]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=timeout_s)
+        stats = glob.glob(os.path.join(out_dir, "**", "*kernel_stats.csv"), recursive=True)
+        if r.returncode != 0 or not stats:
+            return {"error": f"rocprofv3 run failed (exit {r.returncode})", "tail": r.stdout[-2000:]}
+        folded = {}
+        for row in csv.DictReader(open(stats[0])):
+            key = _kernel_key(row["Name"])
+            if key is None:
+                continue
+            f = folded.setdefault(key, {"calls": 0, "total_us": 0.0})
+            f["calls"] += int(row["Calls"])
+            f["total_us"] += float(row["TotalDurationNs"]) / 1e3
+        for f in folded.values():
+            f["avg_us"] = round(f["total_us"] / max(1, f["calls"]), 2)
+            f["total_us"] = round(f["total_us"], 2)
+        return {"command": "rocprofv3 --kernel-trace --stats -- python tools/bench_inferencer.py --child",
+                "workload": "per dtype: batch_size 8 over 16 images (+ one 8-image warm-up call); fp16 also batch_size 1 "
+                            "over 4 images", "kernels": folded}
+    finally:
+        shutil.rmtree(out_dir, ignore_errors=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=32)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--batch-sizes", default="1,4,8")
+    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_inferencer: needs a GPU")
+    if a.child:
+        child()
+        return
+    images = synthetic_images(a.images)
+    bss = [int(v) for v in a.batch_sizes.split(",")]
+    res = {}
+    for name, inf in inferencers().items():
+        dt = DTYPES[name]
+        res[name] = {}
+        for bs in bss:
+            with torch.no_grad():
+                inf(images[:max(8, bs)], device=DEV, dtype=dt, batch_size=bs)   # warm-up: kernels, allocator, shapes
+                best = None
+                for _ in range(a.repeats):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = inf(images, device=DEV, dtype=dt, batch_size=bs)
+                    dt_s = time.perf_counter() - t0   # (ends with the detections on the host: no sync needed)
+                    best = dt_s if best is None else min(best, dt_s)
+            assert len(out["predictions"]) == len(images)
+            res[name][f"batch_size_{bs}"] = round(len(images) / best, 2)
+            print(f"[bench_inferencer] {name} batch_size {bs}: {res[name][f'batch_size_{bs}']} images/s", file=sys.stderr,
+                  flush=True)
+        if 1 in bss and 8 in bss:
+            res[name]["speedup_8_vs_1"] = round(res[name]["batch_size_8"] / res[name]["batch_size_1"], 3)
+    line = {"metric": "Inferencer images/s (Swin-L config, 1152x768 pipeline, random weights)", "unit": "images/s",
+            "images": a.images, "image_sizes_wh": SIZES_WH, "repeats": a.repeats, "timing": "host clock, best pass",
+            "device": torch.cuda.get_device_name(0), "results": res}
+    if not a.no_profile:
+        line["kernel_times"] = profile()
+    print(json.dumps(line))
+
+
+if __name__ == "__main__":
+    main()
