@@ -162,7 +162,8 @@ class CoDINOHead(nn.Module):
             tmp = torch.cat((tmp[..., :2] + refs, tmp[..., 2:]), -1)
         B = tmp.shape[0]
         if capture is not None:
-            capture.update(final_state=state, final_refs_unact=refs, outputs_classes=cls, outputs_coords=hip_ops.sigmoid(tmp))
+            capture.update(final_state=state, final_refs_unact=refs, outputs_classes=cls, outputs_coords=hip_ops.sigmoid(tmp),
+                           outputs_coords_unact=tmp)
         if self.use_sigmoid:
             scores, idx = hip_ops.topk(hip_ops.sigmoid(cls).view(B, -1), self.max_per_img)
             if hip_ops.decode_boxes_supported(tmp, idx):

@@ -11,6 +11,7 @@
 //
 // Per token (b, s) of level l at (y, x):
 //   ref        = ( f16((x + .5) / f16(vr_w * W_l)),  f16((y + .5) / f16(vr_h * H_l)) )       the reference's fp16 roundings
+//                (x + .5 exact, the quotient in fp32: see the bf16 note at ld16 below)
 //   ref_lvl[k] = f16(ref * vr[b, k])                                                         k = 0..L-1
 //   prop       = f16(logit(p)),  p = (ref_x, ref_y, w, w),  w = f16(0.05 * 2^l)              logit in fp32
 //   keep       = all(-4.6 < prop < 4.6) and not padding
@@ -33,7 +34,10 @@ typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 // 16-bit storage <-> float; BF: bfloat16 (the bf16 model's instantiations: same formulas, that type's roundings and its
-// finfo.max), else fp16
+// finfo.max), else fp16.  One exception to "the reference's roundings": the pixel centre x + .5 is taken exactly (fp32).
+// The reference builds it with linspace in the model dtype, exact in fp16 up to 2048 but not in bf16 from 128 up (a .5
+// step needs 9 significant bits there), so the bf16 reference points are the exact quotient rounded once -- no further
+// from fp32 than the ATen bf16 formulation, and not bit-equal to it on wide levels.
 template <bool BF>
 __device__ __forceinline__ float ld16(unsigned short bits) {
   if (BF) return __uint_as_float(((unsigned)bits) << 16);

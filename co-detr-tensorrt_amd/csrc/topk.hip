@@ -5,8 +5,8 @@
 //
 // Order: descending value, ties by ascending index, NaN first (torch.topk's NaN rule; its tie order is unspecified).
 // Every element gets a unique 40-bit composite  C = key16 << 24 | (2^24 - 1 - index), key16 = the order-preserving
-// integer image of the 16-bit float (NaN -> 0xFFFF): the k largest composites ARE the answer, there is no tie to
-// break.
+// integer image of the 16-bit float (NaN -> 0xFFFF, -0 and +0 -> the same 0x8000): the k largest composites ARE the
+// answer, there is no tie to break.
 //   * rows of up to 204 800 elements (the model's sizes): every thread owns a contiguous share of the row and sweeps
 //     it four times with 16-byte loads (the row stays in L2): two 256-bin histogram rounds give the 16-bit threshold
 //     value (run-length flushing: scores cluster in a few bins), a block scan over (greater, tied) counts places the
@@ -27,6 +27,7 @@ template <bool BF>
 __device__ __forceinline__ unsigned key16(unsigned short bits) {
   const unsigned mag = bits & 0x7fffu;
   if (mag > (BF ? 0x7f80u : 0x7c00u)) return 0xffffu;  // NaN sorts above everything
+  if (mag == 0) return 0x8000u;                         // -0 == +0: equal values, ordered by index like any tie
   return (bits & 0x8000u) ? (~(unsigned)bits & 0xffffu) : ((unsigned)bits | 0x8000u);
 }
 

@@ -638,7 +638,11 @@ int codetr_query_sine_embed_bf16(void *stream, const void *ref_dev, const void *
  *   valid_ratios_dev        [B, L, 2] f16 (w, h)
  *   mask_flat_dev           [B, S] uint8, non-zero = padding (codetr_mask_pyramid's output)
  *   level_shapes_host       HOST array of 2*L int64 (H_l, W_l)
- *   reference_points_dev    out [B, S, 2] f16 (x, y), the reference's own fp16 roundings
+ *   reference_points_dev    out [B, S, 2] f16 (x, y), the reference's own fp16 roundings: (x + .5) / f16(vr_w W_l)
+ *                           rounded once.  The pixel centre x + .5 is exact (fp32); in fp16 so is the reference's
+ *                           linspace up to 2048, but bf16 cannot hold a .5 centre from 128 up, so the bf16 twin is
+ *                           NOT bit-equal to ATen's bf16 linspace formulation: it is the exact quotient rounded once,
+ *                           never further from the fp32 result than that formulation.
  *   reference_by_level_dev  out [B, S, L, 2] f16
  *   proposals_dev           out [B, S, 4] f16: logit of (x, y, 0.05*2^l, 0.05*2^l) where the token is kept,
  *                           finfo(f16).max (NaN where the logit is not finite) where it is dropped

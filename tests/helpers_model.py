@@ -149,7 +149,7 @@ def valid_topk(enc_cls, enc_coord, k, bound=None):
     return torch.topk(score, k, dim=1)[1]
 
 
-def unmatched_detections(own, expected, score_tol=2e-6, box_tol=1e-3, tie_gap=1e-5):
+def unmatched_detections(own, expected, score_tol=2e-6, box_tol=1e-3, tie_gap=1e-5, stats=None):
     """Detections of `expected` = (boxes [K,4], scores [K], labels [K]) that `own` (same layout) does not contain.
 
     Both sides are top-k selections over the same kind of score table, possibly evaluated by different devices
@@ -157,7 +157,8 @@ def unmatched_detections(own, expected, score_tol=2e-6, box_tol=1e-3, tie_gap=1e
     score_tol, |box diff| <= box_tol pixels -- never by rounding to a grid (a value next to a rounding boundary
     would land in different cells on the two sides).  Expected detections whose score lies within `tie_gap` of
     another expected score or of the selection threshold are skipped: WHICH member of a (near-)tie wins the top-k is
-    implementation-defined.  Non-finite rows (padded proposals, see valid_topk) are skipped on both sides."""
+    implementation-defined.  Non-finite rows (padded proposals, see valid_topk) are skipped on both sides.
+    `stats` (a dict, optional) receives "checked": how many expected detections were looked for."""
     import torch
 
     ob, os_, ol = (torch.as_tensor(t).detach().cpu() for t in own)
@@ -167,7 +168,7 @@ def unmatched_detections(own, expected, score_tol=2e-6, box_tol=1e-3, tie_gap=1e
     ok_e = torch.isfinite(eb).all(-1) & torch.isfinite(es)
     fin = es[ok_e]
     thresh = fin.min() if fin.numel() else torch.tensor(0.0, dtype=torch.float64)
-    missing = []
+    missing, checked = [], 0
     for i in range(es.shape[0]):
         if not ok_e[i]:
             continue
@@ -175,9 +176,12 @@ def unmatched_detections(own, expected, score_tol=2e-6, box_tol=1e-3, tie_gap=1e
         gap[i] = float("inf")
         if gap[ok_e].min() <= tie_gap or es[i] - thresh <= tie_gap:
             continue
+        checked += 1
         hit = ok_o & (ol == el[i]) & ((os_ - es[i]).abs() <= score_tol) & ((ob - eb[i]).abs().max(-1)[0] <= box_tol)
         if not bool(hit.any()):
             missing.append((float(es[i]), int(el[i]), [float(v) for v in eb[i]]))
+    if stats is not None:
+        stats["checked"] = checked
     return missing
 
 
@@ -222,3 +226,89 @@ def detection_agreement(cap, cap_o, Himg, Wimg):
     return {"box_err_px_mean": float(db[fin].mean()), "box_err_px_p95": float(db[fin].quantile(0.95)),
             "score_err_mean": float(ds.mean()), "score_err_p95": float(ds.flatten()[::7].quantile(0.95)),
             "top300_pairs_in_common": common}
+
+
+# ---- 16-bit detections against float64 -------------------------------------------------------------------------------
+UNIT_ROUNDOFF = {torch.float16: 2.0 ** -11, torch.bfloat16: 2.0 ** -8}
+
+
+def decode64(coords_unact, idx, num_classes, scale_w, scale_h):
+    """The head's decode in float64 on the kept (query, class) indices: sigmoid, cxcywh -> xyxy, x (W, H, W, H), clamp
+    to [0, W] x [0, H] -> (boxes [B,K,4], error scale [B,K,4]).  A 16-bit decode that rounds the sigmoid, c -+ w/2 and
+    the product with the (rounded) scale errs per coordinate by at most u * scale * (c + w/2 + 2 |c -+ w/2|) to first
+    order: that bracket is the returned error scale (clamping is 1-Lipschitz)."""
+    q = idx // num_classes
+    c = torch.gather(torch.sigmoid(coords_unact.double()), 1, q[..., None].expand(-1, -1, 4))
+    cx, cy, w, h = c.unbind(-1)
+    v = torch.stack((cx - 0.5 * w, cy - 0.5 * h, cx + 0.5 * w, cy + 0.5 * h), -1)
+    scale = v.new_tensor([scale_w, scale_h, scale_w, scale_h])
+    box = torch.minimum((v * scale).clamp(min=0), scale)
+    mag = torch.stack((cx + 0.5 * w, cy + 0.5 * h, cx + 0.5 * w, cy + 0.5 * h), -1) + 2 * v.abs()
+    return box, scale * mag
+
+
+def check_16bit_detections(dets, cap, Himg, Wimg, num_classes=80):
+    """Decode consistency of a 16-bit forward: (boxes, scores, labels) re-derived from the product's own captured class
+    logits and pre-sigmoid coordinates (cap["outputs_classes"], cap["outputs_coords_unact"]).
+
+    1. Exact pipeline: the head ranks its own rounded scores (hip_ops.sigmoid, itself tested against float64) in stable
+       descending order, so labels and scores are pinned bit for bit, ties included; the boxes of those picks are
+       within the decode's rounding (decode64) of float64.
+    2. float64 oracle (codetr_fp32.decode_detections on the same logits / coordinates): the sorted scores are the
+       float64 top-K rounded once (rounding is monotone; fp32 sigmoid adds <= 2^-21), and every float64 detection that
+       is not within two roundings of another one or of the threshold is among the product's outputs.
+    Returns the number of float64 detections that part 2 matched one by one."""
+    import codetr_fp32 as M
+    from codetr import _cabi, hip_ops
+
+    boxes, scores, labels = dets
+    cls, unact = cap["outputs_classes"], cap["outputs_coords_unact"]
+    dtype = cls.dtype
+    u = UNIT_ROUNDOFF[dtype]
+    B, Nq, C = cls.shape
+    K = scores.shape[-1]
+    assert C == num_classes and boxes.dtype == scores.dtype == dtype
+    sw, sh = (float(torch.tensor(float(v)).to(dtype)) for v in (Wimg, Himg))   # the kernel's scale: the model dtype
+    # 1. the product's own ranking: the head's native sigmoid kernel (it serves inference only, so grad mode would
+    # silently route hip_ops.sigmoid to ATen, whose fp32 exp may differ in the last bit and reorder a tie group)
+    before = _cabi.CALLS["small_ops"]
+    with torch.no_grad():
+        s16 = hip_ops.sigmoid(cls).view(B, -1)
+    assert _cabi.CALLS["small_ops"] == before + 1, "the scores were not recomputed by the native sigmoid kernel"
+    sd = s16.double()
+    key = torch.where(sd.isnan(), torch.full_like(sd, float("inf")), sd)
+    idx = torch.sort(key, dim=-1, descending=True, stable=True)[1][:, :K]
+    assert torch.equal(labels, idx % C), "labels are not those of the stable descending order of the scores"
+    assert torch.equal(scores.view(torch.int16), torch.gather(s16, 1, idx).view(torch.int16))
+    exact, mag = decode64(unact, idx, C, sw, sh)
+    assert torch.equal(boxes.isnan(), exact.isnan())
+    fin = ~exact.isnan()
+    err = (boxes.double() - exact).abs()[fin]
+    assert (err <= u * (1 + 4 * u) * mag[fin] + 1e-30).all(), f"box error {float(err.max()):.3e} px"
+    # 2. float64 decode of the same logits and coordinates
+    bx, sc, lb = M.decode_detections(cls.double().cpu(), torch.sigmoid(unact.double()).cpu(), sh, sw, K, C)
+    sc_tol = u + 2.0 ** -21
+    got = scores.double().cpu()
+    assert torch.equal(got.isnan(), sc.isnan()), "NaN scores (NaN logits rank first) differ from the float64 decode"
+    fin = ~sc.isnan()
+    assert ((got - sc).abs()[fin] <= sc_tol * sc.abs()[fin]).all(), "sorted scores differ from the float64 top-K rounded once"
+    box_tol = 5 * u * max(sw, sh)    # u * scale * (c + w/2 + 2 |v|) (1 + 4u), the bracket <= 1 + 0.5 + 3
+    matched = 0
+    for bi in range(B):
+        stats = {}
+        missing = unmatched_detections((boxes[bi], scores[bi], labels[bi]), (bx[bi], sc[bi], lb[bi]),
+                                       score_tol=sc_tol, box_tol=box_tol, tie_gap=2 * sc_tol, stats=stats)
+        assert not missing, f"image {bi}: float64 detections missing from the product's output: {missing}"
+        matched += stats["checked"]
+    return matched
+
+
+def check_two_stage_selection(cap):
+    """the unforced two-stage selection: topk_indices is the stable descending order (NaN first) of the row max of the
+    product's own enc_outputs_class (a selection: exact)"""
+    enc = cap["enc_outputs_class"]
+    k = cap["topk_indices"].shape[-1]
+    m = enc.double().max(-1)[0]
+    key = torch.where(m.isnan(), torch.full_like(m, float("inf")), m)
+    order = torch.sort(key, dim=-1, descending=True, stable=True)[1][:, :k]
+    assert torch.equal(cap["topk_indices"], order), "two-stage top-k is not the stable descending order of the row max"

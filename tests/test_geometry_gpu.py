@@ -4,6 +4,7 @@
   codetr_row_max_f16           enc_outputs_class.max(-1)[0]
   codetr_query_sine_embed_f16  sigmoid x valid ratios + gen_sineembed_for_position of the decoder boxes
   codetr_linear_* row state 2  `memory * keep` folded into enc_output
+(bf16 and the float64 oracles of these kernels: tests/test_bf16_kernels_gpu.py)
 Reference points, per-level points and keep/drop states are fp16-exact restatements: bit-exact.  Proposals and sine
 embeddings are computed in fp32 and rounded once (the ATen fp16 path rounds after every op): compared against the
 fp32 evaluation of the same formula at 1 fp16 ulp."""
@@ -108,18 +109,22 @@ def test_query_sine_embed_matches_formula(B, Nq, d, L):
     assert math.isfinite(float(emb.float().abs().sum()))
 
 
-def test_linear_row_state_2_is_a_zero_input_row():
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_linear_row_state_2_is_a_zero_input_row(dtype):
     from codetr import hip_ops
 
     g = torch.Generator(device=DEV).manual_seed(8)
-    x = torch.randn(2, 300, 256, device=DEV, generator=g).half()
+    x = torch.randn(2, 300, 256, device=DEV, generator=g).to(dtype)
     for N, act in [(256, None), (256, "relu"), (5, None)]:   # row-store path, activation, ragged-N path
-        w = (torch.randn(N, 256, device=DEV, generator=g) / 16).half()
-        b = torch.randn(N, device=DEV, generator=g).half()
+        w = (torch.randn(N, 256, device=DEV, generator=g) / 16).to(dtype)
+        b = torch.randn(N, device=DEV, generator=g).to(dtype)
         state = torch.zeros(2, 300, dtype=torch.uint8, device=DEV)
         state[0, 17:90] = 2
         state[1, ::7] = 2
         y = hip_ops.linear(x, w, b, act=act, row_mask=state)
-        keep = (state == 0).unsqueeze(-1).half()
+        keep = (state == 0).unsqueeze(-1).to(dtype)
         y0 = hip_ops.linear(x * keep, w, b, act=act)
-        assert torch.equal(y, y0)
+        assert y.dtype == dtype and torch.equal(y, y0)
+        # a dropped row is the bias (after the activation) rounded to the storage type, whatever the input row held
+        b_out = torch.relu(b) if act == "relu" else b
+        assert torch.equal(y[state == 2], b_out.expand(int((state == 2).sum()), -1))

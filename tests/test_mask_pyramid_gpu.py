@@ -62,6 +62,40 @@ def test_mask_pyramid_matches_aten(B, H, W, kind):
     assert torch.equal(flat2, rflat)
 
 
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+@pytest.mark.parametrize("B,H,W,kind", [(2, 1280, 1920, "padded"), (2, 333, 517, "random")])
+def test_mask_pyramid_16bit_mask_matches_fp32_reference(dtype, B, H, W, kind):
+    """the 16-bit mask every fp16 / bf16 model passes (2-byte elements): -0.0 reads as "not padding", NaN and any other
+    non-zero value as padding, exactly as the fp32 mask's `!= 0` -- integer work: bit-exact against the fp32 reference"""
+    from codetr import hip_ops
+
+    g = torch.Generator(device=DEV).manual_seed(5)
+    if kind == "random":
+        img = (torch.rand(B, H, W, device=DEV, generator=g) < 0.4).float()
+    else:
+        img = torch.ones(B, H, W, device=DEV)
+        img[0, :int(H * 0.55), :int(W * 0.63)] = 0
+        img[1, :, :int(W * 0.8)] = 0
+    special = torch.rand(B, H, W, device=DEV, generator=g)
+    img[special < 0.05] = -0.0
+    img[(special >= 0.05) & (special < 0.07)] = float("nan")
+    img[(special >= 0.07) & (special < 0.08)] = -2.5
+    img[(special >= 0.08) & (special < 0.09)] = 0.5
+    img[0, :8, :8] = -0.0          # whole source cells: sampled by every level
+    img[1, :8, :8] = float("nan")
+    assert (img.view(torch.int32) == -0x80000000).any()
+    shapes = _pyramid_shapes(H, W)
+    flat, ycum, xcum, counts = hip_ops.mask_pyramid(img.to(dtype), shapes)
+    rflat, rycum, rxcum, rcounts = _reference(img, shapes)
+    assert torch.equal(flat, rflat) and torch.equal(counts, rcounts)
+    assert not bool(flat[0, 0]) and bool(flat[1, 0])
+    start = 0
+    for lvl, hw in enumerate(shapes):
+        y, x = hip_ops.level_cums(ycum, xcum, B, start, hw)
+        assert torch.equal(y, rycum[lvl]) and torch.equal(x, rxcum[lvl]), f"level {lvl}"
+        start += hw[0] * hw[1]
+
+
 def test_mask_pyramid_rejects_bad_arguments():
     from codetr import _cabi
 

@@ -247,11 +247,67 @@ def _full_codetr_fp32_vs_oracle(backbone, hw):
         assert not missing, f"image {bi}: detections of the oracle decode missing from the product's output: {missing}"
 
 
-@pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_tiny_swin_16bit_vs_oracle(dtype):
+    """Tiny Co-DINO Swin in fp16 / bf16 against the fp32 oracle, forced top-k, padded second image.  Bounds: rel-L2
+    1e-2 of each tensor for fp16 (this module's docstring) and times 2^-8 / 2^-11 = 8 for bf16 (first order in the
+    unit roundoff); class logits 2.5x that, as for the R50 model.  Then the step after the logits, which the fp32 test
+    checks and the 16-bit path did not: the detections re-derived from the product's own logits and coordinates
+    (helpers_model.check_16bit_detections), and the unforced two-stage selection (check_two_stage_selection)."""
+    import codetr
+    from helpers_model import check_16bit_detections, check_two_stage_selection
+
+    torch.manual_seed(0)
+    model = codetr.CoDETR(**_tiny_codetr_cfg("swin"))
+    model.init_weights()
+    spec = [(k, tuple(v.shape)) for k, v in model.named_parameters()]
+    full = dict(model.state_dict())
+    full.update(seeded_params(spec, 77, scale=1.5))
+    model.load_state_dict(full)
+    model = model.to(DEV).to(dtype).eval()
+    H, W = 76, 100
+    g = torch.Generator().manual_seed(1)
+    img = torch.randn(2, 3, H, W, generator=g)
+    mask = torch.zeros(2, H, W)
+    mask[1, :, int(W * 0.8):] = 1
+    mask[1, int(H * 0.9):, :] = 1
+    # the oracle runs in fp32 on the model's 16-bit weights and input
+    full16 = {k: v.to(dtype).float() if v.is_floating_point() else v for k, v in full.items()}
+    img16 = img.to(dtype).float()
+    cap_o = {}
+    kw = dict(num_heads=(1, 2, 4, 8), window_size=4)
+    M.codetr_forward(full16, img16, mask, backbone="swin", num_query=50, max_per_img=20, capture=cap_o, **kw)
+    picks = valid_topk(cap_o["enc_outputs_class"], cap_o["enc_outputs_coord_unact"], 50)
+    M.codetr_forward(full16, img16, mask, backbone="swin", num_query=50, max_per_img=20, forced_topk=picks, capture=cap_o,
+                     **kw)
+    cap = {}
+    with torch.no_grad():
+        dets = model(img.to(DEV).to(dtype), mask.to(DEV).to(dtype), forced_topk_indices=cap_o["topk_indices"].to(DEV),
+                     capture=cap)
+    rel = 1e-2 * (8.0 if dtype == torch.bfloat16 else 1.0)
+    for i, (a, b) in enumerate(zip(cap["backbone_feats"], cap_o["backbone_feats"])):
+        assert_close_lowp(a.float().cpu().numpy(), b.numpy(), rel, None, f"backbone level {i}")
+    for i, (a, b) in enumerate(zip(cap["neck_feats"], cap_o["neck_feats"])):
+        assert_close_lowp(a.float().cpu().numpy(), b.numpy(), rel, None, f"neck level {i}")
+    assert_close_lowp(cap["memory"].float().cpu().numpy(), cap_o["memory"].numpy(), rel, None, "encoder memory")
+    assert_close_lowp(cap["outputs_classes"].float().cpu().numpy(), cap_o["outputs_classes"].numpy(), 2.5 * rel, None,
+                      "class logits")
+    boxes, scores, labels = dets
+    assert boxes.shape == (2, 20, 4) and scores.shape == (2, 20) and labels.dtype == torch.int64
+    check_16bit_detections(dets, cap, H, W)
+    cap2 = {}
+    with torch.no_grad():
+        dets2 = model(img.to(DEV).to(dtype), mask.to(DEV).to(dtype), capture=cap2)
+    check_two_stage_selection(cap2)
+    check_16bit_detections(dets2, cap2, H, W)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float16, torch.bfloat16])
 def test_forward_is_bit_stable_with_poisoned_allocator(dtype):
     """The same inputs 8 times with every torch.empty handing out NaNs (helpers_model.poison_allocator): every captured
     stage and the detections are bit-identical run to run -- no race, no atomics, no read of unwritten workspace on the
-    inference path (fp32: ATen GEMMs + the native mask-pyramid / MSDA f32 kernels; fp16: the hand-written kernels)."""
+    inference path (fp32: ATen GEMMs + the native mask-pyramid / MSDA f32 kernels; fp16: the hand-written kernels;
+    bf16: their bf16 instantiations and the bf16-only ones, linear_bf16_f16out and decoder_layer_bf16)."""
     import codetr
     from helpers_model import poison_allocator
 

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 import codetr_fp32 as M
 import fullsize_cases as FC
 from conftest import ROOT
-from helpers_model import assert_close_lowp, seeded_params, valid_topk
+from helpers_model import assert_close_lowp, check_16bit_detections, seeded_params, valid_topk
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -256,6 +256,9 @@ def test_tiny_r50_16bit_token_route_vs_oracle(hw, dtype):
     assert_close_lowp(cap["outputs_classes"].float().cpu().numpy(), cap_o["outputs_classes"].numpy(), 2.5 * rel, None,
                       "class logits")
     assert boxes.shape == (2, 20, 4) and scores.shape == (2, 20) and labels.dtype == torch.int64
+    # the detections against float64 re-derived from the product's own logits and coordinates (sigmoid -> topk ->
+    # decode_boxes at the kernels' rounding; see helpers_model.check_16bit_detections)
+    check_16bit_detections((boxes, scores, labels), cap, H, W)
 
 
 def test_tiny_r50_fp32_keeps_the_nchw_route_bit_for_bit():

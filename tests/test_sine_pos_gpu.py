@@ -45,6 +45,27 @@ def test_sine_pos_tokens_vs_module_fp32(H, W, normalize):
     torch.testing.assert_close(dest.float(), ref, rtol=0, atol=tol)
 
 
+@pytest.mark.parametrize("H,W,normalize", [(1, 1, True), (20, 30, True), (33, 17, False), (320, 480, True)])
+def test_sine_pos_tokens_bf16_vs_module_fp32(H, W, normalize):
+    """bf16 storage against the fp32 module: the kernel's fp32 arithmetic is the fp16 instantiation's, so the fp16
+    test's absolute tolerance covers it; the only other difference is the final bf16 rounding of a value v (sin / cos +
+    the level embedding), <= 2^-8 |v|"""
+    from codetr import hip_ops
+    from codetr.positional_encoding import SinePositionalEncoding
+
+    g = torch.Generator(device=DEV).manual_seed(H + 1)
+    mask = torch.zeros(2, H, W, dtype=torch.bool, device=DEV)
+    mask[1, :, int(W * 0.7):] = True
+    mask[1, int(H * 0.8):, :] = True
+    lvl = (torch.randn(256, device=DEV, generator=g) * 0.5).bfloat16()
+    pe = SinePositionalEncoding(num_feats=128, temperature=20, normalize=normalize)
+    ref = pe.forward_tokens(mask, dtype=torch.float32) + lvl.float()
+    dest = torch.empty(2, H * W, 256, device=DEV, dtype=torch.bfloat16)
+    hip_ops.sine_pos_tokens_into(mask, dest, 0, lvl, 128, 20, pe.scale, pe.eps, pe.offset, normalize)
+    tol = 2e-3 if normalize else 2e-2   # as in the fp16 test above
+    torch.testing.assert_close(dest.float(), ref, rtol=2.0 ** -8, atol=tol)
+
+
 def test_sine_pos_tokens_bf16_matches_f16_kernel():
     """bf16 storage instantiation: same fp32 arithmetic as the f16 kernel, rounded to bf16 instead"""
     from codetr import hip_ops

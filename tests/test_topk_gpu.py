@@ -27,7 +27,8 @@ def _check(x, k):
     # documented rule and the CUDA implementation's; torch-ROCm's topk leaves sign-bit NaNs at the bottom)
     xf = x.float()
     nan = torch.isnan(xf)
-    key = torch.where(nan, torch.full_like(xf, float("inf")), xf.clamp(min=-3e38, max=3e38))   # +-inf strictly inside NaN
+    xd = xf.double()   # (float64: +-inf map to +-1e300, strictly inside NaN and strictly outside +-finfo(bf16).max)
+    key = torch.where(nan, torch.full_like(xd, float("inf")), xd.clamp(min=-1e300, max=1e300))
     order = torch.sort(key, dim=-1, descending=True, stable=True)[1][..., :k]
     assert torch.equal(i, order), "indices are not the stable descending order"
     if not nan.any():
@@ -64,6 +65,71 @@ def test_nan_inf_and_negative_values():
     x[1, 100:200] = -65504.0
     _check(x, 900)
     _check(-x.abs(), 64)
+
+
+def test_heavy_ties_like_bf16_sigmoid_scores():
+    """bf16 keeps 8 significant bits: the head's sigmoid scores take 128 values in [0.5, 1), so the top 300 of 72000
+    is a few tie groups, cut in the middle of one"""
+    g = torch.Generator(device=DEV).manual_seed(3)
+    x = torch.sigmoid(torch.randn(4, 72000, device=DEV, generator=g) * 2).bfloat16()
+    assert x.unique().numel() < 2000 and int((x >= 0.5).float().sum(-1).min()) > 300
+    _check(x, 300)
+    _check(torch.zeros(2, 5000, device=DEV, dtype=torch.bfloat16), 300)
+    _check(torch.cat((torch.zeros(1, 100, device=DEV), -torch.zeros(1, 100, device=DEV)), 1).bfloat16(), 150)
+
+
+@pytest.mark.parametrize("rows,n", [(2, 30785), (1, 204600)])
+def test_encoder_selection_shape_bf16_ties(rows, n):
+    """the two-stage selection (top 900 of the per-token scores) on bf16 logits: ties everywhere; the long row goes
+    through the chunked entry (codetr_topk_chunked_bf16)"""
+    import ctypes
+
+    from codetr import _cabi
+
+    g = torch.Generator(device=DEV).manual_seed(n)
+    x = (torch.randn(rows, n, device=DEV, generator=g) * 3).bfloat16()
+    assert x.unique().numel() < n // 10
+    ws = ctypes.c_int64(0)
+    chunks = _cabi.load().codetr_topk_chunks(n, 900, rows, ctypes.cast(ctypes.pointer(ws), ctypes.c_void_p))
+    if n == 204600:
+        assert chunks > 1, "the long row is expected to take the chunked entry"
+    _check(x, 900)
+    x[:, ::7] = x[:, :1]        # one large tie group spread over the whole row
+    _check(x, 900)
+
+
+def test_nan_inf_zero_and_extremes_bf16():
+    """NaN of both signs first (by index), +inf, finite values, +-0 as equals, -finfo(bf16).max above -inf"""
+    dt = torch.bfloat16
+    g = torch.Generator(device=DEV).manual_seed(4)
+    x = torch.randn(3, 4000, device=DEV, generator=g).to(dt)
+    x[0, 5] = float("nan")
+    x.view(torch.int16)[0, 3000] = -0x40      # bits 0xffc0: sign-bit NaN
+    x[0, 17] = float("inf")
+    x[0, 18] = torch.finfo(dt).max
+    x[1, 9] = float("-inf")
+    x[1, 100:200] = -torch.finfo(dt).max
+    x[1, 300:400:2] = -0.0                    # -0 before +0, interleaved: equal values, so ascending index decides
+    x[1, 301:400:2] = 0.0
+    x[2, :] = -torch.finfo(dt).max
+    x[2, 1000:1500] = float("-inf")
+    x.view(torch.int16)[2, 3999] = -0x40
+    assert torch.isnan(x[0, 3000]) and x[0, 3000].view(torch.int16) < 0
+    _check(x, 900)
+    _check(-x.abs(), 64)
+    _check(x[1:2, 100:400].contiguous(), 300)
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["fp16", "bf16"])
+def test_signed_zeros_are_one_value(dtype):
+    """-0 == +0: a zero group cut by k keeps its lowest indices, whichever sign comes first"""
+    z = torch.zeros(2, 200, device=DEV, dtype=dtype)
+    z[0, :100] = -0.0                          # all -0 first, then +0
+    z[1, ::2] = -0.0                           # interleaved, -0 at even indices
+    assert (z.view(torch.int16) < 0).sum() == 200
+    _check(z, 150)
+    x = torch.cat((-torch.ones(2, 50, device=DEV), z.float(), torch.ones(2, 50, device=DEV)), 1).to(dtype)
+    _check(x, 120)                             # 50 ones, then 70 of the zero group in index order
 
 
 def test_unsupported_falls_back_to_torch():
