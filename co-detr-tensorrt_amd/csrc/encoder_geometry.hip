@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -29,9 +30,6 @@ struct Levels {
   int h[kMaxLevels], w[kMaxLevels];
   int64_t start[kMaxLevels];
 };
-typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 // 16-bit storage <-> float; BF: bfloat16 (the bf16 model's instantiations: same formulas, that type's roundings and its
 // finfo.max), else fp16.  One exception to "the reference's roundings": the pixel centre x + .5 is taken exactly (fp32).
@@ -40,22 +38,11 @@ typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 // from fp32 than the ATen bf16 formulation, and not bit-equal to it on wide levels.
 template <bool BF>
 __device__ __forceinline__ float ld16(unsigned short bits) {
-  if (BF) return __uint_as_float(((unsigned)bits) << 16);
-  _Float16 h;
-  __builtin_memcpy(&h, &bits, 2);
-  return (float)h;
+  return BF ? bf16_to_f32(bits) : HalfT::to_f32(bits);
 }
 template <bool BF>
 __device__ __forceinline__ unsigned short st16(float v) {
-  if (BF) {
-    const unsigned u = __float_as_uint(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  }
-  _Float16 h = (_Float16)v;
-  unsigned short bits;
-  __builtin_memcpy(&bits, &h, 2);
-  return bits;
+  return BF ? bf16_from_f32(v) : HalfT::from_f32(v);
 }
 template <bool BF>
 __device__ __forceinline__ float h_round(float v) { return ld16<BF>(st16<BF>(v)); }

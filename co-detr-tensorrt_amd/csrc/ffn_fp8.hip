@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -48,11 +49,6 @@ __device__ unsigned long long* g_ffn8_stamps = nullptr;
 #define FFN8_T(i) do { } while (0)
 #endif
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned pk_fp8x4(float a, float b, float c, float d) {
   a = __builtin_amdgcn_fmed3f(a, -kFp8Max, kFp8Max);
@@ -69,23 +65,6 @@ __device__ __forceinline__ unsigned pk_fp8x4(float a, float b, float c, float d)
 __device__ __forceinline__ int sw128(int row) {
   const int q = (row >> 1) & 7;
   return q ^ ((q & 2) << 1);
-}
-
-// one LDS-DMA piece: 256 threads x 16 B = 4 KiB.  `src` is wave-uniform (kernel argument + scalar offsets), `voff` the
-// thread's byte offset, the same for every piece of an operand -- so a piece costs no vector arithmetic; `dst` uniform.
-// Issued as inline assembly, not through __builtin_amdgcn_global_load_lds: the compiler's wait-count pass files the
-// builtin with the out-of-order LDS traffic and from then on turns every wait for a ds_read into lgkmcnt(0) -- each MFMA
-// group then waits for the operand reads issued just before it (for the tiles three steps ahead) and the read-ahead is
-// void.  LDS-DMA only counts in vmcnt, which this kernel waits on by hand; with the instruction opaque the compiler
-// emits counted lgkmcnt(N) waits.
-__device__ __forceinline__ void dma16(const unsigned char* src, unsigned voff, unsigned char* dst) {
-  const unsigned lds_addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)dst);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr) : "memory", "m0");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // per-output-channel constants of the epilogue, one 64-byte record per 4 channels (n = 4 i .. 4 i + 3)
@@ -127,10 +106,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
   const unsigned w1_voff = (unsigned)((tid >> 4) * C + (((tid & 15) ^ ((tid >> 4) & 15)) * 16));
   const unsigned w2_voff = (unsigned)((tid >> 3) * Hd + (((tid & 7) ^ sw128(tid >> 3)) * 16));
   auto stage_w1 = [&](int p, int c, unsigned char* dst) {
-    dma16(W1q + (size_t)c * kW1Bytes + p * 4096, w1_voff, dst + (p * kThreads + wave * 64) * 16);
+    lds_dma16(W1q + (size_t)c * kW1Bytes + p * 4096, w1_voff, dst + (p * kThreads + wave * 64) * 16);
   };
   auto stage_w2 = [&](int q, int c, unsigned char* dst) {
-    dma16(W2q + (size_t)q * 32 * Hd + c * BH, w2_voff, dst + (q * kThreads + wave * 64) * 16);
+    lds_dma16(W2q + (size_t)q * 32 * Hd + c * BH, w2_voff, dst + (q * kThreads + wave * 64) * 16);
   };
 #pragma unroll
   for (int p = 0; p < 8; ++p) stage_w1(p, 0, ringA);
@@ -500,7 +479,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 #ifdef FFN8_STAMPS
   FFN8_T(5);
   if (tid == 0 && g_ffn8_stamps) {

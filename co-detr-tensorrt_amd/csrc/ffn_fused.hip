@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 // diagnostic builds only (tools/micro/ffn_ablate.hip -DCODETR_FFN_ABL=mask; WRONG results by construction, never shipped):
 // 1 = no LDS-DMA inside the chunk loop, 2 = no MFMAs, 4 = no W fragment reads inside the chunk loop, 8 = no waits / barriers in the
@@ -51,56 +52,6 @@ constexpr int kW2Bytes = C * BH * 2;   // 32 KiB: [256 n][64 h]
 constexpr int kStageBytes = kW1Bytes + kW2Bytes;
 constexpr int kMaxHidden = 8192;       // b1 lives in LDS behind the two stages (16 KiB)
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
-// element types: fp16 / bf16 storage, fp32 accumulation on the matrix cores either way
-struct F16E {
-  using e = _Float16;
-  using v8 = f16x8;
-  using v4 = f16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  // v_pk_max_f16: one op per two values
-  __device__ static v8 relu(v8 x) {
-    const v8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    return __builtin_elementwise_max(x, z);
-  }
-};
-struct BF16E {
-  using e = __bf16;
-  using v8 = bf16x8;
-  using v4 = bf16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-  // sign-magnitude 16-bit floats order like int16 on the non-negative side: v_pk_max_i16(x, 0) is ReLU (-0 -> +0)
-  __device__ static v8 relu(v8 x) {
-    s16x8 i;
-    __builtin_memcpy(&i, &x, 16);
-    const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    i = __builtin_elementwise_max(i, z);
-    __builtin_memcpy(&x, &i, 16);
-    return x;
-  }
-};
-
-// one LDS-DMA piece: 256 threads x 16 B = 4 KiB.  `src` is wave-uniform (kernel argument + scalar offsets), `voff` the
-// thread's byte offset, `dst` the wave's uniform LDS destination.  Inline assembly, not __builtin_amdgcn_global_load_lds:
-// the compiler's wait-count pass files the builtin with out-of-order LDS traffic and from then on turns every wait for a
-// ds_read into lgkmcnt(0), which voids the fragment read-ahead; the instruction only counts in vmcnt, which this kernel
-// waits on by hand (see ffn_fp8.hip).
-__device__ __forceinline__ void dma16(const unsigned char* src, unsigned voff, unsigned char* dst) {
-  const unsigned lds_addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)dst);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // Persistent: gridDim.x workgroups (one per CU) walk the 128-row tiles blockIdx.x, + gridDim.x, ...; the W ring keeps
 // streaming across tiles (every tile reads the same W), the next tile's rows are requested at the start of the
@@ -129,8 +80,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     const unsigned short* __restrict__ ID = nullptr) {
   // [W1 stage 0 | W1 stage 1 | W2 stage 0 | W2 stage 1 | b1 | LayerNorm gamma, beta | b2 | bo]: 146 KiB, one object
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * kStageBytes + kMaxHidden * 2 + 2048];
-  using E = typename ET::e;
-  using V8 = typename ET::v8;
+  using E = typename ET::elem;
+  using V8 = typename ET::frag;
   using V4 = typename ET::v4;
   constexpr int MT = MTT, WR = 16 * MT, TR = 4 * WR;   // 16-row tiles / rows per wave / rows per workgroup
   const int tid = threadIdx.x, lane = tid & 63;
@@ -157,13 +108,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
   const unsigned char* W2b = reinterpret_cast<const unsigned char*>(W2);
   const unsigned char* Wob = reinterpret_cast<const unsigned char*>(Wo);
   auto stage_w1 = [&](int p, int c, unsigned char* dst) {
-    dma16(W1b + (size_t)c * kW1Bytes + p * 4096, w1_voff[p & 1], dst + (p * kThreads + wave * 64) * 16);
+    lds_dma16(W1b + (size_t)c * kW1Bytes + p * 4096, w1_voff[p & 1], dst + (p * kThreads + wave * 64) * 16);
   };
   auto stage_wo = [&](int p, int c, unsigned char* dst) {   // chunk c of Wo: rows 64 c .. + 63, the W1 chunk geometry
-    dma16(Wob + (size_t)c * kW1Bytes + p * 4096, w1_voff[p & 1], dst + (p * kThreads + wave * 64) * 16);
+    lds_dma16(Wob + (size_t)c * kW1Bytes + p * 4096, w1_voff[p & 1], dst + (p * kThreads + wave * 64) * 16);
   };
   auto stage_w2 = [&](int q, int c, unsigned char* dst) {
-    dma16(W2b + (size_t)q * 64 * Hd + c * (BH * 2), w2_voff, dst + (q * kThreads + wave * 64) * 16);
+    lds_dma16(W2b + (size_t)q * 64 * Hd + c * (BH * 2), w2_voff, dst + (q * kThreads + wave * 64) * 16);
   };
 #pragma unroll
   for (int p = 0; p < 8; ++p) {
@@ -438,7 +389,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
       for (int ks = 0; ks < 8; ++ks) {
         if (ks + 1 < 8 && !(CODETR_FFN_ABL_MASK & 4)) read_w1(ks + 1, aw[(ks + 1) & 1]);
         // (OPROJ: the next tile starts with product 0 -- the source is a scalar select, no branch inside the schedule)
-        if (!(CODETR_FFN_ABL_MASK & 1)) dma16(nsrc1 + ks * 4096, w1_voff[ks & 1], nW1 + (ks * kThreads + wave * 64) * 16);
+        if (!(CODETR_FFN_ABL_MASK & 1)) lds_dma16(nsrc1 + ks * 4096, w1_voff[ks & 1], nW1 + (ks * kThreads + wave * 64) * 16);
 #pragma unroll
         for (int i = 0; i < 4 * MT; ++i)
           if (!(CODETR_FFN_ABL_MASK & 2))
@@ -619,7 +570,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
       }
     }
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
 }
 
 // W2 [256, hidden] -> same shape with the columns of every 64-block reordered to MFMA k-slot order:
@@ -719,7 +670,7 @@ int codetr_ffn_relu_ln2_f16(void* stream, const void* x_dev, const void* w1_dev,
                             int64_t hidden, const void* ln_in_gamma_dev, const void* ln_in_beta_dev, float ln_in_eps,
                             const void* ln_gamma_dev, const void* ln_beta_dev, float ln_eps, const void* pos_dev,
                             void* y_plus_pos_dev) {
-  return ffn_entry<F16E>(stream, x_dev, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden, ln_in_gamma_dev,
+  return ffn_entry<HalfT>(stream, x_dev, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden, ln_in_gamma_dev,
                          ln_in_beta_dev, ln_in_eps, ln_gamma_dev, ln_beta_dev, ln_eps, pos_dev, y_plus_pos_dev);
 }
 
@@ -728,7 +679,7 @@ int codetr_ffn_relu_ln2_bf16(void* stream, const void* x_dev, const void* w1_dev
                             int64_t hidden, const void* ln_in_gamma_dev, const void* ln_in_beta_dev, float ln_in_eps,
                             const void* ln_gamma_dev, const void* ln_beta_dev, float ln_eps, const void* pos_dev,
                             void* y_plus_pos_dev) {
-  return ffn_entry<BF16E>(stream, x_dev, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden, ln_in_gamma_dev,
+  return ffn_entry<BFloatT>(stream, x_dev, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden, ln_in_gamma_dev,
                          ln_in_beta_dev, ln_in_eps, ln_gamma_dev, ln_beta_dev, ln_eps, pos_dev, y_plus_pos_dev);
 }
 
@@ -739,7 +690,7 @@ int codetr_ffn_oproj_relu_ln2_f16(void* stream, const void* attn_dev, const void
                                   const void* ln_gamma_dev, const void* ln_beta_dev, float ln_eps, const void* pos_dev,
                                   void* y_plus_pos_dev) {
   if (!wo_dev) return CODETR_E_BADARG;
-  return ffn_entry<F16E>(stream, attn_dev, w1_perm_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden, ln_in_gamma_dev,
+  return ffn_entry<HalfT>(stream, attn_dev, w1_perm_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden, ln_in_gamma_dev,
                          ln_in_beta_dev, ln_in_eps, ln_gamma_dev, ln_beta_dev, ln_eps, pos_dev, y_plus_pos_dev, wo_dev, bo_dev,
                          identity_dev);
 }
@@ -751,7 +702,7 @@ int codetr_ffn_oproj_relu_ln2_bf16(void* stream, const void* attn_dev, const voi
                                    const void* ln_gamma_dev, const void* ln_beta_dev, float ln_eps, const void* pos_dev,
                                    void* y_plus_pos_dev) {
   if (!wo_dev) return CODETR_E_BADARG;
-  return ffn_entry<BF16E>(stream, attn_dev, w1_perm_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden,
+  return ffn_entry<BFloatT>(stream, attn_dev, w1_perm_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C_in, hidden,
                           ln_in_gamma_dev, ln_in_beta_dev, ln_in_eps, ln_gamma_dev, ln_beta_dev, ln_eps, pos_dev,
                           y_plus_pos_dev, wo_dev, bo_dev, identity_dev);
 }

@@ -11,9 +11,9 @@
 //   * one 256-thread workgroup (4 waves, 2x2) owns a 128(M) x 128(N) output tile; each wave a
 //     64x64 quadrant = 4x4 MFMA tiles of 16x16, K-step 64 (2 MFMAs deep per tile).
 //   * both operands are K-contiguous (X rows, W rows), so both tiles are staged the same way:
-//     global -> LDS with 16-byte LDS-DMA (global_load_lds_dwordx4, no VGPR round trip) into a ring
+//     global -> LDS with 16-byte LDS-DMA (lds_dma16, no VGPR round trip) into a ring
 //     of 2-4 LDS buffers; up to 3 K-tiles stay in flight across the one raw s_barrier per K step
-//     (counted s_waitcnt vmcnt), 64 KiB of LDS in every configuration -> 2 workgroups per CU.
+//     (counted wait_vmcnt), 64 KiB of LDS in every configuration -> 2 workgroups per CU.
 //   * LDS image = [128 rows][8 x 16-B chunks]; the DMA destination is lane-linear, so the
 //     bank-conflict swizzle is applied on the SOURCE address and undone on the fragment read:
 //     chunk position = chunk ^ ((row >> 1) & 7)  -> the 16 rows of a ds_read_b128 lane group
@@ -33,6 +33,7 @@
 #include <stdlib.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -41,74 +42,6 @@ constexpr int kThreads = 256;
 constexpr int kStagePitch = 64 * 2 + 16;            // epilogue staging: bytes per staged row of a wave's 64x64 quadrant
 constexpr int kStagingBytes = 4 * 64 * kStagePitch;  // 36,864 B for the 4 waves
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct HalfT {
-  using frag = f16x8;
-  using elem = _Float16;
-  __device__ static s16x4 pack4(const float (&v)[4]) {  // 2 x v_cvt_pk_f16_f32 (round-to-nearest-even)
-    f16x4 h = {(_Float16)v[0], (_Float16)v[1], (_Float16)v[2], (_Float16)v[3]};
-    s16x4 o;
-    __builtin_memcpy(&o, &h, 8);
-    return o;
-  }
-  __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-  __device__ static float to_f32(unsigned short bits) {
-    _Float16 h;
-    __builtin_memcpy(&h, &bits, 2);
-    return (float)h;
-  }
-  __device__ static unsigned short from_f32(float v) {
-    _Float16 h = (_Float16)v;
-    unsigned short bits;
-    __builtin_memcpy(&bits, &h, 2);
-    return bits;
-  }
-};
-struct BFloatT {
-  using frag = bf16x8;
-  using elem = __bf16;
-  // fp32 -> bf16 on the hardware converter (v_cvt_pk_bf16_f32, round to nearest even, NaN stays quiet): the 5-instruction
-  // integer rounding of rounds 1-4 made every bf16 epilogue ~30 vector instructions per 4 outputs longer than its fp16 twin
-  __device__ static s16x4 pack4(const float (&v)[4]) {
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-    const bf16x4v h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
-    return __builtin_bit_cast(s16x4, h);
-  }
-  __device__ static f32x4 mfma(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-  __device__ static float to_f32(unsigned short bits) { return __uint_as_float(((unsigned)bits) << 16); }
-  __device__ static unsigned short from_f32(float v) {
-    const __bf16 h = (__bf16)v;
-    return __builtin_bit_cast(unsigned short, h);
-  }
-};
-
-__device__ __forceinline__ unsigned xcd_tile(unsigned bid, unsigned nblk) {
-  const unsigned q = nblk >> 3, r = nblk & 7u, x = bid & 7u, i = bid >> 3;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
-// nn.GELU (erf form): 0.5 x (1 + erf(x / sqrt 2)).  libm's erff costs ~50 VALU ops per element and made the
-// GELU epilogues VALU-bound; erf is evaluated with Abramowitz-Stegun 7.1.26 instead
-// (|erf error| <= 1.5e-7, i.e. < 2^-22 relative on the output: three orders of magnitude below the fp16 / bf16
-// rounding of the result).
-__device__ __forceinline__ float gelu_erf(float x) {
-  // 0.5 x (1 + erf(x / sqrt 2)) = 0.5 x + |x| (0.5 - (0.5 p(t) t) exp(-x^2 / 2)),  t = 1 / (1 + 0.3275911 |x| / sqrt 2):
-  // the sign of erf folds into |x|, the halves into the coefficients -- 11 plain ops + v_rcp + v_exp (15 + 2 before)
-  const float u = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, u, 1.0f));
-  float p = fmaf(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
-  p = fmaf(p, t, 0.5f * 1.421413741f);
-  p = fmaf(p, t, 0.5f * -0.284496736f);
-  p = fmaf(p, t, 0.5f * 0.254829592f);
-  const float ez = __builtin_amdgcn_exp2f(u * u * (-0.5f * 1.4426950408889634f));
-  return fmaf(u, fmaf(-(p * t), ez, 0.5f), 0.5f * x);
-}
 
 // act 3 (ReLU after the residual, the ResNet bottleneck's relu(bn3(conv3(x)) + identity)): the accumulator leaves
 // without activation, the ReLU is applied to the sum with the residual (the same two roundings as act 0 + residual,
@@ -144,8 +77,7 @@ __device__ __forceinline__ void stage_tile(const unsigned short* __restrict__ sr
     const unsigned short* g = src + (size_t)grow * K + k0 + chunk * 8;
     // wave-uniform LDS base of this instruction; the hardware adds lane*16
     unsigned char* l = lds_tile + (q * kThreads + wave * 64) * 16;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+    lds_dma16_auto(g, l);
   }
 }
 
@@ -165,39 +97,13 @@ __device__ __forceinline__ const unsigned short* piece_src(const unsigned short*
 
 __device__ __forceinline__ void dma_piece(const unsigned short* g, unsigned char* lds_tile, int q, int wave) {
   unsigned char* l = lds_tile + (q * kThreads + wave * 64) * 16;
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+  lds_dma16_auto(g, l);
 }
 
 template <class T, int BKT>
 __device__ __forceinline__ typename T::frag read_frag(const unsigned char* lds_tile, int row, int chunk) {
   const int pos = chunk ^ sw<BKT>(row);
   return *reinterpret_cast<const typename T::frag*>(lds_tile + row * (BKT * 2) + pos * 16);
-}
-
-// one LDS-DMA piece (16 B per lane, 1 KiB per wave-instruction) with a wave-uniform source base in SGPRs and a per-thread
-// byte offset; `dst` is the wave's uniform LDS destination.  Inline assembly: the compiler's wait-count pass files
-// __builtin_amdgcn_global_load_lds with out-of-order LDS traffic and turns every later wait for a ds_read into
-// lgkmcnt(0); the instruction itself only counts in vmcnt, which the callers wait on by hand.
-__device__ __forceinline__ void lds_dma16s(const unsigned char* src, unsigned voff, unsigned char* dst) {
-  const unsigned lds_addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)dst);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr) : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt_n() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  else if constexpr (N == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if constexpr (N == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if constexpr (N == 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if constexpr (N == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-  else if constexpr (N == 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-  else if constexpr (N == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  else static_assert(N < 0, "add the count");
 }
 
 // ---- implicit im2col operand of codetr_conv_tokens_* ----------------------------------------------------------
@@ -252,7 +158,7 @@ struct ConvRows {
 
 // ACT: 0 none, 1 relu, 2 gelu(erf), 3 relu after the residual.  BKT x STAGES = the K pipeline: STAGES LDS buffers of one (W tile, X tile)
 // pair each, STAGES-1 tiles of LDS-DMA in flight across the per-K-step barrier (raw s_barrier + counted
-// s_waitcnt vmcnt: a __syncthreads() would drain the DMA queue, cdna_hip_programming.md section 5).
+// wait_vmcnt: a __syncthreads() would drain the DMA queue, cdna_hip_programming.md section 5).
 // SPLITK: blockIdx.y picks a range of `kps` K tiles; the block's fp32 partial tile goes to Y viewed as
 // float[gridDim.y][M][N] (no bias / activation / residual: splitk_reduce_kernel applies them to the sum).
 // CONV: X is not a dense [M, K] matrix but the implicit im2col matrix of a convolution over a token-major map (ConvRows
@@ -757,24 +663,22 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
     }
   }
   auto sdmaW = [&](int q, int kt, unsigned char* slot) {
-    lds_dma16s(Wt + (size_t)kt * (BKT * 2), woff[q], slot + (q * NT + wave_u * 64) * 16);
+    lds_dma16(Wt + (size_t)kt * (BKT * 2), woff[q], slot + (q * NT + wave_u * 64) * 16);
   };
   auto sdmaX = [&](int q, int kt, unsigned char* slot) {
-    lds_dma16s(Xt + (size_t)kt * (BKT * 2), xoff[q], slot + (q * NT + wave_u * 64) * 16);
+    lds_dma16(Xt + (size_t)kt * (BKT * 2), xoff[q], slot + (q * NT + wave_u * 64) * 16);
   };
   auto issue = [&](int t, int slot) {
     unsigned char* buf = lds + (slot & 1) * kStageBytes;
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       unsigned char* l = buf + (q * NT + wave * 64) * 16;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gw[q] + (size_t)t * BKT),
-                                       (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+      lds_dma16_auto(gw[q] + (size_t)t * BKT, l);
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       unsigned char* l = buf + kTileBytes + (q * NT + wave * 64) * 16;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gx[q] + (size_t)t * BKT),
-                                       (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+      lds_dma16_auto(gx[q] + (size_t)t * BKT, l);
     }
   };
   const int nk = K / BKT;
@@ -782,10 +686,6 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
   // tiles sharing an operand slice do not ask for it at the same moment) was measured neutral to -6 % and removed
   // (profiles/r03_gemm256_ablation.txt).
   auto ktile = [&](int i) { return i < nk ? i : nk - 1; };
-  auto dma16 = [&](const unsigned short* g, unsigned char* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-  };
   if (XDEEP && SDMA) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) sdmaW(q, ktile(0), lds + 3 * kTileBytes);
@@ -796,12 +696,12 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
   } else if (XDEEP) {   // issue order W(0), X(0), X(1): the youngest four pieces may stay in flight at the first wait
     const size_t k0 = (size_t)ktile(0) * BKT;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) dma16(gw[q] + k0, lds + 3 * kTileBytes + (q * NT + wave * 64) * 16);
+    for (int q = 0; q < 4; ++q) lds_dma16_auto(gw[q] + k0, lds + 3 * kTileBytes + (q * NT + wave * 64) * 16);
 #pragma unroll
-    for (int q = 0; q < 4; ++q) dma16(gx[q] + k0, lds + (q * NT + wave * 64) * 16);
+    for (int q = 0; q < 4; ++q) lds_dma16_auto(gx[q] + k0, lds + (q * NT + wave * 64) * 16);
     const size_t k1 = (size_t)ktile(1) * BKT;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) dma16(gx[q] + k1, lds + kTileBytes + (q * NT + wave * 64) * 16);
+    for (int q = 0; q < 4; ++q) lds_dma16_auto(gx[q] + k1, lds + kTileBytes + (q * NT + wave * 64) * 16);
   } else {
     issue(ktile(0), 0);
   }
@@ -893,14 +793,14 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
     if (kGemmAbl & 1) {
     } else if (XDEEP) {   // W first: it is needed one tile from now, X two
 #pragma unroll
-      for (int q = 0; q < 4; ++q) dma16(gw[q] + koff, nbufW + (q * NT + wave * 64) * 16);
+      for (int q = 0; q < 4; ++q) lds_dma16_auto(gw[q] + koff, nbufW + (q * NT + wave * 64) * 16);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) dma16(gx[q] + koffx, nbufX + (q * NT + wave * 64) * 16);
+      for (int q = 0; q < 4; ++q) lds_dma16_auto(gx[q] + koffx, nbufX + (q * NT + wave * 64) * 16);
     } else {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        dma16(gw[q] + koff, nbufW + (q * NT + wave * 64) * 16);
-        dma16(gx[q] + koff, nbufX + (q * NT + wave * 64) * 16);
+        lds_dma16_auto(gw[q] + koff, nbufW + (q * NT + wave * 64) * 16);
+        lds_dma16_auto(gx[q] + koff, nbufX + (q * NT + wave * 64) * 16);
       }
     }
 #pragma unroll
@@ -1004,7 +904,7 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
 #ifdef CODETR_GEMM_STAMPS
   if (threadIdx.x == 0 && g_stamps) {
     st2 = __builtin_amdgcn_s_memtime();   // all stores of wave 0 issued (not completed)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vmcnt<0>();
     const unsigned long long st3 = __builtin_amdgcn_s_memtime();   // ... and completed
     unsigned long long* o = g_stamps + 8 * (size_t)blockIdx.x;
     o[0] = st0; o[1] = st1; o[2] = st2; o[3] = st3; o[4] = rt0; o[5] = __builtin_amdgcn_s_memrealtime();
@@ -1161,7 +1061,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
 #pragma unroll
     for (int q = 0; q < kPieces; ++q) {
       const unsigned r = piece_row[q] < rmax ? piece_row[q] : rmax;
-      lds_dma16s(Wb + (size_t)c * kChunkBytes, r * (unsigned)(K * 2) + piece_off[q], dst + (q * 256 + wave * 64) * 16);
+      lds_dma16(Wb + (size_t)c * kChunkBytes, r * (unsigned)(K * 2) + piece_off[q], dst + (q * 256 + wave * 64) * 16);
     }
   };
   stage_chunk(0, lds);
@@ -1357,7 +1257,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
 #endif
   for (int c = 0; c < nchunks; ++c) {
     XS_STAMP(0);
-    if (!(CODETR_XS_ABL & 8)) wait_vmcnt_n<kPieces>();
+    if (!(CODETR_XS_ABL & 8)) wait_vmcnt<kPieces>();
     XS_STAMP(1);
     if (!(CODETR_XS_ABL & 8)) __builtin_amdgcn_s_barrier();
     XS_STAMP(2);
@@ -1486,7 +1386,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
     if (HAS_RES && (nchunks & 1)) load_residual(np);   // (an even count requested it in the last chunk)
     flush_pair(np);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the redundant fetches of the last two iterations
+  wait_vmcnt<0>();  // the redundant fetches of the last two iterations
 #ifdef CODETR_XS_STAMPS
   if (threadIdx.x == 0 && g_xs_stamps) {
     unsigned long long* o = g_xs_stamps + 12 * (size_t)blockIdx.x;

@@ -23,37 +23,14 @@
 #include <stdlib.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 #include "mx_scale.h"
 
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int kStagePitch = 64 * 2 + 16;  // epilogue staging: bytes per staged row of a wave's 64-column slice
 constexpr float kFp8Max = 448.0f;         // largest finite e4m3 (OCP e4m3fn)
-
-__device__ __forceinline__ unsigned xcd_tile(unsigned bid, unsigned nblk) {
-  const unsigned q = nblk >> 3, r = nblk & 7u, x = bid & 7u, i = bid >> 3;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
-}
-
-__device__ __forceinline__ float gelu_erf(float x) {
-  // 0.5 x (1 + erf(x / sqrt 2)) = 0.5 x + |x| (0.5 - (0.5 p(t) t) exp(-x^2 / 2)),  t = 1 / (1 + 0.3275911 |x| / sqrt 2):
-  // the sign of erf folds into |x|, the halves into the coefficients -- 11 plain ops + v_rcp + v_exp (15 + 2 before)
-  const float u = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, u, 1.0f));
-  float p = fmaf(0.5f * 1.061405429f, t, 0.5f * -1.453152027f);
-  p = fmaf(p, t, 0.5f * 1.421413741f);
-  p = fmaf(p, t, 0.5f * -0.284496736f);
-  p = fmaf(p, t, 0.5f * 0.254829592f);
-  const float ez = __builtin_amdgcn_exp2f(u * u * (-0.5f * 1.4426950408889634f));
-  return fmaf(u, fmaf(-(p * t), ez, 0.5f), 0.5f * x);
-}
 
 // XOR swizzle of the 16-byte chunk index of a 128-byte LDS row.  A lane's fragment is two ds_read_b128 (chunks 2g, 2g+1,
 // g = lane >> 4), and ds_read_b128 is served in the lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32): a group
@@ -164,10 +141,6 @@ __global__ __launch_bounds__(512) void linear_256_fp8_kernel(const unsigned char
     gw[q] = W + (size_t)gn * K + chunk * 16;
     gx[q] = X + (size_t)gm * K + chunk * 16;
   }
-  auto dma = [&](const unsigned char* g, unsigned char* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-  };
   const int nk = K / 128;
   const int64_t MB = mx_blocks128(M);
   const unsigned char* sx_blk = MX ? sx + (size_t)(tm * 2 + wm < MB ? tm * 2 + wm : MB - 1) * 512 : nullptr;
@@ -175,19 +148,19 @@ __global__ __launch_bounds__(512) void linear_256_fp8_kernel(const unsigned char
   if (MX) sxn = ld_scales(sx_blk, (unsigned)lane * 8);
   // issue order W(0), X(0), X(1): the youngest four pieces may stay in flight at the first wait
 #pragma unroll
-  for (int q = 0; q < 4; ++q) dma(gw[q], lds + 3 * kTileBytes + (q * NT + wave * 64) * 16);
+  for (int q = 0; q < 4; ++q) lds_dma16_auto(gw[q], lds + 3 * kTileBytes + (q * NT + wave * 64) * 16);
 #pragma unroll
-  for (int q = 0; q < 4; ++q) dma(gx[q], lds + (q * NT + wave * 64) * 16);
+  for (int q = 0; q < 4; ++q) lds_dma16_auto(gx[q], lds + (q * NT + wave * 64) * 16);
   {
     const size_t k1 = (size_t)(nk > 1 ? 1 : 0) * 128;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) dma(gx[q] + k1, lds + kTileBytes + (q * NT + wave * 64) * 16);
+    for (int q = 0; q < 4; ++q) lds_dma16_auto(gx[q] + k1, lds + kTileBytes + (q * NT + wave * 64) * 16);
   }
   int xs = 0;  // ring slot of X(t)
   // one k-tile.  MX: `s_use` = the tile's scale bytes, `s_load` receives the next tile's
   auto k_tile = [&](const int t, unsigned long long& s_use, unsigned long long& s_load) {
     // W(t), X(t) (and the scales of tile t) landed; the four pieces of X(t+1) may be in flight
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    wait_vmcnt<4>();
     __builtin_amdgcn_s_barrier();  // tile t is in LDS for everyone; everyone is done reading tile t-1
     const unsigned char* bufW = lds + (3 + (t & 1)) * kTileBytes;
     const unsigned char* bufX = lds + xs * kTileBytes;
@@ -210,8 +183,8 @@ __global__ __launch_bounds__(512) void linear_256_fp8_kernel(const unsigned char
       if (j < 7)
         b[(j + 1) & 1] = MX ? read_frag_mx(bufX, wm * 128 + (j + 1) * 16 + frow, fg)
                             : read_frag(bufX, wm * 128 + (j + 1) * 16 + frow, fg);
-      if (j < 4) dma(gw[j] + koffw, nbufW + (j * NT + wave * 64) * 16);
-      else dma(gx[j - 4] + koffx, nbufX + ((j - 4) * NT + wave * 64) * 16);
+      if (j < 4) lds_dma16_auto(gw[j] + koffw, nbufW + (j * NT + wave * 64) * 16);
+      else lds_dma16_auto(gx[j - 4] + koffx, nbufX + ((j - 4) * NT + wave * 64) * 16);
       const int sb = (int)(j < 4 ? (unsigned)s_use : (unsigned)(s_use >> 32));
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -236,7 +209,7 @@ __global__ __launch_bounds__(512) void linear_256_fp8_kernel(const unsigned char
   } else {
     for (int t = 0; t < nk; ++t) k_tile(t, sxc, sxn);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();  // all fragment reads done, no DMA in flight: LDS is free for the epilogue
 
   // per-lane column constants: 4 consecutive n per n-tile

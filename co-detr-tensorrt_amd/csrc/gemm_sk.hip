@@ -23,7 +23,7 @@
 //     (at most 4 parts per tile): a part stores its fp32 accumulators to a per-(workgroup, wave) slab and takes a ticket
 //     on the tile's per-wave counter; the wave that draws the last ticket adds the other parts and runs the epilogue of
 //     its piece -- no workgroup ever waits for another one (placement- and dispatch-order independent; write-through
-//     slab stores + s_waitcnt vmcnt(0) + relaxed agent atomic, the last arriver takes an agent-scope acquire;
+//     slab stores + wait_vmcnt<0>() + relaxed agent atomic, the last arriver takes an agent-scope acquire;
 //     MI355X_MICROARCH.md, inter-workgroup visibility).  It is correct (tools/micro/gemm_sk_bench, tests) but NOT the
 //     default: at this model's K <= 3072 a 256 x 256 fp32 partial (256 KiB out, 256 KiB back in) costs as much as the
 //     tile's own operand traffic, and the split measured 10-50 % slower than the quantisation it removes.
@@ -45,9 +45,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
-#include "gemm_elem.h"
-
-using namespace codetr_gemm;
+#include "device_prims.h"
 
 namespace {
 
@@ -88,18 +86,6 @@ struct SkArgs {
 __device__ __forceinline__ int key64(int row) {
   const int q = (row >> 2) & 3;
   return q ^ ((q & 1) << 1);
-}
-
-// one LDS-DMA piece: 16 B per lane from (wave-uniform 64-bit base in SGPRs) + (per-thread 32-bit byte offset) to the
-// wave-uniform LDS address `lds_addr` + lane * 16.  M0 is written in the statement that reads it.
-__device__ __forceinline__ void lds_dma16(const unsigned char* src, unsigned voff, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr)
-               : "memory", "m0");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // ---- the work list of one workgroup: stream-K range first, then the data-parallel rounds ----
@@ -263,14 +249,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int g = 0; g < PP; ++g) produce_piece(g, s);
     produce_advance();
   }
-  wait_vm<PP * (NS - 1)>();
+  wait_vmcnt<PP * (NS - 1)>();
   __builtin_amdgcn_s_barrier();
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     if (j < 4) F0.a[j] = *reinterpret_cast<const frag*>(lds + offA + j * 1024);
     F0.b[j] = *reinterpret_cast<const frag*>(lds + offB + j * 1024);
   }
-  wait_vm<PP * (NS - 2)>();
+  wait_vmcnt<PP * (NS - 2)>();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   int post = 0;   // phases left in which the previous epilogue's stores may stay in flight
@@ -302,10 +288,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (!(kAbl & 8)) {                                                                                               \
       /* the NS - 2 phases behind an epilogue leave its 32 output stores out of the count (vmcnt retires in order) */ \
       if (post > 0) {                                                                                                \
-        wait_vm<VMN + 32>();                                                                                         \
+        wait_vmcnt<VMN + 32>();                                                                                         \
         --post;                                                                                                      \
       } else {                                                                                                       \
-        wait_vm<VMN>();                                                                                              \
+        wait_vmcnt<VMN>();                                                                                              \
       }                                                                                                              \
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                                             \
       __builtin_amdgcn_s_barrier();                                                                                  \
@@ -363,7 +349,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             __builtin_amdgcn_raw_buffer_store_b128(v, rs, lane * 16, (i * 8 + j) * 1024, 16 /* sc1: write-through */);
           }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's slab has left the CU (and its L2)
+      wait_vmcnt<0>();   // this wave's slab has left the CU (and its L2)
       // the workgroups that hold a part of this tile: w_a .. w_b (owner of unit u = ceil((u + 1) Gs / S) - 1)
       const long long ua = (long long)t * a.nk, ub = ua + a.nk - 1;
       const int w_a = (int)(((ua + 1) * a.Gs + a.S - 1) / a.S) - 1, w_b = (int)(((ub + 1) * a.Gs + a.S - 1) / a.S) - 1;
@@ -376,7 +362,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       finish = (int)ticket == parts - 1;
       if (finish) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vmcnt<0>();
         for (int w2 = w_a; w2 <= w_b; ++w2) {
           const int b2 = sk_begin(a, w2);
           if (w2 == wg || b2 >= sk_begin(a, w2 + 1)) continue;
@@ -420,7 +406,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       // buffer descriptors on the piece's corner (wave-uniform) + ONE 32-bit lane offset; the row of a store goes into the
       // scalar offset.  (Per-lane 64-bit addresses were hoisted and spilled by the compiler: 32 stores, each behind a
-      // scratch reload and `s_waitcnt vmcnt(0)` -- every store waited for the one before and for the DMA pieces in flight.)
+      // scratch reload and `wait_vmcnt<0>()` -- every store waited for the one before and for the DMA pieces in flight.)
       const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
           reinterpret_cast<unsigned char*>(a.Y) + ((size_t)m0 * a.N + n0) * 2, 0, span, 0x00020000);
       if (HAS_RES) load_res(0, 4);   // residual rows: four row sets in flight, the other four requested two row sets later
@@ -473,7 +459,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     cursor_next(cc, a, wg);
   }
 #undef SK_PHASE
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the producer's redundant fetches past the end
+  wait_vmcnt<0>();   // the producer's redundant fetches past the end
 }
 
 // ---- host side ----

@@ -14,17 +14,17 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kRowsPerSlab = 128;  // rows reduced by one workgroup in pass 1 (600 workgroups at the stride-8 level)
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // BF = false: fp16 storage, true: bf16 storage (fp32 statistics and arithmetic either way)
 template <bool BF>
 __device__ __forceinline__ float h2f(short b) {
-  if (BF) return __uint_as_float(((unsigned)(unsigned short)b) << 16);
+  if (BF) return bf16_to_f32((unsigned short)b);
   _Float16 h;
   __builtin_memcpy(&h, &b, 2);
   return (float)h;

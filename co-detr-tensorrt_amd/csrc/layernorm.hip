@@ -13,11 +13,11 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 struct LnHalf {
   __device__ static float up(short b) {
@@ -33,7 +33,7 @@ struct LnHalf {
   }
 };
 struct LnBf16 {
-  __device__ static float up(short b) { return __uint_as_float(((unsigned)(unsigned short)b) << 16); }
+  __device__ static float up(short b) { return bf16_to_f32((unsigned short)b); }
   __device__ static short down(float v) {   // v_cvt_pk_bf16_f32 (round to nearest even, quiet NaN)
     const __bf16 h = (__bf16)v;
     return __builtin_bit_cast(short, h);

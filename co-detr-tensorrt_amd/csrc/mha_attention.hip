@@ -15,6 +15,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -25,26 +26,6 @@ constexpr int kQPerWg = 16 * kWaves;  // 128 queries per workgroup
 constexpr int kChunkTiles = 8;        // 128 keys per online-softmax step
 constexpr int kMaxKeys = 1024;        // K and V images: 2 x 64 KB of LDS
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct F16E {
-  using e = _Float16;
-  using v8 = f16x8;
-  using v4 = f16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-struct BF16E {
-  using e = __bf16;
-  using v8 = bf16x8;
-  using v4 = bf16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
 
 // XOR swizzle of the 16-byte chunk of a 64-byte (head_dim 32) LDS row.  With j = (row >> 2) & 3 the key f(j) = j ^ ((j & 1) << 1)
 // = {0, 3, 2, 1} keeps both read shapes conflict-free under the hardware's lane groups (tests/test_lds_bank_model.py):
@@ -57,14 +38,14 @@ __device__ __forceinline__ int swz(int row, int chunk) {
 }
 
 template <class ET>
-__global__ __launch_bounds__(kThreads) void mha_attention_kernel(const typename ET::e* __restrict__ q,
-                                                                 const typename ET::e* __restrict__ k,
-                                                                 const typename ET::e* __restrict__ v,
-                                                                 typename ET::e* __restrict__ out, int Nq, int Nk, int H,
+__global__ __launch_bounds__(kThreads) void mha_attention_kernel(const typename ET::elem* __restrict__ q,
+                                                                 const typename ET::elem* __restrict__ k,
+                                                                 const typename ET::elem* __restrict__ v,
+                                                                 typename ET::elem* __restrict__ out, int Nq, int Nk, int H,
                                                                  int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                                                  int64_t o_stride, int q_tiles, float scale_log2e) {
-  using E = typename ET::e;
-  using V8 = typename ET::v8;
+  using E = typename ET::elem;
+  using V8 = typename ET::frag;
   using V4 = typename ET::v4;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -200,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void mha_attention_kernel(const typename 
 template <class ET>
 int mha_entry(void* stream, const void* q, const void* k, const void* v, void* out, int64_t B, int64_t Nq, int64_t Nk,
               int H, int head_dim, int64_t q_stride, int64_t k_stride, int64_t v_stride, int64_t o_stride) {
-  using E = typename ET::e;
+  using E = typename ET::elem;
   if (!q || !k || !v || !out || B <= 0 || Nq <= 0 || Nk <= 0 || H <= 0) return CODETR_E_BADARG;
   if (head_dim != HD || Nk > kMaxKeys) return CODETR_E_UNSUPPORTED;
   const int64_t C = (int64_t)H * HD;
@@ -243,14 +224,14 @@ extern "C" {
 int codetr_mha_attention_f16(void* stream, const void* q_dev, const void* k_dev, const void* v_dev, void* out_dev,
                              int64_t B, int64_t Nq, int64_t Nk, int num_heads, int head_dim, int64_t q_row_stride,
                              int64_t k_row_stride, int64_t v_row_stride, int64_t out_row_stride) {
-  return mha_entry<F16E>(stream, q_dev, k_dev, v_dev, out_dev, B, Nq, Nk, num_heads, head_dim, q_row_stride, k_row_stride,
+  return mha_entry<HalfT>(stream, q_dev, k_dev, v_dev, out_dev, B, Nq, Nk, num_heads, head_dim, q_row_stride, k_row_stride,
                          v_row_stride, out_row_stride);
 }
 
 int codetr_mha_attention_bf16(void* stream, const void* q_dev, const void* k_dev, const void* v_dev, void* out_dev,
                               int64_t B, int64_t Nq, int64_t Nk, int num_heads, int head_dim, int64_t q_row_stride,
                               int64_t k_row_stride, int64_t v_row_stride, int64_t out_row_stride) {
-  return mha_entry<BF16E>(stream, q_dev, k_dev, v_dev, out_dev, B, Nq, Nk, num_heads, head_dim, q_row_stride,
+  return mha_entry<BFloatT>(stream, q_dev, k_dev, v_dev, out_dev, B, Nq, Nk, num_heads, head_dim, q_row_stride,
                           k_row_stride, v_row_stride, out_row_stride);
 }
 

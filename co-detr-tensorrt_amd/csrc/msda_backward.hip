@@ -19,10 +19,10 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 template <class ST> struct BwdTraits;
 template <> struct BwdTraits<float> {

@@ -36,6 +36,7 @@
 #include <type_traits>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -65,9 +66,6 @@ __device__ unsigned long long* g_msda4_stamps;
 #define M4_PUT(k, v)
 #endif
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 struct Geom4 {
   int M, S, RX, RY;
@@ -118,64 +116,18 @@ __device__ __forceinline__ int ext_hi_d(int r, int n, int R, int hi, int first) 
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ float unif(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
-__device__ __forceinline__ unsigned xcd_tile(unsigned bid, unsigned nblk) {
-  const unsigned q = nblk >> 3, r = nblk & 7u, x = bid & 7u, i = bid >> 3;
-  const unsigned first = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return first + i;
-}
-
-// quad (4-lane) data movement on the DPP path
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __uint_as_float(dpp_u<CTRL>(__float_as_uint(v)));
-}
-__device__ __forceinline__ unsigned quad_bcast_u(unsigned v, int owner) {
-  switch (owner) {
-    case 0: return dpp_u<0x00>(v);
-    case 1: return dpp_u<0x55>(v);
-    case 2: return dpp_u<0xAA>(v);
-    default: return dpp_u<0xFF>(v);
-  }
-}
-constexpr int kXor1 = 0xB1, kXor2 = 0x4E;  // quad_perm [1,0,3,2] / [2,3,0,1]
-// quad broadcast of `v` from lane `owner` plus this lane's `add`: ONE v_add_u32_dpp
-__device__ __forceinline__ unsigned quad_bcast_add(unsigned v, int owner, unsigned add) {
-  unsigned d;
-  switch (owner) {
-    case 0: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-    case 1: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-    case 2: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-    default: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-  }
-  return d;
-}
-__device__ __forceinline__ h2 as_h2(unsigned u) { return __builtin_bit_cast(h2, u); }
+__device__ __forceinline__ f16x2 as_h2(unsigned u) { return __builtin_bit_cast(f16x2, u); }
 __device__ __forceinline__ unsigned pack_h2(float a, float b) {   // v_cvt_pk_f16_f32 on gfx950 (round to nearest even)
-  const h2 v = {(_Float16)a, (_Float16)b};
+  const f16x2 v = {(_Float16)a, (_Float16)b};
   return __builtin_bit_cast(unsigned, v);
 }
 __device__ __forceinline__ float h_lo(unsigned u) { return (float)as_h2(u)[0]; }
 __device__ __forceinline__ float h_hi(unsigned u) { return (float)as_h2(u)[1]; }
 // acc += (float)h.lo / (float)h.hi in one instruction each
-__device__ __forceinline__ void acc_h2(float& lo, float& hi, h2 h) {
+__device__ __forceinline__ void acc_h2(float& lo, float& hi, f16x2 h) {
   const unsigned u = __builtin_bit_cast(unsigned, h);
   asm("v_fma_mix_f32 %0, %1, 1.0, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(u));
   asm("v_fma_mix_f32 %0, %1, 1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(hi) : "v"(u));
-}
-// one LDS-DMA piece: 16 B per lane from (wave-uniform 64-bit base in SGPRs) + (per-lane 32-bit byte offset) to the
-// wave-uniform LDS address `lds_addr` + lane * 16 (M0 is written in the statement that reads it)
-__device__ __forceinline__ void lds_dma16(const unsigned char* src, unsigned voff, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr)
-               : "memory", "m0");
-}
-__device__ __forceinline__ int floor_i(float v) {   // floor + float -> int in one instruction
-  int d;
-  asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(d) : "v"(v));
-  return d;
 }
 
 // Storage type of the packed projection and of the output (the staged VALUE map is fp16 in either case: the blend runs on
@@ -189,10 +141,9 @@ struct EF16 {
   }
 };
 struct EBF16 {
-  __device__ static float lo(unsigned u) { return __uint_as_float(u << 16); }
+  __device__ static float lo(unsigned u) { return bf16_to_f32((unsigned short)u); }
   __device__ static float hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
   __device__ static unsigned pk(float a, float b) {   // v_cvt_pk_bf16_f32 (round to nearest even)
-    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
     const bf16x2 v = {(__bf16)a, (__bf16)b};
     return __builtin_bit_cast(unsigned, v);
   }
@@ -321,19 +272,19 @@ __device__ __forceinline__ void gather(float (&acc)[8], const Prep (&pp)[NLV], c
   };
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d) fetch(d, d);
-  h2 h[4];
+  f16x2 h[4];
 #pragma unroll
   for (int s_ = 0; s_ < NS; ++s_) {
     const int b = s_ % NB;
     if (s_ + DEPTH < NS) fetch(s_ + DEPTH, (s_ + DEPTH) % NB);
-    const h2 a = as_h2(wA[b]), c = as_h2(wB[b]);
-    const h2 w4[4] = {h2{a[0], a[0]}, h2{a[1], a[1]}, h2{c[0], c[0]}, h2{c[1], c[1]}};
+    const f16x2 a = as_h2(wA[b]), c = as_h2(wB[b]);
+    const f16x2 w4[4] = {f16x2{a[0], a[0]}, f16x2{a[1], a[1]}, f16x2{c[0], c[0]}, f16x2{c[1], c[1]}};
 #pragma unroll
     for (int cr = 0; cr < 4; ++cr) {
       const f16x8 r = rows[b][cr];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const h2 v = {r[2 * j], r[2 * j + 1]};
+        const f16x2 v = {r[2 * j], r[2 * j + 1]};
         h[j] = ((s_ & 1) == 0 && cr == 0) ? v * w4[cr] : __builtin_elementwise_fma(v, w4[cr], h[j]);
       }
     }
@@ -386,14 +337,14 @@ struct Fix {
 #pragma unroll
     for (int j = 0; j < kQ; ++j) {
       if (base + j < cnt) {
-        const h2 a = as_h2(rc[j][2]), c = as_h2(rc[j][3]);
-        const h2 w4[4] = {h2{a[0], a[0]}, h2{a[1], a[1]}, h2{c[0], c[0]}, h2{c[1], c[1]}};
-        h2 h[4];
+        const f16x2 a = as_h2(rc[j][2]), c = as_h2(rc[j][3]);
+        const f16x2 w4[4] = {f16x2{a[0], a[0]}, f16x2{a[1], a[1]}, f16x2{c[0], c[0]}, f16x2{c[1], c[1]}};
+        f16x2 h[4];
 #pragma unroll
         for (int cr = 0; cr < 4; ++cr)
 #pragma unroll
           for (int jj = 0; jj < 4; ++jj) {
-            const h2 v = {r4[j][cr][2 * jj], r4[j][cr][2 * jj + 1]};
+            const f16x2 v = {r4[j][cr][2 * jj], r4[j][cr][2 * jj + 1]};
             h[jj] = cr == 0 ? v * w4[cr] : __builtin_elementwise_fma(v, w4[cr], h[jj]);
           }
 #pragma unroll
@@ -655,7 +606,7 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
       }
     }
     M4_T(c);
-    if (!(kAbl & 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (!(kAbl & 1)) wait_vmcnt<0>();
     M4_T(d);
     if (!(kAbl & 16)) __syncthreads();
     M4_T(e);

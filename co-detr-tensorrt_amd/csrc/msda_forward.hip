@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 #include "msda_op4_plan.h"
 
 namespace {
@@ -52,10 +53,6 @@ constexpr int kMaxTiledLdsBytes = 64 * 1024;
 #define MSDA_WAVES_PER_EU 4
 #endif
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 struct F16 {
   using storage = _Float16;
@@ -68,13 +65,8 @@ struct BF16 {
   using storage = unsigned short;
   using vec = u16x8;  // 16 B
   static constexpr int VEC = 8;
-  __device__ static float to_f32(storage v) { return __uint_as_float(((unsigned)v) << 16); }
-  __device__ static storage from_f32(float v) {
-    // round-to-nearest-even; NaN stays NaN (quiet)
-    unsigned u = __float_as_uint(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  }
+  __device__ static float to_f32(storage v) { return bf16_to_f32(v); }
+  __device__ static storage from_f32(float v) { return bf16_from_f32(v); }
 };
 struct F32 {
   using storage = float;
@@ -83,17 +75,6 @@ struct F32 {
   __device__ static float to_f32(storage v) { return v; }
   __device__ static storage from_f32(float v) { return v; }
 };
-
-// ------------------------------------------------------------------------------------------
-// XCD-aware tile order: hardware deals workgroups round-robin over the 8 XCDs, so blocks with
-// equal (blockIdx % 8) share an L2.  Give each such group one contiguous run of tiles.
-// Bijective for any grid size (cdna_hip_programming.md T1).  Placement only affects speed.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned xcd_tile(unsigned bid, unsigned nblk) {
-  const unsigned q = nblk >> 3, r = nblk & 7u, x = bid & 7u, i = bid >> 3;
-  const unsigned first = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return first + i;
-}
 
 // One LDS entry = 32 B: byte offsets of the 4 corners (clamped, always dereferenceable) and
 // their fp32 weights (bilinear * attention, 0 for out-of-image corners / gated points).

@@ -39,6 +39,7 @@
 #include <type_traits>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 #include "msda_op4_plan.h"
 
 namespace {
@@ -57,11 +58,6 @@ static_assert(kWaves * 16 * kRecBytes <= (int)kWinBytes, "the operand records al
 #endif
 constexpr int kAbl = MSDA_OP4_ABL;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 // floor(a / b) for 0 <= a < 2^22, 0 < b (one reciprocal + a fix-up)
 __device__ __forceinline__ int fdiv(int a, int b) {
@@ -73,32 +69,7 @@ __device__ __forceinline__ int fdiv(int a, int b) {
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, true);
-}
-__device__ __forceinline__ unsigned quad_bcast_u(unsigned v, int owner) {
-  switch (owner) {
-    case 0: return dpp_u<0x00>(v);
-    case 1: return dpp_u<0x55>(v);
-    case 2: return dpp_u<0xAA>(v);
-    default: return dpp_u<0xFF>(v);
-  }
-}
-__device__ __forceinline__ float quad_bcast_f(float v, int owner) { return __uint_as_float(quad_bcast_u(__float_as_uint(v), owner)); }
-constexpr int kXor1 = 0xB1, kXor2 = 0x4E;  // quad_perm [1,0,3,2] / [2,3,0,1]
-// quad broadcast of `v` from lane `owner` plus this lane's `add`: ONE v_add_u32_dpp
-__device__ __forceinline__ unsigned quad_bcast_add(unsigned v, int owner, unsigned add) {
-  unsigned d;
-  switch (owner) {
-    case 0: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-    case 1: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-    case 2: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-    default: asm("v_add_u32_dpp %0, %1, %2 quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf" : "=v"(d) : "v"(v), "v"(add)); break;
-  }
-  return d;
-}
-__device__ __forceinline__ h2 as_h2(unsigned u) { return __builtin_bit_cast(h2, u); }
+__device__ __forceinline__ f16x2 as_h2(unsigned u) { return __builtin_bit_cast(f16x2, u); }
 
 // The op's two 16-bit element types, as (low, high) element pairs of a dword.  Both are 2 bytes wide: staging, operand
 // records, plan and fix-up queue do not depend on which; only widening, the blend and the final rounding do.
@@ -110,13 +81,13 @@ struct OpF16 {
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(hi) : "v"(u), "v"(w));
   }
   __device__ __forceinline__ static unsigned pack2(float a, float b) {   // v_cvt_pk_f16_f32 (round to nearest even)
-    const h2 v = {(_Float16)a, (_Float16)b};
+    const f16x2 v = {(_Float16)a, (_Float16)b};
     return __builtin_bit_cast(unsigned, v);
   }
 };
 struct OpBF16 {
   // exact widening: a bf16 value is the top half of the fp32 one (one shift / one mask)
-  __device__ __forceinline__ static float elem(unsigned u, int i) { return __uint_as_float(i ? u & 0xffff0000u : u << 16); }
+  __device__ __forceinline__ static float elem(unsigned u, int i) { return i ? __uint_as_float(u & 0xffff0000u) : bf16_to_f32((unsigned short)u); }
   // gfx950 has no mixed-precision FMA that reads bf16: both halves widened, then two fp32 FMAs -- twice the fp16 blend's
   // vector instructions.  (One v_pk_fma_f32 per pair instead measured 2-5 % slower: profiles/r07_msda_op_bf16.txt)
   __device__ __forceinline__ static void fma2(float& lo, float& hi, unsigned u, float w) {
@@ -124,19 +95,10 @@ struct OpBF16 {
     hi = fmaf(elem(u, 1), w, hi);
   }
   __device__ __forceinline__ static unsigned pack2(float a, float b) {   // v_cvt_pk_bf16_f32 (round to nearest even; a NaN stays a NaN)
-    const bf2 v = {(__bf16)a, (__bf16)b};
+    const bf16x2 v = {(__bf16)a, (__bf16)b};
     return __builtin_bit_cast(unsigned, v);
   }
 };
-__device__ __forceinline__ void lds_dma16(const unsigned char* src, unsigned voff, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr)
-               : "memory", "m0");
-}
-__device__ __forceinline__ int floor_i(float v) {   // floor + float -> int in one instruction
-  int d;
-  asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(d) : "v"(v));
-  return d;
-}
 
 // What a wave keeps about one level (all wave-uniform: SGPRs)
 struct Lv {
@@ -537,7 +499,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
           }
         }
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vmcnt<0>();
       __syncthreads();
 #pragma unroll
       for (int it = 0; it < kMaxIt; ++it)

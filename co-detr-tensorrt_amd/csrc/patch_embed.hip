@@ -13,13 +13,12 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
 constexpr int kTok = 64;  // tokens per workgroup
 
-typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void patch_im2col_k4_kernel(const unsigned short* __restrict__ x,
                                                               unsigned short* __restrict__ out, int C, int H, int W,

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -30,7 +31,7 @@ struct Bf16 {
 
 __device__ __forceinline__ float to_f32(float v) { return v; }
 __device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
-__device__ __forceinline__ float to_f32(Bf16 v) { return __uint_as_float(((unsigned)v.bits) << 16); }
+__device__ __forceinline__ float to_f32(Bf16 v) { return bf16_to_f32(v.bits); }
 
 template <class T>
 __device__ __forceinline__ T from_f32(float v) {
@@ -38,9 +39,7 @@ __device__ __forceinline__ T from_f32(float v) {
 }
 template <>
 __device__ __forceinline__ Bf16 from_f32<Bf16>(float v) {
-  const unsigned u = __float_as_uint(v);
-  if ((u & 0x7fffffffu) > 0x7f800000u) return Bf16{(unsigned short)((u >> 16) | 0x40)};
-  return Bf16{(unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};
+  return Bf16{bf16_from_f32(v)};
 }
 
 struct ResizeAxis {

@@ -10,10 +10,10 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
-typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 // one thread = one 8-column piece of one output row; the 8 columns are gathered element by element (three channels
 // and 7-wide windows: no two columns of a piece share a 16-byte source run that a vector load could fetch)
@@ -45,10 +45,7 @@ __global__ __launch_bounds__(256) void conv_im2col_nchw_kernel(const unsigned sh
 }
 
 __device__ __forceinline__ float b16_to_f32(unsigned short bits, bool bf16) {
-  if (bf16) return __uint_as_float(((unsigned)bits) << 16);
-  _Float16 h;
-  __builtin_memcpy(&h, &bits, 2);
-  return (float)h;
+  return bf16 ? bf16_to_f32(bits) : HalfT::to_f32(bits);
 }
 
 // torch's rule (max_pool2d's CUDA kernels): start at -inf, scan the in-map taps row by row, take a value when it is

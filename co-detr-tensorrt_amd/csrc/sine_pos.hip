@@ -12,12 +12,11 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
 constexpr int kThreads = 256;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // E = _Float16 or __bf16 (storage of the encoding and of level_embed; fp32 arithmetic either way)
 template <class E, class V8>

@@ -10,30 +10,19 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
-typedef short s16x8 __attribute__((ext_vector_type(8)));
 
 // 16-bit storage <-> float; BF: bfloat16 (the bf16 model's instantiations), else fp16
 template <bool BF>
 __device__ __forceinline__ float h2f(unsigned short bits) {
-  if (BF) return __uint_as_float(((unsigned)bits) << 16);
-  _Float16 h;
-  __builtin_memcpy(&h, &bits, 2);
-  return (float)h;
+  return BF ? bf16_to_f32(bits) : HalfT::to_f32(bits);
 }
 template <bool BF>
 __device__ __forceinline__ unsigned short f2h(float v) {
-  if (BF) {
-    const unsigned u = __float_as_uint(v);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);   // NaN stays NaN
-    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  }
-  _Float16 h = (_Float16)v;
-  unsigned short bits;
-  __builtin_memcpy(&bits, &h, 2);
-  return bits;
+  return BF ? bf16_from_f32(v) : HalfT::from_f32(v);
 }
 template <bool BF>
 __device__ __forceinline__ float rh(float v) { return h2f<BF>(f2h<BF>(v)); }  // round to the storage type, keep as float

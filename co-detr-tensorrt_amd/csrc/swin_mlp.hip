@@ -30,55 +30,12 @@
 #include <type_traits>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
 constexpr int kThreads = 256;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-struct F16E {
-  using e = _Float16;
-  using v8 = f16x8;
-  using v4 = f16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-struct BF16E {
-  using e = __bf16;
-  using v8 = bf16x8;
-  using v4 = bf16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
-
-// nn.GELU (erf form) on two values: gemm_elem.h's gelu_erf2 (Abramowitz-Stegun 7.1.26, |error| <= 1.5e-7)
-__device__ __forceinline__ f32x2 gelu2(f32x2 x) {
-  const f32x2 u = {fabsf(x.x), fabsf(x.y)};
-  const f32x2 d = __builtin_elementwise_fma(f32x2{0.3275911f * 0.70710678118654752f, 0.3275911f * 0.70710678118654752f}, u, f32x2{1.0f, 1.0f});
-  const f32x2 t = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-  f32x2 p = __builtin_elementwise_fma(f32x2{0.5f * 1.061405429f, 0.5f * 1.061405429f}, t, f32x2{0.5f * -1.453152027f, 0.5f * -1.453152027f});
-  p = __builtin_elementwise_fma(p, t, f32x2{0.5f * 1.421413741f, 0.5f * 1.421413741f});
-  p = __builtin_elementwise_fma(p, t, f32x2{0.5f * -0.284496736f, 0.5f * -0.284496736f});
-  p = __builtin_elementwise_fma(p, t, f32x2{0.5f * 0.254829592f, 0.5f * 0.254829592f});
-  const f32x2 e = (u * u) * f32x2{-0.5f * 1.4426950408889634f, -0.5f * 1.4426950408889634f};
-  const f32x2 ez = {__builtin_amdgcn_exp2f(e.x), __builtin_amdgcn_exp2f(e.y)};
-  const f32x2 h = __builtin_elementwise_fma(-(p * t), ez, f32x2{0.5f, 0.5f});
-  return __builtin_elementwise_fma(u, h, x * f32x2{0.5f, 0.5f});
-}
-
-__device__ __forceinline__ void dma16(const unsigned char* src, unsigned voff, unsigned char* dst) {
-  const unsigned lds_addr = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)dst);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // C = 192: BH = 64, C = 384: BH = 32, one workgroup per CU (WPE = 1); C = 192 also as BH = 32 with TWO workgroups per CU
 // (WPE = 2: 12 KiB chunks, 256 registers per wave -- the second wave of a SIMD runs its MFMAs under this one's GELU)
@@ -88,8 +45,8 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE, W
     const float ln_eps, const unsigned short* __restrict__ W1, const unsigned short* __restrict__ b1,
     const unsigned short* __restrict__ W2p, const unsigned short* __restrict__ b2, unsigned short* __restrict__ Y, const int M,
     const int ntiles) {
-  using E = typename ET::e;
-  using V8 = typename ET::v8;
+  using E = typename ET::elem;
+  using V8 = typename ET::frag;
   using V4 = typename ET::v4;
   constexpr int Hd = 4 * C, NCHUNK = Hd / BH; // 12 / 48 chunks
   constexpr int KS = C / 32;                  // k-steps of the first product: 6 / 12
@@ -143,10 +100,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE, W
   const unsigned char* const W1b = reinterpret_cast<const unsigned char*>(W1);
   const unsigned char* const W2b = reinterpret_cast<const unsigned char*>(W2p);
   auto stage_w1 = [&](int p, int c, unsigned char* dst) {   // piece p of chunk c
-    dma16(W1b + (size_t)c * kChunkBytes, w1_voff[p], dst + (p * kThreads + wave * 64) * 16);
+    lds_dma16(W1b + (size_t)c * kChunkBytes, w1_voff[p], dst + (p * kThreads + wave * 64) * 16);
   };
   auto stage_w2 = [&](int p, int c, unsigned char* dst) {   // (chunk c = packed columns c BH .. of every row)
-    dma16(W2b + (size_t)c * RB2, w2_voff[p], dst + (p * kThreads + wave * 64) * 16);
+    lds_dma16(W2b + (size_t)c * RB2, w2_voff[p], dst + (p * kThreads + wave * 64) * 16);
   };
 #pragma unroll
   for (int p = 0; p < NP; ++p) stage_w1(p, 0, ringA);
@@ -275,7 +232,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE, W
     auto gelu_half = [&](const f32x4 (&hacc)[HT][MT], V8 (&pf)[KS2][MT], int q, int hh) {
       const int ht = q / MT, mt = q % MT;
       const f32x4 v = hacc[ht][mt];
-      const f32x2 g = gelu2(hh ? f32x2{v[2], v[3]} : f32x2{v[0], v[1]});
+      const f32x2 g = gelu_erf2(hh ? f32x2{v[2], v[3]} : f32x2{v[0], v[1]});
       pf[ht >> 1][mt][(ht & 1) * 4 + 2 * hh] = (E)g.x;
       pf[ht >> 1][mt][(ht & 1) * 4 + 2 * hh + 1] = (E)g.y;
     };
@@ -429,13 +386,13 @@ int codetr_swin_mlp_supported(int64_t M, int64_t C, int64_t hidden) {
 int codetr_swin_mlp_f16(void* stream, const void* x_dev, const void* ln_gamma_dev, const void* ln_beta_dev, float ln_eps,
                         const void* w1_dev, const void* b1_dev, const void* w2_packed_dev, const void* b2_dev, void* y_dev,
                         int64_t M, int64_t C) {
-  return launch_swin_mlp<F16E>(stream, x_dev, ln_gamma_dev, ln_beta_dev, ln_eps, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C);
+  return launch_swin_mlp<HalfT>(stream, x_dev, ln_gamma_dev, ln_beta_dev, ln_eps, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C);
 }
 
 int codetr_swin_mlp_bf16(void* stream, const void* x_dev, const void* ln_gamma_dev, const void* ln_beta_dev, float ln_eps,
                          const void* w1_dev, const void* b1_dev, const void* w2_packed_dev, const void* b2_dev, void* y_dev,
                          int64_t M, int64_t C) {
-  return launch_swin_mlp<BF16E>(stream, x_dev, ln_gamma_dev, ln_beta_dev, ln_eps, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C);
+  return launch_swin_mlp<BFloatT>(stream, x_dev, ln_gamma_dev, ln_beta_dev, ln_eps, w1_dev, b1_dev, w2_packed_dev, b2_dev, y_dev, M, C);
 }
 
 }  // extern "C"

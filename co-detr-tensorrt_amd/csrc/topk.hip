@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 
 namespace {
 
@@ -170,7 +171,6 @@ __global__ __launch_bounds__(kThreads) void topk_kernel(const unsigned short* __
 
 constexpr int kRegVecs = 25;  // 16-byte vectors per thread held in registers: rows up to 1024 * 25 * 8 elements
 
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ unsigned short elem16(const u32x4& v, int e) {
   const unsigned w = v[e >> 1];

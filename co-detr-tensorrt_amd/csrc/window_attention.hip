@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
 #include "mx_scale.h"
 
 namespace {
@@ -39,27 +40,6 @@ constexpr int HD = 32;  // head_dim of every Swin variant
 constexpr int kWaves = 4;
 constexpr int kThreads = 64 * kWaves;
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// element types: fp16 / bf16 storage, fp32 scores and accumulation either way
-struct F16E {
-  using e = _Float16;
-  using v8 = f16x8;
-  using v4 = f16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-};
-struct BF16E {
-  using e = __bf16;
-  using v8 = bf16x8;
-  using v4 = bf16x4;
-  __device__ static f32x4 mfma(v8 a, v8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-};
 
 struct Geometry {
   int B, H, W, Hp, Wp, shift, nH, nWx, nWin;  // nWin = (Hp/ws)*(Wp/ws)
@@ -109,13 +89,13 @@ __device__ __forceinline__ int swz(int row, int chunk) {
 // -4 ... -12 % per launch, profiles/r06_window_attention.txt).  N % 16 == 0 only.
 template <class ET, int WS, bool OUT8 = false, bool OUTMX = false, bool PB = false>
 __global__ __launch_bounds__(kThreads) void window_attention_kernel(
-    const typename ET::e* __restrict__ qkv,       // [B, H*W, 3C]
-    const typename ET::e* __restrict__ qkv_bias,  // [3C] (zeros if the layer has no bias)
-    const typename ET::e* __restrict__ rel_bias,  // [nH, N, N]
+    const typename ET::elem* __restrict__ qkv,       // [B, H*W, 3C]
+    const typename ET::elem* __restrict__ qkv_bias,  // [3C] (zeros if the layer has no bias)
+    const typename ET::elem* __restrict__ rel_bias,  // [nH, N, N]
     void* __restrict__ out_v,                     // [B, H*W, C] 16-bit, or e4m3 bytes (OUT8)
     Geometry g, int n_problems, float out_inv_scale, unsigned char* __restrict__ out_scales) {
-  using E = typename ET::e;
-  using V8 = typename ET::v8;
+  using E = typename ET::elem;
+  using V8 = typename ET::frag;
   using V4 = typename ET::v4;
   constexpr int N = WS * WS;
   constexpr int NT = (N + 15) / 16;   // 16-token tiles
@@ -413,8 +393,8 @@ int launch_ws(hipStream_t st, const void* qkv, const void* qkv_bias, const void*
   if (n > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
   const unsigned blocks = (unsigned)((n + kWaves - 1) / kWaves);
   hipLaunchKernelGGL((window_attention_kernel<ET, WS, OUT8, OUTMX, PB>), dim3(blocks), dim3(kThreads), 0, st,
-                     static_cast<const typename ET::e*>(qkv), static_cast<const typename ET::e*>(qkv_bias),
-                     static_cast<const typename ET::e*>(rel_bias), out, g, (int)n, out_inv_scale, out_scales);
+                     static_cast<const typename ET::elem*>(qkv), static_cast<const typename ET::elem*>(qkv_bias),
+                     static_cast<const typename ET::elem*>(rel_bias), out, g, (int)n, out_inv_scale, out_scales);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -465,14 +445,14 @@ extern "C" {
 int codetr_window_attention_f16(void* stream, const void* qkv_dev, const void* qkv_bias_dev, const void* rel_bias_dev,
                                 void* out_dev, int64_t B, int64_t H, int64_t W, int num_heads, int head_dim,
                                 int window_size, int shift) {
-  return window_attention_entry<F16E>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads, head_dim,
+  return window_attention_entry<HalfT>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads, head_dim,
                                       window_size, shift);
 }
 
 int codetr_window_attention_bf16(void* stream, const void* qkv_dev, const void* qkv_bias_dev, const void* rel_bias_dev,
                                  void* out_dev, int64_t B, int64_t H, int64_t W, int num_heads, int head_dim,
                                  int window_size, int shift) {
-  return window_attention_entry<BF16E>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads,
+  return window_attention_entry<BFloatT>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads,
                                        head_dim, window_size, shift);
 }
 
@@ -481,7 +461,7 @@ int codetr_window_attention_fp8mx_f16(void* stream, const void* qkv_dev, const v
                                       int64_t W, int num_heads, int head_dim, int window_size, int shift) {
   if (!out_scales_dev) return CODETR_E_BADARG;
   if ((num_heads * (int64_t)head_dim) % 128 != 0 || (reinterpret_cast<uintptr_t>(out8_dev) & 3)) return CODETR_E_UNSUPPORTED;
-  return window_attention_entry<F16E, true, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out8_dev, B, H, W, num_heads,
+  return window_attention_entry<HalfT, true, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out8_dev, B, H, W, num_heads,
                                                   head_dim, window_size, shift, 1.0f,
                                                   static_cast<unsigned char*>(out_scales_dev));
 }
@@ -491,7 +471,7 @@ int codetr_window_attention_fp8out_f16(void* stream, const void* qkv_dev, const 
                                        int64_t W, int num_heads, int head_dim, int window_size, int shift) {
   if (!(out_scale > 0.f)) return CODETR_E_BADARG;
   if ((num_heads * (int64_t)head_dim) % 4 != 0 || (reinterpret_cast<uintptr_t>(out8_dev) & 3)) return CODETR_E_BADARG;
-  return window_attention_entry<F16E, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out8_dev, B, H, W, num_heads,
+  return window_attention_entry<HalfT, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out8_dev, B, H, W, num_heads,
                                             head_dim, window_size, shift, 1.0f / out_scale);
 }
 
@@ -503,22 +483,22 @@ int codetr_window_attention_ex(void* stream, const void* qkv_dev, const void* qk
   if (elem != 0 && elem != 1) return CODETR_E_BADARG;
   if (out_mode == 0) {
     if (elem == 1)
-      return window_attention_entry<BF16E>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads, head_dim,
+      return window_attention_entry<BFloatT>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads, head_dim,
                                            window_size, shift, 1.0f, nullptr, bias_layout);
-    return window_attention_entry<F16E>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads, head_dim,
+    return window_attention_entry<HalfT>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads, head_dim,
                                         window_size, shift, 1.0f, nullptr, bias_layout);
   }
   if (elem != 0) return CODETR_E_UNSUPPORTED;   // the e4m3 outputs take fp16 qkv
   if (out_mode == 1) {
     if (!(out_scale > 0.f)) return CODETR_E_BADARG;
     if ((num_heads * (int64_t)head_dim) % 4 != 0 || (reinterpret_cast<uintptr_t>(out_dev) & 3)) return CODETR_E_BADARG;
-    return window_attention_entry<F16E, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads,
+    return window_attention_entry<HalfT, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads,
                                               head_dim, window_size, shift, 1.0f / out_scale, nullptr, bias_layout);
   }
   if (out_mode == 2) {
     if (!out_scales_dev) return CODETR_E_BADARG;
     if ((num_heads * (int64_t)head_dim) % 128 != 0 || (reinterpret_cast<uintptr_t>(out_dev) & 3)) return CODETR_E_UNSUPPORTED;
-    return window_attention_entry<F16E, true, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads,
+    return window_attention_entry<HalfT, true, true>(stream, qkv_dev, qkv_bias_dev, rel_bias_dev, out_dev, B, H, W, num_heads,
                                                     head_dim, window_size, shift, 1.0f,
                                                     static_cast<unsigned char*>(out_scales_dev), bias_layout);
   }

@@ -1,6 +1,16 @@
 """Cut one kernel out of a hipcc -S --cuda-device-only listing and summarise it: instruction counts by kind, spills,
-and (optionally) the longest loop bodies.  Usage: python tools/isa_extract.py file.s <substring of the mangled name> [out.s]"""
+and (optionally) the longest loop bodies.  Usage: python tools/isa_extract.py file.s <substring of the mangled name> [out.s]
+
+Compare two listings (or two directories of *.s with equal file names), e.g. before and after a change to a shared header:
+    python tools/isa_extract.py diff old.s new.s [--rename OLD=NEW ...]
+Kernels are paired by demangled name without namespace qualifiers (--rename maps a type name of the old listing that the
+change renamed); of each pair the instruction text is compared after dropping labels, directives, comments and symbol
+names, and the .amdhsa_ resource block (registers, LDS, scratch).  One line per kernel: `identical`, `same instructions,
+different order`, or `different` with counts; the exit status is 1 if any kernel is different or unpaired."""
+import collections
+import os
 import re
+import subprocess
 import sys
 
 
@@ -21,7 +31,102 @@ def kernels(path):
     return out
 
 
+def resources(path):
+    """mangled name -> the .amdhsa_ lines of the kernel's descriptor"""
+    out, name = {}, None
+    for line in open(path):
+        s = line.strip()
+        if s.startswith(".amdhsa_kernel "):
+            name = s.split()[1]
+            out[name] = []
+        elif s.startswith(".end_amdhsa_kernel"):
+            name = None
+        elif name:
+            out[name].append(_no_symbols(s))
+    return out
+
+
+def _no_symbols(s):
+    s = re.sub(r"\b(_Z\w+|__hip_cuid_\w+)", "SYM", s)
+    return re.sub(r"\.L(BB|JTI|tmp|func_\w+?)\d+(_\d+)?", lambda m: ".L" + m.group(1) + (m.group(2) or ""), s)
+
+
+def instructions(body):
+    out = []
+    for line in body[1:]:
+        s = line.split(";")[0].strip()
+        if s and not s.startswith(".") and not s.endswith(":"):
+            out.append(_no_symbols(" ".join(s.split())))
+    return out
+
+
+def demangled(names):
+    for tool in ("/opt/rocm/llvm/bin/llvm-cxxfilt", "llvm-cxxfilt", "c++filt"):
+        try:
+            res = subprocess.run([tool], input="\n".join(names) + "\n", stdout=subprocess.PIPE, text=True, check=True)
+            return res.stdout.split("\n")[:len(names)]
+        except (OSError, subprocess.CalledProcessError):
+            continue
+    sys.exit("no demangler found (llvm-cxxfilt or c++filt)")
+
+
+def by_plain_name(path, renames):
+    ks, res = kernels(path), resources(path)
+    out = {}
+    for mangled, plain in zip(ks, demangled(list(ks))):
+        plain = re.sub(r"(\(anonymous namespace\)|\b\w+)::", "", plain)
+        for old, new in renames:
+            plain = re.sub(r"\b%s\b" % re.escape(old), new, plain)
+        assert plain not in out, plain
+        out[plain] = (instructions(ks[mangled]), res.get(mangled))
+    return out
+
+
+def diff_listings(old, new, renames):
+    a, b = by_plain_name(old, renames), by_plain_name(new, [])
+    bad = 0
+    for name in sorted(set(a) | set(b)):
+        short = name if len(name) <= 150 else name[:147] + "..."
+        if name not in a or name not in b:
+            print(f"  {'only in new' if name in b else 'only in old'}: {short}")
+            bad += 1
+            continue
+        (ia, ra), (ib, rb) = a[name], b[name]
+        ca, cb = collections.Counter(ia), collections.Counter(ib)
+        if ia == ib and ra == rb:
+            verdict = "identical"
+        elif ca == cb and ra == rb:
+            moved = sum(x != y for x, y in zip(ia, ib))
+            verdict = f"same instructions, different order ({moved} of {len(ia)} positions; registers, LDS, scratch equal)"
+        else:
+            gone, came = sum((ca - cb).values()), sum((cb - ca).values())
+            verdict = f"different: {len(ia)} -> {len(ib)} instructions, {gone} only in old, {came} only in new"
+            if ra != rb:
+                verdict += "; resources: " + ", ".join(f"{x} -> {y}" for x, y in zip(ra or [], rb or []) if x != y)
+            bad += 1
+        print(f"  {verdict}: {short}")
+    return len(set(a) | set(b)), bad
+
+
+def diff_main(argv):
+    renames = [tuple(argv[i + 1].split("=")) for i, x in enumerate(argv) if x == "--rename"]
+    old, new = [x for i, x in enumerate(argv) if x != "--rename" and (i == 0 or argv[i - 1] != "--rename")]
+    if os.path.isdir(old):
+        pairs = [(os.path.join(old, f), os.path.join(new, f)) for f in sorted(os.listdir(old)) if f.endswith(".s")]
+    else:
+        pairs = [(old, new)]
+    total = bad = 0
+    for o, n in pairs:
+        print(os.path.basename(o))
+        t, b = diff_listings(o, n, renames)
+        total, bad = total + t, bad + b
+    print(f"{total} kernels and device functions in {len(pairs)} listing(s): {bad} different or unpaired")
+    return 1 if bad else 0
+
+
 def main():
+    if sys.argv[1] == "diff":
+        sys.exit(diff_main(sys.argv[2:]))
     ks = kernels(sys.argv[1])
     key = sys.argv[2]
     for n, body in ks.items():

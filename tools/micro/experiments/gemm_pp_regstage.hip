@@ -46,9 +46,7 @@
 #include <type_traits>
 
 #include "codetr_hip.h"
-#include "gemm_elem.h"
-
-using namespace codetr_gemm;
+#include "device_prims.h"
 
 namespace {
 
@@ -100,16 +98,6 @@ struct PpArgs {
 __device__ __forceinline__ int key64(int row) {
   const int q = (row >> 2) & 3;
   return q ^ ((q & 1) << 1);
-}
-
-__device__ __forceinline__ void lds_dma16(const unsigned char* src, unsigned voff, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr)
-               : "memory", "m0");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // a workgroup barrier that nothing is scheduled across (MFMAs are register-only: the scheduler would otherwise move them
@@ -304,7 +292,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int g = 0; g < PP; ++g) produce_piece(g, s);
     produce_advance();
   }
-  wait_vm<VMN>();
+  wait_vmcnt<VMN>();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the bias rows written above
   seg_barrier();
   int post = 0;   // LOAD segments left in which the previous epilogue's stores may stay in flight
@@ -336,10 +324,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (part == PH - 1) {
       // the NS - 2 LOAD segments behind an epilogue leave its 32 output stores out of the count (vmcnt retires in order)
       if (post > 0) {
-        wait_vm<VMN + 32>();
+        wait_vmcnt<VMN + 32>();
         --post;
       } else {
-        wait_vm<VMN>();
+        wait_vmcnt<VMN>();
       }
     }
     PP_T(2);
@@ -397,7 +385,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     post = stored && !(kAbl & 16) ? NS - 2 : 0;
     c_tile = item_tile(a, wg, ++c_idx);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the producer's redundant fetches past the end
+  wait_vmcnt<0>();   // the producer's redundant fetches past the end
   PP_STAMPS_OUT();
 }
 
@@ -516,7 +504,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   auto load_seg = [&](auto p1_c, int part) {
     PP_T(0);
 #ifdef CODETR_PP_STAMPS
-    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // the set written below has landed (the compiler's own waits follow)
+    wait_vmcnt<4>();   // the set written below has landed (the compiler's own waits follow)
 #endif
     PP_T(1);
     constexpr int P1 = decltype(p1_c)::value;

@@ -50,9 +50,7 @@
 #include <type_traits>
 
 #include "codetr_hip.h"
-#include "gemm_elem.h"
-
-using namespace codetr_gemm;
+#include "device_prims.h"
 
 namespace {
 
@@ -105,16 +103,6 @@ struct PpArgs {
 __device__ __forceinline__ int key64(int row) {
   const int q = (row >> 2) & 3;
   return q ^ ((q & 1) << 1);
-}
-
-__device__ __forceinline__ void lds_dma16(const unsigned char* src, unsigned voff, unsigned lds_addr) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(src), "s"(lds_addr)
-               : "memory", "m0");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // a workgroup barrier that nothing is scheduled across (MFMAs are register-only: the scheduler would otherwise move them
@@ -310,7 +298,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int g = 0; g < PP; ++g) produce_piece(g, s);
     produce_advance();
   }
-  wait_vm<VMN>();
+  wait_vmcnt<VMN>();
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // the bias rows written above
   seg_barrier();
   int post = 0;   // LOAD segments left in which the previous epilogue's stores may stay in flight
@@ -342,10 +330,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (part == PH - 1) {
       // the NS - 2 LOAD segments behind an epilogue leave its 32 output stores out of the count (vmcnt retires in order)
       if (post > 0) {
-        wait_vm<VMN + 32>();
+        wait_vmcnt<VMN + 32>();
         --post;
       } else {
-        wait_vm<VMN>();
+        wait_vmcnt<VMN>();
       }
     }
     PP_T(2);
@@ -403,7 +391,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     post = stored && !(kAbl & 16) ? NS - 2 : 0;
     c_tile = item_tile(a, wg, ++c_idx);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the producer's redundant fetches past the end
+  wait_vmcnt<0>();   // the producer's redundant fetches past the end
   PP_STAMPS_OUT();
 }
 
@@ -507,7 +495,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   produce(pw, true, lds0);
   produce(px, false, lds0 + 2 * kTileOp);
   produce(px, false, lds0 + 3 * kTileOp);
-  wait_vm<4>();
+  wait_vmcnt<4>();
   seg_barrier();
   int wsl = 0, xsl = 0;   // slots of W(t), X(t)
 
@@ -544,7 +532,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       pieces();
     }
     PP_T(1);
-    if (ks == 1) wait_vm<4>();
+    if (ks == 1) wait_vmcnt<4>();
     PP_T(2);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     PP_T(3);
@@ -593,7 +581,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     PP_ACC(6, 8, 9);
     c_tile = item_tile(a, wg, ++c_idx);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the producers' redundant fetches past the end
+  wait_vmcnt<0>();   // the producers' redundant fetches past the end
   PP_STAMPS_OUT();
 }
 
@@ -688,7 +676,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // ---- prologue: half-stages 0 .. 3 issued, 0 and 1 landed for everybody ----
 #pragma unroll
   for (int s_ = 0; s_ < NS - 1; ++s_) produce(s_);
-  wait_vm<2 * PP>();
+  wait_vmcnt<2 * PP>();
   seg_barrier();
   int rs = 0;   // ring slot of the half-stage the next LOAD segment of this wave reads
 
@@ -732,7 +720,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   };
   auto close_epoch = [&]() {
     PP_T(3);
-    wait_vm<2 * PP>();
+    wait_vmcnt<2 * PP>();
     PP_T(4);
     seg_barrier();
     PP_T(7);
@@ -775,7 +763,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     PP_ACC(6, 8, 9);
     c_tile = item_tile(a, wg, ++c_idx);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the producer's redundant fetches past the end
+  wait_vmcnt<0>();   // the producer's redundant fetches past the end
   PP_STAMPS_OUT();
 }
 
