@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcodetr_hip.so")
-ABI_VERSION = 53
+ABI_VERSION = 54
 
 _i64, _i32, _vp, _cp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p
 
@@ -111,6 +111,12 @@ SIGNATURES = {
                                                   ctypes.c_float, _vp, _vp, _vp, _vp]),
     "codetr_postprocess_detections_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
                                                  ctypes.c_float, _vp, _vp, _vp, _vp]),
+    "codetr_postprocess_softnms_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
+                                              ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_postprocess_softnms_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
+                                               ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_postprocess_softnms_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
+                                              ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_patch_merge_layernorm_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_patch_merge_layernorm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_mask_pyramid": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32]),
@@ -178,7 +184,7 @@ _lib = None
 CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 0, "layernorm": 0, "window_attention": 0, "groupnorm_tokens": 0,
          "sine_pos_tokens": 0, "ffn_fused": 0, "ffn_oproj_fused": 0, "linear_splitk": 0, "linear_sk": 0, "mask_pyramid": 0,
          "query_sine_embed": 0, "encoder_geometry": 0, "row_max": 0, "preprocess": 0, "batched_nms": 0,
-         "preprocess_batch": 0, "postprocess_detections": 0,
+         "preprocess_batch": 0, "postprocess_detections": 0, "postprocess_softnms": 0,
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
@@ -558,6 +564,25 @@ def postprocess_detections(boxes, scores, labels, divisors, score_threshold, iou
         0 if iou_threshold is None else 1, 0.0 if iou_threshold is None else float(iou_threshold), boxes_out.data_ptr(),
         scores_out.data_ptr(), labels_out.data_ptr(), count.data_ptr())
     check(rc, "codetr_postprocess_detections")
+
+
+_SOFTNMS_BY_DTYPE = {torch.float16: "codetr_postprocess_softnms_f16", torch.bfloat16: "codetr_postprocess_softnms_bf16",
+                     torch.float32: "codetr_postprocess_softnms_f32"}
+SOFTNMS_METHODS = {"naive": 0, "linear": 1}   # CODETR_SOFTNMS_NAIVE / CODETR_SOFTNMS_LINEAR
+
+
+def postprocess_softnms(boxes, scores, labels, divisors, score_threshold, method, iou_threshold, min_score, max_keep,
+                        boxes_out, scores_out, labels_out, index_out, count):
+    """operands as postprocess_detections; method 0 naive / 1 linear; max_keep <= 0 keeps all; index_out [N,Q] int32
+    (include/codetr_hip.h states the semantics)"""
+    CALLS["postprocess_softnms"] += 1
+    N, Q = scores.shape
+    rc = getattr(load(), _SOFTNMS_BY_DTYPE[scores.dtype])(
+        current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), divisors.data_ptr(),
+        N, Q, 0 if score_threshold is None else 1, 0.0 if score_threshold is None else float(score_threshold),
+        int(method), float(iou_threshold), float(min_score), int(max_keep), boxes_out.data_ptr(), scores_out.data_ptr(),
+        labels_out.data_ptr(), index_out.data_ptr(), count.data_ptr())
+    check(rc, "codetr_postprocess_softnms")
 
 
 def mask_pyramid(img_masks, shapes):

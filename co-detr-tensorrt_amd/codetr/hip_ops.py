@@ -28,6 +28,7 @@ NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_win
           "preprocess_image(u8 -> f16/f32, cv2-exact resize + pad + normalise + mask)", "batched_nms(f32)",
           "preprocess_batch(u8 -> f16/bf16/f32, <= 32 images of any size per launch, stacked + padded)",
           "postprocess_detections(f16/bf16/f32: threshold + sort + per-class NMS + rescale, one workgroup per image)",
+          "postprocess_detections_soft(f16/bf16/f32: threshold + per-class soft-NMS (linear / naive) + max_per_img + rescale)",
           "patch_merge_layernorm(f16: Swin 2x2 gather + LayerNorm)",
           "msda_encoder_packed(f16/bf16: LDS-staged gather for the encoder's self-attention, csrc/msda_encoder4.hip)",
           "patch_embed(f16/bf16: 4x4 patch gather + GEMM)",
@@ -572,9 +573,87 @@ def postprocess_detections(boxes, scores, labels, divisors, score_threshold=None
 
 
 def detections_to_host(dets):
-    """postprocess_detections' result on the host: one device-to-host copy of the packed buffer"""
+    """postprocess_detections' (or postprocess_detections_soft's, `index` included) result on the host: one
+    device-to-host copy of the packed buffer"""
     N, Q = dets.scores.shape
-    return _detection_views(dets.packed.cpu(), N, Q, dets.scores.dtype)
+    views = _soft_detection_views if isinstance(dets, SoftDetections) else _detection_views
+    return views(dets.packed.cpu(), N, Q, dets.scores.dtype)
+
+
+# postprocess_detections_soft's result: the fields of Detections + index [N,Q] int32, the query index of every output
+# row -- five views of the one byte buffer `packed`
+SoftDetections = collections.namedtuple("SoftDetections", "boxes scores labels count index packed")
+
+
+def _soft_detection_views(packed, N, Q, dtype):
+    es = torch.empty((), dtype=dtype).element_size()
+    o1 = N * Q * 8
+    o2 = o1 + N * 4
+    o3 = o2 + N * Q * 4
+    o4 = o3 + N * Q * 4 * es
+    o5 = o4 + N * Q * es
+    return SoftDetections(packed[o3:o4].view(dtype).view(N, Q, 4), packed[o4:o5].view(dtype).view(N, Q),
+                          packed[:o1].view(torch.int64).view(N, Q), packed[o1:o2].view(torch.int32),
+                          packed[o2:o3].view(torch.int32).view(N, Q), packed)
+
+
+def _soft_method(method):
+    if method == "gaussian":
+        raise NotImplementedError("soft-NMS method 'gaussian' is not provided (exp() cannot be held bit-exact against "
+                                  "the CPU reference and no shipped config uses it): 'linear' or 'naive'")
+    if method not in _cabi.SOFTNMS_METHODS:
+        raise ValueError(f"soft-NMS method must be 'linear' or 'naive', got {method!r}")
+    return _cabi.SOFTNMS_METHODS[method]
+
+
+def postprocess_detections_soft(boxes, scores, labels, divisors, score_threshold=None, iou_threshold=0.3,
+                                method="linear", min_score=1e-3, max_per_img=None):
+    """The post-processing the model configs specify (test_cfg[0]: nms type 'soft_nms', max_per_img) + run_inference's
+    `boxes / scale_factor` for a whole batch in one launch (csrc/prepost.hip; semantics: include/codetr_hip.h): mmcv's
+    soft-NMS per class -- overlapping boxes are not removed but their scores decayed by 1 - IoU (`linear`) or set to 0
+    (`naive`) when IoU >= iou_threshold, a box leaves once its score is < min_score --, the detections sorted by decayed
+    score, the first max_per_img kept (None: all).  Operands as postprocess_detections; the defaults are mmcv's.
+    -> SoftDetections: scores are the decayed ones, `index` the query index of every row."""
+    _gpu(scores, "postprocess_detections_soft")
+    m = _soft_method(method)
+    dtype = scores.dtype
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32) or boxes.dtype != dtype or divisors.dtype != dtype:
+        raise ValueError("postprocess_detections_soft: boxes, scores and divisors in one dtype of f16 / bf16 / f32")
+    if scores.dim() != 2:
+        raise ValueError("postprocess_detections_soft: boxes [N,Q,4], scores [N,Q], labels [N,Q], divisors [N,4]")
+    N, Q = scores.shape
+    if tuple(boxes.shape) != (N, Q, 4) or tuple(labels.shape) != (N, Q) or tuple(divisors.shape) != (N, 4):
+        raise ValueError("postprocess_detections_soft: boxes [N,Q,4], scores [N,Q], labels [N,Q], divisors [N,4]")
+    nbytes = N * Q * 12 + N * 4 + N * Q * 5 * scores.element_size()
+    if N == 0 or Q == 0:   # nothing to launch for: every count is 0
+        return _soft_detection_views(torch.zeros((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
+    out = _soft_detection_views(torch.empty((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
+    with torch.cuda.device(scores.device):
+        _cabi.postprocess_softnms(boxes.contiguous(), scores.contiguous(), labels.to(torch.int64).contiguous(),
+                                  divisors.contiguous(), score_threshold, m, iou_threshold, min_score,
+                                  0 if max_per_img is None else int(max_per_img), out.boxes, out.scores, out.labels,
+                                  out.index, out.count)
+    return out
+
+
+def soft_nms(boxes, scores, labels, iou_threshold, method="linear", min_score=1e-3):
+    """mmcv batched_nms(..., nms_cfg=dict(type='soft_nms')) semantics for one image's detections (boxes [n,4],
+    scores [n], labels [n]; n <= 1024), the counterpart of `batched_nms`: -> (new_scores, keep), the decayed scores of
+    the kept boxes in descending order (dtype of `scores`) and their indices.  The N = 1 launch of
+    postprocess_detections_soft with unit divisors."""
+    _gpu(boxes, "soft_nms")
+    _soft_method(method)
+    n = boxes.shape[0]
+    if n == 0:
+        return scores.new_empty((0,)), torch.empty((0,), dtype=torch.int64, device=boxes.device)
+    if n > _cabi.POSTPROCESS_MAX_Q:
+        raise ValueError(f"soft_nms: at most {_cabi.POSTPROCESS_MAX_Q} boxes per call, got {n}")
+    dtype = scores.dtype if scores.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float32
+    dets = postprocess_detections_soft(boxes.to(dtype)[None], scores.to(dtype)[None], labels[None],
+                                       torch.ones((1, 4), dtype=dtype, device=boxes.device), None, iou_threshold, method,
+                                       min_score, None)
+    c = int(dets.count[0])
+    return dets.scores[0, :c].to(scores.dtype), dets.index[0, :c].to(torch.int64)
 
 
 def mask_pyramid(img_masks, shapes):

@@ -19,6 +19,14 @@ reference, which loops image by image: per chunk one pinned staging buffer and o
 pads and stacks them all (``preprocess_batch``: mmdet's ``stack_batch`` shape), one forward, one launch for threshold
 + NMS + rescale of every image (``postprocess_batch``) and one download.  Every image's result is what the per-image
 path returns for it when the model's detections do not depend on the other images of the batch.
+
+``nms_type`` (beyond the reference, which runs hard NMS whatever the config says): ``None`` keeps the reference's
+behaviour -- hard NMS at the config's ``iou_threshold``, ``max_per_img`` ignored.  ``"config"`` follows ``test_cfg[0]``
+as mmdet does: ``nms.type`` ``'nms'`` is hard NMS, ``'soft_nms'`` is mmcv's soft-NMS with the config's ``method``
+(default ``linear``), ``min_score`` (default 1e-3) and ``iou_threshold``; then the best ``max_per_img`` detections.
+``"nms"`` / ``"soft_nms"`` force the mode with the other parameters still from the config.  In soft mode the returned
+scores are the decayed ones, every call takes the chunked path and ``postprocess_batch`` is one
+``hip_ops.postprocess_detections_soft`` launch per chunk; ``run_inference`` uses ``hip_ops.soft_nms``.
 """
 from typing import Dict, List, Optional
 
@@ -35,9 +43,35 @@ def rescale_size(h, w, scale):
     return int(h * f + 0.5), int(w * f + 0.5)
 
 
+def nms_settings(test_cfg, nms_type=None):
+    """How `Inferencer(..., nms_type=...)` reads the query head's test_cfg (mmdet: `batched_nms(.., test_cfg.nms)` then
+    `[:max_per_img]`): -> dict(type 'nms' | 'soft_nms', method, min_score, max_per_img or None).  nms_type None is the
+    reference's simplification: hard NMS and no cut, whatever the config says."""
+    if nms_type not in (None, "config", "nms", "soft_nms"):
+        raise ValueError(f"nms_type must be None, 'config', 'nms' or 'soft_nms', got {nms_type!r}")
+    nms_cfg = dict(test_cfg["nms"]) if "nms" in test_cfg else {}
+    out = dict(type="nms", method=nms_cfg.get("method", "linear"), min_score=float(nms_cfg.get("min_score", 1e-3)),
+               max_per_img=None, forced_without_entry=False)   # (mmcv's soft_nms defaults: linear, 1e-3)
+    if nms_type is None:
+        return out
+    out["type"] = nms_cfg.get("type", "nms") if nms_type == "config" else nms_type
+    if out["type"] not in ("nms", "soft_nms"):
+        raise NotImplementedError(f"nms type {out['type']!r}: 'nms' and 'soft_nms' are built")
+    if "nms" not in test_cfg:
+        if nms_type == "config":
+            raise NotImplementedError("test_cfg[0] without an nms entry: only the NMS forms of mmdet's post-processing "
+                                      "are built")
+        out["forced_without_entry"] = True
+    if test_cfg.get("max_per_img", -1) > 0:
+        out["max_per_img"] = int(test_cfg["max_per_img"])
+    if out["type"] == "soft_nms":
+        hip_ops._soft_method(out["method"])   # 'gaussian' raises NotImplementedError, an unknown name ValueError
+    return out
+
+
 class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
-                 iou_threshold: Optional[float] = None):
+                 iou_threshold: Optional[float] = None, nms_type: Optional[str] = None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -51,6 +85,13 @@ class Inferencer:
             self.iou_threshold = test_cfg["nms"].get("iou_threshold", 0.8)
             if iou_threshold is not None:
                 self.iou_threshold = iou_threshold
+        nms = nms_settings(test_cfg, nms_type)
+        if nms["forced_without_entry"]:   # a forced mode on a config without an nms entry: mmcv's default threshold
+            self.with_nms = True
+            self.iou_threshold = 0.3 if iou_threshold is None else iou_threshold
+        self.nms_type, self.max_per_img = nms["type"], nms["max_per_img"]
+        self.soft_method, self.min_score = nms["method"], nms["min_score"]
+        self.soft = self.with_nms and self.nms_type == "soft_nms"
         pre = dict(self.cfg.model.data_preprocessor)
         if pre.pop("type") != "DetDataPreprocessor":
             raise AssertionError("data_preprocessor must be DetDataPreprocessor")
@@ -135,15 +176,22 @@ class Inferencer:
 
     # ---- post -----------------------------------------------------------------------------------------
     def postprocess_predictions(self, batch_boxes, batch_scores, batch_labels):
-        """score threshold + per-class NMS per image (reference :380-400)"""
+        """score threshold + per-class NMS per image (reference :380-400); with nms_type, the configured NMS and the
+        max_per_img cut"""
         out = []
         for boxes, scores, labels in zip(batch_boxes, batch_scores, batch_labels):
             if self.score_threshold > 0:
                 valid = scores > self.score_threshold
                 scores, boxes, labels = scores[valid], boxes[valid], labels[valid]
-            if self.with_nms:
+            if self.soft:
+                scores, keep = hip_ops.soft_nms(boxes, scores, labels, self.iou_threshold, self.soft_method,
+                                                self.min_score)
+                boxes, labels = boxes[keep], labels[keep]
+            elif self.with_nms:
                 keep = hip_ops.batched_nms(boxes, scores, labels, self.iou_threshold)
                 boxes, scores, labels = boxes[keep], scores[keep], labels[keep]
+            if self.max_per_img is not None:   # (after NMS the detections are in descending score order)
+                boxes, scores, labels = boxes[:self.max_per_img], scores[:self.max_per_img], labels[:self.max_per_img]
             out.append((boxes, scores, labels))
         return out
 
@@ -164,13 +212,20 @@ class Inferencer:
         boxes, scores, labels = predictions
         # the rescale divisor exactly as run_inference builds it (boxes.new_tensor of the Python floats)
         div = torch.tensor([[m["scale_factor"][0], m["scale_factor"][1]] * 2 for m in metas], dtype=boxes.dtype)
-        dets = hip_ops.postprocess_detections(boxes, scores, labels, div.to(boxes.device),
-                                              self.score_threshold if self.score_threshold > 0 else None,
-                                              self.iou_threshold if self.with_nms else None)
+        thr = self.score_threshold if self.score_threshold > 0 else None
+        if self.soft:
+            dets = hip_ops.postprocess_detections_soft(boxes, scores, labels, div.to(boxes.device), thr,
+                                                       self.iou_threshold, self.soft_method, self.min_score,
+                                                       self.max_per_img)
+        else:
+            dets = hip_ops.postprocess_detections(boxes, scores, labels, div.to(boxes.device), thr,
+                                                  self.iou_threshold if self.with_nms else None)
         host = hip_ops.detections_to_host(dets)
         out = []
         for i in range(len(metas)):
             c = int(host.count[i])
+            if self.max_per_img is not None:
+                c = min(c, self.max_per_img)
             out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
                         "bboxes": host.boxes[i, :c].float().tolist()})
         return out
@@ -186,7 +241,7 @@ class Inferencer:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
         batch_size = int(batch_size)
         results_dict = {"predictions": [], "visualization": []}
-        if batch_size == 1 and dtype != torch.bfloat16:
+        if batch_size == 1 and dtype != torch.bfloat16 and not self.soft:
             for image in images:
                 with torch.no_grad():
                     x, m, meta = self.preprocess(image, device, dtype)

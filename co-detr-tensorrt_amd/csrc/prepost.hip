@@ -16,6 +16,11 @@
 // postprocess_kernel  postprocess_predictions + the rescale of run_inference (codetr/inferencer.py:343-400) for a
 //                     batch, one workgroup per image: score threshold at the storage precision, stable descending sort
 //                     (bitonic, index tie-break), the NMS of batched_nms_kernel, boxes / scale factor, compacted output.
+// postprocess_softnms_kernel  the same place in the pipeline with the post-processing the model configs ask for
+//                     (configs/co_dino_5scale_r50_lsj_8xb2_1x_coco.py:80: max_per_img=300, nms type 'soft_nms'): mmcv's
+//                     soft-NMS, methods linear and naive, per class, then the max_per_img cut.  Classes are independent,
+//                     so after one sort by label every wave runs the greedy chains of whole classes on its own, without
+//                     a workgroup barrier per pick; a second sort orders the emitted detections by decayed score.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -298,6 +303,222 @@ __global__ __launch_bounds__(1024) void postprocess_kernel(const T* __restrict__
   if (tid == 0) count[n] = total;
 }
 
+// ---- soft-NMS (include/codetr_hip.h states the semantics) ---------------------------------------------------------
+
+// IoU of the picked box k and candidate j, fp32 with one rounding per operation (no contraction into an FMA: the areas are
+// stored rounded products, and the CPU reference rounds w * h before it subtracts); NaN for two zero-area boxes
+__device__ __forceinline__ float soft_overlap(float4 bk, float ak, float4 bj, float aj) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(0.f, fminf(bk.z, bj.z) - fmaxf(bk.x, bj.x));
+  const float h = fmaxf(0.f, fminf(bk.w, bj.w) - fmaxf(bk.y, bj.y));
+  const float inter = w * h;
+  const float uni = ak + aj;
+  return inter / (uni - inter);
+}
+
+__device__ __forceinline__ float box_area(float4 b) {
+#pragma clang fp contract(off)
+  const float w = b.z - b.x, h = b.w - b.y;
+  return w * h;
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    const unsigned long long o = __shfl_xor(v, m, 64);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// in-place descending bitonic sort of P (a power of two <= 1024) 64-bit keys in LDS; ends with a barrier (for P >= 2)
+__device__ __forceinline__ void bitonic_desc_u64(unsigned long long* s, int P, int tid) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (tid < P / 2) {
+        const int lo = 2 * tid - (tid & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long a = s[lo], b = s[hi];
+        if ((a < b) == desc) {
+          s[lo] = b;
+          s[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// grid N, 1024 threads: image n's Q candidates -> its soft-NMS detections in output order (decayed score descending,
+// ties by ascending query index), cut to max_keep, count[n] of them.  Rows [count, Q) of the outputs are zero.
+template <class T>
+__global__ __launch_bounds__(1024) void postprocess_softnms_kernel(
+    const T* __restrict__ boxes, const T* __restrict__ scores, const int64_t* __restrict__ labels,
+    const T* __restrict__ divisors, int Q, int use_thr, float thr, int linear, float iou_thr, float min_score,
+    int max_keep, T* __restrict__ boxes_out, T* __restrict__ scores_out, int64_t* __restrict__ labels_out,
+    int* __restrict__ index_out, int* __restrict__ count) {
+  constexpr int kWaves = kPostMaxQ / 64;
+  __shared__ unsigned long long s_lab[kPostMaxQ];  // sort 1, major key: the label's bits (live candidates)
+  __shared__ unsigned s_idx[kPostMaxQ];            // sort 1, minor key: 2^32 - 1 - query index; 0 = dropped
+  __shared__ unsigned long long s_out[kPostMaxQ];  // emitted: decayed score key << 32 | (2^32 - 1 - query index); else 0
+  __shared__ float4 s_box[kPostMaxQ];              // by position after sort 1 (label segments, ascending query index)
+  __shared__ float s_area[kPostMaxQ];
+  __shared__ float s_score[kPostMaxQ];             // current (decaying) score; touched by the position's own lane only
+  __shared__ unsigned short s_seg[kPostMaxQ + 1];  // first position of every label segment, then V
+  __shared__ unsigned short s_pos[kPostMaxQ];      // query index -> position
+  __shared__ unsigned long long s_wmax[kWaves];
+  __shared__ int s_wave[kWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const size_t n = blockIdx.x;
+  const T* bx = boxes + n * Q * 4;
+  const T* sc = scores + n * Q;
+  const int64_t* lb = labels + n * Q;
+  int P = 1;  // the sorts run over the next power of two >= Q
+  while (P < Q) P <<= 1;
+
+  // 1. score threshold at T's precision (as postprocess_kernel), then the global maximum g (ties: lowest index)
+  const float thr_t = to_f32(from_f32<T>(thr));
+  unsigned long long key = 0;
+  float s = 0.f;
+  if (tid < Q) {
+    s = to_f32(sc[tid]);
+    if (!use_thr || s > thr_t) key = ((unsigned long long)score_key(s) << 32) | (unsigned long long)(0xffffffffu - (unsigned)tid);
+  }
+  const unsigned long long wmax = wave_max_u64(key);
+  if (lane == 0) s_wmax[wave] = wmax;
+  __syncthreads();
+  unsigned long long g = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) g = s_wmax[w] > g ? s_wmax[w] : g;
+  // 2. everything below min_score goes, except g (mmcv emits its first pick unchecked)
+  const bool live = key != 0ull && (key == g || !(s < min_score));
+  s_lab[tid] = live ? (unsigned long long)lb[tid] : 0ull;
+  s_idx[tid] = live ? 0xffffffffu - (unsigned)tid : 0u;
+  s_out[tid] = 0ull;
+  const int V = __syncthreads_count(live);  // barrier: the sort keys are complete
+
+  // 3. bitonic sort by (label, 2^32 - 1 - index), descending: every label a contiguous segment in ascending index
+  //    order, the dropped slots last
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      if (tid < P / 2) {
+        const int lo = 2 * tid - (tid & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long al = s_lab[lo], bl = s_lab[hi];
+        const unsigned ai = s_idx[lo], bi = s_idx[hi];
+        const bool less = al < bl || (al == bl && ai < bi);
+        if (less == desc && (al != bl || ai != bi)) {
+          s_lab[lo] = bl;
+          s_lab[hi] = al;
+          s_idx[lo] = bi;
+          s_idx[hi] = ai;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const bool head = tid < V && (tid == 0 || s_lab[tid] != s_lab[tid - 1]);
+  if (tid < V) {
+    const unsigned src = 0xffffffffu - s_idx[tid];
+    const float4 b = make_float4(to_f32(bx[4 * src]), to_f32(bx[4 * src + 1]), to_f32(bx[4 * src + 2]),
+                                 to_f32(bx[4 * src + 3]));
+    s_box[tid] = b;
+    s_area[tid] = box_area(b);
+    s_score[tid] = to_f32(sc[src]);
+    s_pos[src] = (unsigned short)tid;
+  }
+  const unsigned long long hbal = __ballot(head);
+  if (lane == 0) s_wave[wave] = __popcll(hbal);
+  __syncthreads();
+  int hpos = __popcll(hbal & ((1ull << lane) - 1ull)), S = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    const int c = s_wave[w];
+    hpos += w < wave ? c : 0;
+    S += c;
+  }
+  if (head) s_seg[hpos] = (unsigned short)tid;
+  if (tid == 0) s_seg[S] = (unsigned short)V;
+  __syncthreads();
+
+  // 4. the greedy chains: a wave takes whole segments; lane l holds positions a + l + 64 e (bit e of `alive`).  The pick is
+  //    a wave reduction of (score key, 2^32 - 1 - position): highest current score, ties to the lowest position = the
+  //    lowest query index.  No workgroup barrier in here: a position's score is read and written by its own lane only.
+  for (int seg = wave; seg < S; seg += kWaves) {
+    const int a = s_seg[seg], b = s_seg[seg + 1];
+    const int ne = (b - a + 63) >> 6;  // <= 16
+    unsigned alive = 0;
+    for (int e = 0; e < ne; ++e) alive |= (a + lane + 64 * e < b) ? 1u << e : 0u;
+    for (;;) {
+      unsigned long long best = 0;
+      for (int e = 0; e < ne; ++e) {
+        if (alive >> e & 1u) {
+          const int p = a + lane + 64 * e;
+          const unsigned long long k = ((unsigned long long)score_key(s_score[p]) << 32) | (unsigned long long)(0xffffffffu - (unsigned)p);
+          best = k > best ? k : best;
+        }
+      }
+      best = wave_max_u64(best);
+      if (best == 0ull) break;  // (wave-uniform) the segment is exhausted
+      const int k = (int)(0xffffffffu - (unsigned)best);
+      if (((k - a) & 63) == lane) {  // the owner emits k with its current score and retires it
+        alive &= ~(1u << ((k - a) >> 6));
+        s_out[k] = (best & 0xffffffff00000000ull) | (unsigned long long)s_idx[k];
+      }
+      const float4 bk = s_box[k];
+      const float ak = s_area[k];
+      for (int e = 0; e < ne; ++e) {
+        if (alive >> e & 1u) {
+          const int p = a + lane + 64 * e;
+          const float ovr = soft_overlap(bk, ak, s_box[p], s_area[p]);
+          float sj = s_score[p];
+          if (ovr >= iou_thr) {  // (a NaN overlap compares false: weight 1)
+            sj = sj * (linear ? 1.f - ovr : 0.f);
+            s_score[p] = sj;
+          }
+          if (sj < min_score) alive &= ~(1u << e);
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // 5. order the emitted detections by (decayed score, 2^32 - 1 - index), cut, rescale: fp32 divide, one rounding to T
+  bitonic_desc_u64(s_out, P, tid);
+  const unsigned long long okey = s_out[tid];
+  const int E = __syncthreads_count(okey != 0ull);
+  const int M = (max_keep > 0 && max_keep < E) ? max_keep : E;
+  T* bo = boxes_out + n * Q * 4;
+  T* so = scores_out + n * Q;
+  int64_t* lo = labels_out + n * Q;
+  int* io = index_out + n * Q;
+  if (tid < M) {
+    const unsigned src = 0xffffffffu - (unsigned)okey;
+    const int p = s_pos[src];
+    const T* dv = divisors + n * 4;
+    const float4 b = s_box[p];
+    bo[4 * tid] = from_f32<T>(b.x / to_f32(dv[0]));
+    bo[4 * tid + 1] = from_f32<T>(b.y / to_f32(dv[1]));
+    bo[4 * tid + 2] = from_f32<T>(b.z / to_f32(dv[2]));
+    bo[4 * tid + 3] = from_f32<T>(b.w / to_f32(dv[3]));
+    so[tid] = from_f32<T>(s_score[p]);
+    lo[tid] = lb[src];
+    io[tid] = (int)src;
+  } else if (tid < Q) {
+    const T z = from_f32<T>(0.f);
+    bo[4 * tid] = z;
+    bo[4 * tid + 1] = z;
+    bo[4 * tid + 2] = z;
+    bo[4 * tid + 3] = z;
+    so[tid] = z;
+    lo[tid] = 0;
+    io[tid] = 0;
+  }
+  if (tid == 0) count[n] = M;
+}
+
 template <class OutT>
 int launch_pre(void* stream, const void* src, int64_t Hs, int64_t Ws, int64_t Hr, int64_t Wr, int64_t Hp, int64_t Wp,
                const float* mean, const float* stdv, const int* pad, void* dst, void* mask) {
@@ -363,6 +584,27 @@ int launch_post(void* stream, const void* boxes, const void* scores, const int64
   return err == hipSuccess ? 0 : (int)err;
 }
 
+template <class T>
+int launch_softnms(void* stream, const void* boxes, const void* scores, const int64_t* labels, const void* divisors,
+                   int64_t N, int64_t Q, int apply_threshold, float score_threshold, int method, float iou_threshold,
+                   float min_score, int64_t max_keep, void* boxes_out, void* scores_out, int64_t* labels_out,
+                   int* index_out, int* count) {
+  if (!boxes || !scores || !labels || !divisors || !boxes_out || !scores_out || !labels_out || !index_out || !count ||
+      N <= 0 || Q <= 0)
+    return CODETR_E_BADARG;
+  if (method != CODETR_SOFTNMS_NAIVE && method != CODETR_SOFTNMS_LINEAR) return CODETR_E_BADARG;
+  if (!__builtin_isfinite(iou_threshold) || !__builtin_isfinite(min_score)) return CODETR_E_BADARG;
+  if (Q > kPostMaxQ || N > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
+  const int keep = max_keep <= 0 || max_keep > Q ? 0 : (int)max_keep;
+  hipLaunchKernelGGL((postprocess_softnms_kernel<T>), dim3((unsigned)N), dim3(kPostMaxQ), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                     labels, static_cast<const T*>(divisors), (int)Q, apply_threshold ? 1 : 0, score_threshold,
+                     method == CODETR_SOFTNMS_LINEAR ? 1 : 0, iou_threshold, min_score, keep, static_cast<T*>(boxes_out),
+                     static_cast<T*>(scores_out), labels_out, index_out, count);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
 }  // namespace
 
 extern "C" {
@@ -416,5 +658,18 @@ CODETR_PRE_BATCH_ENTRY(codetr_preprocess_batch_u8_f32, float)
 CODETR_POST_ENTRY(codetr_postprocess_detections_f16, _Float16)
 CODETR_POST_ENTRY(codetr_postprocess_detections_bf16, Bf16)
 CODETR_POST_ENTRY(codetr_postprocess_detections_f32, float)
+
+#define CODETR_SOFTNMS_ENTRY(NAME, T)                                                                                 \
+  int NAME(void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,                    \
+           const void* divisor_dev, int64_t N, int64_t Q, int apply_threshold, float score_threshold, int method,     \
+           float iou_threshold, float min_score, int64_t max_keep, void* boxes_out_dev, void* scores_out_dev,         \
+           int64_t* labels_out_dev, int* index_out_dev, int* count_dev) {                                             \
+    return launch_softnms<T>(stream, boxes_dev, scores_dev, labels_dev, divisor_dev, N, Q, apply_threshold,           \
+                             score_threshold, method, iou_threshold, min_score, max_keep, boxes_out_dev,              \
+                             scores_out_dev, labels_out_dev, index_out_dev, count_dev);                               \
+  }
+CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_f16, _Float16)
+CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_bf16, Bf16)
+CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_f32, float)
 
 }  // extern "C"

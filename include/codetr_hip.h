@@ -34,7 +34,7 @@ extern "C" {
 #define CODETR_E_UNSUPPORTED (-4) /* shape outside what the kernel family implements             */
 
 /* ABI version of this header; bumped on any signature change. */
-#define CODETR_HIP_ABI_VERSION 53
+#define CODETR_HIP_ABI_VERSION 54
 int codetr_hip_abi_version(void);
 /* Human-readable message for a code returned by any entry point (static storage). */
 const char *codetr_hip_strerror(int code);
@@ -718,6 +718,35 @@ int codetr_batched_nms_f32(void *stream, const float *boxes_sorted_dev, const in
  *   Outputs, compacted per image: boxes_out_dev [N, Q, 4], scores_out_dev [N, Q] (T), labels_out_dev [N, Q] int64,
  *   count_dev [N] int32 = how many rows of image n are detections; the rows after them are zero.
  *   CODETR_E_BADARG for null pointers, N <= 0 or Q <= 0; CODETR_E_TOO_LARGE for Q > CODETR_POSTPROCESS_MAX_Q.
+ *
+ * codetr_postprocess_softnms_*: the post-processing the model configs specify -- test_cfg[0] =
+ *   dict(max_per_img=300, nms=dict(type='soft_nms', iou_threshold=0.8)), configs/co_dino_5scale_r50_lsj_8xb2_1x_coco.py:80,
+ *   inherited by all three configs -- i.e. mmcv 2.x batched_nms(..., nms_cfg=dict(type='soft_nms')) (methods linear and
+ *   naive) followed by mmdet's results[:max_per_img], with the rescale of run_inference; same operands as
+ *   codetr_postprocess_detections_*, one workgroup per image.  For image n with candidates (box_j, score_j, label_j),
+ *   j the query index:
+ *     1. boxes and scores convert to fp32 (exact); everything below is fp32 with one rounding per operation, and
+ *        area_j = (x2 - x1) * (y2 - y1) is rounded once and stored;
+ *     2. apply_threshold: as codetr_postprocess_detections_* (score > threshold at T's precision); a NaN score is
+ *        dropped in this mode (a deviation: what mmcv does with a NaN is an accident of its scan order);
+ *     3. g = the surviving candidate with the highest score (ties: lowest j); every candidate other than g whose score
+ *        is < min_score is dropped (mmcv emits its first pick unchecked and tests all others in its first pass);
+ *     4. per label, independently, while a candidate of the label is alive: pick the alive k with the highest current
+ *        score (ties: lowest j), emit (k, current score), retire k; for every other alive j of the label
+ *        w = max(0, min(x2) - max(x1)), h likewise, inter = w * h, ovr = inter / (area_k + area_j - inter);
+ *        weight = (ovr >= iou_threshold) ? (method linear: 1 - ovr, naive: 0) : 1; s_j = s_j * weight; j is dropped if
+ *        s_j < min_score.  A NaN ovr (two zero-area boxes) compares false: weight 1;
+ *     5. the emitted detections are sorted by decayed score descending (ties: ascending j); the first max_keep stay
+ *        (max_keep <= 0: all);
+ *     6. boxes / divisor_dev in fp32 rounded once to T; the score is the decayed score rounded once to T.
+ *   "Highest score" is the order of codetr_postprocess_detections_*'s sort: -0 equals +0, a NaN with the sign bit clear
+ *   is above +inf, one with it set below -inf.  Two deliberate differences from mmcv: classes are separated by
+ *   comparing labels, not by adding label * (max + 1) to the coordinates (as codetr_batched_nms_f32 already does; it
+ *   also keeps the IoUs from being rounded at coordinates around 1.5e5), and ties go to the lowest query index rather
+ *   than following mmcv's swap-with-last bookkeeping.  Method gaussian is not provided.
+ *   Outputs as codetr_postprocess_detections_* plus index_out_dev [N, Q] int32, the query index of every output row.
+ *   CODETR_E_BADARG for null pointers, N <= 0, Q <= 0, a method other than the two below, an iou_threshold or min_score
+ *   that is not finite; CODETR_E_TOO_LARGE for Q > CODETR_POSTPROCESS_MAX_Q.  All checks run before any HIP call.
  * ------------------------------------------------------------------------------------------ */
 #define CODETR_PREPROCESS_BATCH_MAX 32
 #define CODETR_POSTPROCESS_MAX_Q 1024
@@ -748,6 +777,23 @@ int codetr_postprocess_detections_f32(void *stream, const void *boxes_dev, const
                                       int apply_threshold, float score_threshold, int apply_nms, float iou_threshold,
                                       void *boxes_out_dev, void *scores_out_dev, int64_t *labels_out_dev,
                                       int *count_dev);
+#define CODETR_SOFTNMS_NAIVE 0
+#define CODETR_SOFTNMS_LINEAR 1
+int codetr_postprocess_softnms_f16(void *stream, const void *boxes_dev, const void *scores_dev,
+                                   const int64_t *labels_dev, const void *divisor_dev, int64_t N, int64_t Q,
+                                   int apply_threshold, float score_threshold, int method, float iou_threshold,
+                                   float min_score, int64_t max_keep, void *boxes_out_dev, void *scores_out_dev,
+                                   int64_t *labels_out_dev, int *index_out_dev, int *count_dev);
+int codetr_postprocess_softnms_bf16(void *stream, const void *boxes_dev, const void *scores_dev,
+                                    const int64_t *labels_dev, const void *divisor_dev, int64_t N, int64_t Q,
+                                    int apply_threshold, float score_threshold, int method, float iou_threshold,
+                                    float min_score, int64_t max_keep, void *boxes_out_dev, void *scores_out_dev,
+                                    int64_t *labels_out_dev, int *index_out_dev, int *count_dev);
+int codetr_postprocess_softnms_f32(void *stream, const void *boxes_dev, const void *scores_dev,
+                                   const int64_t *labels_dev, const void *divisor_dev, int64_t N, int64_t Q,
+                                   int apply_threshold, float score_threshold, int method, float iou_threshold,
+                                   float min_score, int64_t max_keep, void *boxes_out_dev, void *scores_out_dev,
+                                   int64_t *labels_out_dev, int *index_out_dev, int *count_dev);
 
 /* ------------------------------------------------------------------------------------------
  * Backward of multi-scale deformable attention (training path).

@@ -5,7 +5,13 @@ mixed sizes (640x480, 1280x720, 1920x1080, 800x1333, cycled).  A timed pass is `
 images and ends with their detections on the host as Python lists, so the host clock around it is the user's latency;
 each figure is the best of --repeats passes after one warm-up pass.  fp16 at batch_size 1 is the per-image path
 (preprocess_image, F.pad, batched_nms, per-image syncs); every other cell is the batched path (one upload, one
-preprocess_batch launch, one forward, one postprocess_detections launch, one download per chunk).
+preprocess_batch launch, one forward, one postprocess_detections launch, one download per chunk).  The `fp16_soft_nms`
+row is the same fp16 model behind `Inferencer(..., nms_type="config")`: soft-NMS + max_per_img as the config asks, the
+batched path at every batch size with one postprocess_softnms launch per chunk.
+
+`postprocess_launch_us`: the two post-processing kernels alone on the same inputs -- 8 images x 300 candidates, fp16,
+no score threshold (every candidate live), IoU 0.8, labels random over 80 classes / all candidates under one label --
+HIP events around 200 back-to-back launches after 20 warm-up launches, microseconds per launch.
 
 Kernel times: unless --no-profile, a child process runs the same Inferencer calls (batch 8 over 16 images in fp16 and
 bf16, batch 1 over 4 images in fp16) under `rocprofv3 --kernel-trace --stats`; the per-launch times of the pre- and
@@ -35,7 +41,8 @@ import torch  # noqa: E402
 DEV = "cuda:0"
 SIZES_WH = [(640, 480), (1280, 720), (1920, 1080), (800, 1333)]
 DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
-KERNELS = ("preprocess_batch_kernel", "postprocess_kernel", "preprocess_kernel", "batched_nms_kernel")
+KERNELS = ("preprocess_batch_kernel", "postprocess_softnms_kernel", "postprocess_kernel", "preprocess_kernel",
+           "batched_nms_kernel")
 
 
 def synthetic_images(n, seed=0):
@@ -62,6 +69,48 @@ def inferencers():
     return out
 
 
+def post_kernel_times(launches=200, warmup=20):
+    """us per launch of postprocess_softnms_kernel and postprocess_kernel on the same 8 x 300 fp16 candidates"""
+    from codetr import hip_ops
+
+    g = torch.Generator().manual_seed(0)
+    N, Q = 8, 300
+    c = torch.rand(N, Q, 2, generator=g) * 800
+    wh = torch.rand(N, Q, 2, generator=g) * 150 + 2
+    boxes = torch.cat((c, c + wh), -1)
+    boxes[:, Q // 2:] = boxes[:, :Q - Q // 2] + (torch.rand(N, Q - Q // 2, 4, generator=g) - 0.5) * 6   # near duplicates
+    boxes, scores = boxes.half().to(DEV), torch.rand(N, Q, generator=g).half().to(DEV)
+    div = torch.full((N, 4), 0.6, dtype=torch.float16, device=DEV)
+    out = {}
+    for name, labels in (("80_classes", torch.randint(0, 80, (N, Q), generator=g)), ("one_label", torch.zeros(N, Q).long())):
+        labels = labels.to(DEV)
+        calls = {"postprocess_softnms_kernel": lambda: hip_ops.postprocess_detections_soft(boxes, scores, labels, div, None, 0.8,
+                                                                                          "linear", 1e-3, 300),
+                 "postprocess_kernel": lambda: hip_ops.postprocess_detections(boxes, scores, labels, div, None, 0.8)}
+        out[name] = {}
+        for kernel, call in calls.items():
+            for _ in range(warmup):
+                dets = call()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0.record()
+            for _ in range(launches):
+                dets = call()
+            t1.record()
+            torch.cuda.synchronize()
+            out[name][kernel] = {"us_per_launch": round(t0.elapsed_time(t1) * 1e3 / launches, 2),
+                                 "detections": int(dets.count.sum())}
+    return out
+
+
+def soft_inferencer(inf):
+    """the same model behind the post-processing its config specifies (soft-NMS, max_per_img)"""
+    import bench
+    from codetr.inferencer import Inferencer
+
+    return Inferencer(inf.model, bench.CFG, dataset_meta=None, nms_type="config")
+
+
 def child(n_batch=16, n_single=4):
     """the workload traced by rocprofv3"""
     images = synthetic_images(n_batch, seed=1)
@@ -70,6 +119,8 @@ def child(n_batch=16, n_single=4):
         inf(images, device=DEV, dtype=DTYPES[name], batch_size=8)
         if name == "fp16":
             inf(images[:n_single], device=DEV, dtype=torch.float16, batch_size=1)
+            soft = soft_inferencer(inf)
+            soft(images, device=DEV, dtype=torch.float16, batch_size=8)
     torch.cuda.synchronize()
 
 
@@ -108,7 +159,7 @@ def profile(timeout_s=900):
             f["total_us"] = round(f["total_us"], 2)
         return {"command": "rocprofv3 --kernel-trace --stats -- python tools/bench_inferencer.py --child",
                 "workload": "per dtype: batch_size 8 over 16 images (+ one 8-image warm-up call); fp16 also batch_size 1 "
-                            "over 4 images", "kernels": folded}
+                            "over 4 images and nms_type='config' (soft-NMS) batch_size 8 over 16 images", "kernels": folded}
     finally:
         shutil.rmtree(out_dir, ignore_errors=True)
 
@@ -129,8 +180,10 @@ def main():
     images = synthetic_images(a.images)
     bss = [int(v) for v in a.batch_sizes.split(",")]
     res = {}
-    for name, inf in inferencers().items():
-        dt = DTYPES[name]
+    infs = inferencers()
+    infs["fp16_soft_nms"] = soft_inferencer(infs["fp16"])
+    for name, inf in infs.items():
+        dt = DTYPES[name.split("_")[0]]
         res[name] = {}
         for bs in bss:
             with torch.no_grad():
@@ -151,6 +204,7 @@ def main():
     line = {"metric": "Inferencer images/s (Swin-L config, 1152x768 pipeline, random weights)", "unit": "images/s",
             "images": a.images, "image_sizes_wh": SIZES_WH, "repeats": a.repeats, "timing": "host clock, best pass",
             "device": torch.cuda.get_device_name(0), "results": res}
+    line["postprocess_launch_us"] = post_kernel_times()
     if not a.no_profile:
         line["kernel_times"] = profile()
     print(json.dumps(line))

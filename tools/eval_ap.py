@@ -5,6 +5,7 @@ Why: the north star's accuracy bar is "box AP within 0.1 of fp32" (reference REA
 Co-DINO Swin-L checkpoint; detections leave the model through inferencer.py:380-402).  Two uses:
 
   * real weights + COCO:    python tools/eval_ap.py coco --config <cfg.py> --weights <ckpt.pth> --coco <root> [--dtype fp16]
+                            [--nms hard|config]   (config: soft-NMS + max_per_img as the config's test_cfg asks)
       runs codetr.Inferencer over val2017 (PIL decoding) and scores against instances_val2017.json -- needs the
       checkpoint and the dataset, neither of which exists offline; the evaluator itself is what the tests exercise;
   * offline PROXY:          python tools/eval_ap.py proxy [--images 8] [--size 768x512] [--dtype fp16|fp8]
@@ -214,7 +215,9 @@ def run_coco(args):
     dtype = {"fp16": torch.float16, "bf16": torch.bfloat16, "fp32": torch.float32}[args.dtype]
     model, meta = codetr.build_CoDETR(args.config, args.weights, "cuda:0")
     model = model.to(dtype)
-    inf = Inferencer(model, args.config, meta, score_threshold=0.0)
+    # --nms config: the post-processing the config specifies (soft-NMS + max_per_img, what the published AP was
+    # produced with); hard: the reference Inferencer's hard NMS at the config's IoU threshold, no cut
+    inf = Inferencer(model, args.config, meta, score_threshold=0.0, nms_type="config" if args.nms == "config" else None)
     dets, gts = [], []
     images = ann["images"][:args.limit] if args.limit else ann["images"]
     for im in images:
@@ -244,6 +247,8 @@ def main():
     c.add_argument("--coco", required=True)
     c.add_argument("--dtype", default="fp16")
     c.add_argument("--limit", type=int, default=0)
+    c.add_argument("--nms", choices=("hard", "config"), default="hard",
+                   help="hard: the reference Inferencer's hard NMS; config: test_cfg's nms type (soft_nms) + max_per_img")
     a = ap.parse_args()
     (run_proxy if a.mode == "proxy" else run_coco)(a)
 
