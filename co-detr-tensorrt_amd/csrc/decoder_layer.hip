@@ -28,11 +28,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <type_traits>
 #include <utility>
 
 #include "codetr_hip.h"
+#include "device_prims.h"
+#include "large_lds.h"
 
 // diagnostic builds only (-DCODETR_DEC_ABL=mask; WRONG results by construction, never shipped): 1 = no MSDA gather
 #ifndef CODETR_DEC_ABL
@@ -70,23 +71,10 @@ constexpr int kMaxL = 8;
 #endif
 constexpr int kDepth = CODETR_DEC_DEPTH;       // weight fragments (1 KB each) a wave keeps in flight: 256 KB per workgroup
 
-// Element type of activations and weights.  The kernel is written against `f16` / `f16x8` / `f16x4` and one MFMA wrapper;
-// decoder_layer_bf16.hip compiles this same source with CODETR_DEC_BF16 defined: bf16 storage, v_mfma_f32_16x16x32_bf16,
-// the same fp32 arithmetic everywhere in between (LayerNorms, softmax, sampling geometry, the fp32 blend of the gather),
-// entry point codetr_decoder_layer_bf16.  The pure-host queries exist once, in the fp16 translation unit.
-#ifdef CODETR_DEC_BF16
-typedef __bf16 f16;
-typedef __bf16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 f16x4 __attribute__((ext_vector_type(4)));
-#define CODETR_DEC_ENTRY codetr_decoder_layer_bf16
-#else
-typedef _Float16 f16;
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-#define CODETR_DEC_ENTRY codetr_decoder_layer_f16
-#endif
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// Element type of activations and weights: the kernel and its helpers are templates on the trait ET of device_prims.h
+// (HalfT / BFloatT: ET::elem storage, ET::frag / ET::v4 vectors of 8 / 4, ET::mfma = v_mfma_f32_16x16x32 of the type).
+// The fp32 arithmetic in between (LayerNorms, softmax, sampling geometry, the fp32 blend of the gather) is the same for
+// both; every conversion is a plain (elem) cast.
 
 // ---- packed weight blobs (include/codetr_hip.h documents the order): matrices first, then the small vectors, which
 // the kernel copies to LDS once (a bias read from global memory would sit behind the whole weight stream: vector
@@ -115,11 +103,12 @@ constexpr int kPosW1 = 0, kPosW2 = kC * 2 * kC, kPosVec = kPosW2 + kC * kC, kPos
               kPosTotal = kPosVec + kPosNVec;
 constexpr int kMaxTailVec = 11 * kC + 512 + kF + 8;   // n_ol <= 512
 
+template <class E>
 struct DecArgs {
-  const f16* x; const f16* attn; const f16* qpos; const f16* ref; const float* vr32; const f16* value;
+  const E* x; const E* attn; const E* qpos; const E* ref; const float* vr32; const E* value;
   const int64_t* shapes; const int64_t* starts;
-  const f16* tail_w; const f16* pos_w; const f16* head_w; const f16* final_norm;
-  f16* x_out; f16* ref_out; f16* qpos_out; f16* qk_out; f16* v_out;
+  const E* tail_w; const E* pos_w; const E* head_w; const E* final_norm;
+  E* x_out; E* ref_out; E* qpos_out; E* qk_out; E* v_out;
   int rows, Nq, S, L, P, n_ol;
   float eps, log2_temperature;
   TailW tw;
@@ -178,9 +167,10 @@ struct Sched {
 // phase numbers of the tail (the head's are Sched::kHeadBase + 0..4)
 constexpr int P_WO = 0, P_WOL = 1, P_WOUT = 2, P_FFN = 3, P_WR1 = kTailPhases - 3, P_WR2 = kTailPhases - 2, P_WR3 = kTailPhases - 1;
 
+template <class ET>
 struct Stream {
-  f16x8 fifo[kDepth];
-  const f16* mat[M_COUNT];
+  typename ET::frag fifo[kDepth];
+  const typename ET::elem* mat[M_COUNT];
   int wave, lane8, rot;
 };
 
@@ -188,8 +178,9 @@ struct Stream {
 // matrix is the 1 KB block at ((tile * K/32 + ks) * 64 + lane) * 8 halfs holding W[16 tile + l15][32 ks + 8 grp .. + 7] for
 // lane = 16 grp + l15 -- a wave instruction reads 8 whole 128-byte lines (row-major rows would be 16 half lines) and
 // the lane's address is a scalar + 16 * lane.
-template <class S, int I>
-__device__ __forceinline__ void issue(Stream& c) {
+template <class ET, class S, int I>
+__device__ __forceinline__ void issue(Stream<ET>& c) {
+  using V8 = typename ET::frag;
   if constexpr (I < S::total) {
     constexpr typename S::Loc loc = S::locate(I);
     constexpr Ph ph = S::at(loc.p);
@@ -200,14 +191,14 @@ __device__ __forceinline__ void issue(Stream& c) {
       const int ch = (ph.sub + c.rot) & (kF / 256 - 1);
       const int tile = (ph.mat == M_W1 ? ch * 16 : 0) + loc.t * kWaves + c.wave;
       const int ks = (ph.mat == M_W2 ? ch * 8 : 0) + loc.ks;
-      c.fifo[I % kDepth] = *reinterpret_cast<const f16x8*>(c.mat[ph.mat] + ((size_t)(tile * KST + ks) * 64) * 8 + c.lane8);
+      c.fifo[I % kDepth] = *reinterpret_cast<const V8*>(c.mat[ph.mat] + ((size_t)(tile * KST + ks) * 64) * 8 + c.lane8);
     } else {
       // (rotating the k-steps of the other products per workgroup as well was measured: slower, 858 -> 933 us per decoder)
       constexpr int ks = (ph.mat == M_WP1 ? ph.sub * 8 : 0) + loc.ks;
       constexpr int tile_c = loc.t * kWaves;               // + wave
       const int tile = ph.mat == M_WR3 ? 0 : tile_c + c.wave;   // (Wr3 is ONE tile: every wave walks it, wave 0's result counts)
-      const f16* p = c.mat[ph.mat] + ((size_t)(tile * KST + ks) * 64) * 8 + c.lane8;
-      c.fifo[I % kDepth] = *reinterpret_cast<const f16x8*>(p);
+      const typename ET::elem* p = c.mat[ph.mat] + ((size_t)(tile * KST + ks) * 64) * 8 + c.lane8;
+      c.fifo[I % kDepth] = *reinterpret_cast<const V8*>(p);
     }
   }
 }
@@ -222,48 +213,51 @@ constexpr int issued_upto(int I) {
   const int now = want < lim ? want : lim;
   return now > prev ? now : prev;
 }
-template <class S, int LO, int... Ks>
-__device__ __forceinline__ void issue_range(Stream& c, std::integer_sequence<int, Ks...>) {
-  (issue<S, LO + Ks>(c), ...);
+template <class ET, class S, int LO, int... Ks>
+__device__ __forceinline__ void issue_range(Stream<ET>& c, std::integer_sequence<int, Ks...>) {
+  (issue<ET, S, LO + Ks>(c), ...);
 }
-template <class S, int... Is>
-__device__ __forceinline__ void prime(Stream& c, std::integer_sequence<int, Is...>) {
-  (issue<S, Is>(c), ...);
+template <class ET, class S, int... Is>
+__device__ __forceinline__ void prime(Stream<ET>& c, std::integer_sequence<int, Is...>) {
+  (issue<ET, S, Is>(c), ...);
 }
-
-#ifdef CODETR_DEC_BF16
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-#else
-__device__ __forceinline__ f32x4 mfma16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
-#endif
 
 // one product of the schedule: acc[t] += W(tile wave + 8 t) . X^T over 8 k-steps, every consumed fragment replaced by
 // the one kDepth further down the stream
-template <class S, int P, int NT, int J>
-__device__ __forceinline__ void gemm_step(Stream& c, f32x4 (&acc)[NT], const f16x8 (&xf)[8]) {
+template <class S, int P, int J, class ET, int NT>
+__device__ __forceinline__ void gemm_step(Stream<ET>& c, f32x4 (&acc)[NT], const typename ET::frag (&xf)[8]) {
   constexpr int I = S::start(P) + J;
-  acc[J / 8] = mfma16(c.fifo[I % kDepth], xf[J % 8], acc[J / 8]);
+  acc[J / 8] = ET::mfma(c.fifo[I % kDepth], xf[J % 8], acc[J / 8]);
   constexpr int lo = issued_upto<S>(I - 1), hi = issued_upto<S>(I);
-  issue_range<S, lo>(c, std::make_integer_sequence<int, hi - lo>{});
+  issue_range<ET, S, lo>(c, std::make_integer_sequence<int, hi - lo>{});
 }
-template <class S, int P, int NT, int... Js>
-__device__ __forceinline__ void gemm_steps(Stream& c, f32x4 (&acc)[NT], const f16x8 (&xf)[8], std::integer_sequence<int, Js...>) {
-  (gemm_step<S, P, NT, Js>(c, acc, xf), ...);
+template <class S, int P, class ET, int NT, int... Js>
+__device__ __forceinline__ void gemm_steps(Stream<ET>& c, f32x4 (&acc)[NT], const typename ET::frag (&xf)[8],
+                                           std::integer_sequence<int, Js...>) {
+  (gemm_step<S, P, Js>(c, acc, xf), ...);
 }
-template <class S, int P, int NT>
-__device__ __forceinline__ void gemm(Stream& c, f32x4 (&acc)[NT], const f16x8 (&xf)[8]) {
+template <class S, int P, class ET, int NT>
+__device__ __forceinline__ void gemm(Stream<ET>& c, f32x4 (&acc)[NT], const typename ET::frag (&xf)[8]) {
   static_assert(S::at(P).nt == NT, "accumulator tiles do not match the schedule");
-  gemm_steps<S, P, NT>(c, acc, xf, std::make_integer_sequence<int, NT * 8>{});
+  gemm_steps<S, P>(c, acc, xf, std::make_integer_sequence<int, NT * 8>{});
 }
 
 // the 16 activation rows of an LDS buffer as MFMA B fragments: lane (row l15, group grp) holds X[row][32 ks + 8 grp ..]
-__device__ __forceinline__ void xload(f16x8 (&xf)[8], const f16* xs, const int stride, const int l15, const int grp) {
+template <class ET>
+__device__ __forceinline__ void xload(typename ET::frag (&xf)[8], const typename ET::elem* xs, const int stride, const int l15,
+                                      const int grp) {
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) xf[ks] = *reinterpret_cast<const f16x8*>(xs + l15 * stride + ks * 32 + grp * 8);
+  for (int ks = 0; ks < 8; ++ks) xf[ks] = *reinterpret_cast<const typename ET::frag*>(xs + l15 * stride + ks * 32 + grp * 8);
 }
 
-__device__ __forceinline__ f16x4 ld4(const f16* p) { return *reinterpret_cast<const f16x4*>(p); }
-__device__ __forceinline__ void st4(f16* p, f16x4 v) { *reinterpret_cast<f16x4*>(p) = v; }
+template <class ET>
+__device__ __forceinline__ typename ET::v4 ld4(const typename ET::elem* p) {
+  return *reinterpret_cast<const typename ET::v4*>(p);
+}
+template <class ET>
+__device__ __forceinline__ void st4(typename ET::elem* p, typename ET::v4 v) {
+  *reinterpret_cast<typename ET::v4*>(p) = v;
+}
 
 // workgroup barrier that orders LDS traffic only: the weight fragments in flight stay in flight
 __device__ __forceinline__ void lds_barrier() {
@@ -280,10 +274,12 @@ __device__ __forceinline__ float wave_sum(float v) {
 
 // LayerNorm of rows 2 * wave, 2 * wave + 1 of an fp16 (SRC32 = false) or fp32 [16][256] LDS buffer; gamma / beta in
 // LDS.  Two-pass statistics in fp32 as csrc/layernorm.hip.  `emit(row, col, y[4])` receives the result.
-template <bool SRC32, class Emit>
-__device__ __forceinline__ void ln_rows(const void* src, const f16* gamma, const f16* beta, const float eps, const int wave,
-                                        const int lane, Emit emit) {
-  const f16x4 g4 = ld4(gamma + 4 * lane), b4 = ld4(beta + 4 * lane);
+template <class ET, bool SRC32, class Emit>
+__device__ __forceinline__ void ln_rows(const void* src, const typename ET::elem* gamma, const typename ET::elem* beta,
+                                        const float eps, const int wave, const int lane, Emit emit) {
+  using E = typename ET::elem;
+  using V4 = typename ET::v4;
+  const V4 g4 = ld4<ET>(gamma + 4 * lane), b4 = ld4<ET>(beta + 4 * lane);
 #pragma unroll
   for (int rr = 0; rr < 2; ++rr) {
     const int row = 2 * wave + rr;
@@ -293,7 +289,7 @@ __device__ __forceinline__ void ln_rows(const void* src, const f16* gamma, const
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = t[e];
     } else {
-      const f16x4 t = ld4(static_cast<const f16*>(src) + row * kSC + 4 * lane);
+      const V4 t = ld4<ET>(static_cast<const E*>(src) + row * kSC + 4 * lane);
 #pragma unroll
       for (int e = 0; e < 4; ++e) v[e] = (float)t[e];
     }
@@ -312,29 +308,38 @@ __device__ __forceinline__ void ln_rows(const void* src, const f16* gamma, const
   }
 }
 
-template <bool TAIL, bool HEAD>
-__global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a) {
+// f(integral_constant<int, 0>), f(integral_constant<int, 1>), ...: a loop whose index is a compile-time constant in the body
+template <class F, int... Is>
+__device__ __forceinline__ void for_each_int(F f, std::integer_sequence<int, Is...>) {
+  (f(std::integral_constant<int, Is>{}), ...);
+}
+
+template <class ET, bool TAIL, bool HEAD>
+__global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs<typename ET::elem> a) {
+  using E = typename ET::elem;
+  using V8 = typename ET::frag;
+  using V4 = typename ET::v4;
   using S = Sched<TAIL, HEAD>;
   constexpr int HB_ = S::kHeadBase;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   // ---- LDS map ----
-  f16* XA = reinterpret_cast<f16*>(smem);                 // [16][kSC]  current activations (x, x1, x2, x3)
-  f16* XB = XA + kRows * kSC;                             // [16][kSC]
-  f16* XC = XB + kRows * kSC;                             // [16][kSC]
-  f16* XD = XC + kRows * kSC;                             // [16][kSC]
-  f16* QP = XD + kRows * kSC;                             // [16][kSC]  query_pos of the layer
-  f16* PJ = QP + kRows * kSC;                             // [16][kS2]  (offsets | logits) of the rows; later the sine embedding
-  f16* VT = PJ + kRows * kS2;                             // tail vectors (biases, LayerNorm parameters)
-  f16* VH = VT + kMaxTailVec;                             // head vectors
-  f16* VP = VH + kHeadNVec;                               // ref_point_head vectors
-  f16* VF = VP + kPosNVec;                                // output norm
+  E* XA = reinterpret_cast<E*>(smem);                 // [16][kSC]  current activations (x, x1, x2, x3)
+  E* XB = XA + kRows * kSC;                             // [16][kSC]
+  E* XC = XB + kRows * kSC;                             // [16][kSC]
+  E* XD = XC + kRows * kSC;                             // [16][kSC]
+  E* QP = XD + kRows * kSC;                             // [16][kSC]  query_pos of the layer
+  E* PJ = QP + kRows * kSC;                             // [16][kS2]  (offsets | logits) of the rows; later the sine embedding
+  E* VT = PJ + kRows * kS2;                             // tail vectors (biases, LayerNorm parameters)
+  E* VH = VT + kMaxTailVec;                             // head vectors
+  E* VP = VH + kHeadNVec;                               // ref_point_head vectors
+  E* VF = VP + kPosNVec;                                // output norm
   float* RF = reinterpret_cast<float*>(VF + 2 * kC);      // [16][4] sigmoid(ref) fp32, then [16][4] unactivated boxes
   int* s_meta = reinterpret_cast<int*>(RF + 2 * kRows * 4);   // [kMaxL][4] level table (H, W, start, -)
   float* s_vr = reinterpret_cast<float*>(s_meta + kMaxL * 4); // [16 rows][kMaxL][2] valid ratios of each row's image
   unsigned char* EB = reinterpret_cast<unsigned char*>(s_vr + kRows * kMaxL * 2);   // big region: entries | hidden | fp32 rows
   Entry* entries = reinterpret_cast<Entry*>(EB);          // [LP][128 pairs]
-  f16* HB = reinterpret_cast<f16*>(EB);                   // [2][16][kSC] hidden chunks of the FFN
-  float* YF = reinterpret_cast<float*>(EB + 2 * kRows * kSC * sizeof(f16));   // [16][kSF] fp32 pre-LayerNorm rows
+  E* HB = reinterpret_cast<E*>(EB);                   // [2][16][kSC] hidden chunks of the FFN
+  float* YF = reinterpret_cast<float*>(EB + 2 * kRows * kSC * sizeof(E));   // [16][kSF] fp32 pre-LayerNorm rows
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, grp = lane >> 4;
   const int row0 = blockIdx.x * kRows;
@@ -348,13 +353,13 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
   const TailW& tw = a.tw;
 
   // ---- everything small goes to LDS first: rows, vectors, level table, valid ratios, reference boxes ----
-  *reinterpret_cast<f16x8*>(XA + cr * kSC + cc) = *reinterpret_cast<const f16x8*>(a.x + (size_t)crow * kC + cc);
+  *reinterpret_cast<V8*>(XA + cr * kSC + cc) = *reinterpret_cast<const V8*>(a.x + (size_t)crow * kC + cc);
   if (TAIL) {
-    *reinterpret_cast<f16x8*>(XB + cr * kSC + cc) = *reinterpret_cast<const f16x8*>(a.attn + (size_t)crow * kC + cc);
-    *reinterpret_cast<f16x8*>(QP + cr * kSC + cc) = *reinterpret_cast<const f16x8*>(a.qpos + (size_t)crow * kC + cc);
+    *reinterpret_cast<V8*>(XB + cr * kSC + cc) = *reinterpret_cast<const V8*>(a.attn + (size_t)crow * kC + cc);
+    *reinterpret_cast<V8*>(QP + cr * kSC + cc) = *reinterpret_cast<const V8*>(a.qpos + (size_t)crow * kC + cc);
     for (int i = tid * 8; i < tw.nvec; i += kThreads * 8)
-      *reinterpret_cast<f16x8*>(VT + i) = *reinterpret_cast<const f16x8*>(a.tail_w + tw.vec + i);
-    if (!HEAD && tid < 2 * kC / 8) *reinterpret_cast<f16x8*>(VF + tid * 8) = *reinterpret_cast<const f16x8*>(a.final_norm + tid * 8);
+      *reinterpret_cast<V8*>(VT + i) = *reinterpret_cast<const V8*>(a.tail_w + tw.vec + i);
+    if (!HEAD && tid < 2 * kC / 8) *reinterpret_cast<V8*>(VF + tid * 8) = *reinterpret_cast<const V8*>(a.final_norm + tid * 8);
     if (tid < L) {
       s_meta[4 * tid] = (int)a.shapes[2 * tid];
       s_meta[4 * tid + 1] = (int)a.shapes[2 * tid + 1];
@@ -363,8 +368,8 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
     }
   }
   if (HEAD) {
-    if (tid < kHeadNVec / 8) *reinterpret_cast<f16x8*>(VH + tid * 8) = *reinterpret_cast<const f16x8*>(a.head_w + kHeadVec + tid * 8);
-    if (tid < kPosNVec / 8) *reinterpret_cast<f16x8*>(VP + tid * 8) = *reinterpret_cast<const f16x8*>(a.pos_w + kPosVec + tid * 8);
+    if (tid < kHeadNVec / 8) *reinterpret_cast<V8*>(VH + tid * 8) = *reinterpret_cast<const V8*>(a.head_w + kHeadVec + tid * 8);
+    if (tid < kPosNVec / 8) *reinterpret_cast<V8*>(VP + tid * 8) = *reinterpret_cast<const V8*>(a.pos_w + kPosVec + tid * 8);
   }
   if (tid < kRows * L * 2) {
     const int r = tid / (L * 2), j = tid % (L * 2);
@@ -379,7 +384,7 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
   }
 
   // ---- start the weight stream ----
-  Stream st;
+  Stream<ET> st;
   st.wave = wave;
   st.lane8 = lane * 8;
 #ifdef CODETR_DEC_NOROT
@@ -404,61 +409,61 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
     st.mat[M_WV] = a.head_w + kHeadWv;
   }
   DEC_STAMP(0);
-  prime<S>(st, std::make_integer_sequence<int, issued_upto<S>(-1)>{});
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(issued_upto<S>(-1)) : "memory");   // the rows / vectors above have landed; the stream flies on
+  prime<ET, S>(st, std::make_integer_sequence<int, issued_upto<S>(-1)>{});
+  wait_vmcnt<issued_upto<S>(-1)>();   // the rows / vectors above have landed; the stream flies on
   lds_barrier();
   DEC_STAMP(1);
 
   if constexpr (TAIL) {
     // ================= out-projection of the self-attention + identity, LN1 =================
     {
-      f16x8 xf[8];
-      xload(xf, XB, kSC, l15, grp);
+      V8 xf[8];
+      xload<ET>(xf, XB, kSC, l15, grp);
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      gemm<S, P_WO, 2>(st, acc, xf);
+      gemm<S, P_WO>(st, acc, xf);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int n = (wave + t * kWaves) * 16 + 4 * grp;
-        const f16x4 b4 = ld4(VT + tw.bo + n), r4 = ld4(XA + l15 * kSC + n);
-        f16x4 o;
+        const V4 b4 = ld4<ET>(VT + tw.bo + n), r4 = ld4<ET>(XA + l15 * kSC + n);
+        V4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (f16)((float)(f16)(acc[t][e] + (float)b4[e]) + (float)r4[e]);
-        st4(XC + l15 * kSC + n, o);
+        for (int e = 0; e < 4; ++e) o[e] = (E)((float)(E)(acc[t][e] + (float)b4[e]) + (float)r4[e]);
+        st4<ET>(XC + l15 * kSC + n, o);
       }
     }
     lds_barrier();
     DEC_STAMP(2);
-    ln_rows<false>(XC, VT + tw.g1, VT + tw.e1, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
-      const f16x4 p4 = ld4(QP + row * kSC + col);
-      f16x4 x1, q2;
+    ln_rows<ET, false>(XC, VT + tw.g1, VT + tw.e1, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
+      const V4 p4 = ld4<ET>(QP + row * kSC + col);
+      V4 x1, q2;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        x1[e] = (f16)y[e];
-        q2[e] = (f16)((float)x1[e] + (float)p4[e]);
+        x1[e] = (E)y[e];
+        q2[e] = (E)((float)x1[e] + (float)p4[e]);
       }
-      st4(XA + row * kSC + col, x1);
-      st4(XB + row * kSC + col, q2);
+      st4<ET>(XA + row * kSC + col, x1);
+      st4<ET>(XB + row * kSC + col, q2);
     });
     lds_barrier();
     DEC_STAMP(3);
     // ================= (offsets | logits) projection =================
     {
       const int nt_ol = a.n_ol >> 4;
-      f16x8 xf[8];
-      xload(xf, XB, kSC, l15, grp);
+      V8 xf[8];
+      xload<ET>(xf, XB, kSC, l15, grp);
       f32x4 acc[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-      gemm<S, P_WOL, 4>(st, acc, xf);
+      gemm<S, P_WOL>(st, acc, xf);
 #pragma unroll
       for (int t = 0; t < 4; ++t)
         if (wave + t * kWaves < nt_ol) {
           const int n = (wave + t * kWaves) * 16 + 4 * grp;
-          const f16x4 b4 = ld4(VT + tw.bol + n);
-          f16x4 o;
+          const V4 b4 = ld4<ET>(VT + tw.bol + n);
+          V4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (f16)(acc[t][e] + (float)b4[e]);
-          st4(PJ + l15 * kS2 + n, o);
+          for (int e = 0; e < 4; ++e) o[e] = (E)(acc[t][e] + (float)b4[e]);
+          st4<ET>(PJ + l15 * kS2 + n, o);
         }
     }
     lds_barrier();
@@ -468,7 +473,7 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
       const int pl = tid >> 2, sub = tid & 3, r = pl >> 3, m = pl & 7;
       const int gr = row0 + r < a.rows ? row0 + r : a.rows - 1;
       const int b = gr / a.Nq;
-      const f16* pj = PJ + r * kS2;
+      const E* pj = PJ + r * kS2;
       const float* s32 = RF + r * 4;
       const float* vr = s_vr + r * kMaxL * 2;
       constexpr int KMAX = kMaxLP / 4;
@@ -499,8 +504,8 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
       sum += __shfl_xor(sum, 2, 64);
       sum += __shfl_xor(sum, 1, 64);
       const float inv = 1.0f / sum;
-      const unsigned row_bytes = kM * kD * sizeof(f16);
-      const unsigned pair_base = (unsigned)b * (unsigned)a.S * row_bytes + (unsigned)m * (kD * sizeof(f16));
+      const unsigned row_bytes = kM * kD * sizeof(E);
+      const unsigned pair_base = (unsigned)b * (unsigned)a.S * row_bytes + (unsigned)m * (kD * sizeof(E));
 #pragma unroll
       for (int k = 0; k < KMAX; ++k) {
         const int pt = sub + 4 * k;
@@ -550,13 +555,13 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
       const Entry* my = entries + pl;
       int i = (CODETR_DEC_ABL & 1) ? LP : 0;
       for (; i < LP; i += GROUP) {
-        f16x8 raw[GROUP][4];
+        V8 raw[GROUP][4];
 #pragma unroll
         for (int g = 0; g < GROUP; ++g)
           if (i + g < LP) {
             const u32x4 off = my[(i + g) * 128].off;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) raw[g][k] = *reinterpret_cast<const f16x8*>(vbase + (size_t)(off[k] + lane_byte));
+            for (int k = 0; k < 4; ++k) raw[g][k] = *reinterpret_cast<const V8*>(vbase + (size_t)(off[k] + lane_byte));
           }
 #pragma unroll
         for (int g = 0; g < GROUP; ++g)
@@ -570,75 +575,67 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
             }
           }
       }
-      f16x8 packed;
+      V8 packed;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) packed[j] = (f16)acc[j];
-      *reinterpret_cast<f16x8*>(XB + r * kSC + m * kD + sub * 8) = packed;
+      for (int j = 0; j < 8; ++j) packed[j] = (E)acc[j];
+      *reinterpret_cast<V8*>(XB + r * kSC + m * kD + sub * 8) = packed;
     }
     lds_barrier();
     DEC_STAMP(6);
     // ================= output projection + identity, LN2 =================
     {
-      f16x8 xf[8];
-      xload(xf, XB, kSC, l15, grp);
+      V8 xf[8];
+      xload<ET>(xf, XB, kSC, l15, grp);
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      gemm<S, P_WOUT, 2>(st, acc, xf);
+      gemm<S, P_WOUT>(st, acc, xf);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int n = (wave + t * kWaves) * 16 + 4 * grp;
-        const f16x4 b4 = ld4(VT + tw.bout + n), r4 = ld4(XA + l15 * kSC + n);
-        f16x4 o;
+        const V4 b4 = ld4<ET>(VT + tw.bout + n), r4 = ld4<ET>(XA + l15 * kSC + n);
+        V4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (f16)((float)(f16)(acc[t][e] + (float)b4[e]) + (float)r4[e]);
-        st4(XC + l15 * kSC + n, o);
+        for (int e = 0; e < 4; ++e) o[e] = (E)((float)(E)(acc[t][e] + (float)b4[e]) + (float)r4[e]);
+        st4<ET>(XC + l15 * kSC + n, o);
       }
     }
     lds_barrier();
-    ln_rows<false>(XC, VT + tw.g2, VT + tw.e2, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
-      f16x4 x2;
+    ln_rows<ET, false>(XC, VT + tw.g2, VT + tw.e2, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
+      V4 x2;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) x2[e] = (f16)y[e];
-      st4(XA + row * kSC + col, x2);
+      for (int e = 0; e < 4; ++e) x2[e] = (E)y[e];
+      st4<ET>(XA + row * kSC + col, x2);
     });
     lds_barrier();
     DEC_STAMP(7);
     // ================= FFN: hidden chunks of 256, Y accumulated in registers, LN3 =================
     {
-      f16x8 xf[8];
-      xload(xf, XA, kSC, l15, grp);
+      V8 xf[8];
+      xload<ET>(xf, XA, kSC, l15, grp);
       f32x4 yacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
       auto chunk = [&](auto cc_) {
         constexpr int c = decltype(cc_)::value;
-        f16* hb = HB + (c & 1) * kRows * kSC;
+        E* hb = HB + (c & 1) * kRows * kSC;
         f32x4 hacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-        gemm<S, P_FFN + 2 * c, 2>(st, hacc, xf);
+        gemm<S, P_FFN + 2 * c>(st, hacc, xf);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const int n = (wave + t * kWaves) * 16 + 4 * grp;
-          const f16x4 b4 = ld4(VT + tw.b1 + ((c + st.rot) & (kF / 256 - 1)) * 256 + n);
-          f16x4 o;
+          const V4 b4 = ld4<ET>(VT + tw.b1 + ((c + st.rot) & (kF / 256 - 1)) * 256 + n);
+          V4 o;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) o[e] = (f16)fmaxf(hacc[t][e] + (float)b4[e], 0.f);
-          st4(hb + l15 * kSC + n, o);
+          for (int e = 0; e < 4; ++e) o[e] = (E)fmaxf(hacc[t][e] + (float)b4[e], 0.f);
+          st4<ET>(hb + l15 * kSC + n, o);
         }
         lds_barrier();
-        f16x8 hf[8];
-        xload(hf, hb, kSC, l15, grp);
-        gemm<S, P_FFN + 2 * c + 1, 2>(st, yacc, hf);
+        V8 hf[8];
+        xload<ET>(hf, hb, kSC, l15, grp);
+        gemm<S, P_FFN + 2 * c + 1>(st, yacc, hf);
       };
-      chunk(std::integral_constant<int, 0>{});
-      chunk(std::integral_constant<int, 1>{});
-      chunk(std::integral_constant<int, 2>{});
-      chunk(std::integral_constant<int, 3>{});
-      chunk(std::integral_constant<int, 4>{});
-      chunk(std::integral_constant<int, 5>{});
-      chunk(std::integral_constant<int, 6>{});
-      chunk(std::integral_constant<int, 7>{});
-      static_assert(kF / 256 == 8, "the chunk list above");
+      for_each_int(chunk, std::make_integer_sequence<int, kF / 256>{});
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int n = (wave + t * kWaves) * 16 + 4 * grp;
-        const f16x4 b4 = ld4(VT + tw.b2 + n), r4 = ld4(XA + l15 * kSC + n);
+        const V4 b4 = ld4<ET>(VT + tw.b2 + n), r4 = ld4<ET>(XA + l15 * kSC + n);
         f32x4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) o[e] = yacc[t][e] + (float)b4[e] + (float)r4[e];
@@ -647,65 +644,65 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
     }
     lds_barrier();
     DEC_STAMP(8);
-    ln_rows<true>(YF, VT + tw.g3, VT + tw.e3, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
-      f16x4 x3;
+    ln_rows<ET, true>(YF, VT + tw.g3, VT + tw.e3, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
+      V4 x3;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) x3[e] = (f16)y[e];
-      st4(XA + row * kSC + col, x3);
-      if (HEAD && row0 + row < a.rows) st4(a.x_out + (size_t)(row0 + row) * kC + col, x3);
+      for (int e = 0; e < 4; ++e) x3[e] = (E)y[e];
+      st4<ET>(XA + row * kSC + col, x3);
+      if (HEAD && row0 + row < a.rows) st4<ET>(a.x_out + (size_t)(row0 + row) * kC + col, x3);
     });
     lds_barrier();
     if (!HEAD) {
       // the decoder's output norm on the (rounded) last layer output
-      ln_rows<false>(XA, VF, VF + kC, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
-        f16x4 o;
+      ln_rows<ET, false>(XA, VF, VF + kC, a.eps, wave, lane, [&](int row, int col, const float (&y)[4]) {
+        V4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (f16)y[e];
-        if (row0 + row < a.rows) st4(a.x_out + (size_t)(row0 + row) * kC + col, o);
+        for (int e = 0; e < 4; ++e) o[e] = (E)y[e];
+        if (row0 + row < a.rows) st4<ET>(a.x_out + (size_t)(row0 + row) * kC + col, o);
       });
     }
     DEC_STAMP(9);
     // ================= box refinement: ref' = ref + reg_branch(x3) =================
     {
-      f16x8 xf[8];
-      xload(xf, XA, kSC, l15, grp);
+      V8 xf[8];
+      xload<ET>(xf, XA, kSC, l15, grp);
       f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-      gemm<S, P_WR1, 2>(st, acc, xf);
+      gemm<S, P_WR1>(st, acc, xf);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int n = (wave + t * kWaves) * 16 + 4 * grp;
-        const f16x4 b4 = ld4(VT + tw.br1 + n);
-        f16x4 o;
+        const V4 b4 = ld4<ET>(VT + tw.br1 + n);
+        V4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (f16)fmaxf(acc[t][e] + (float)b4[e], 0.f);
-        st4(XB + l15 * kSC + n, o);
+        for (int e = 0; e < 4; ++e) o[e] = (E)fmaxf(acc[t][e] + (float)b4[e], 0.f);
+        st4<ET>(XB + l15 * kSC + n, o);
       }
       lds_barrier();
-      xload(xf, XB, kSC, l15, grp);
+      xload<ET>(xf, XB, kSC, l15, grp);
       acc[0] = acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      gemm<S, P_WR2, 2>(st, acc, xf);
+      gemm<S, P_WR2>(st, acc, xf);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int n = (wave + t * kWaves) * 16 + 4 * grp;
-        const f16x4 b4 = ld4(VT + tw.br2 + n);
-        f16x4 o;
+        const V4 b4 = ld4<ET>(VT + tw.br2 + n);
+        V4 o;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = (f16)fmaxf(acc[t][e] + (float)b4[e], 0.f);
-        st4(XC + l15 * kSC + n, o);
+        for (int e = 0; e < 4; ++e) o[e] = (E)fmaxf(acc[t][e] + (float)b4[e], 0.f);
+        st4<ET>(XC + l15 * kSC + n, o);
       }
       lds_barrier();
-      xload(xf, XC, kSC, l15, grp);
+      xload<ET>(xf, XC, kSC, l15, grp);
       f32x4 d[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
-      gemm<S, P_WR3, 1>(st, d, xf);   // (every wave walks the stream; wave 0 holds the 4 real rows)
+      gemm<S, P_WR3>(st, d, xf);   // (every wave walks the stream; wave 0 holds the 4 real rows)
       if (wave == 0 && grp == 0) {    // lane (row l15, group 0) holds the row's 4 box deltas
-        const f16x4 b4 = ld4(VT + tw.br3);
-        f16x4 o;
+        const V4 b4 = ld4<ET>(VT + tw.br3);
+        V4 o;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          o[e] = (f16)((float)(f16)(d[0][e] + (float)b4[e]) + RF[kRows * 4 + l15 * 4 + e]);
+          o[e] = (E)((float)(E)(d[0][e] + (float)b4[e]) + RF[kRows * 4 + l15 * 4 + e]);
           RF[kRows * 4 + l15 * 4 + e] = (float)o[e];
         }
-        if (mrow_ok) st4(a.ref_out + (size_t)mrow * 4, o);
+        if (mrow_ok) st4<ET>(a.ref_out + (size_t)mrow * 4, o);
       }
     }
     lds_barrier();
@@ -728,83 +725,83 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
       const float v0 = s * s_vr[r * kMaxL * 2 + (coord & 1)];
       const float e = v0 * 6.283185307179586f;
       const int ch0 = c * 8 - j * F;
-      f16x8 o;
+      V8 o;
 #pragma unroll
       for (int p = 0; p < 4; ++p) {
         const int f = (ch0 >> 1) + p;
         const float rev = e * __builtin_amdgcn_exp2f(-a.log2_temperature * (2.0f * (float)f / (float)F)) * 0.15915494309189535f;
-        o[2 * p] = (f16)__builtin_amdgcn_sinf(rev);
-        o[2 * p + 1] = (f16)__builtin_amdgcn_cosf(rev);
+        o[2 * p] = (E)__builtin_amdgcn_sinf(rev);
+        o[2 * p + 1] = (E)__builtin_amdgcn_cosf(rev);
       }
-      *reinterpret_cast<f16x8*>(PJ + r * kS2 + c * 8) = o;
+      *reinterpret_cast<V8*>(PJ + r * kS2 + c * 8) = o;
     }
   }
   lds_barrier();
   DEC_STAMP(11);
   {
-    f16x8 xf[8];
+    V8 xf[8];
     f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    xload(xf, PJ, kS2, l15, grp);
-    gemm<S, HB_ + 0, 2>(st, acc, xf);
-    xload(xf, PJ + kC, kS2, l15, grp);
-    gemm<S, HB_ + 1, 2>(st, acc, xf);
+    xload<ET>(xf, PJ, kS2, l15, grp);
+    gemm<S, HB_ + 0>(st, acc, xf);
+    xload<ET>(xf, PJ + kC, kS2, l15, grp);
+    gemm<S, HB_ + 1>(st, acc, xf);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int n = (wave + t * kWaves) * 16 + 4 * grp;
-      const f16x4 b4 = ld4(VP + kPosB1 + n);
-      f16x4 o;
+      const V4 b4 = ld4<ET>(VP + kPosB1 + n);
+      V4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (f16)fmaxf(acc[t][e] + (float)b4[e], 0.f);
-      st4(XB + l15 * kSC + n, o);
+      for (int e = 0; e < 4; ++e) o[e] = (E)fmaxf(acc[t][e] + (float)b4[e], 0.f);
+      st4<ET>(XB + l15 * kSC + n, o);
     }
     lds_barrier();
-    xload(xf, XB, kSC, l15, grp);
+    xload<ET>(xf, XB, kSC, l15, grp);
     acc[0] = acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    gemm<S, HB_ + 2, 2>(st, acc, xf);
+    gemm<S, HB_ + 2>(st, acc, xf);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int n = (wave + t * kWaves) * 16 + 4 * grp;
-      const f16x4 b4 = ld4(VP + kPosB2 + n), x4 = ld4(XA + l15 * kSC + n);
-      f16x4 qp, q;
+      const V4 b4 = ld4<ET>(VP + kPosB2 + n), x4 = ld4<ET>(XA + l15 * kSC + n);
+      V4 qp, q;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        qp[e] = (f16)(acc[t][e] + (float)b4[e]);
-        q[e] = (f16)((float)x4[e] + (float)qp[e]);
+        qp[e] = (E)(acc[t][e] + (float)b4[e]);
+        q[e] = (E)((float)x4[e] + (float)qp[e]);
       }
-      st4(XD + l15 * kSC + n, q);
-      if (mrow_ok) st4(a.qpos_out + (size_t)mrow * kC + n, qp);
+      st4<ET>(XD + l15 * kSC + n, q);
+      if (mrow_ok) st4<ET>(a.qpos_out + (size_t)mrow * kC + n, qp);
     }
   }
   lds_barrier();
   DEC_STAMP(12);
   // in-projections of the next self-attention: [q | k] from x + qpos, v from x
   {
-    f16x8 xf[8];
-    xload(xf, XD, kSC, l15, grp);
+    V8 xf[8];
+    xload<ET>(xf, XD, kSC, l15, grp);
     f32x4 acc[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    gemm<S, HB_ + 3, 4>(st, acc, xf);
+    gemm<S, HB_ + 3>(st, acc, xf);
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const int n = (wave + t * kWaves) * 16 + 4 * grp;
-      const f16x4 b4 = ld4(VH + kHeadBqk + n);
-      f16x4 o;
+      const V4 b4 = ld4<ET>(VH + kHeadBqk + n);
+      V4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (f16)(acc[t][e] + (float)b4[e]);
-      if (mrow_ok) st4(a.qk_out + (size_t)mrow * (2 * kC) + n, o);
+      for (int e = 0; e < 4; ++e) o[e] = (E)(acc[t][e] + (float)b4[e]);
+      if (mrow_ok) st4<ET>(a.qk_out + (size_t)mrow * (2 * kC) + n, o);
     }
-    xload(xf, XA, kSC, l15, grp);
+    xload<ET>(xf, XA, kSC, l15, grp);
     f32x4 vacc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-    gemm<S, HB_ + 4, 2>(st, vacc, xf);
+    gemm<S, HB_ + 4>(st, vacc, xf);
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const int n = (wave + t * kWaves) * 16 + 4 * grp;
-      const f16x4 b4 = ld4(VH + kHeadBv + n);
-      f16x4 o;
+      const V4 b4 = ld4<ET>(VH + kHeadBv + n);
+      V4 o;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = (f16)(vacc[t][e] + (float)b4[e]);
-      if (mrow_ok) st4(a.v_out + (size_t)mrow * kC + n, o);
+      for (int e = 0; e < 4; ++e) o[e] = (E)(vacc[t][e] + (float)b4[e]);
+      if (mrow_ok) st4<ET>(a.v_out + (size_t)mrow * kC + n, o);
     }
   }
   DEC_STAMP(13);
@@ -812,10 +809,11 @@ __global__ __launch_bounds__(kThreads) void decoder_layer_kernel(const DecArgs a
 }
 
 size_t lds_bytes(int LP) {
-  const size_t fixed = (size_t)(5 * kRows * kSC + kRows * kS2 + kMaxTailVec + kHeadNVec + kPosNVec + 2 * kC) * sizeof(f16) +
+  constexpr size_t kEB = 2;   // bytes of an element, fp16 or bf16
+  const size_t fixed = (size_t)(5 * kRows * kSC + kRows * kS2 + kMaxTailVec + kHeadNVec + kPosNVec + 2 * kC) * kEB +
                        2 * kRows * 4 * sizeof(float) + kMaxL * 4 * sizeof(int) + kRows * kMaxL * 2 * sizeof(float);
   const size_t ent = (size_t)LP * 128 * sizeof(Entry);
-  const size_t ffn = 2 * kRows * kSC * sizeof(f16) + kRows * kSF * sizeof(float);
+  const size_t ffn = 2 * kRows * kSC * kEB + kRows * kSF * sizeof(float);
   return fixed + (ent > ffn ? ent : ffn);
 }
 
@@ -825,11 +823,58 @@ bool dims_ok(int num_heads, int head_dim, int L, int P, int hidden, int ref_dim,
          lds_bytes(L * P) <= 160 * 1024;   // (entries of every sample point of 128 (row, head) pairs live in LDS)
 }
 
+template <class ET, bool TAIL, bool HEAD>
+int launch(const DecArgs<typename ET::elem>& a, size_t lds, hipStream_t stream) {
+  if (const hipError_t e = allow_large_lds<decoder_layer_kernel<ET, TAIL, HEAD>>(160 * 1024); e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL((decoder_layer_kernel<ET, TAIL, HEAD>), dim3((unsigned)((a.rows + kRows - 1) / kRows)), dim3(kThreads), lds,
+                     stream, a);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
+template <class ET>
+int dec_entry(void* stream, const void* x_dev, const void* attn_dev, const void* qpos_dev, const void* ref_dev,
+              const float* valid_ratios32_dev, const void* value_dev, const int64_t* spatial_shapes_dev,
+              const int64_t* level_start_dev, const void* tail_w_dev, const void* pos_w_dev, const void* head_w_dev,
+              const void* final_norm_dev, void* x_out_dev, void* ref_out_dev, void* qpos_out_dev, void* qk_out_dev,
+              void* v_out_dev, int64_t B, int64_t Nq, int64_t S, int num_levels, int num_points, int hidden, float ln_eps,
+              float temperature) {
+  using E = typename ET::elem;
+  const bool tail = attn_dev != nullptr, head = head_w_dev != nullptr;
+  if (!x_dev || !ref_dev || !valid_ratios32_dev || B <= 0 || Nq <= 0 || temperature <= 0.f) return CODETR_E_BADARG;
+  if (!tail && !head) return CODETR_E_BADARG;
+  if (tail && (!qpos_dev || !value_dev || !spatial_shapes_dev || !level_start_dev || !tail_w_dev || !x_out_dev ||
+               !ref_out_dev || S <= 0))
+    return CODETR_E_BADARG;
+  if (head && (!pos_w_dev || !qpos_out_dev || !qk_out_dev || !v_out_dev)) return CODETR_E_BADARG;
+  if (tail && !head && !final_norm_dev) return CODETR_E_BADARG;
+  if (!dims_ok(kM, kD, num_levels, num_points, hidden, 4, kC / 2)) return CODETR_E_UNSUPPORTED;
+  if (B * Nq > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
+  if (tail && (double)B * (double)S * (kM * kD * 2) > 4294967295.0) return CODETR_E_TOO_LARGE;   // 32-bit value offsets
+  const void* ptrs[] = {x_dev, attn_dev, qpos_dev, value_dev, tail_w_dev, pos_w_dev, head_w_dev, final_norm_dev,
+                        x_out_dev, qpos_out_dev, qk_out_dev, v_out_dev};
+  for (const void* p : ptrs)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return CODETR_E_BADARG;
+  if ((reinterpret_cast<uintptr_t>(ref_dev) | reinterpret_cast<uintptr_t>(ref_out_dev)) & 7) return CODETR_E_BADARG;
+  auto in = [](const void* p) { return static_cast<const E*>(p); };
+  auto out = [](void* p) { return static_cast<E*>(p); };
+  const int n_ol = kM * num_levels * num_points * 3;
+  const DecArgs<E> a{in(x_dev), in(attn_dev), in(qpos_dev), in(ref_dev), valid_ratios32_dev, in(value_dev),
+                     spatial_shapes_dev, level_start_dev,
+                     in(tail_w_dev), in(pos_w_dev), in(head_w_dev), in(final_norm_dev),
+                     out(x_out_dev), out(ref_out_dev), out(qpos_out_dev), out(qk_out_dev), out(v_out_dev),
+                     (int)(B * Nq), (int)Nq, (int)S, num_levels, num_points, n_ol,
+                     ln_eps, log2f(temperature),
+                     tail_layout(n_ol)};   // (the member order of DecArgs, line for line)
+  const size_t lds = lds_bytes(num_levels * num_points);
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  return tail ? (head ? launch<ET, true, true>(a, lds, st) : launch<ET, true, false>(a, lds, st)) : launch<ET, false, true>(a, lds, st);
+}
+
 }  // namespace
 
 extern "C" {
 
-#ifndef CODETR_DEC_BF16
 #ifdef CODETR_DEC_STAMPS
 int codetr_decoder_layer_debug_stamps(unsigned long long* host_out) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_dec_stamps), sizeof(unsigned long long) * 32);
@@ -854,81 +899,26 @@ int64_t codetr_decoder_layer_blob_halfs(int which, int num_levels, int num_point
   }
 }
 
-#endif   // !CODETR_DEC_BF16
-
-int CODETR_DEC_ENTRY(void* stream, const void* x_dev, const void* attn_dev, const void* qpos_dev, const void* ref_dev,
+int codetr_decoder_layer_f16(void* stream, const void* x_dev, const void* attn_dev, const void* qpos_dev, const void* ref_dev,
                              const float* valid_ratios32_dev, const void* value_dev, const int64_t* spatial_shapes_dev,
                              const int64_t* level_start_dev, const void* tail_w_dev, const void* pos_w_dev,
                              const void* head_w_dev, const void* final_norm_dev, void* x_out_dev, void* ref_out_dev,
                              void* qpos_out_dev, void* qk_out_dev, void* v_out_dev, int64_t B, int64_t Nq, int64_t S,
                              int num_levels, int num_points, int hidden, float ln_eps, float temperature) {
-  const bool tail = attn_dev != nullptr, head = head_w_dev != nullptr;
-  if (!x_dev || !ref_dev || !valid_ratios32_dev || B <= 0 || Nq <= 0 || temperature <= 0.f) return CODETR_E_BADARG;
-  if (!tail && !head) return CODETR_E_BADARG;
-  if (tail && (!qpos_dev || !value_dev || !spatial_shapes_dev || !level_start_dev || !tail_w_dev || !x_out_dev ||
-               !ref_out_dev || S <= 0))
-    return CODETR_E_BADARG;
-  if (head && (!pos_w_dev || !qpos_out_dev || !qk_out_dev || !v_out_dev)) return CODETR_E_BADARG;
-  if (tail && !head && !final_norm_dev) return CODETR_E_BADARG;
-  if (!dims_ok(kM, kD, num_levels, num_points, hidden, 4, kC / 2)) return CODETR_E_UNSUPPORTED;
-  if (B * Nq > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
-  if (tail && (double)B * (double)S * (kM * kD * 2) > 4294967295.0) return CODETR_E_TOO_LARGE;   // 32-bit value offsets
-  const void* ptrs[] = {x_dev, attn_dev, qpos_dev, value_dev, tail_w_dev, pos_w_dev, head_w_dev, final_norm_dev,
-                        x_out_dev, qpos_out_dev, qk_out_dev, v_out_dev};
-  for (const void* p : ptrs)
-    if (reinterpret_cast<uintptr_t>(p) & 15) return CODETR_E_BADARG;
-  if ((reinterpret_cast<uintptr_t>(ref_dev) | reinterpret_cast<uintptr_t>(ref_out_dev)) & 7) return CODETR_E_BADARG;
-  DecArgs a{};
-  a.x = static_cast<const f16*>(x_dev);
-  a.attn = static_cast<const f16*>(attn_dev);
-  a.qpos = static_cast<const f16*>(qpos_dev);
-  a.ref = static_cast<const f16*>(ref_dev);
-  a.vr32 = valid_ratios32_dev;
-  a.value = static_cast<const f16*>(value_dev);
-  a.shapes = spatial_shapes_dev;
-  a.starts = level_start_dev;
-  a.tail_w = static_cast<const f16*>(tail_w_dev);
-  a.pos_w = static_cast<const f16*>(pos_w_dev);
-  a.head_w = static_cast<const f16*>(head_w_dev);
-  a.final_norm = static_cast<const f16*>(final_norm_dev);
-  a.x_out = static_cast<f16*>(x_out_dev);
-  a.ref_out = static_cast<f16*>(ref_out_dev);
-  a.qpos_out = static_cast<f16*>(qpos_out_dev);
-  a.qk_out = static_cast<f16*>(qk_out_dev);
-  a.v_out = static_cast<f16*>(v_out_dev);
-  a.rows = (int)(B * Nq);
-  a.Nq = (int)Nq;
-  a.S = (int)S;
-  a.L = num_levels;
-  a.P = num_points;
-  a.n_ol = kM * num_levels * num_points * 3;
-  a.eps = ln_eps;
-  a.log2_temperature = log2f(temperature);
-  a.tw = tail_layout(a.n_ol);
-  const size_t lds = lds_bytes(num_levels * num_points);
-  const void* kfn = tail ? (head ? reinterpret_cast<const void*>(decoder_layer_kernel<true, true>)
-                                : reinterpret_cast<const void*>(decoder_layer_kernel<true, false>))
-                         : reinterpret_cast<const void*>(decoder_layer_kernel<false, true>);
-  {
-    static std::atomic<uint32_t> done[64];   // bit = instantiation, index = device ordinal
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0, done[0].store(0);
-    const uint32_t bit = tail ? (head ? 1u : 2u) : 4u;
-    if (!(done[dev].load(std::memory_order_acquire) & bit)) {
-      const hipError_t e = hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return (int)e;
-      done[dev].fetch_or(bit, std::memory_order_release);
-    }
-  }
-  const unsigned blocks = (unsigned)((a.rows + kRows - 1) / kRows);
-  if (tail && head)
-    hipLaunchKernelGGL((decoder_layer_kernel<true, true>), dim3(blocks), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a);
-  else if (tail)
-    hipLaunchKernelGGL((decoder_layer_kernel<true, false>), dim3(blocks), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a);
-  else
-    hipLaunchKernelGGL((decoder_layer_kernel<false, true>), dim3(blocks), dim3(kThreads), lds, static_cast<hipStream_t>(stream), a);
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return dec_entry<HalfT>(stream, x_dev, attn_dev, qpos_dev, ref_dev, valid_ratios32_dev, value_dev, spatial_shapes_dev,
+                          level_start_dev, tail_w_dev, pos_w_dev, head_w_dev, final_norm_dev, x_out_dev, ref_out_dev,
+                          qpos_out_dev, qk_out_dev, v_out_dev, B, Nq, S, num_levels, num_points, hidden, ln_eps, temperature);
+}
+
+int codetr_decoder_layer_bf16(void* stream, const void* x_dev, const void* attn_dev, const void* qpos_dev, const void* ref_dev,
+                              const float* valid_ratios32_dev, const void* value_dev, const int64_t* spatial_shapes_dev,
+                              const int64_t* level_start_dev, const void* tail_w_dev, const void* pos_w_dev,
+                              const void* head_w_dev, const void* final_norm_dev, void* x_out_dev, void* ref_out_dev,
+                              void* qpos_out_dev, void* qk_out_dev, void* v_out_dev, int64_t B, int64_t Nq, int64_t S,
+                              int num_levels, int num_points, int hidden, float ln_eps, float temperature) {
+  return dec_entry<BFloatT>(stream, x_dev, attn_dev, qpos_dev, ref_dev, valid_ratios32_dev, value_dev, spatial_shapes_dev,
+                            level_start_dev, tail_w_dev, pos_w_dev, head_w_dev, final_norm_dev, x_out_dev, ref_out_dev,
+                            qpos_out_dev, qk_out_dev, v_out_dev, B, Nq, S, num_levels, num_points, hidden, ln_eps, temperature);
 }
 
 }  // extern "C"

@@ -11,11 +11,11 @@
 // accumulation, one rounding at the store.
 #include <hip/hip_runtime.h>
 
-#include <atomic>
 #include <stdint.h>
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "large_lds.h"
 
 namespace {
 
@@ -196,18 +196,7 @@ int mha_entry(void* stream, const void* q, const void* k, const void* v, void* o
   if (blocks > 0x7fffffffLL || Nq > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
   const int NP = ((int)Nk + 31) & ~31;
   const size_t lds = (size_t)NP * 128;
-  {
-    // per device (the attribute belongs to the current device's function object), not per process
-    static std::atomic<bool> done[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0, done[0].store(false);
-    if (!done[dev].load(std::memory_order_acquire)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(mha_attention_kernel<ET>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, kMaxKeys * 128);
-      if (e != hipSuccess) return (int)e;
-      done[dev].store(true, std::memory_order_release);
-    }
-  }
+  if (const hipError_t e = allow_large_lds<mha_attention_kernel<ET>>(kMaxKeys * 128); e != hipSuccess) return (int)e;
   const float scale_log2e = 1.4426950408889634f / sqrtf((float)HD);
   hipLaunchKernelGGL(mha_attention_kernel<ET>, dim3((unsigned)blocks), dim3(kThreads), lds,
                      static_cast<hipStream_t>(stream), static_cast<const E*>(q), static_cast<const E*>(k),

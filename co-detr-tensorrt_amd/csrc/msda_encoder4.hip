@@ -32,11 +32,11 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "large_lds.h"
 
 namespace {
 
@@ -756,17 +756,10 @@ int launch4(hipStream_t st, const void* value, const int64_t* shapes, const void
   pl.g.head_major = head_major ? 1 : 0;
   typedef void (*Kern)(const _Float16*, const unsigned short*, unsigned short*, const Geom4, const int);
   const Kern kern = threads == 512 ? msda_encoder_v4_kernel<ET, 512> : msda_encoder_v4_kernel<ET, 256>;
-  {
-    static std::atomic<uint32_t> done[64];   // > 64 KB of dynamic LDS: the attribute is per (device, function); one table per ET
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0, done[0].store(0);
-    const uint32_t bit = threads == 512 ? 2u : 1u;
-    if (!(done[dev].load(std::memory_order_acquire) & bit)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kMaxLds);
-      if (e != hipSuccess) return (int)e;
-      done[dev].fetch_or(bit, std::memory_order_release);
-    }
-  }
+  if (const hipError_t e = threads == 512 ? allow_large_lds<msda_encoder_v4_kernel<ET, 512>>(kMaxLds)
+                                          : allow_large_lds<msda_encoder_v4_kernel<ET, 256>>(kMaxLds);
+      e != hipSuccess)
+    return (int)e;
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3((unsigned)threads), pl.lds, st, static_cast<const _Float16*>(value),
                      static_cast<const unsigned short*>(packed), static_cast<unsigned short*>(out), pl.g, (int)packed_stride);
   const hipError_t err = hipGetLastError();

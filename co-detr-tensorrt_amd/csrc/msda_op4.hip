@@ -35,11 +35,11 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
-#include <atomic>
 #include <type_traits>
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "large_lds.h"
 #include "msda_op4_plan.h"
 
 namespace {
@@ -553,17 +553,7 @@ int op4_forward(void* stream, const void* value_dev, const int64_t* spatial_shap
   if ((reinterpret_cast<uintptr_t>(value_dev) | reinterpret_cast<uintptr_t>(loc_dev) | reinterpret_cast<uintptr_t>(out_dev)) & 15)
     return CODETR_E_UNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(weight_dev) & 7) return CODETR_E_UNSUPPORTED;
-  {
-    static std::atomic<uint32_t> done[64];   // > 64 KB of dynamic LDS: the attribute is per (device, function)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0, done[0].store(0);
-    if (!done[dev].load(std::memory_order_acquire)) {
-      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(msda_op4_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)kLdsBytes);
-      if (e != hipSuccess) return (int)e;
-      done[dev].store(1, std::memory_order_release);
-    }
-  }
+  if (const hipError_t e = allow_large_lds<msda_op4_kernel<T>>((int)kLdsBytes); e != hipSuccess) return (int)e;
   const int grid = device_cus() / 8 * 8 * 2;   // two workgroups per CU, a multiple of 8
   hipLaunchKernelGGL(msda_op4_kernel<T>, dim3((unsigned)grid), dim3(kThreads), kLdsBytes, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(value_dev), spatial_shapes_dev, level_start_dev,

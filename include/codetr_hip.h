@@ -953,7 +953,7 @@ int codetr_decoder_layer_f16(void *stream, const void *x_dev, const void *attn_d
                              int64_t Nq, int64_t S, int num_levels, int num_points, int hidden, float ln_eps,
                              float temperature);
 /* bf16 twin: bf16 activations / weights / outputs, v_mfma_f32_16x16x32_bf16, the same fp32 arithmetic in between (the
- * same source compiled with bf16 storage, csrc/decoder_layer_bf16.hip). */
+ * kernel template of csrc/decoder_layer.hip instantiated on the bf16 element trait). */
 int codetr_decoder_layer_bf16(void *stream, const void *x_dev, const void *attn_dev, const void *qpos_dev,
                              const void *ref_dev, const float *valid_ratios32_dev, const void *value_dev,
                              const int64_t *spatial_shapes_dev, const int64_t *level_start_dev, const void *tail_w_dev,

@@ -96,8 +96,8 @@ def test_one_launch_per_layer_matches_the_separate_launches(B, Nq, layers, level
 
 
 def test_bf16_one_launch_per_layer_matches_the_separate_launches():
-    """codetr_decoder_layer_bf16 (the same source compiled with bf16 storage): same launch counts as fp16, and as close to
-    the separate bf16 launches as 8 mantissa bits allow (different summation order; a bf16 ulp is 2^-8)"""
+    """codetr_decoder_layer_bf16 (the kernel template instantiated on the bf16 element trait): same launch counts as fp16,
+    and as close to the separate bf16 launches as 8 mantissa bits allow (different summation order; a bf16 ulp is 2^-8)"""
     from codetr import _cabi
 
     layers = 3

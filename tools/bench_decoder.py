@@ -1,5 +1,5 @@
 """Time the DINO decoder (6 layers, 900 queries) alone, as a replayed HIP graph, at the headline pyramid.
-    python tools/bench_decoder.py [--batch 1] [--res 1920x1280]
+    python tools/bench_decoder.py [--batch 1] [--res 1920x1280] [--dtype fp16|bf16]
 Inputs are captured from one full forward of the seeded random-init model (bench.build_model)."""
 import argparse
 import os
@@ -17,6 +17,7 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--res", default="1920x1280")
     ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--dtype", default="fp16", choices=["fp16", "bf16"])
     a = ap.parse_args()
     import bench
     from codetr import _cabi
@@ -25,11 +26,12 @@ def main():
         _cabi.LIB_PATH, _cabi._lib, _cabi._rec_lib = os.environ["CODETR_LIB"], None, None
     dev = torch.device("cuda:0")
     W, H = (int(v) for v in a.res.split("x"))
-    model = bench.build_model(dev, torch.float16)
+    dtype = {"fp16": torch.float16, "bf16": torch.bfloat16}[a.dtype]
+    model = bench.build_model(dev, dtype)
     dec = model.query_head.transformer.decoder
     g = torch.Generator().manual_seed(1)
-    img = torch.randn(a.batch, 3, H, W, generator=g).to(dev, torch.float16)
-    mask = torch.zeros(a.batch, H, W, device=dev, dtype=torch.float16)
+    img = torch.randn(a.batch, 3, H, W, generator=g).to(dev, dtype)
+    mask = torch.zeros(a.batch, H, W, device=dev, dtype=dtype)
     grabbed = {}
     orig = dec.forward_bf
 
@@ -74,7 +76,7 @@ def main():
         t = list(buf)
         print("stamps of a tail + head launch (clock ticks since the kernel's first stamp):", [int(v - t[0]) for v in t[:14]])
         print("stamps of the last (tail-only) launch:", [int(v - t[16]) for v in t[16:26]])
-    print(f"decoder batch {a.batch} {a.res}: {e0.elapsed_time(e1) / a.iters * 1e3:.1f} us per replay, {launches} C-ABI launches")
+    print(f"decoder {a.dtype} batch {a.batch} {a.res}: {e0.elapsed_time(e1) / a.iters * 1e3:.1f} us per replay, {launches} C-ABI launches")
 
 
 if __name__ == "__main__":

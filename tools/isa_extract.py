@@ -2,9 +2,10 @@
 and (optionally) the longest loop bodies.  Usage: python tools/isa_extract.py file.s <substring of the mangled name> [out.s]
 
 Compare two listings (or two directories of *.s with equal file names), e.g. before and after a change to a shared header:
-    python tools/isa_extract.py diff old.s new.s [--rename OLD=NEW ...]
-Kernels are paired by demangled name without namespace qualifiers (--rename maps a type name of the old listing that the
-change renamed); of each pair the instruction text is compared after dropping labels, directives, comments and symbol
+    python tools/isa_extract.py diff old.s new.s [--rename OLD=NEW ...] [--only TEXT]
+Kernels are paired by demangled name without namespace qualifiers (--rename maps a piece of a name of the old listing that
+the change renamed, e.g. 'kernel<=kernel<HalfT, ' for a template that gained a parameter; --only keeps the kernels of
+either listing whose name, after renaming, contains TEXT -- one element type of a listing that holds two); of each pair the instruction text is compared after dropping labels, directives, comments and symbol
 names, and the .amdhsa_ resource block (registers, LDS, scratch).  One line per kernel: `identical`, `same instructions,
 different order`, or `different` with counts; the exit status is 1 if any kernel is different or unpaired."""
 import collections
@@ -82,8 +83,8 @@ def by_plain_name(path, renames):
     return out
 
 
-def diff_listings(old, new, renames):
-    a, b = by_plain_name(old, renames), by_plain_name(new, [])
+def diff_listings(old, new, renames, only=""):
+    a, b = ({k: v for k, v in by_plain_name(path, rn).items() if only in k} for path, rn in ((old, renames), (new, [])))
     bad = 0
     for name in sorted(set(a) | set(b)):
         short = name if len(name) <= 150 else name[:147] + "..."
@@ -110,7 +111,9 @@ def diff_listings(old, new, renames):
 
 def diff_main(argv):
     renames = [tuple(argv[i + 1].split("=")) for i, x in enumerate(argv) if x == "--rename"]
-    old, new = [x for i, x in enumerate(argv) if x != "--rename" and (i == 0 or argv[i - 1] != "--rename")]
+    only = "".join(argv[i + 1] for i, x in enumerate(argv) if x == "--only")
+    flags = ("--rename", "--only")
+    old, new = [x for i, x in enumerate(argv) if x not in flags and (i == 0 or argv[i - 1] not in flags)]
     if os.path.isdir(old):
         pairs = [(os.path.join(old, f), os.path.join(new, f)) for f in sorted(os.listdir(old)) if f.endswith(".s")]
     else:
@@ -118,7 +121,7 @@ def diff_main(argv):
     total = bad = 0
     for o, n in pairs:
         print(os.path.basename(o))
-        t, b = diff_listings(o, n, renames)
+        t, b = diff_listings(o, n, renames, only)
         total, bad = total + t, bad + b
     print(f"{total} kernels and device functions in {len(pairs)} listing(s): {bad} different or unpaired")
     return 1 if bad else 0
