@@ -117,6 +117,15 @@ SIGNATURES = {
                                                ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_postprocess_softnms_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
                                               ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_preprocess_views_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_preprocess_views_u8_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_preprocess_views_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_tta_merge_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
+                                    ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_tta_merge_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
+                                     ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_tta_merge_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
+                                    ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_patch_merge_layernorm_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_patch_merge_layernorm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_mask_pyramid": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32]),
@@ -185,6 +194,7 @@ CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 
          "sine_pos_tokens": 0, "ffn_fused": 0, "ffn_oproj_fused": 0, "linear_splitk": 0, "linear_sk": 0, "mask_pyramid": 0,
          "query_sine_embed": 0, "encoder_geometry": 0, "row_max": 0, "preprocess": 0, "batched_nms": 0,
          "preprocess_batch": 0, "postprocess_detections": 0, "postprocess_softnms": 0,
+         "preprocess_views": 0, "tta_merge": 0,
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
@@ -583,6 +593,43 @@ def postprocess_softnms(boxes, scores, labels, divisors, score_threshold, method
         int(method), float(iou_threshold), float(min_score), int(max_keep), boxes_out.data_ptr(), scores_out.data_ptr(),
         labels_out.data_ptr(), index_out.data_ptr(), count.data_ptr())
     check(rc, "codetr_postprocess_softnms")
+
+
+TTA_MAX_VIEWS = 16             # CODETR_TTA_MAX_VIEWS: views per codetr_tta_merge_* launch
+TTA_MAX_CANDIDATES = 4096      # CODETR_TTA_MAX_CANDIDATES: views * detections per view
+TTA_NMS_MODES = {"nms": 0, "naive": 1, "linear": 2}   # CODETR_TTA_NMS_HARD / _SOFT_NAIVE / _SOFT_LINEAR
+_PRE_VIEWS_BY_DTYPE = {torch.float16: "codetr_preprocess_views_u8_f16", torch.bfloat16: "codetr_preprocess_views_u8_bf16",
+                       torch.float32: "codetr_preprocess_views_u8_f32"}
+_TTA_MERGE_BY_DTYPE = {torch.float16: "codetr_tta_merge_f16", torch.bfloat16: "codetr_tta_merge_bf16",
+                       torch.float32: "codetr_tta_merge_f32"}
+
+
+def preprocess_views_u8(src, rows, batch_hw, mean, std, pad_value, pad_fill, dst, mask):
+    """preprocess_batch_u8 with eight values per row: (..., W_pad, flip); flip = 1 mirrors the resized image inside its
+    resized width; rows may share a src_offset"""
+    CALLS["preprocess_views"] += 1
+    N = len(rows)
+    H, W = batch_hw
+    table = (ctypes.c_int64 * (8 * N))(*[int(v) for row in rows for v in row])
+    f3 = ctypes.c_float * 3
+    rc = getattr(load(), _PRE_VIEWS_BY_DTYPE[dst.dtype])(
+        current_stream_ptr(src.device), src.data_ptr(), src.numel(), N, table, H, W, f3(*[float(v) for v in mean]),
+        f3(*[float(v) for v in std]), (ctypes.c_int * 3)(*[int(v) for v in pad_value]), float(pad_fill), dst.data_ptr(),
+        mask.data_ptr() if mask is not None else None)
+    check(rc, "codetr_preprocess_views_u8")
+
+
+def tta_merge(boxes, scores, labels, count, flip_mask, width, mode, iou_threshold, min_score, max_keep, boxes_out,
+              scores_out, labels_out, index_out, count_out):
+    """boxes [V,N,Q,4] / scores [V,N,Q] in one dtype, labels [V,N,Q] int64, count [V,N] int32, width [N] fp32; mode a
+    value of TTA_NMS_MODES; outputs [N,K,..] with K = max_keep, or V*Q when max_keep <= 0 (include/codetr_hip.h)"""
+    CALLS["tta_merge"] += 1
+    V, N, Q = scores.shape
+    rc = getattr(load(), _TTA_MERGE_BY_DTYPE[scores.dtype])(
+        current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(),
+        V, N, Q, int(flip_mask), width.data_ptr(), int(mode), float(iou_threshold), float(min_score), int(max_keep),
+        boxes_out.data_ptr(), scores_out.data_ptr(), labels_out.data_ptr(), index_out.data_ptr(), count_out.data_ptr())
+    check(rc, "codetr_tta_merge")
 
 
 def mask_pyramid(img_masks, shapes):

@@ -656,6 +656,99 @@ def soft_nms(boxes, scores, labels, iou_threshold, method="linear", min_score=1e
     return dets.scores[0, :c].to(scores.dtype), dets.index[0, :c].to(torch.int64)
 
 
+TTA_MAX_VIEWS = _cabi.TTA_MAX_VIEWS
+TTA_MAX_CANDIDATES = _cabi.TTA_MAX_CANDIDATES
+
+
+def preprocess_views(src_u8, rows8, batch_hw, mean, std, pad_val=(0, 0, 0), pad_value=0.0, dtype=torch.float16,
+                     with_mask=True):
+    """preprocess_batch for test-time augmentation's views: rows8 has one row per VIEW, (src_offset, H_src, W_src,
+    H_resized, W_resized, H_pad, W_pad, flip).  flip = 1 writes the resized image mirrored left to right inside its
+    resized width (mmdet flips after Resize and before any padding: the padding stays on the right, the mask does not
+    change); rows may share a src_offset, so the views of an image read its one uploaded copy.  -> (batch_inputs
+    [N, 3, H, W], img_masks [N, H, W] or None), N = len(rows8); one launch per PREPROCESS_BATCH_MAX rows."""
+    _gpu(src_u8, "preprocess_views")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
+        raise ValueError("expected one contiguous flat uint8 buffer")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"preprocess_views writes f16, bf16 or f32, not {dtype}")
+    if any(len(r) != 8 for r in rows8):
+        raise ValueError("preprocess_views: eight values per row, the last one the flip (0 or 1)")
+    N = len(rows8)
+    H, W = (int(v) for v in batch_hw)
+    x = torch.empty((N, 3, H, W), dtype=dtype, device=src_u8.device)
+    m = torch.empty((N, H, W), dtype=dtype, device=src_u8.device) if with_mask else None
+    with torch.cuda.device(src_u8.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            _cabi.preprocess_views_u8(src_u8, rows8[i:j], (H, W), mean, std, pad_val, pad_value, x[i:j],
+                                      m[i:j] if m is not None else None)
+    return x, m
+
+
+def _tta_mode(nms):
+    """tta_cfg.nms -> (mode of codetr_tta_merge_*, iou_threshold, min_score); mmcv's defaults where a key is absent"""
+    kind = nms.get("type", "nms")
+    if kind == "nms":
+        return _cabi.TTA_NMS_MODES["nms"], float(nms.get("iou_threshold", 0.5)), 0.0
+    if kind != "soft_nms":
+        raise NotImplementedError(f"tta nms type {kind!r}: 'nms' and 'soft_nms' are built")
+    method = nms.get("method", "linear")
+    _soft_method(method)   # 'gaussian' raises NotImplementedError, an unknown name ValueError
+    return _cabi.TTA_NMS_MODES[method], float(nms.get("iou_threshold", 0.3)), float(nms.get("min_score", 1e-3))
+
+
+def tta_merge(view_dets, flips, widths, nms=None, max_per_img=None):
+    """mmdet DetTTAModel._merge_single_sample for a batch of N images in one launch (csrc/prepost.hip; semantics:
+    include/codetr_hip.h): the views' detections un-flipped, concatenated, batched_nms(nms), the best max_per_img kept.
+      view_dets    the per-view results of postprocess_detections / postprocess_detections_soft, boxes already in
+                   original-image coordinates.  Each entry holds one or more views of all N images, view-major (its
+                   leading dimension is a multiple of N); the entries are concatenated in order, so view v is row block v
+      flips        one bool per view: the view was flipped horizontally
+      widths       [N] original image widths (a tensor on the device, or numbers)
+      nms          dict(type='nms' | 'soft_nms', iou_threshold, [method 'linear' | 'naive', min_score]); None: hard, 0.5
+      max_per_img  None: all
+    -> SoftDetections over [N, K] rows (K = max_per_img, or V * Q): `index` is c = v * Q + j of every row, scores are
+    the decayed ones in the soft modes; `detections_to_host` fetches all of it in one copy."""
+    mode, iou, min_score = _tta_mode(dict(nms) if nms is not None else {})
+    if not view_dets:
+        raise ValueError("tta_merge: no views")
+    scores0 = view_dets[0].scores
+    _gpu(scores0, "tta_merge")
+    dtype, dev, Q = scores0.dtype, scores0.device, scores0.shape[-1]
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError("tta_merge: detections in f16, bf16 or f32")
+    if not torch.is_tensor(widths):
+        widths = torch.tensor([float(w) for w in widths], dtype=torch.float32)
+    N = widths.numel()
+    if N == 0 or any(d.scores.dim() != 2 or d.scores.shape[0] % N or d.scores.shape[1] != Q or d.scores.dtype != dtype
+                     for d in view_dets):
+        raise ValueError("tta_merge: every entry [views * N, Q] detections of one dtype, N = len(widths) > 0")
+    V = sum(d.scores.shape[0] for d in view_dets) // N
+    flips = [bool(f) for f in flips]
+    if len(flips) != V:
+        raise ValueError(f"tta_merge: {V} views but {len(flips)} flip flags")
+    if V > TTA_MAX_VIEWS or V * Q > TTA_MAX_CANDIDATES:
+        raise ValueError(f"tta_merge: at most {TTA_MAX_VIEWS} views and {TTA_MAX_CANDIDATES} candidates per image, "
+                         f"got {V} views of {Q}")
+    one = len(view_dets) == 1
+    boxes = (view_dets[0].boxes if one else torch.cat([d.boxes for d in view_dets])).contiguous()
+    scores = (view_dets[0].scores if one else torch.cat([d.scores for d in view_dets])).contiguous()
+    labels = (view_dets[0].labels if one else torch.cat([d.labels for d in view_dets])).contiguous()
+    count = (view_dets[0].count if one else torch.cat([d.count for d in view_dets])).contiguous()
+    keep = 0 if max_per_img is None else int(max_per_img)
+    K = keep if keep > 0 else V * Q
+    nbytes = N * K * 12 + N * 4 + N * K * 5 * scores.element_size()
+    if Q == 0:
+        return _soft_detection_views(torch.zeros((nbytes,), dtype=torch.uint8, device=dev), N, K, dtype)
+    out = _soft_detection_views(torch.empty((nbytes,), dtype=torch.uint8, device=dev), N, K, dtype)
+    with torch.cuda.device(dev):
+        _cabi.tta_merge(boxes.view(V, N, Q, 4), scores.view(V, N, Q), labels.view(V, N, Q), count.view(V, N),
+                        sum(1 << v for v, f in enumerate(flips) if f), widths.to(dev, torch.float32).contiguous(), mode,
+                        iou, min_score, keep, out.boxes, out.scores, out.labels, out.index, out.count)
+    return out
+
+
 def mask_pyramid(img_masks, shapes):
     """img_masks [B,H,W] (float 0/1, bool or uint8; non-zero = padding) + level shapes [(H_l, W_l)] ->
     (mask_flat [B,S] bool, ycum, xcum, valid_counts [B,L,2] fp32): the level masks (nearest resize), their running

@@ -27,6 +27,20 @@ as mmdet does: ``nms.type`` ``'nms'`` is hard NMS, ``'soft_nms'`` is mmcv's soft
 ``"nms"`` / ``"soft_nms"`` force the mode with the other parameters still from the config.  In soft mode the returned
 scores are the decayed ones, every call takes the chunked path and ``postprocess_batch`` is one
 ``hip_ops.postprocess_detections_soft`` launch per chunk; ``run_inference`` uses ``hip_ops.soft_nms``.
+
+``tta`` (beyond the reference; mmdet's ``DetTTAModel`` + ``TestTimeAug``): ``None``, the default, changes nothing.  A dict
+``dict(scales=[(long, short), ...], flip=bool, nms=dict(type='nms' | 'soft_nms', iou_threshold[, method, min_score]),
+max_per_img=int | None)`` -- or ``"config"``, which reads ``cfg.tta_model['tta_cfg']`` and the ``Resize`` scales /
+``RandomFlip`` probabilities of the ``TestTimeAug`` step of ``cfg.tta_pipeline`` -- runs every image as
+``len(scales) * (2 if flip else 1)`` views and fuses their detections on the device.  View order:
+``v = s * (2 if flip else 1) + f``, scales in the given order, the unflipped view of a scale before its flipped one.
+Per chunk of ``batch_size`` images: one pinned staging copy and one upload (images, widths and every view's rescale
+divisor); per scale one ``preprocess_views`` launch
+(the chunk's images times the flips: keep-ratio resize to that scale, divisor padding, stacking -- no fixed-size ``Pad``
+step, which mmdet's TTA pipelines do not have), one forward and one of the post-processing launches above with each
+view's own scale factors as divisors; then one ``hip_ops.tta_merge`` launch and one download.  At most 16 views and
+``views * num_queries <= 4096``.  Parity with mmdet / mmcv is unpinned (neither is installed here); as in the soft-NMS
+kernel classes are told apart by comparing labels, ties go to the lowest index and the IoU arithmetic is the project's.
 """
 from typing import Dict, List, Optional
 
@@ -69,9 +83,71 @@ def nms_settings(test_cfg, nms_type=None):
     return out
 
 
+
+def _pairs(scale):
+    """a Resize `scale` (one (long, short) pair, or a list of them) -> list of pairs"""
+    if len(scale) == 2 and all(isinstance(v, (int, float)) for v in scale):
+        return [tuple(int(v) for v in scale)]
+    return [tuple(int(v) for v in pair) for pair in scale]
+
+
+def tta_settings(cfg, tta):
+    """How `Inferencer(..., tta=...)` reads its argument: None -> None; a dict(scales, flip, nms, max_per_img) is
+    validated; "config" takes `cfg.tta_model['tta_cfg']` (nms, max_per_img) and, from the TestTimeAug step of
+    `cfg.tta_pipeline`, every Resize scale and whether the RandomFlip branch holds both prob 0 and prob 1 (ValueError
+    when the config has neither entry).  -> dict(scales [(long, short)], flip, nms dict(type, iou_threshold, method,
+    min_score), max_per_img or None, views [(scale, flipped)] in launch order: v = s * (2 if flip else 1) + f,
+    unflipped first)."""
+    if tta is None:
+        return None
+    if tta == "config":
+        model, pipeline = cfg.get("tta_model"), cfg.get("tta_pipeline")
+        if model is None or pipeline is None:
+            raise ValueError("tta='config': the config has no tta_model / tta_pipeline")
+        tta_cfg = dict(model.get("tta_cfg", {}))
+        steps = [s for s in pipeline if s.get("type") == "TestTimeAug"]
+        if len(steps) != 1:
+            raise ValueError("tta='config': tta_pipeline needs exactly one TestTimeAug step")
+        scales, probs = [], []
+        for branch in steps[0]["transforms"]:
+            for t in branch:
+                if t.get("type") == "Resize":
+                    if not t.get("keep_ratio", False):
+                        raise NotImplementedError("TTA views are keep_ratio=True resizes")
+                    scales += _pairs(t["scale"])
+                elif t.get("type") == "RandomFlip":
+                    if t.get("direction", "horizontal") != "horizontal":
+                        raise NotImplementedError("only the horizontal flip is built")
+                    probs.append(float(t.get("prob", 0.0)))
+        if any(p not in (0.0, 1.0) for p in probs) or (probs and 0.0 not in probs):
+            raise NotImplementedError(f"RandomFlip probabilities {probs}: a TTA flip branch is prob=0. [and prob=1.]")
+        tta = dict(scales=scales, flip=1.0 in probs, nms=tta_cfg.get("nms", dict(type="nms", iou_threshold=0.5)),
+                   max_per_img=tta_cfg.get("max_per_img"))
+    if not isinstance(tta, dict) or set(tta) - {"scales", "flip", "nms", "max_per_img"} or "scales" not in tta:
+        raise ValueError("tta must be None, 'config' or dict(scales, flip, nms, max_per_img)")
+    scales = _pairs(tta["scales"]) if tta["scales"] else []
+    if not scales or any(len(p) != 2 or min(p) <= 0 for p in scales):
+        raise ValueError("tta scales: a non-empty list of positive (long, short) pairs")
+    flip = bool(tta.get("flip", False))
+    nms = dict(tta.get("nms") or dict(type="nms", iou_threshold=0.5))
+    kind = nms.get("type", "nms")
+    if kind not in ("nms", "soft_nms"):
+        raise NotImplementedError(f"tta nms type {kind!r}: 'nms' and 'soft_nms' are built")
+    out_nms = dict(type=kind, iou_threshold=float(nms.get("iou_threshold", 0.5 if kind == "nms" else 0.3)),
+                   method=nms.get("method", "linear"), min_score=float(nms.get("min_score", 1e-3)))
+    if kind == "soft_nms":
+        hip_ops._soft_method(out_nms["method"])   # 'gaussian' raises NotImplementedError, an unknown name ValueError
+    mpi = tta.get("max_per_img")
+    views = [(s, f) for s in scales for f in ((False, True) if flip else (False,))]
+    if len(views) > hip_ops.TTA_MAX_VIEWS:
+        raise ValueError(f"tta: {len(views)} views, at most {hip_ops.TTA_MAX_VIEWS} (scales x flips) are merged")
+    return dict(scales=scales, flip=flip, nms=out_nms, max_per_img=int(mpi) if mpi is not None and mpi > 0 else None,
+                views=views)
+
+
 class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
-                 iou_threshold: Optional[float] = None, nms_type: Optional[str] = None):
+                 iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -114,6 +190,7 @@ class Inferencer:
                 self.pad_val = tuple(pv) if isinstance(pv, (tuple, list)) else (pv,) * 3
         if self.scale is None:
             raise ValueError("Resize is not found in the test pipeline")
+        self.tta = tta_settings(self.cfg, tta)
         self.num_predicted_imgs = 0
 
     # ---- pre ------------------------------------------------------------------------------------------
@@ -205,27 +282,114 @@ class Inferencer:
             results.append(dict(bboxes=boxes, scores=scores, labels=labels))
         return results
 
+    @staticmethod
+    def divisors(metas, dtype):
+        """the rescale divisor [len(metas), 4] exactly as run_inference builds it (boxes.new_tensor of the Python floats)"""
+        return torch.tensor([[m["scale_factor"][0], m["scale_factor"][1]] * 2 for m in metas], dtype=dtype)
+
+    def postprocess_device(self, predictions, metas, div=None):
+        """postprocess_batch's one launch, its result left on the device (hip_ops.Detections / SoftDetections); `div`:
+        `divisors(metas, dtype)` already on the device"""
+        boxes, scores, labels = predictions
+        if div is None:
+            div = self.divisors(metas, boxes.dtype).to(boxes.device)
+        thr = self.score_threshold if self.score_threshold > 0 else None
+        if self.soft:
+            return hip_ops.postprocess_detections_soft(boxes, scores, labels, div, thr, self.iou_threshold,
+                                                       self.soft_method, self.min_score, self.max_per_img)
+        return hip_ops.postprocess_detections(boxes, scores, labels, div, thr,
+                                              self.iou_threshold if self.with_nms else None)
+
     def postprocess_batch(self, predictions, metas):
         """the model's (boxes [N,Q,4], scores [N,Q], labels [N,Q]) -> one result dict per image ({"labels", "scores",
         "bboxes"} as Python lists, what `__call__` returns): score threshold, per-class NMS and / scale_factor of
         `run_inference` for the whole batch in one launch, then one device-to-host copy"""
-        boxes, scores, labels = predictions
-        # the rescale divisor exactly as run_inference builds it (boxes.new_tensor of the Python floats)
-        div = torch.tensor([[m["scale_factor"][0], m["scale_factor"][1]] * 2 for m in metas], dtype=boxes.dtype)
-        thr = self.score_threshold if self.score_threshold > 0 else None
-        if self.soft:
-            dets = hip_ops.postprocess_detections_soft(boxes, scores, labels, div.to(boxes.device), thr,
-                                                       self.iou_threshold, self.soft_method, self.min_score,
-                                                       self.max_per_img)
-        else:
-            dets = hip_ops.postprocess_detections(boxes, scores, labels, div.to(boxes.device), thr,
-                                                  self.iou_threshold if self.with_nms else None)
-        host = hip_ops.detections_to_host(dets)
+        host = hip_ops.detections_to_host(self.postprocess_device(predictions, metas))
         out = []
         for i in range(len(metas)):
             c = int(host.count[i])
             if self.max_per_img is not None:
                 c = min(c, self.max_per_img)
+            out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
+                        "bboxes": host.boxes[i, :c].float().tolist()})
+        return out
+
+    # ---- test-time augmentation ---------------------------------------------------------------------------
+    def upload(self, images: List[np.ndarray], device="cuda:0", tail: Optional[torch.Tensor] = None):
+        """RGB uint8 images back to back in one pinned staging buffer, one host-to-device copy -> (flat uint8 device
+        buffer, the byte offset of every image, `tail` on the device).  `tail`: a small host tensor that rides in the
+        same copy, 16-byte aligned behind the images (the TTA path's image widths and rescale divisors)."""
+        offsets, offset = [], 0
+        for image in images:
+            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+                raise ValueError("expected RGB uint8 images of shape (H, W, 3)")
+            offsets.append(offset)
+            offset += image.size
+        if not offsets:
+            raise ValueError("upload: no images")
+        tail_at = -(-offset // 16) * 16
+        tail_bytes = tail.contiguous().view(-1).view(torch.uint8) if tail is not None else None
+        total = offset if tail is None else tail_at + tail_bytes.numel()
+        staging = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        for image, o in zip(images, offsets):
+            host[o:o + image.size] = np.ascontiguousarray(image).reshape(-1)
+        if tail is not None:
+            host[offset:tail_at] = 0
+            staging[tail_at:] = tail_bytes
+        dev = staging.to(device, non_blocking=True)
+        return dev[:offset], offsets, (dev[tail_at:].view(tail.dtype).view(tail.shape) if tail is not None else None)
+
+    def view_rows(self, offsets, shapes, scale, flips):
+        """One TTA scale of a chunk: images of `shapes` (H, W) at byte `offsets`, resized keep-ratio into `scale`, once
+        per entry of `flips` (False / True: mirrored), padded to pad_size_divisor and stacked.  Rows are flip-major --
+        row f * N + n is image n under flips[f] -- so the post-processed result reshapes to [len(flips), N, Q].
+        -> (rows for hip_ops.preprocess_views, metas per row, (H, W) of the batch)"""
+        d = self.pad_size_divisor
+        rows, metas = [], []
+        for f in flips:
+            for o, (H, W) in zip(offsets, shapes):
+                nh, nw = rescale_size(H, W, scale)
+                rows.append((o, H, W, nh, nw, nh, nw, 1 if f else 0))
+                pad_shape = (-(-nh // d) * d, -(-nw // d) * d) if d > 1 else (nh, nw)
+                metas.append(dict(ori_shape=(H, W), img_shape=(nh, nw), img_unpadded_shape=(nh, nw), pad_shape=pad_shape,
+                                  scale_factor=(nw / W, nh / H), flip=bool(f)))
+        Hb, Wb = max(m["pad_shape"][0] for m in metas), max(m["pad_shape"][1] for m in metas)
+        for m in metas:
+            m["batch_input_shape"] = (Hb, Wb)
+        return rows, metas, (Hb, Wb)
+
+    def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32):
+        """one chunk through every view and the merge -> one result dict per image (see the module docstring).  The
+        chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor."""
+        t = self.tta
+        flips = (False, True) if t["flip"] else (False,)
+        shapes = [im.shape[:2] for im in images]
+        N, offsets, offset = len(images), [], 0
+        for im in images:
+            offsets.append(offset)
+            offset += im.size
+        plans = [self.view_rows(offsets, shapes, scale, flips) for scale in t["scales"]]
+        widths = torch.tensor([float(w) for _, w in shapes], dtype=torch.float32)
+        div = torch.cat([self.divisors(metas, dtype) for _, metas, _ in plans])      # [S * F * N, 4]
+        tail = torch.cat((widths.view(torch.uint8), div.view(-1).view(torch.uint8)))
+        src, _, tail = self.upload(images, device, tail)
+        widths = tail[:4 * N].view(torch.float32)
+        div = tail[4 * N:].view(dtype).view(len(plans), len(flips) * N, 4)
+        view_dets = []
+        for s, (rows, metas, batch_hw) in enumerate(plans):
+            x, m = hip_ops.preprocess_views(src, rows, batch_hw, self.mean, self.std, self.pad_val, self.pad_value, dtype)
+            preds = self.model(x, m)
+            Q = preds[1].shape[1]
+            if s == 0 and len(t["views"]) * Q > hip_ops.TTA_MAX_CANDIDATES:   # (Q is the model's: known after a forward)
+                raise ValueError(f"tta: {len(t['views'])} views of {Q} detections exceed the merge kernel's "
+                                 f"{hip_ops.TTA_MAX_CANDIDATES} candidates per image")
+            view_dets.append(self.postprocess_device(preds, metas, div[s]))
+        dets = hip_ops.tta_merge(view_dets, [f for _, f in t["views"]], widths, t["nms"], t["max_per_img"])
+        host = hip_ops.detections_to_host(dets)
+        out = []
+        for i in range(N):
+            c = int(host.count[i])
             out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
                         "bboxes": host.boxes[i, :c].float().tolist()})
         return out
@@ -241,7 +405,7 @@ class Inferencer:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
         batch_size = int(batch_size)
         results_dict = {"predictions": [], "visualization": []}
-        if batch_size == 1 and dtype != torch.bfloat16 and not self.soft:
+        if batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None:
             for image in images:
                 with torch.no_grad():
                     x, m, meta = self.preprocess(image, device, dtype)
@@ -256,8 +420,11 @@ class Inferencer:
         for start in range(0, len(images), batch_size):
             chunk = images[start:start + batch_size]
             with torch.no_grad():
-                x, m, metas = self.preprocess_batch(chunk, device, dtype)
-                preds = self.postprocess_batch(self.model(x, m), metas)
+                if self.tta is not None:
+                    preds = self.tta_batch(chunk, device, dtype)
+                else:
+                    x, m, metas = self.preprocess_batch(chunk, device, dtype)
+                    preds = self.postprocess_batch(self.model(x, m), metas)
             for pred in preds:
                 if print_result:
                     print(pred)

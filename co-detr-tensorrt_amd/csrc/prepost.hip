@@ -21,11 +21,18 @@
 //                     soft-NMS, methods linear and naive, per class, then the max_per_img cut.  Classes are independent,
 //                     so after one sort by label every wave runs the greedy chains of whole classes on its own, without
 //                     a workgroup barrier per pick; a second sort orders the emitted detections by decayed score.
+// preprocess_views_kernel  preprocess_batch_kernel with a mirror bit per row: test-time augmentation's flipped views
+//                     (mmdet RandomFlip runs after Resize and before the padding, so the image is mirrored inside its
+//                     resized width and the padding stays on the right); rows may read the same source image.
+// tta_merge_kernel    mmdet DetTTAModel._merge_single_sample for up to 4096 candidates per image: the views' detections
+//                     un-flipped and concatenated, per-class hard or soft NMS in the form of postprocess_softnms_kernel
+//                     (label segments, one wave per chain, 64 positions per lane), sorted by score, cut to max_per_img.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "large_lds.h"
 
 namespace {
 
@@ -142,6 +149,33 @@ __global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned ch
   if (y < im.Hp && x < im.Wp) {
     int v[3] = {nm.pad[0], nm.pad[1], nm.pad[2]};
     if (inside) resized_pixel(src + im.src_offset, im.Hs, im.Ws, im.Hr, im.Wr, y, x, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = normalise(v[c], nm.mean[c], nm.stdv[c]);
+  }
+  const size_t plane = (size_t)H * W, p = (size_t)y * W + x;
+  OutT* d = dst + (size_t)n * 3 * plane;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) d[c * plane + p] = from_f32<OutT>(o[c]);
+  if (mask) mask[(size_t)n * plane + p] = from_f32<OutT>(inside ? 0.f : 1.f);
+}
+
+// preprocess_batch_kernel with a mirror bit per row (bit n of `flips`; the table holds at most 32 rows): a mirrored row
+// reads the resized image right to left inside its resized width -- the Pad region and everything beyond it stay put.
+// (Its own body, resize and normalise shared: folding the two kernels into one function changed the batch kernel's code.)
+template <class OutT>
+__global__ __launch_bounds__(256) void preprocess_views_kernel(const unsigned char* __restrict__ src, BatchTable tab,
+                                                               unsigned flips, BatchNorm nm, int H, int W,
+                                                               OutT* __restrict__ dst, OutT* __restrict__ mask) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  const int y = blockIdx.y;
+  const int n = blockIdx.z;
+  if (x >= W) return;
+  const BatchImage im = tab.img[n];
+  const bool inside = y < im.Hr && x < im.Wr;
+  float o[3] = {nm.fill, nm.fill, nm.fill};
+  if (y < im.Hp && x < im.Wp) {
+    int v[3] = {nm.pad[0], nm.pad[1], nm.pad[2]};
+    if (inside) resized_pixel(src + im.src_offset, im.Hs, im.Ws, im.Hr, im.Wr, y, (flips >> n & 1u) ? im.Wr - 1 - x : x, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c] = normalise(v[c], nm.mean[c], nm.stdv[c]);
   }
@@ -519,6 +553,259 @@ __global__ __launch_bounds__(1024) void postprocess_softnms_kernel(
   if (tid == 0) count[n] = M;
 }
 
+// ---- merge of test-time augmentation's views (include/codetr_hip.h states the semantics) ---------------------------
+
+constexpr int kTtaMaxC = CODETR_TTA_MAX_CANDIDATES;  // V * Q of a merge: positions 0 .. 4095 fit the 16-bit tables
+constexpr int kTtaThreads = 1024, kTtaWaves = kTtaThreads / 64;
+
+// dynamic LDS of tta_merge_kernel over P slots: box 16, label / output key 8, score 4, index 4, position 2, segment 2
+// bytes per slot = 36 P + 16; 144 KB at P = 4096, hence the opt-in of large_lds.h.  The areas are not stored: with
+// contraction off (w * h) of the same box is the same rounded product every time it is computed.
+constexpr size_t tta_lds_bytes(int P) { return (size_t)P * 36 + 16; }
+
+// sum of one int per thread over the 1024-thread workgroup (two barriers; s_wave is free again after the second)
+__device__ __forceinline__ int tta_block_sum(int v, int* s_wave, int lane, int wave) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  __syncthreads();
+  if (lane == 0) s_wave[wave] = v;
+  __syncthreads();
+  int total = 0;
+#pragma unroll
+  for (int w = 0; w < kTtaWaves; ++w) total += s_wave[w];
+  return total;
+}
+
+// bitonic_desc_u64 for P up to 4096: every thread takes P / 2048 pairs of a step
+__device__ __forceinline__ void tta_bitonic_desc_u64(unsigned long long* s, int P, int tid) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < P / 2; t += kTtaThreads) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long a = s[lo], b = s[hi];
+        if ((a < b) == desc) {
+          s[lo] = b;
+          s[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// grid N, 1024 threads: image n's V views of Q detections (rows j < count[v, n] are candidates, c = v Q + j) -> the merged
+// detections in output order, cut to max_keep, count_out[n] of them; rows [count_out, K) of the outputs are zero.
+// P = the power of two >= V Q.  mode: CODETR_TTA_NMS_*.
+template <class T>
+__global__ __launch_bounds__(kTtaThreads) void tta_merge_kernel(
+    const T* __restrict__ boxes, const T* __restrict__ scores, const int64_t* __restrict__ labels,
+    const int* __restrict__ count, int V, int N, int Q, int P, unsigned flip_mask, const float* __restrict__ width,
+    int mode, float iou_thr, float min_score, int max_keep, int K, T* __restrict__ boxes_out,
+    T* __restrict__ scores_out, int64_t* __restrict__ labels_out, int* __restrict__ index_out,
+    int* __restrict__ count_out) {
+  extern __shared__ __align__(16) unsigned char tta_lds[];
+  float4* s_box = reinterpret_cast<float4*>(tta_lds);  // by position after sort 1 (label segments, ascending c)
+  unsigned long long* s_lab = reinterpret_cast<unsigned long long*>(tta_lds + (size_t)16 * P);  // sort 1, major key
+  unsigned long long* s_out = s_lab;  // (after the segments are found) emitted: score key << 32 | (2^32 - 1 - c); else 0
+  float* s_score = reinterpret_cast<float*>(tta_lds + (size_t)24 * P);  // current score; its own lane's only
+  unsigned* s_idx = reinterpret_cast<unsigned*>(tta_lds + (size_t)28 * P);  // sort 1, minor key: 2^32 - 1 - c; 0 = none
+  unsigned short* s_pos = reinterpret_cast<unsigned short*>(tta_lds + (size_t)32 * P);  // c -> position
+  unsigned short* s_seg = reinterpret_cast<unsigned short*>(tta_lds + (size_t)34 * P);  // segment starts, then Vn
+  __shared__ unsigned long long s_wmax[kTtaWaves];
+  __shared__ int s_wave[kTtaWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = blockIdx.x;
+  const int C = V * Q;
+  const bool soft = mode != CODETR_TTA_NMS_HARD;
+  const bool linear = mode == CODETR_TTA_NMS_SOFT_LINEAR;
+  // element (v, n, j) of the stacked inputs
+  auto at = [&](int c, int& v) -> size_t {
+    v = c / Q;
+    return ((size_t)v * N + n) * Q + (size_t)(c - v * Q);
+  };
+
+  // 1. soft modes: the global maximum g (ties: lowest c), which the min_score drop spares
+  unsigned long long g = 0;
+  if (soft) {
+    unsigned long long best = 0;
+    for (int c = tid; c < C; c += kTtaThreads) {
+      int v;
+      const size_t e = at(c, v);
+      if (c - v * Q < count[v * N + n]) {
+        const unsigned long long k = ((unsigned long long)score_key(to_f32(scores[e])) << 32) | (unsigned long long)(0xffffffffu - (unsigned)c);
+        best = k > best ? k : best;
+      }
+    }
+    best = wave_max_u64(best);
+    if (lane == 0) s_wmax[wave] = best;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < kTtaWaves; ++w) g = s_wmax[w] > g ? s_wmax[w] : g;
+  }
+  // 2. the sort keys of the live candidates: (label, 2^32 - 1 - c); everything else 0
+  int nlive = 0;
+  for (int c = tid; c < P; c += kTtaThreads) {
+    bool live = false;
+    unsigned long long lab = 0;
+    if (c < C) {
+      int v;
+      const size_t e = at(c, v);
+      if (c - v * Q < count[v * N + n]) {
+        const float s = to_f32(scores[e]);
+        const unsigned long long k = ((unsigned long long)score_key(s) << 32) | (unsigned long long)(0xffffffffu - (unsigned)c);
+        live = !soft || k == g || !(s < min_score);
+        lab = (unsigned long long)labels[e];
+      }
+    }
+    s_lab[c] = live ? lab : 0ull;
+    s_idx[c] = live ? 0xffffffffu - (unsigned)c : 0u;
+    nlive += live ? 1 : 0;
+  }
+  const int Vn = tta_block_sum(nlive, s_wave, lane, wave);  // (its barriers: the sort keys are complete)
+
+  // 3. bitonic sort by (label, 2^32 - 1 - c), descending: every label a contiguous segment in ascending c, empty slots last
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int t = tid; t < P / 2; t += kTtaThreads) {
+        const int lo = 2 * t - (t & (stride - 1));
+        const int hi = lo + stride;
+        const bool desc = (lo & size) == 0;
+        const unsigned long long al = s_lab[lo], bl = s_lab[hi];
+        const unsigned ai = s_idx[lo], bi = s_idx[hi];
+        const bool less = al < bl || (al == bl && ai < bi);
+        if (less == desc && (al != bl || ai != bi)) {
+          s_lab[lo] = bl;
+          s_lab[hi] = al;
+          s_idx[lo] = bi;
+          s_idx[hi] = ai;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  const float Wimg = width[n];
+  for (int p = tid; p < Vn; p += kTtaThreads) {
+    const unsigned c = 0xffffffffu - s_idx[p];
+    int v;
+    const size_t e = at((int)c, v);
+    float4 b = make_float4(to_f32(boxes[4 * e]), to_f32(boxes[4 * e + 1]), to_f32(boxes[4 * e + 2]), to_f32(boxes[4 * e + 3]));
+    if (flip_mask >> v & 1u) {  // un-flip: (W - x2, y1, W - x1, y2)
+      const float x1 = Wimg - b.z, x2 = Wimg - b.x;
+      b.x = x1;
+      b.z = x2;
+    }
+    s_box[p] = b;
+    s_score[p] = to_f32(scores[e]);
+    s_pos[c] = (unsigned short)p;
+  }
+  int S = 0;  // label segments (uniform)
+  for (int base = 0; base < P; base += kTtaThreads) {
+    const int p = base + tid;
+    const bool head = p < Vn && (p == 0 || s_lab[p] != s_lab[p - 1]);
+    const unsigned long long hbal = __ballot(head);
+    __syncthreads();  // s_wave is free (the previous round's reads are done)
+    if (lane == 0) s_wave[wave] = __popcll(hbal);
+    __syncthreads();
+    int hpos = S + __popcll(hbal & ((1ull << lane) - 1ull));
+#pragma unroll
+    for (int w = 0; w < kTtaWaves; ++w) {
+      const int cw = s_wave[w];
+      hpos += w < wave ? cw : 0;
+      S += cw;
+    }
+    if (head) s_seg[hpos] = (unsigned short)p;
+  }
+  if (tid == 0) s_seg[S] = (unsigned short)Vn;
+  __syncthreads();  // the labels were read for the last time: their array becomes s_out
+  for (int p = tid; p < P; p += kTtaThreads) s_out[p] = 0ull;
+  __syncthreads();
+
+  // 4. the greedy chains, as postprocess_softnms_kernel's: a wave takes whole segments, lane l holds positions
+  //    a + l + 64 e (bit e of `alive`, e < 64), no workgroup barrier per pick.  The hard rule is one more weight: 0 and gone.
+  for (int seg = wave; seg < S; seg += kTtaWaves) {
+    const int a = s_seg[seg], b = s_seg[seg + 1];
+    const int ne = (b - a + 63) >> 6;  // <= 64
+    unsigned long long alive = 0;
+    for (int e = 0; e < ne; ++e) alive |= (a + lane + 64 * e < b) ? 1ull << e : 0ull;
+    for (;;) {
+      unsigned long long best = 0;
+      for (int e = 0; e < ne; ++e) {
+        if (alive >> e & 1ull) {
+          const int p = a + lane + 64 * e;
+          const unsigned long long k = ((unsigned long long)score_key(s_score[p]) << 32) | (unsigned long long)(0xffffffffu - (unsigned)p);
+          best = k > best ? k : best;
+        }
+      }
+      best = wave_max_u64(best);
+      if (best == 0ull) break;  // (wave-uniform) the segment is exhausted
+      const int k = (int)(0xffffffffu - (unsigned)best);
+      if (((k - a) & 63) == lane) {  // the owner emits k with its current score and retires it
+        alive &= ~(1ull << ((k - a) >> 6));
+        s_out[k] = (best & 0xffffffff00000000ull) | (unsigned long long)s_idx[k];
+      }
+      const float4 bk = s_box[k];
+      const float ak = box_area(bk);
+      for (int e = 0; e < ne; ++e) {
+        if (alive >> e & 1ull) {
+          const int p = a + lane + 64 * e;
+          const float4 bj = s_box[p];
+          const float ovr = soft_overlap(bk, ak, bj, box_area(bj));
+          if (!soft) {
+            if (ovr > iou_thr) alive &= ~(1ull << e);  // (a NaN overlap compares false: kept)
+          } else {
+            float sj = s_score[p];
+            if (ovr >= iou_thr) {
+              sj = sj * (linear ? 1.f - ovr : 0.f);
+              s_score[p] = sj;
+            }
+            if (sj < min_score) alive &= ~(1ull << e);
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // 5. order the emitted detections by (score, 2^32 - 1 - c), cut, round once to T
+  tta_bitonic_desc_u64(s_out, P, tid);
+  int nout = 0;
+  for (int p = tid; p < P; p += kTtaThreads) nout += s_out[p] != 0ull ? 1 : 0;
+  const int E = tta_block_sum(nout, s_wave, lane, wave);
+  const int M = (max_keep > 0 && max_keep < E) ? max_keep : E;
+  T* bo = boxes_out + (size_t)n * K * 4;
+  T* so = scores_out + (size_t)n * K;
+  int64_t* lo = labels_out + (size_t)n * K;
+  int* io = index_out + (size_t)n * K;
+  for (int r = tid; r < K; r += kTtaThreads) {
+    if (r < M) {
+      const unsigned c = 0xffffffffu - (unsigned)s_out[r];
+      const int p = s_pos[c];
+      int v;
+      const size_t e = at((int)c, v);
+      const float4 b = s_box[p];
+      bo[4 * r] = from_f32<T>(b.x);
+      bo[4 * r + 1] = from_f32<T>(b.y);
+      bo[4 * r + 2] = from_f32<T>(b.z);
+      bo[4 * r + 3] = from_f32<T>(b.w);
+      so[r] = from_f32<T>(s_score[p]);
+      lo[r] = labels[e];
+      io[r] = (int)c;
+    } else {
+      const T z = from_f32<T>(0.f);
+      bo[4 * r] = z;
+      bo[4 * r + 1] = z;
+      bo[4 * r + 2] = z;
+      bo[4 * r + 3] = z;
+      so[r] = z;
+      lo[r] = 0;
+      io[r] = 0;
+    }
+  }
+  if (tid == 0) count_out[n] = M;
+}
+
 template <class OutT>
 int launch_pre(void* stream, const void* src, int64_t Hs, int64_t Ws, int64_t Hr, int64_t Wr, int64_t Hp, int64_t Wp,
                const float* mean, const float* stdv, const int* pad, void* dst, void* mask) {
@@ -535,14 +822,14 @@ int launch_pre(void* stream, const void* src, int64_t Hs, int64_t Ws, int64_t Hr
   return err == hipSuccess ? 0 : (int)err;
 }
 
-template <class OutT>
-int launch_pre_batch(void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int64_t H,
-                     int64_t W, const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst,
-                     void* mask) {
+// the checks of a batched preprocess call and its kernel arguments; `cols` = 7 (codetr_preprocess_batch_u8_*) or 8
+// (codetr_preprocess_views_u8_*: the eighth value of a row is its flip, gathered into `flips`)
+int pre_batch_args(const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int cols, int64_t H, int64_t W,
+                   const float* mean, const float* stdv, const int* pad, float pad_fill, const void* dst, BatchTable& tab,
+                   BatchNorm& nm, unsigned& flips) {
   if (!src || !images || !mean || !stdv || !pad || !dst || src_bytes <= 0 || N <= 0 || H <= 0 || W <= 0)
     return CODETR_E_BADARG;
   if (N > kPreBatchMax || H > 65535 || W > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
-  BatchNorm nm;
   for (int c = 0; c < 3; ++c) {
     if (stdv[c] == 0.f || pad[c] < 0 || pad[c] > 255) return CODETR_E_BADARG;
     nm.mean[c] = mean[c];
@@ -550,19 +837,49 @@ int launch_pre_batch(void* stream, const void* src, int64_t src_bytes, int64_t N
     nm.pad[c] = pad[c];
   }
   nm.fill = pad_fill;
-  BatchTable tab = {};
+  flips = 0;
   for (int64_t n = 0; n < N; ++n) {
-    const int64_t* r = images + 7 * n;  // src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad
+    const int64_t* r = images + cols * n;  // src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad[, flip]
     const int64_t off = r[0], Hs = r[1], Ws = r[2], Hr = r[3], Wr = r[4], Hp = r[5], Wp = r[6];
     if (off < 0 || Hs <= 0 || Ws <= 0 || Hr <= 0 || Wr <= 0 || Hp < Hr || Wp < Wr || Hp > H || Wp > W)
       return CODETR_E_BADARG;
+    if (cols == 8 && r[7] != 0 && r[7] != 1) return CODETR_E_BADARG;
     if (Hs > 32767 || Ws > 32767) return CODETR_E_TOO_LARGE;
     if (off > src_bytes || Hs * Ws * 3 > src_bytes - off) return CODETR_E_BADARG;  // the image must lie in the buffer
     tab.img[n] = BatchImage{off, (int)Hs, (int)Ws, (int)Hr, (int)Wr, (int)Hp, (int)Wp};
+    if (cols == 8 && r[7] == 1) flips |= 1u << n;
   }
+  return 0;
+}
+
+template <class OutT>
+int launch_pre_batch(void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int64_t H,
+                     int64_t W, const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst,
+                     void* mask) {
+  BatchTable tab = {};
+  BatchNorm nm;
+  unsigned flips;
+  if (const int rc = pre_batch_args(src, src_bytes, N, images, 7, H, W, mean, stdv, pad, pad_fill, dst, tab, nm, flips))
+    return rc;
   hipLaunchKernelGGL((preprocess_batch_kernel<OutT>), dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N),
                      dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), tab, nm,
                      (int)H, (int)W, static_cast<OutT*>(dst), static_cast<OutT*>(mask));
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
+template <class OutT>
+int launch_pre_views(void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int64_t H,
+                     int64_t W, const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst,
+                     void* mask) {
+  BatchTable tab = {};
+  BatchNorm nm;
+  unsigned flips;
+  if (const int rc = pre_batch_args(src, src_bytes, N, images, 8, H, W, mean, stdv, pad, pad_fill, dst, tab, nm, flips))
+    return rc;
+  hipLaunchKernelGGL((preprocess_views_kernel<OutT>), dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N),
+                     dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), tab, flips,
+                     nm, (int)H, (int)W, static_cast<OutT*>(dst), static_cast<OutT*>(mask));
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -601,6 +918,35 @@ int launch_softnms(void* stream, const void* boxes, const void* scores, const in
                      labels, static_cast<const T*>(divisors), (int)Q, apply_threshold ? 1 : 0, score_threshold,
                      method == CODETR_SOFTNMS_LINEAR ? 1 : 0, iou_threshold, min_score, keep, static_cast<T*>(boxes_out),
                      static_cast<T*>(scores_out), labels_out, index_out, count);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
+template <class T>
+int launch_tta_merge(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count,
+                     int64_t V, int64_t N, int64_t Q, uint32_t flip_mask, const float* width, int mode,
+                     float iou_threshold, float min_score, int64_t max_keep, void* boxes_out, void* scores_out,
+                     int64_t* labels_out, int* index_out, int* count_out) {
+  if (!boxes || !scores || !labels || !count || !width || !boxes_out || !scores_out || !labels_out || !index_out ||
+      !count_out || V <= 0 || N <= 0 || Q <= 0)
+    return CODETR_E_BADARG;
+  if (mode != CODETR_TTA_NMS_HARD && mode != CODETR_TTA_NMS_SOFT_NAIVE && mode != CODETR_TTA_NMS_SOFT_LINEAR)
+    return CODETR_E_BADARG;
+  if (!__builtin_isfinite(iou_threshold) || !__builtin_isfinite(min_score)) return CODETR_E_BADARG;
+  if (V < 32 && (flip_mask >> V) != 0u) return CODETR_E_BADARG;  // a flip bit of a view that does not exist
+  if (V > CODETR_TTA_MAX_VIEWS || Q > kTtaMaxC || V * Q > kTtaMaxC || N > 0x7fffffffLL / kTtaMaxC ||
+      max_keep > 0x7fffffffLL)
+    return CODETR_E_TOO_LARGE;
+  const int C = (int)(V * Q);
+  int P = 1;
+  while (P < C) P <<= 1;
+  if (const hipError_t e = allow_large_lds<tta_merge_kernel<T>>((int)tta_lds_bytes(kTtaMaxC)); e != hipSuccess)
+    return (int)e;
+  hipLaunchKernelGGL((tta_merge_kernel<T>), dim3((unsigned)N), dim3(kTtaThreads), tta_lds_bytes(P),
+                     static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                     labels, count, (int)V, (int)N, (int)Q, P, flip_mask, width, mode, iou_threshold, min_score,
+                     max_keep > 0 ? (int)max_keep : 0, max_keep > 0 ? (int)max_keep : C, static_cast<T*>(boxes_out),
+                     static_cast<T*>(scores_out), labels_out, index_out, count_out);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -671,5 +1017,29 @@ CODETR_POST_ENTRY(codetr_postprocess_detections_f32, float)
 CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_f16, _Float16)
 CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_bf16, Bf16)
 CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_f32, float)
+
+#define CODETR_PRE_VIEWS_ENTRY(NAME, OUT_T)                                                                           \
+  int NAME(void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* images_host, int64_t H,    \
+           int64_t W, const float* mean_host, const float* std_host, const int* pad_value_host, float pad_fill,       \
+           void* dst_dev, void* mask_dev) {                                                                           \
+    return launch_pre_views<OUT_T>(stream, src_dev, src_bytes, N, images_host, H, W, mean_host, std_host,             \
+                                   pad_value_host, pad_fill, dst_dev, mask_dev);                                      \
+  }
+CODETR_PRE_VIEWS_ENTRY(codetr_preprocess_views_u8_f16, _Float16)
+CODETR_PRE_VIEWS_ENTRY(codetr_preprocess_views_u8_bf16, Bf16)
+CODETR_PRE_VIEWS_ENTRY(codetr_preprocess_views_u8_f32, float)
+
+#define CODETR_TTA_MERGE_ENTRY(NAME, T)                                                                               \
+  int NAME(void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,                    \
+           const int* count_dev, int64_t V, int64_t N, int64_t Q, uint32_t flip_mask, const float* width_dev,         \
+           int mode, float iou_threshold, float min_score, int64_t max_keep, void* boxes_out_dev,                     \
+           void* scores_out_dev, int64_t* labels_out_dev, int* index_out_dev, int* count_out_dev) {                   \
+    return launch_tta_merge<T>(stream, boxes_dev, scores_dev, labels_dev, count_dev, V, N, Q, flip_mask, width_dev,   \
+                               mode, iou_threshold, min_score, max_keep, boxes_out_dev, scores_out_dev,               \
+                               labels_out_dev, index_out_dev, count_out_dev);                                         \
+  }
+CODETR_TTA_MERGE_ENTRY(codetr_tta_merge_f16, _Float16)
+CODETR_TTA_MERGE_ENTRY(codetr_tta_merge_bf16, Bf16)
+CODETR_TTA_MERGE_ENTRY(codetr_tta_merge_f32, float)
 
 }  // extern "C"

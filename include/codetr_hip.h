@@ -796,6 +796,80 @@ int codetr_postprocess_softnms_f32(void *stream, const void *boxes_dev, const vo
                                    int64_t *labels_out_dev, int *index_out_dev, int *count_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Test-time augmentation (mmdet 3.x DetTTAModel + the TestTimeAug pipeline): one image as several views -- scales,
+ * horizontal flip -- and the fusion of the views' detections, both on the device.
+ *
+ * codetr_preprocess_views_u8_*: codetr_preprocess_batch_u8_* with one more column per row,
+ *     images_host        HOST [N][8] int64: src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad, flip
+ *   A row with flip = 1 holds the resized image mirrored left to right inside its resized width: output column
+ *   x < W_resized is what column W_resized - 1 - x is with flip = 0 (mmdet's RandomFlip runs after Resize and before any
+ *   padding, so the padding stays on the right).  The Pad region beyond the image, the divisor padding, pad_fill and the
+ *   mask are those of flip = 0.  Rows may name the same src_offset: several views read one uploaded image.  A flip
+ *   other than 0 or 1 is CODETR_E_BADARG; every other limit and error code is codetr_preprocess_batch_u8_*'s.
+ *
+ * codetr_tta_merge_*: DetTTAModel._merge_single_sample -- un-flip, concatenate, batched_nms(tta_cfg.nms), cut to
+ *   max_per_img -- for N images of V views, one workgroup per image.  The operands are the stacked outputs of the
+ *   per-view codetr_postprocess_* launches, already in original-image coordinates:
+ *     boxes_dev [V, N, Q, 4], scores_dev [V, N, Q] in T; labels_dev [V, N, Q] int64; count_dev [V, N] int32: rows
+ *     j < count[v, n] of view v are image n's candidates; flip_mask: bit v set = view v was flipped; width_dev [N]
+ *     fp32: the original image width W.  The candidate index is c = v * Q + j.
+ *     1. boxes and scores convert to fp32 (exact); a flipped view's box becomes (W - x2, y1, W - x1, y2), one fp32
+ *        rounding per coordinate; everything below is fp32 with one rounding per operation, never contracted, and
+ *        area_c = (x2 - x1) * (y2 - y1) is one rounded product (steps 1 and 4 of codetr_postprocess_softnms_*: the same
+ *        ovr = inter / (area_k + area_c - inter));
+ *     2. "highest score" is codetr_postprocess_detections_*'s order (-0 equals +0, NaN with the sign bit clear above
+ *        +inf); ties go to the lowest c;
+ *     3. mode CODETR_TTA_NMS_HARD, per label, while a candidate of the label is alive: pick the alive k with the
+ *        highest score, emit (k, score_k), retire k and every alive c of the label with ovr > iou_threshold (a NaN ovr
+ *        compares false).  min_score is not used;
+ *        modes CODETR_TTA_NMS_SOFT_NAIVE / _SOFT_LINEAR: steps 3 to 5 of codetr_postprocess_softnms_* over the
+ *        concatenated candidates (the min_score drop that spares the global maximum, the per-label decay chains);
+ *     4. the emitted detections are sorted by (decayed) score descending, ties by ascending c; the first max_keep stay
+ *        (max_keep <= 0: all).
+ *   Outputs, K = max_keep (V * Q when max_keep <= 0): boxes_out_dev [N, K, 4], scores_out_dev [N, K] in T (the fp32
+ *   value rounded once), labels_out_dev [N, K] int64, index_out_dev [N, K] int32 = the c of every row, count_out_dev [N]
+ *   int32; rows beyond count_out[n] are zero.  Parity with mmdet / mmcv is unpinned (neither is installed where this is
+ *   tested); the deviations are those of codetr_postprocess_softnms_*: labels are compared instead of offsetting the
+ *   coordinates, ties go to the lowest index, and the IoU arithmetic is this library's.
+ *   The workgroup keeps all candidates in LDS (36 bytes per slot of the power of two >= V * Q, 144 KB at 4096): no
+ *   workspace operand.  CODETR_E_BADARG for a null pointer, V, N or Q <= 0, a flip bit at or above V, a mode other than
+ *   the three below, an iou_threshold or min_score that is not finite; CODETR_E_TOO_LARGE for V > CODETR_TTA_MAX_VIEWS
+ *   or V * Q > CODETR_TTA_MAX_CANDIDATES.  All checks run before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define CODETR_TTA_MAX_VIEWS 16
+#define CODETR_TTA_MAX_CANDIDATES 4096
+#define CODETR_TTA_NMS_HARD 0
+#define CODETR_TTA_NMS_SOFT_NAIVE 1
+#define CODETR_TTA_NMS_SOFT_LINEAR 2
+int codetr_preprocess_views_u8_f16(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                   const int64_t *images_host, int64_t H, int64_t W, const float *mean_host,
+                                   const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                   void *mask_dev);
+int codetr_preprocess_views_u8_bf16(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                    const int64_t *images_host, int64_t H, int64_t W, const float *mean_host,
+                                    const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                    void *mask_dev);
+int codetr_preprocess_views_u8_f32(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                   const int64_t *images_host, int64_t H, int64_t W, const float *mean_host,
+                                   const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                   void *mask_dev);
+int codetr_tta_merge_f16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                         const int *count_dev, int64_t V, int64_t N, int64_t Q, uint32_t flip_mask,
+                         const float *width_dev, int mode, float iou_threshold, float min_score, int64_t max_keep,
+                         void *boxes_out_dev, void *scores_out_dev, int64_t *labels_out_dev, int *index_out_dev,
+                         int *count_out_dev);
+int codetr_tta_merge_bf16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                          const int *count_dev, int64_t V, int64_t N, int64_t Q, uint32_t flip_mask,
+                          const float *width_dev, int mode, float iou_threshold, float min_score, int64_t max_keep,
+                          void *boxes_out_dev, void *scores_out_dev, int64_t *labels_out_dev, int *index_out_dev,
+                          int *count_out_dev);
+int codetr_tta_merge_f32(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                         const int *count_dev, int64_t V, int64_t N, int64_t Q, uint32_t flip_mask,
+                         const float *width_dev, int mode, float iou_threshold, float min_score, int64_t max_keep,
+                         void *boxes_out_dev, void *scores_out_dev, int64_t *labels_out_dev, int *index_out_dev,
+                         int *count_out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Backward of multi-scale deformable attention (training path).
  *
  * Replaces ms_deformable_col2im_cuda<T> / ms_deform_attn_backward (codetr/csrc/ms_deform_attn.cu:781-897, 975-1028;

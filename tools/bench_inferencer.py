@@ -17,7 +17,14 @@ Kernel times: unless --no-profile, a child process runs the same Inferencer call
 bf16, batch 1 over 4 images in fp16) under `rocprofv3 --kernel-trace --stats`; the per-launch times of the pre- and
 post-processing kernels are read from its kernel statistics.
 
-    python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile]      -> one JSON line
+`--tta` adds a `tta` sub-record (test-time augmentation, fp16): images/s of `Inferencer(tta=dict(scales=TTA_SCALES,
+flip=...))` at batch_size 4 over --tta-images images, with and without the flip, beside the sum of three plain runs of
+the same Inferencer with its Resize set to each scale (and no fixed Pad) -- the way to the same unflipped views without
+the feature --; and the two TTA kernels alone, HIP events as above: tta_merge at N = 8, Q = 300 with 2 and 6 views for
+both label layouts, preprocess_views beside preprocess_batch on the same 8 images resized into (1152, 768) (twice the rows: each
+image plain and mirrored).
+
+    python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta]      -> one JSON line
 """
 import argparse
 import csv
@@ -103,6 +110,102 @@ def post_kernel_times(launches=200, warmup=20):
     return out
 
 
+TTA_SCALES = [(960, 640), (1152, 768), (1344, 896)]
+
+
+def _event_us(call, launches=200, warmup=20):
+    for _ in range(warmup):
+        call()
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    t0.record()
+    for _ in range(launches):
+        call()
+    t1.record()
+    torch.cuda.synchronize()
+    return round(t0.elapsed_time(t1) * 1e3 / launches, 2)
+
+
+def tta_kernel_times():
+    """us per launch of tta_merge_kernel (N = 8, Q = 300, fp16; V = 2 and 6; hard NMS at 0.5 and linear soft-NMS) and of
+    preprocess_views_kernel beside preprocess_batch_kernel"""
+    from codetr import hip_ops
+    from codetr.inferencer import rescale_size
+
+    g = torch.Generator().manual_seed(0)
+    N, Q = 8, 300
+    c = torch.rand(N, Q, 2, generator=g) * 800
+    wh = torch.rand(N, Q, 2, generator=g) * 150 + 2
+    base = torch.cat((c, c + wh), -1)
+    widths = torch.full((N,), 1000.0, device=DEV)
+    out = {"tta_merge_kernel": {}}
+    for V in (2, 6):
+        boxes = (base[None] + (torch.rand(V, N, Q, 4, generator=g) - 0.5) * 6).half().to(DEV)   # near duplicates across views
+        scores = torch.rand(V, N, Q, generator=g).half().to(DEV)
+        count = torch.full((V * N,), Q, dtype=torch.int32, device=DEV)
+        for name, labels in (("80_classes", torch.randint(0, 80, (N, Q), generator=g)), ("one_label", torch.zeros(N, Q).long())):
+            labels = labels[None].expand(V, N, Q).contiguous().to(DEV)
+            dets = [hip_ops.Detections(boxes.view(V * N, Q, 4), scores.view(V * N, Q), labels.view(V * N, Q), count, None)]
+            for mode, nms in (("hard", dict(type="nms", iou_threshold=0.5)),
+                              ("soft_linear", dict(type="soft_nms", iou_threshold=0.5, method="linear"))):
+                call = lambda: hip_ops.tta_merge(dets, [v % 2 == 1 for v in range(V)], widths, nms, 300)  # noqa: E731
+                out["tta_merge_kernel"][f"V{V}_{name}_{mode}"] = {"us_per_launch": _event_us(call),
+                                                                  "detections": int(call().count.sum())}
+    images = synthetic_images(N, seed=2)
+    src = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).to(DEV)
+    rows, off = [], 0
+    for im in images:
+        nh, nw = rescale_size(im.shape[0], im.shape[1], (1152, 768))
+        rows.append((off, im.shape[0], im.shape[1], nh, nw, nh, nw))
+        off += im.size
+    mean, std = (123.675, 116.28, 103.53), (58.395, 57.12, 57.375)
+    rows8 = [r + (f,) for f in (0, 1) for r in rows]
+    out["preprocess_batch_kernel_8_rows_us"] = _event_us(
+        lambda: hip_ops.preprocess_batch(src, rows, (1152, 1152), mean, std, dtype=torch.float16))
+    out["preprocess_views_kernel_8_plain_rows_us"] = _event_us(
+        lambda: hip_ops.preprocess_views(src, rows8[:8], (1152, 1152), mean, std, dtype=torch.float16))
+    out["preprocess_views_kernel_16_rows_us"] = _event_us(
+        lambda: hip_ops.preprocess_views(src, rows8, (1152, 1152), mean, std, dtype=torch.float16))
+    return out
+
+
+def _passes(inf, images, bs, repeats):
+    """seconds of every timed pass of inf(images, batch_size=bs) after one warm-up pass"""
+    with torch.no_grad():
+        inf(images[:bs], device=DEV, dtype=torch.float16, batch_size=bs)
+        times = []
+        for _ in range(repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            inf(images, device=DEV, dtype=torch.float16, batch_size=bs)
+            times.append(time.perf_counter() - t0)
+    return times
+
+
+def tta_record(inf, n_images, repeats, bs=4):
+    import bench
+    from codetr.inferencer import Inferencer
+
+    images = synthetic_images(n_images, seed=3)
+    rec = {"scales": TTA_SCALES, "batch_size": bs, "images": n_images, "repeats": repeats, "dtype": "fp16"}
+    for name, flip in (("tta_3_scales_flip", True), ("tta_3_scales", False)):
+        t = Inferencer(inf.model, bench.CFG, dataset_meta=None, tta=dict(scales=TTA_SCALES, flip=flip,
+                                                                         nms=dict(type="nms", iou_threshold=0.6), max_per_img=100))
+        times = _passes(t, images, bs, repeats)
+        rec[name] = {"images_per_s": round(n_images / min(times), 3), "pass_s": [round(v, 4) for v in times]}
+    # the Inferencer reads `scale` and `pad_size` on every call (preprocess_batch), so one instance serves all scales
+    plain, total = Inferencer(inf.model, bench.CFG, dataset_meta=None), []
+    plain.pad_size = None
+    for scale in TTA_SCALES:
+        plain.scale = scale
+        total.append(_passes(plain, images, bs, repeats))
+    sums = [sum(t[i] for t in total) for i in range(repeats)]
+    rec["three_plain_runs"] = {"images_per_s": round(n_images / sum(min(t) for t in total), 3),
+                               "pass_s_per_scale": [[round(v, 4) for v in t] for t in total], "sum_s": [round(v, 4) for v in sums]}
+    rec["kernels_us"] = tta_kernel_times()
+    return rec
+
+
 def soft_inferencer(inf):
     """the same model behind the post-processing its config specifies (soft-NMS, max_per_img)"""
     import bench
@@ -170,6 +273,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--batch-sizes", default="1,4,8")
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--tta", action="store_true", help="add the test-time-augmentation sub-record")
+    ap.add_argument("--tta-images", type=int, default=8)
+    ap.add_argument("--tta-only", action="store_true", help="only the tta sub-record (implies --tta)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -181,6 +287,11 @@ def main():
     bss = [int(v) for v in a.batch_sizes.split(",")]
     res = {}
     infs = inferencers()
+    if a.tta_only:
+        print(json.dumps({"metric": "Inferencer test-time augmentation (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass",
+                          "tta": tta_record(infs["fp16"], a.tta_images, a.repeats)}))
+        return
     infs["fp16_soft_nms"] = soft_inferencer(infs["fp16"])
     for name, inf in infs.items():
         dt = DTYPES[name.split("_")[0]]
@@ -205,6 +316,8 @@ def main():
             "images": a.images, "image_sizes_wh": SIZES_WH, "repeats": a.repeats, "timing": "host clock, best pass",
             "device": torch.cuda.get_device_name(0), "results": res}
     line["postprocess_launch_us"] = post_kernel_times()
+    if a.tta:
+        line["tta"] = tta_record(infs["fp16"], a.tta_images, a.repeats)
     if not a.no_profile:
         line["kernel_times"] = profile()
     print(json.dumps(line))

@@ -195,6 +195,21 @@ def run_proxy(args):
             json.dump(report, f, indent=1)
 
 
+def parse_tta(text):
+    """--tta SCALES[,flip]: 'LONGxSHORT+LONGxSHORT...[,flip]', e.g. '1333x800+2000x1200,flip' -> the Inferencer's tta
+    dict; the views are merged with hard NMS at IoU 0.6 and cut to 100 detections per image"""
+    parts = text.split(",")
+    if len(parts) > 2 or (len(parts) == 2 and parts[1] != "flip"):
+        raise SystemExit(f"--tta {text!r}: expected SCALES[,flip] with SCALES = LONGxSHORT[+LONGxSHORT...]")
+    try:
+        scales = [tuple(int(v) for v in s.split("x")) for s in parts[0].split("+")]
+    except ValueError:
+        scales = []
+    if not scales or any(len(s) != 2 for s in scales):
+        raise SystemExit(f"--tta {text!r}: expected SCALES[,flip] with SCALES = LONGxSHORT[+LONGxSHORT...]")
+    return dict(scales=scales, flip=len(parts) == 2, nms=dict(type="nms", iou_threshold=0.6), max_per_img=100)
+
+
 def run_coco(args):
     for p in (os.path.join(ROOT, "co-detr-tensorrt_amd"),):
         if p not in sys.path:
@@ -217,7 +232,8 @@ def run_coco(args):
     model = model.to(dtype)
     # --nms config: the post-processing the config specifies (soft-NMS + max_per_img, what the published AP was
     # produced with); hard: the reference Inferencer's hard NMS at the config's IoU threshold, no cut
-    inf = Inferencer(model, args.config, meta, score_threshold=0.0, nms_type="config" if args.nms == "config" else None)
+    inf = Inferencer(model, args.config, meta, score_threshold=0.0, nms_type="config" if args.nms == "config" else None,
+                     tta=parse_tta(args.tta) if args.tta else None)
     dets, gts = [], []
     images = ann["images"][:args.limit] if args.limit else ann["images"]
     for im in images:
@@ -249,6 +265,9 @@ def main():
     c.add_argument("--limit", type=int, default=0)
     c.add_argument("--nms", choices=("hard", "config"), default="hard",
                    help="hard: the reference Inferencer's hard NMS; config: test_cfg's nms type (soft_nms) + max_per_img")
+    c.add_argument("--tta", default=None, metavar="SCALES[,flip]",
+                   help="test-time augmentation: scales as LONGxSHORT joined by '+', e.g. 1333x800+2000x1200,flip; the "
+                        "views are merged with hard NMS at IoU 0.6, 100 detections per image")
     a = ap.parse_args()
     (run_proxy if a.mode == "proxy" else run_coco)(a)
 
