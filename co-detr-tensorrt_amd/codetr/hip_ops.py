@@ -509,6 +509,24 @@ def batched_nms(boxes, scores, labels, iou_threshold):
 PREPROCESS_BATCH_MAX = _cabi.PREPROCESS_BATCH_MAX
 
 
+def _preprocess_rows(name, launch, src_u8, rows, batch_hw, mean, std, pad_val, pad_value, dtype, with_mask):
+    """the body of preprocess_batch and preprocess_views: one `launch` per PREPROCESS_BATCH_MAX rows into one batch"""
+    _gpu(src_u8, name)
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
+        raise ValueError("expected one contiguous flat uint8 buffer")
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"{name} writes f16, bf16 or f32, not {dtype}")
+    N = len(rows)
+    H, W = (int(v) for v in batch_hw)
+    x = torch.empty((N, 3, H, W), dtype=dtype, device=src_u8.device)
+    m = torch.empty((N, H, W), dtype=dtype, device=src_u8.device) if with_mask else None
+    with torch.cuda.device(src_u8.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            launch(src_u8, rows[i:j], (H, W), mean, std, pad_val, pad_value, x[i:j], m[i:j] if m is not None else None)
+    return x, m
+
+
 def preprocess_batch(src_u8, images, batch_hw, mean, std, pad_val=(0, 0, 0), pad_value=0.0, dtype=torch.float16,
                      with_mask=True):
     """Many uint8 HWC RGB images of different sizes, back to back in ONE flat device buffer -> the stacked
@@ -516,36 +534,66 @@ def preprocess_batch(src_u8, images, batch_hw, mean, std, pad_val=(0, 0, 0), pad
     (src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad).  Per image preprocess_image's arithmetic into its
     (H_pad, W_pad) Pad region; beyond it `pad_value` as is and mask 1 (DetDataPreprocessor's divisor padding and
     stack_batch).  One launch per PREPROCESS_BATCH_MAX images (csrc/prepost.hip)."""
-    _gpu(src_u8, "preprocess_batch")
-    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
-        raise ValueError("expected one contiguous flat uint8 buffer")
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise ValueError(f"preprocess_batch writes f16, bf16 or f32, not {dtype}")
-    N = len(images)
-    H, W = (int(v) for v in batch_hw)
-    x = torch.empty((N, 3, H, W), dtype=dtype, device=src_u8.device)
-    m = torch.empty((N, H, W), dtype=dtype, device=src_u8.device) if with_mask else None
-    with torch.cuda.device(src_u8.device):
-        for i in range(0, N, PREPROCESS_BATCH_MAX):
-            j = min(N, i + PREPROCESS_BATCH_MAX)
-            _cabi.preprocess_batch_u8(src_u8, images[i:j], (H, W), mean, std, pad_val, pad_value, x[i:j],
-                                      m[i:j] if m is not None else None)
-    return x, m
+    return _preprocess_rows("preprocess_batch", _cabi.preprocess_batch_u8, src_u8, images, batch_hw, mean, std, pad_val,
+                            pad_value, dtype, with_mask)
+
+
+def preprocess_views(src_u8, rows8, batch_hw, mean, std, pad_val=(0, 0, 0), pad_value=0.0, dtype=torch.float16,
+                     with_mask=True):
+    """preprocess_batch for test-time augmentation's views: rows8 has one row per VIEW, (src_offset, H_src, W_src,
+    H_resized, W_resized, H_pad, W_pad, flip).  flip = 1 writes the resized image mirrored left to right inside its
+    resized width (mmdet flips after Resize and before any padding: the padding stays on the right, the mask does not
+    change); rows may share a src_offset, so the views of an image read its one uploaded copy.  -> (batch_inputs
+    [N, 3, H, W], img_masks [N, H, W] or None), N = len(rows8); one launch per PREPROCESS_BATCH_MAX rows."""
+    if any(len(r) != 8 for r in rows8):
+        raise ValueError("preprocess_views: eight values per row, the last one the flip (0 or 1)")
+    return _preprocess_rows("preprocess_views", _cabi.preprocess_views_u8, src_u8, rows8, batch_hw, mean, std, pad_val,
+                            pad_value, dtype, with_mask)
 
 
 # postprocess_detections' result: boxes [N,Q,4] / scores [N,Q] (input dtype), labels [N,Q] int64, count [N] int32 --
 # image i's detections are rows [:count[i]] -- all four views of the one byte buffer `packed`
 Detections = collections.namedtuple("Detections", "boxes scores labels count packed")
+# postprocess_detections_soft's and tta_merge's result: the fields of Detections + index [N,Q] int32, the input index
+# of every output row -- five views of the one byte buffer `packed`
+SoftDetections = collections.namedtuple("SoftDetections", "boxes scores labels count index packed")
 
 
-def _detection_views(packed, N, Q, dtype):
+def _detection_views(packed, N, Q, dtype, with_index):
+    """the views of a packed result: labels, count, [index,] boxes, scores in this order"""
     es = torch.empty((), dtype=dtype).element_size()
     o1 = N * Q * 8
     o2 = o1 + N * 4
-    o3 = o2 + N * Q * 4 * es
-    o4 = o3 + N * Q * es
-    return Detections(packed[o2:o3].view(dtype).view(N, Q, 4), packed[o3:o4].view(dtype).view(N, Q),
-                      packed[:o1].view(torch.int64).view(N, Q), packed[o1:o2].view(torch.int32), packed)
+    o3 = o2 + (N * Q * 4 if with_index else 0)
+    o4 = o3 + N * Q * 4 * es
+    o5 = o4 + N * Q * es
+    boxes, scores = packed[o3:o4].view(dtype).view(N, Q, 4), packed[o4:o5].view(dtype).view(N, Q)
+    labels, count = packed[:o1].view(torch.int64).view(N, Q), packed[o1:o2].view(torch.int32)
+    if not with_index:
+        return Detections(boxes, scores, labels, count, packed)
+    return SoftDetections(boxes, scores, labels, count, packed[o2:o3].view(torch.int32).view(N, Q), packed)
+
+
+def _new_detections(N, Q, dtype, device, with_index, zeros):
+    """the packed result over [N, Q] rows, for a launch to fill; `zeros`: nothing will be launched, every count is 0"""
+    es = torch.empty((), dtype=dtype).element_size()
+    nbytes = N * Q * (12 if with_index else 8) + N * 4 + N * Q * 5 * es
+    alloc = torch.zeros if zeros else torch.empty
+    return _detection_views(alloc((nbytes,), dtype=torch.uint8, device=device), N, Q, dtype, with_index)
+
+
+def _post_operands(name, boxes, scores, labels, divisors):
+    """the operand checks of postprocess_detections and postprocess_detections_soft (`name`) -> N, Q"""
+    dtype = scores.dtype
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32) or boxes.dtype != dtype or divisors.dtype != dtype:
+        raise ValueError(f"{name}: boxes, scores and divisors in one dtype of f16 / bf16 / f32")
+    shapes = f"{name}: boxes [N,Q,4], scores [N,Q], labels [N,Q], divisors [N,4]"
+    if scores.dim() != 2:
+        raise ValueError(shapes)
+    N, Q = scores.shape
+    if tuple(boxes.shape) != (N, Q, 4) or tuple(labels.shape) != (N, Q) or tuple(divisors.shape) != (N, 4):
+        raise ValueError(shapes)
+    return N, Q
 
 
 def postprocess_detections(boxes, scores, labels, divisors, score_threshold=None, iou_threshold=None):
@@ -555,16 +603,11 @@ def postprocess_detections(boxes, scores, labels, divisors, score_threshold=None
     iou_threshold: per-class NMS in descending score order (None: none, index order kept).  -> Detections, compacted
     per image; `detections_to_host` fetches all of it in one copy."""
     _gpu(scores, "postprocess_detections")
-    dtype = scores.dtype
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32) or boxes.dtype != dtype or divisors.dtype != dtype:
-        raise ValueError("postprocess_detections: boxes, scores and divisors in one dtype of f16 / bf16 / f32")
-    N, Q = scores.shape
-    if tuple(boxes.shape) != (N, Q, 4) or tuple(labels.shape) != (N, Q) or tuple(divisors.shape) != (N, 4):
-        raise ValueError("postprocess_detections: boxes [N,Q,4], scores [N,Q], labels [N,Q], divisors [N,4]")
-    nbytes = N * Q * 8 + N * 4 + N * Q * 5 * scores.element_size()
-    if N == 0 or Q == 0:   # nothing to launch for: every count is 0
-        return _detection_views(torch.zeros((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
-    out = _detection_views(torch.empty((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
+    N, Q = _post_operands("postprocess_detections", boxes, scores, labels, divisors)
+    nothing = N == 0 or Q == 0
+    out = _new_detections(N, Q, scores.dtype, scores.device, False, nothing)
+    if nothing:
+        return out
     with torch.cuda.device(scores.device):
         _cabi.postprocess_detections(boxes.contiguous(), scores.contiguous(), labels.to(torch.int64).contiguous(),
                                      divisors.contiguous(), score_threshold, iou_threshold, out.boxes, out.scores,
@@ -576,25 +619,7 @@ def detections_to_host(dets):
     """postprocess_detections' (or postprocess_detections_soft's, `index` included) result on the host: one
     device-to-host copy of the packed buffer"""
     N, Q = dets.scores.shape
-    views = _soft_detection_views if isinstance(dets, SoftDetections) else _detection_views
-    return views(dets.packed.cpu(), N, Q, dets.scores.dtype)
-
-
-# postprocess_detections_soft's result: the fields of Detections + index [N,Q] int32, the query index of every output
-# row -- five views of the one byte buffer `packed`
-SoftDetections = collections.namedtuple("SoftDetections", "boxes scores labels count index packed")
-
-
-def _soft_detection_views(packed, N, Q, dtype):
-    es = torch.empty((), dtype=dtype).element_size()
-    o1 = N * Q * 8
-    o2 = o1 + N * 4
-    o3 = o2 + N * Q * 4
-    o4 = o3 + N * Q * 4 * es
-    o5 = o4 + N * Q * es
-    return SoftDetections(packed[o3:o4].view(dtype).view(N, Q, 4), packed[o4:o5].view(dtype).view(N, Q),
-                          packed[:o1].view(torch.int64).view(N, Q), packed[o1:o2].view(torch.int32),
-                          packed[o2:o3].view(torch.int32).view(N, Q), packed)
+    return _detection_views(dets.packed.cpu(), N, Q, dets.scores.dtype, isinstance(dets, SoftDetections))
 
 
 def _soft_method(method):
@@ -616,18 +641,11 @@ def postprocess_detections_soft(boxes, scores, labels, divisors, score_threshold
     -> SoftDetections: scores are the decayed ones, `index` the query index of every row."""
     _gpu(scores, "postprocess_detections_soft")
     m = _soft_method(method)
-    dtype = scores.dtype
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32) or boxes.dtype != dtype or divisors.dtype != dtype:
-        raise ValueError("postprocess_detections_soft: boxes, scores and divisors in one dtype of f16 / bf16 / f32")
-    if scores.dim() != 2:
-        raise ValueError("postprocess_detections_soft: boxes [N,Q,4], scores [N,Q], labels [N,Q], divisors [N,4]")
-    N, Q = scores.shape
-    if tuple(boxes.shape) != (N, Q, 4) or tuple(labels.shape) != (N, Q) or tuple(divisors.shape) != (N, 4):
-        raise ValueError("postprocess_detections_soft: boxes [N,Q,4], scores [N,Q], labels [N,Q], divisors [N,4]")
-    nbytes = N * Q * 12 + N * 4 + N * Q * 5 * scores.element_size()
-    if N == 0 or Q == 0:   # nothing to launch for: every count is 0
-        return _soft_detection_views(torch.zeros((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
-    out = _soft_detection_views(torch.empty((nbytes,), dtype=torch.uint8, device=scores.device), N, Q, dtype)
+    N, Q = _post_operands("postprocess_detections_soft", boxes, scores, labels, divisors)
+    nothing = N == 0 or Q == 0
+    out = _new_detections(N, Q, scores.dtype, scores.device, True, nothing)
+    if nothing:
+        return out
     with torch.cuda.device(scores.device):
         _cabi.postprocess_softnms(boxes.contiguous(), scores.contiguous(), labels.to(torch.int64).contiguous(),
                                   divisors.contiguous(), score_threshold, m, iou_threshold, min_score,
@@ -658,32 +676,6 @@ def soft_nms(boxes, scores, labels, iou_threshold, method="linear", min_score=1e
 
 TTA_MAX_VIEWS = _cabi.TTA_MAX_VIEWS
 TTA_MAX_CANDIDATES = _cabi.TTA_MAX_CANDIDATES
-
-
-def preprocess_views(src_u8, rows8, batch_hw, mean, std, pad_val=(0, 0, 0), pad_value=0.0, dtype=torch.float16,
-                     with_mask=True):
-    """preprocess_batch for test-time augmentation's views: rows8 has one row per VIEW, (src_offset, H_src, W_src,
-    H_resized, W_resized, H_pad, W_pad, flip).  flip = 1 writes the resized image mirrored left to right inside its
-    resized width (mmdet flips after Resize and before any padding: the padding stays on the right, the mask does not
-    change); rows may share a src_offset, so the views of an image read its one uploaded copy.  -> (batch_inputs
-    [N, 3, H, W], img_masks [N, H, W] or None), N = len(rows8); one launch per PREPROCESS_BATCH_MAX rows."""
-    _gpu(src_u8, "preprocess_views")
-    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
-        raise ValueError("expected one contiguous flat uint8 buffer")
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise ValueError(f"preprocess_views writes f16, bf16 or f32, not {dtype}")
-    if any(len(r) != 8 for r in rows8):
-        raise ValueError("preprocess_views: eight values per row, the last one the flip (0 or 1)")
-    N = len(rows8)
-    H, W = (int(v) for v in batch_hw)
-    x = torch.empty((N, 3, H, W), dtype=dtype, device=src_u8.device)
-    m = torch.empty((N, H, W), dtype=dtype, device=src_u8.device) if with_mask else None
-    with torch.cuda.device(src_u8.device):
-        for i in range(0, N, PREPROCESS_BATCH_MAX):
-            j = min(N, i + PREPROCESS_BATCH_MAX)
-            _cabi.preprocess_views_u8(src_u8, rows8[i:j], (H, W), mean, std, pad_val, pad_value, x[i:j],
-                                      m[i:j] if m is not None else None)
-    return x, m
 
 
 def _tta_mode(nms):
@@ -738,10 +730,9 @@ def tta_merge(view_dets, flips, widths, nms=None, max_per_img=None):
     count = (view_dets[0].count if one else torch.cat([d.count for d in view_dets])).contiguous()
     keep = 0 if max_per_img is None else int(max_per_img)
     K = keep if keep > 0 else V * Q
-    nbytes = N * K * 12 + N * 4 + N * K * 5 * scores.element_size()
+    out = _new_detections(N, K, dtype, dev, True, Q == 0)
     if Q == 0:
-        return _soft_detection_views(torch.zeros((nbytes,), dtype=torch.uint8, device=dev), N, K, dtype)
-    out = _soft_detection_views(torch.empty((nbytes,), dtype=torch.uint8, device=dev), N, K, dtype)
+        return out
     with torch.cuda.device(dev):
         _cabi.tta_merge(boxes.view(V, N, Q, 4), scores.view(V, N, Q), labels.view(V, N, Q), count.view(V, N),
                         sum(1 << v for v, f in enumerate(flips) if f), widths.to(dev, torch.float32).contiguous(), mode,

@@ -25,8 +25,12 @@
 //                     (mmdet RandomFlip runs after Resize and before the padding, so the image is mirrored inside its
 //                     resized width and the padding stays on the right); rows may read the same source image.
 // tta_merge_kernel    mmdet DetTTAModel._merge_single_sample for up to 4096 candidates per image: the views' detections
-//                     un-flipped and concatenated, per-class hard or soft NMS in the form of postprocess_softnms_kernel
-//                     (label segments, one wave per chain, 64 positions per lane), sorted by score, cut to max_per_img.
+//                     un-flipped and concatenated, per-class hard or soft NMS (label segments, one wave per chain, 64
+//                     positions per lane), sorted by score, cut to max_per_img.
+// The last two kernels are their own front ends over ONE set of device functions: pack_key (the tie rule), bitonic_desc
+// (either key layout), block_scan / block_sum / block_max_u64, segment_starts, run_segments (the greedy chain with both
+// threshold rules) and write_row / zero_row.  postprocess_kernel and the kernels above it are on the Inferencer's default
+// path, whose machine code is pinned: postprocess_kernel keeps its own sort, scan and epilogue.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -337,23 +341,93 @@ __global__ __launch_bounds__(1024) void postprocess_kernel(const T* __restrict__
   if (tid == 0) count[n] = total;
 }
 
-// ---- soft-NMS (include/codetr_hip.h states the semantics) ---------------------------------------------------------
+// ---- building blocks of the 1024-thread workgroups of postprocess_softnms_kernel and tta_merge_kernel: each of the two
+// is its own front end followed by the same calls (postprocess_kernel above uses none of them: its machine code is pinned)
+constexpr int kNmsThreads = 1024, kNmsWaves = kNmsThreads / 64;
+static_assert(kPostMaxQ == kNmsThreads, "one candidate per thread");
 
-// IoU of the picked box k and candidate j, fp32 with one rounding per operation (no contraction into an FMA: the areas are
-// stored rounded products, and the CPU reference rounds w * h before it subtracts); NaN for two zero-area boxes
-__device__ __forceinline__ float soft_overlap(float4 bk, float ak, float4 bj, float aj) {
-#pragma clang fp contract(off)
-  const float w = fmaxf(0.f, fminf(bk.z, bj.z) - fmaxf(bk.x, bj.x));
-  const float h = fmaxf(0.f, fminf(bk.w, bj.w) - fmaxf(bk.y, bj.y));
-  const float inter = w * h;
-  const float uni = ak + aj;
-  return inter / (uni - inter);
+// an index as the minor part of a descending key: the lower index sorts first.  Its own inverse.
+__device__ __forceinline__ unsigned inv_index(unsigned idx) { return 0xffffffffu - idx; }
+// THE tie rule: (score key, index) as one 64-bit key -- the higher score first, equal scores in ascending index order
+__device__ __forceinline__ unsigned long long pack_key(unsigned key, unsigned idx) {
+  return ((unsigned long long)key << 32) | (unsigned long long)inv_index(idx);
+}
+__device__ __forceinline__ unsigned long long pack_key(float score, unsigned idx) { return pack_key(score_key(score), idx); }
+
+// the key layouts of the bitonic sort: order(lo, hi, desc) swaps slots lo < hi unless the larger (desc) / smaller one is in lo
+struct ScoreKeys {  // one 64-bit key per slot
+  unsigned long long* key;
+  __device__ __forceinline__ void order(int lo, int hi, bool desc) const {
+    const unsigned long long a = key[lo], b = key[hi];
+    if ((a < b) == desc) {
+      key[lo] = b;
+      key[hi] = a;
+    }
+  }
+};
+struct LabelIndexKeys {  // (label bits, inverted index) per slot, the empty slots (0, 0); equal pairs do not swap
+  unsigned long long* lab;
+  unsigned* idx;
+  __device__ __forceinline__ void order(int lo, int hi, bool desc) const {
+    const unsigned long long al = lab[lo], bl = lab[hi];
+    const unsigned ai = idx[lo], bi = idx[hi];
+    const bool less = al < bl || (al == bl && ai < bi);
+    if (less == desc && (al != bl || ai != bi)) {
+      lab[lo] = bl;
+      lab[hi] = al;
+      idx[lo] = bi;
+      idx[hi] = ai;
+    }
+  }
+};
+
+// in-place descending bitonic sort of P (a power of two <= kMaxP) LDS slots; a thread takes pairs tid, tid + 1024, ... of a
+// step, which is one pair and no loop for kMaxP <= 2048.  Ends with a barrier (for P >= 2).
+template <int kMaxP, class Keys>
+__device__ __forceinline__ void bitonic_desc(Keys keys, int P, int tid) {
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+#pragma unroll
+      for (int t = tid; t < kMaxP / 2; t += kNmsThreads) {
+        if (t < P / 2) {
+          const int lo = 2 * t - (t & (stride - 1));
+          keys.order(lo, lo + stride, (lo & size) == 0);
+        }
+      }
+      __syncthreads();
+    }
+  }
 }
 
-__device__ __forceinline__ float box_area(float4 b) {
-#pragma clang fp contract(off)
-  const float w = b.z - b.x, h = b.w - b.y;
-  return w * h;
+// exclusive scan of a predicate over the workgroup (ballot + wave totals) -> the number of set predicates in the threads
+// before this one, `total` = in all of them.  One barrier after s_wave is written: the caller sees to it that s_wave is free.
+__device__ __forceinline__ int block_scan(bool pred, int* s_wave, int lane, int wave, int& total) {
+  const unsigned long long bal = __ballot(pred);
+  if (lane == 0) s_wave[wave] = __popcll(bal);
+  __syncthreads();
+  int pos = __popcll(bal & ((1ull << lane) - 1ull));
+  total = 0;
+#pragma unroll
+  for (int w = 0; w < kNmsWaves; ++w) {
+    const int c = s_wave[w];
+    pos += w < wave ? c : 0;
+    total += c;
+  }
+  return pos;
+}
+
+// sum of one int per thread over the workgroup, for the kernel with several slots per thread (a 0 / 1 per thread is
+// __syncthreads_count).  Two barriers: s_wave may be in use before, everything written before is visible after.
+__device__ __forceinline__ int block_sum(int v, int* s_wave, int lane, int wave) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
+  __syncthreads();
+  if (lane == 0) s_wave[wave] = v;
+  __syncthreads();
+  int total = 0;
+#pragma unroll
+  for (int w = 0; w < kNmsWaves; ++w) total += s_wave[w];
+  return total;
 }
 
 __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
@@ -365,21 +439,130 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
   return v;
 }
 
-// in-place descending bitonic sort of P (a power of two <= 1024) 64-bit keys in LDS; ends with a barrier (for P >= 2)
-__device__ __forceinline__ void bitonic_desc_u64(unsigned long long* s, int P, int tid) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (tid < P / 2) {
-        const int lo = 2 * tid - (tid & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long a = s[lo], b = s[hi];
-        if ((a < b) == desc) {
-          s[lo] = b;
-          s[hi] = a;
+// maximum of one key per thread over the workgroup (one barrier)
+__device__ __forceinline__ unsigned long long block_max_u64(unsigned long long v, unsigned long long* s_wmax, int lane,
+                                                            int wave) {
+  v = wave_max_u64(v);
+  if (lane == 0) s_wmax[wave] = v;
+  __syncthreads();
+  unsigned long long g = 0;
+#pragma unroll
+  for (int w = 0; w < kNmsWaves; ++w) g = s_wmax[w] > g ? s_wmax[w] : g;
+  return g;
+}
+
+// output row r of an image: the box rounded once to T (a rescale is the caller's: IEEE divide before the call)
+template <class T>
+__device__ __forceinline__ void write_row(T* bo, T* so, int64_t* lo, int* io, int r, float4 box, T score, int64_t label,
+                                          int index) {
+  bo[4 * r] = from_f32<T>(box.x);
+  bo[4 * r + 1] = from_f32<T>(box.y);
+  bo[4 * r + 2] = from_f32<T>(box.z);
+  bo[4 * r + 3] = from_f32<T>(box.w);
+  so[r] = score;
+  lo[r] = label;
+  io[r] = index;
+}
+template <class T>
+__device__ __forceinline__ void zero_row(T* bo, T* so, int64_t* lo, int* io, int r) {
+  write_row(bo, so, lo, io, r, make_float4(0.f, 0.f, 0.f, 0.f), from_f32<T>(0.f), 0, 0);
+}
+
+// ---- per-class greedy NMS over label segments: soft-NMS and the merge of test-time augmentation's views
+// (include/codetr_hip.h states the semantics of both) ----------------------------------------------------------------------
+
+// IoU of the picked box k and candidate j, fp32 with one rounding per operation (no contraction into an FMA: the CPU
+// reference rounds w * h before it subtracts); NaN for two zero-area boxes.  With contraction off (w * h) of the same box
+// is the same rounded product every time it is computed, so an area may be stored or computed again: run_segments'
+// kStoredArea, the one policy difference of the two kernels.
+__device__ __forceinline__ float box_area(float4 b) {
+#pragma clang fp contract(off)
+  const float w = b.z - b.x, h = b.w - b.y;
+  return w * h;
+}
+__device__ __forceinline__ float soft_overlap(float4 bk, float ak, float4 bj, float aj) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(0.f, fminf(bk.z, bj.z) - fmaxf(bk.x, bj.x));
+  const float h = fmaxf(0.f, fminf(bk.w, bj.w) - fmaxf(bk.y, bj.y));
+  const float inter = w * h;
+  const float uni = ak + aj;
+  return inter / (uni - inter);
+}
+
+// after the (label, index) sort of V live candidates: s_seg[0 .. S) = the first position of every label segment,
+// s_seg[S] = V -> S.  kMaxP / 1024 positions per thread, a round each; with one round s_wave must be free at the call.
+// Ends with a barrier.
+template <int kMaxP>
+__device__ __forceinline__ int segment_starts(const unsigned long long* s_lab, int V, unsigned short* s_seg, int* s_wave,
+                                              int tid) {
+  int S = 0;  // (uniform)
+  for (int base = 0; base < kMaxP && (base == 0 || base < V); base += kNmsThreads) {
+    const int p = base + tid;
+    const bool head = p < V && (p == 0 || s_lab[p] != s_lab[p - 1]);
+    if (kMaxP > kNmsThreads) __syncthreads();  // s_wave is free (the reads of the previous round, or of a block_sum, are done)
+    int heads;
+    const int hpos = S + block_scan(head, s_wave, tid & 63, tid >> 6, heads);
+    if (head) s_seg[hpos] = (unsigned short)p;
+    S += heads;
+  }
+  if (tid == 0) s_seg[S] = (unsigned short)V;
+  __syncthreads();
+  return S;
+}
+
+// the greedy chains: a wave takes whole segments; lane l holds positions a + l + 64 e (bit e of `alive`: Mask has a bit for
+// every position of a lane -- unsigned for segments of up to 1024, unsigned long long up to 4096).  The pick is a wave
+// reduction of pack_key(current score, position): highest score, ties to the lowest position = the lowest index.  It is
+// emitted into s_out under its index with the score it has now, then decides over the others of its segment:
+//   hard (only where kHardToo)  overlap > iou_thr: gone                       (a NaN overlap compares false: kept)
+//   soft                        overlap >= iou_thr: score * (1 - overlap), or * 0 unless `linear`; score < min_score: gone
+// kStoredArea: the areas are read from s_area (next to s_score in LDS, so that one instruction reads both), else
+// computed again (s_area unused).  No workgroup barrier in here: a position's score is read and written by its own lane only.
+template <class Mask, bool kHardToo, bool kStoredArea>
+__device__ __forceinline__ void run_segments(const unsigned short* s_seg, int S, const float4* s_box, const float* s_area,
+                                             float* s_score, const unsigned* s_idx, unsigned long long* s_out, bool hard,
+                                             bool linear, float iou_thr, float min_score, int lane, int wave) {
+  constexpr Mask kOne = 1;
+  for (int seg = wave; seg < S; seg += kNmsWaves) {
+    const int a = s_seg[seg], b = s_seg[seg + 1];
+    const int ne = (b - a + 63) >> 6;  // <= the bits of Mask
+    Mask alive = 0;
+    for (int e = 0; e < ne; ++e) alive |= (a + lane + 64 * e < b) ? kOne << e : Mask(0);
+    for (;;) {
+      unsigned long long best = 0;
+      for (int e = 0; e < ne; ++e) {
+        if (alive >> e & kOne) {
+          const int p = a + lane + 64 * e;
+          const unsigned long long k = pack_key(s_score[p], (unsigned)p);
+          best = k > best ? k : best;
         }
       }
-      __syncthreads();
+      best = wave_max_u64(best);
+      if (best == 0ull) break;  // (wave-uniform) the segment is exhausted
+      const int k = (int)inv_index((unsigned)best);
+      if (((k - a) & 63) == lane) {  // the owner emits k with its current score and retires it
+        alive &= ~(kOne << ((k - a) >> 6));
+        s_out[k] = (best & 0xffffffff00000000ull) | s_idx[k];  // (s_idx holds the minor key, inv_index(index), already)
+      }
+      const float4 bk = s_box[k];
+      const float ak = kStoredArea ? s_area[k] : box_area(bk);
+      for (int e = 0; e < ne; ++e) {
+        if (alive >> e & kOne) {
+          const int p = a + lane + 64 * e;
+          const float4 bj = s_box[p];
+          const float ovr = soft_overlap(bk, ak, bj, kStoredArea ? s_area[p] : box_area(bj));
+          if (kHardToo && hard) {
+            if (ovr > iou_thr) alive &= ~(kOne << e);
+          } else {
+            float sj = s_score[p];
+            if (ovr >= iou_thr) {  // (a NaN overlap compares false: weight 1)
+              sj = sj * (linear ? 1.f - ovr : 0.f);
+              s_score[p] = sj;
+            }
+            if (sj < min_score) alive &= ~(kOne << e);
+          }
+        }
+      }
     }
   }
 }
@@ -387,22 +570,21 @@ __device__ __forceinline__ void bitonic_desc_u64(unsigned long long* s, int P, i
 // grid N, 1024 threads: image n's Q candidates -> its soft-NMS detections in output order (decayed score descending,
 // ties by ascending query index), cut to max_keep, count[n] of them.  Rows [count, Q) of the outputs are zero.
 template <class T>
-__global__ __launch_bounds__(1024) void postprocess_softnms_kernel(
+__global__ __launch_bounds__(kNmsThreads) void postprocess_softnms_kernel(
     const T* __restrict__ boxes, const T* __restrict__ scores, const int64_t* __restrict__ labels,
     const T* __restrict__ divisors, int Q, int use_thr, float thr, int linear, float iou_thr, float min_score,
     int max_keep, T* __restrict__ boxes_out, T* __restrict__ scores_out, int64_t* __restrict__ labels_out,
     int* __restrict__ index_out, int* __restrict__ count) {
-  constexpr int kWaves = kPostMaxQ / 64;
   __shared__ unsigned long long s_lab[kPostMaxQ];  // sort 1, major key: the label's bits (live candidates)
-  __shared__ unsigned s_idx[kPostMaxQ];            // sort 1, minor key: 2^32 - 1 - query index; 0 = dropped
-  __shared__ unsigned long long s_out[kPostMaxQ];  // emitted: decayed score key << 32 | (2^32 - 1 - query index); else 0
+  __shared__ unsigned s_idx[kPostMaxQ];            // sort 1, minor key: inv_index(query index); 0 = dropped
+  __shared__ unsigned long long s_out[kPostMaxQ];  // emitted: pack_key(decayed score, query index); else 0
   __shared__ float4 s_box[kPostMaxQ];              // by position after sort 1 (label segments, ascending query index)
-  __shared__ float s_area[kPostMaxQ];
+  __shared__ float s_area[kPostMaxQ];              // (stored here, computed again in the merge, whose LDS has no room)
   __shared__ float s_score[kPostMaxQ];             // current (decaying) score; touched by the position's own lane only
   __shared__ unsigned short s_seg[kPostMaxQ + 1];  // first position of every label segment, then V
   __shared__ unsigned short s_pos[kPostMaxQ];      // query index -> position
-  __shared__ unsigned long long s_wmax[kWaves];
-  __shared__ int s_wave[kWaves];
+  __shared__ unsigned long long s_wmax[kNmsWaves];
+  __shared__ int s_wave[kNmsWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const size_t n = blockIdx.x;
   const T* bx = boxes + n * Q * 4;
@@ -411,51 +593,26 @@ __global__ __launch_bounds__(1024) void postprocess_softnms_kernel(
   int P = 1;  // the sorts run over the next power of two >= Q
   while (P < Q) P <<= 1;
 
-  // 1. score threshold at T's precision (as postprocess_kernel), then the global maximum g (ties: lowest index)
+  // front end: score threshold at T's precision (as postprocess_kernel), the global maximum g (ties: lowest index), then
+  // everything below min_score goes, except g (mmcv emits its first pick unchecked)
   const float thr_t = to_f32(from_f32<T>(thr));
   unsigned long long key = 0;
   float s = 0.f;
   if (tid < Q) {
     s = to_f32(sc[tid]);
-    if (!use_thr || s > thr_t) key = ((unsigned long long)score_key(s) << 32) | (unsigned long long)(0xffffffffu - (unsigned)tid);
+    if (!use_thr || s > thr_t) key = pack_key(s, (unsigned)tid);
   }
-  const unsigned long long wmax = wave_max_u64(key);
-  if (lane == 0) s_wmax[wave] = wmax;
-  __syncthreads();
-  unsigned long long g = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) g = s_wmax[w] > g ? s_wmax[w] : g;
-  // 2. everything below min_score goes, except g (mmcv emits its first pick unchecked)
+  const unsigned long long g = block_max_u64(key, s_wmax, lane, wave);
   const bool live = key != 0ull && (key == g || !(s < min_score));
   s_lab[tid] = live ? (unsigned long long)lb[tid] : 0ull;
-  s_idx[tid] = live ? 0xffffffffu - (unsigned)tid : 0u;
+  s_idx[tid] = live ? inv_index((unsigned)tid) : 0u;
   s_out[tid] = 0ull;
   const int V = __syncthreads_count(live);  // barrier: the sort keys are complete
 
-  // 3. bitonic sort by (label, 2^32 - 1 - index), descending: every label a contiguous segment in ascending index
-  //    order, the dropped slots last
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      if (tid < P / 2) {
-        const int lo = 2 * tid - (tid & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long al = s_lab[lo], bl = s_lab[hi];
-        const unsigned ai = s_idx[lo], bi = s_idx[hi];
-        const bool less = al < bl || (al == bl && ai < bi);
-        if (less == desc && (al != bl || ai != bi)) {
-          s_lab[lo] = bl;
-          s_lab[hi] = al;
-          s_idx[lo] = bi;
-          s_idx[hi] = ai;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  const bool head = tid < V && (tid == 0 || s_lab[tid] != s_lab[tid - 1]);
+  // 1. by (label, index), descending: every label a contiguous segment in ascending index order, the dropped slots last
+  bitonic_desc<kPostMaxQ>(LabelIndexKeys{s_lab, s_idx}, P, tid);
   if (tid < V) {
-    const unsigned src = 0xffffffffu - s_idx[tid];
+    const unsigned src = inv_index(s_idx[tid]);
     const float4 b = make_float4(to_f32(bx[4 * src]), to_f32(bx[4 * src + 1]), to_f32(bx[4 * src + 2]),
                                  to_f32(bx[4 * src + 3]));
     s_box[tid] = b;
@@ -463,143 +620,46 @@ __global__ __launch_bounds__(1024) void postprocess_softnms_kernel(
     s_score[tid] = to_f32(sc[src]);
     s_pos[src] = (unsigned short)tid;
   }
-  const unsigned long long hbal = __ballot(head);
-  if (lane == 0) s_wave[wave] = __popcll(hbal);
+  // 2. - 4. segments, chains (up to 16 positions per lane), the emitted detections by (decayed score, index)
+  const int S = segment_starts<kPostMaxQ>(s_lab, V, s_seg, s_wave, tid);
+  run_segments<unsigned, false, true>(s_seg, S, s_box, s_area, s_score, s_idx, s_out, false, linear != 0, iou_thr, min_score, lane,
+                                      wave);
   __syncthreads();
-  int hpos = __popcll(hbal & ((1ull << lane) - 1ull)), S = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int c = s_wave[w];
-    hpos += w < wave ? c : 0;
-    S += c;
-  }
-  if (head) s_seg[hpos] = (unsigned short)tid;
-  if (tid == 0) s_seg[S] = (unsigned short)V;
-  __syncthreads();
-
-  // 4. the greedy chains: a wave takes whole segments; lane l holds positions a + l + 64 e (bit e of `alive`).  The pick is
-  //    a wave reduction of (score key, 2^32 - 1 - position): highest current score, ties to the lowest position = the
-  //    lowest query index.  No workgroup barrier in here: a position's score is read and written by its own lane only.
-  for (int seg = wave; seg < S; seg += kWaves) {
-    const int a = s_seg[seg], b = s_seg[seg + 1];
-    const int ne = (b - a + 63) >> 6;  // <= 16
-    unsigned alive = 0;
-    for (int e = 0; e < ne; ++e) alive |= (a + lane + 64 * e < b) ? 1u << e : 0u;
-    for (;;) {
-      unsigned long long best = 0;
-      for (int e = 0; e < ne; ++e) {
-        if (alive >> e & 1u) {
-          const int p = a + lane + 64 * e;
-          const unsigned long long k = ((unsigned long long)score_key(s_score[p]) << 32) | (unsigned long long)(0xffffffffu - (unsigned)p);
-          best = k > best ? k : best;
-        }
-      }
-      best = wave_max_u64(best);
-      if (best == 0ull) break;  // (wave-uniform) the segment is exhausted
-      const int k = (int)(0xffffffffu - (unsigned)best);
-      if (((k - a) & 63) == lane) {  // the owner emits k with its current score and retires it
-        alive &= ~(1u << ((k - a) >> 6));
-        s_out[k] = (best & 0xffffffff00000000ull) | (unsigned long long)s_idx[k];
-      }
-      const float4 bk = s_box[k];
-      const float ak = s_area[k];
-      for (int e = 0; e < ne; ++e) {
-        if (alive >> e & 1u) {
-          const int p = a + lane + 64 * e;
-          const float ovr = soft_overlap(bk, ak, s_box[p], s_area[p]);
-          float sj = s_score[p];
-          if (ovr >= iou_thr) {  // (a NaN overlap compares false: weight 1)
-            sj = sj * (linear ? 1.f - ovr : 0.f);
-            s_score[p] = sj;
-          }
-          if (sj < min_score) alive &= ~(1u << e);
-        }
-      }
-    }
-  }
-  __syncthreads();
-
-  // 5. order the emitted detections by (decayed score, 2^32 - 1 - index), cut, rescale: fp32 divide, one rounding to T
-  bitonic_desc_u64(s_out, P, tid);
+  bitonic_desc<kPostMaxQ>(ScoreKeys{s_out}, P, tid);
   const unsigned long long okey = s_out[tid];
   const int E = __syncthreads_count(okey != 0ull);
   const int M = (max_keep > 0 && max_keep < E) ? max_keep : E;
+
+  // 5. cut, rescale: fp32 divide, one rounding to T
   T* bo = boxes_out + n * Q * 4;
   T* so = scores_out + n * Q;
   int64_t* lo = labels_out + n * Q;
   int* io = index_out + n * Q;
   if (tid < M) {
-    const unsigned src = 0xffffffffu - (unsigned)okey;
+    const unsigned src = inv_index((unsigned)okey);
     const int p = s_pos[src];
     const T* dv = divisors + n * 4;
     const float4 b = s_box[p];
-    bo[4 * tid] = from_f32<T>(b.x / to_f32(dv[0]));
-    bo[4 * tid + 1] = from_f32<T>(b.y / to_f32(dv[1]));
-    bo[4 * tid + 2] = from_f32<T>(b.z / to_f32(dv[2]));
-    bo[4 * tid + 3] = from_f32<T>(b.w / to_f32(dv[3]));
-    so[tid] = from_f32<T>(s_score[p]);
-    lo[tid] = lb[src];
-    io[tid] = (int)src;
+    write_row(bo, so, lo, io, tid,
+              make_float4(b.x / to_f32(dv[0]), b.y / to_f32(dv[1]), b.z / to_f32(dv[2]), b.w / to_f32(dv[3])),
+              from_f32<T>(s_score[p]), lb[src], (int)src);
   } else if (tid < Q) {
-    const T z = from_f32<T>(0.f);
-    bo[4 * tid] = z;
-    bo[4 * tid + 1] = z;
-    bo[4 * tid + 2] = z;
-    bo[4 * tid + 3] = z;
-    so[tid] = z;
-    lo[tid] = 0;
-    io[tid] = 0;
+    zero_row(bo, so, lo, io, tid);
   }
   if (tid == 0) count[n] = M;
 }
 
-// ---- merge of test-time augmentation's views (include/codetr_hip.h states the semantics) ---------------------------
-
 constexpr int kTtaMaxC = CODETR_TTA_MAX_CANDIDATES;  // V * Q of a merge: positions 0 .. 4095 fit the 16-bit tables
-constexpr int kTtaThreads = 1024, kTtaWaves = kTtaThreads / 64;
 
 // dynamic LDS of tta_merge_kernel over P slots: box 16, label / output key 8, score 4, index 4, position 2, segment 2
-// bytes per slot = 36 P + 16; 144 KB at P = 4096, hence the opt-in of large_lds.h.  The areas are not stored: with
-// contraction off (w * h) of the same box is the same rounded product every time it is computed.
+// bytes per slot = 36 P + 16; 144 KB at P = 4096, hence the opt-in of large_lds.h
 constexpr size_t tta_lds_bytes(int P) { return (size_t)P * 36 + 16; }
-
-// sum of one int per thread over the 1024-thread workgroup (two barriers; s_wave is free again after the second)
-__device__ __forceinline__ int tta_block_sum(int v, int* s_wave, int lane, int wave) {
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m, 64);
-  __syncthreads();
-  if (lane == 0) s_wave[wave] = v;
-  __syncthreads();
-  int total = 0;
-#pragma unroll
-  for (int w = 0; w < kTtaWaves; ++w) total += s_wave[w];
-  return total;
-}
-
-// bitonic_desc_u64 for P up to 4096: every thread takes P / 2048 pairs of a step
-__device__ __forceinline__ void tta_bitonic_desc_u64(unsigned long long* s, int P, int tid) {
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < P / 2; t += kTtaThreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long a = s[lo], b = s[hi];
-        if ((a < b) == desc) {
-          s[lo] = b;
-          s[hi] = a;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
 
 // grid N, 1024 threads: image n's V views of Q detections (rows j < count[v, n] are candidates, c = v Q + j) -> the merged
 // detections in output order, cut to max_keep, count_out[n] of them; rows [count_out, K) of the outputs are zero.
 // P = the power of two >= V Q.  mode: CODETR_TTA_NMS_*.
 template <class T>
-__global__ __launch_bounds__(kTtaThreads) void tta_merge_kernel(
+__global__ __launch_bounds__(kNmsThreads) void tta_merge_kernel(
     const T* __restrict__ boxes, const T* __restrict__ scores, const int64_t* __restrict__ labels,
     const int* __restrict__ count, int V, int N, int Q, int P, unsigned flip_mask, const float* __restrict__ width,
     int mode, float iou_thr, float min_score, int max_keep, int K, T* __restrict__ boxes_out,
@@ -608,45 +668,40 @@ __global__ __launch_bounds__(kTtaThreads) void tta_merge_kernel(
   extern __shared__ __align__(16) unsigned char tta_lds[];
   float4* s_box = reinterpret_cast<float4*>(tta_lds);  // by position after sort 1 (label segments, ascending c)
   unsigned long long* s_lab = reinterpret_cast<unsigned long long*>(tta_lds + (size_t)16 * P);  // sort 1, major key
-  unsigned long long* s_out = s_lab;  // (after the segments are found) emitted: score key << 32 | (2^32 - 1 - c); else 0
+  unsigned long long* s_out = s_lab;  // (after the segments are found) emitted: pack_key(score, c); else 0
   float* s_score = reinterpret_cast<float*>(tta_lds + (size_t)24 * P);  // current score; its own lane's only
-  unsigned* s_idx = reinterpret_cast<unsigned*>(tta_lds + (size_t)28 * P);  // sort 1, minor key: 2^32 - 1 - c; 0 = none
+  unsigned* s_idx = reinterpret_cast<unsigned*>(tta_lds + (size_t)28 * P);  // sort 1, minor key: inv_index(c); 0 = none
   unsigned short* s_pos = reinterpret_cast<unsigned short*>(tta_lds + (size_t)32 * P);  // c -> position
   unsigned short* s_seg = reinterpret_cast<unsigned short*>(tta_lds + (size_t)34 * P);  // segment starts, then Vn
-  __shared__ unsigned long long s_wmax[kTtaWaves];
-  __shared__ int s_wave[kTtaWaves];
+  __shared__ unsigned long long s_wmax[kNmsWaves];
+  __shared__ int s_wave[kNmsWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n = blockIdx.x;
   const int C = V * Q;
   const bool soft = mode != CODETR_TTA_NMS_HARD;
-  const bool linear = mode == CODETR_TTA_NMS_SOFT_LINEAR;
   // element (v, n, j) of the stacked inputs
   auto at = [&](int c, int& v) -> size_t {
     v = c / Q;
     return ((size_t)v * N + n) * Q + (size_t)(c - v * Q);
   };
 
-  // 1. soft modes: the global maximum g (ties: lowest c), which the min_score drop spares
+  // front end: (soft modes) the global maximum g (ties: lowest c), which the min_score drop spares; then the sort keys of
+  // the live candidates, (label, c), everything else 0
   unsigned long long g = 0;
   if (soft) {
     unsigned long long best = 0;
-    for (int c = tid; c < C; c += kTtaThreads) {
+    for (int c = tid; c < C; c += kNmsThreads) {
       int v;
       const size_t e = at(c, v);
       if (c - v * Q < count[v * N + n]) {
-        const unsigned long long k = ((unsigned long long)score_key(to_f32(scores[e])) << 32) | (unsigned long long)(0xffffffffu - (unsigned)c);
+        const unsigned long long k = pack_key(to_f32(scores[e]), (unsigned)c);
         best = k > best ? k : best;
       }
     }
-    best = wave_max_u64(best);
-    if (lane == 0) s_wmax[wave] = best;
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kTtaWaves; ++w) g = s_wmax[w] > g ? s_wmax[w] : g;
+    g = block_max_u64(best, s_wmax, lane, wave);
   }
-  // 2. the sort keys of the live candidates: (label, 2^32 - 1 - c); everything else 0
   int nlive = 0;
-  for (int c = tid; c < P; c += kTtaThreads) {
+  for (int c = tid; c < P; c += kNmsThreads) {
     bool live = false;
     unsigned long long lab = 0;
     if (c < C) {
@@ -654,40 +709,21 @@ __global__ __launch_bounds__(kTtaThreads) void tta_merge_kernel(
       const size_t e = at(c, v);
       if (c - v * Q < count[v * N + n]) {
         const float s = to_f32(scores[e]);
-        const unsigned long long k = ((unsigned long long)score_key(s) << 32) | (unsigned long long)(0xffffffffu - (unsigned)c);
-        live = !soft || k == g || !(s < min_score);
+        live = !soft || pack_key(s, (unsigned)c) == g || !(s < min_score);
         lab = (unsigned long long)labels[e];
       }
     }
     s_lab[c] = live ? lab : 0ull;
-    s_idx[c] = live ? 0xffffffffu - (unsigned)c : 0u;
+    s_idx[c] = live ? inv_index((unsigned)c) : 0u;
     nlive += live ? 1 : 0;
   }
-  const int Vn = tta_block_sum(nlive, s_wave, lane, wave);  // (its barriers: the sort keys are complete)
+  const int Vn = block_sum(nlive, s_wave, lane, wave);  // (its barriers: the sort keys are complete)
 
-  // 3. bitonic sort by (label, 2^32 - 1 - c), descending: every label a contiguous segment in ascending c, empty slots last
-  for (int size = 2; size <= P; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = tid; t < P / 2; t += kTtaThreads) {
-        const int lo = 2 * t - (t & (stride - 1));
-        const int hi = lo + stride;
-        const bool desc = (lo & size) == 0;
-        const unsigned long long al = s_lab[lo], bl = s_lab[hi];
-        const unsigned ai = s_idx[lo], bi = s_idx[hi];
-        const bool less = al < bl || (al == bl && ai < bi);
-        if (less == desc && (al != bl || ai != bi)) {
-          s_lab[lo] = bl;
-          s_lab[hi] = al;
-          s_idx[lo] = bi;
-          s_idx[hi] = ai;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  // 1. by (label, c), descending: every label a contiguous segment in ascending c, empty slots last; boxes un-flipped
+  bitonic_desc<kTtaMaxC>(LabelIndexKeys{s_lab, s_idx}, P, tid);
   const float Wimg = width[n];
-  for (int p = tid; p < Vn; p += kTtaThreads) {
-    const unsigned c = 0xffffffffu - s_idx[p];
+  for (int p = tid; p < Vn; p += kNmsThreads) {
+    const unsigned c = inv_index(s_idx[p]);
     int v;
     const size_t e = at((int)c, v);
     float4 b = make_float4(to_f32(boxes[4 * e]), to_f32(boxes[4 * e + 1]), to_f32(boxes[4 * e + 2]), to_f32(boxes[4 * e + 3]));
@@ -700,110 +736,44 @@ __global__ __launch_bounds__(kTtaThreads) void tta_merge_kernel(
     s_score[p] = to_f32(scores[e]);
     s_pos[c] = (unsigned short)p;
   }
-  int S = 0;  // label segments (uniform)
-  for (int base = 0; base < P; base += kTtaThreads) {
-    const int p = base + tid;
-    const bool head = p < Vn && (p == 0 || s_lab[p] != s_lab[p - 1]);
-    const unsigned long long hbal = __ballot(head);
-    __syncthreads();  // s_wave is free (the previous round's reads are done)
-    if (lane == 0) s_wave[wave] = __popcll(hbal);
-    __syncthreads();
-    int hpos = S + __popcll(hbal & ((1ull << lane) - 1ull));
-#pragma unroll
-    for (int w = 0; w < kTtaWaves; ++w) {
-      const int cw = s_wave[w];
-      hpos += w < wave ? cw : 0;
-      S += cw;
-    }
-    if (head) s_seg[hpos] = (unsigned short)p;
-  }
-  if (tid == 0) s_seg[S] = (unsigned short)Vn;
-  __syncthreads();  // the labels were read for the last time: their array becomes s_out
-  for (int p = tid; p < P; p += kTtaThreads) s_out[p] = 0ull;
+  // 2. - 4. segments (the labels were then read for the last time: their array becomes s_out), chains (up to 64 positions
+  //    per lane), the emitted detections by (score, c)
+  const int S = segment_starts<kTtaMaxC>(s_lab, Vn, s_seg, s_wave, tid);
+  for (int p = tid; p < P; p += kNmsThreads) s_out[p] = 0ull;
   __syncthreads();
-
-  // 4. the greedy chains, as postprocess_softnms_kernel's: a wave takes whole segments, lane l holds positions
-  //    a + l + 64 e (bit e of `alive`, e < 64), no workgroup barrier per pick.  The hard rule is one more weight: 0 and gone.
-  for (int seg = wave; seg < S; seg += kTtaWaves) {
-    const int a = s_seg[seg], b = s_seg[seg + 1];
-    const int ne = (b - a + 63) >> 6;  // <= 64
-    unsigned long long alive = 0;
-    for (int e = 0; e < ne; ++e) alive |= (a + lane + 64 * e < b) ? 1ull << e : 0ull;
-    for (;;) {
-      unsigned long long best = 0;
-      for (int e = 0; e < ne; ++e) {
-        if (alive >> e & 1ull) {
-          const int p = a + lane + 64 * e;
-          const unsigned long long k = ((unsigned long long)score_key(s_score[p]) << 32) | (unsigned long long)(0xffffffffu - (unsigned)p);
-          best = k > best ? k : best;
-        }
-      }
-      best = wave_max_u64(best);
-      if (best == 0ull) break;  // (wave-uniform) the segment is exhausted
-      const int k = (int)(0xffffffffu - (unsigned)best);
-      if (((k - a) & 63) == lane) {  // the owner emits k with its current score and retires it
-        alive &= ~(1ull << ((k - a) >> 6));
-        s_out[k] = (best & 0xffffffff00000000ull) | (unsigned long long)s_idx[k];
-      }
-      const float4 bk = s_box[k];
-      const float ak = box_area(bk);
-      for (int e = 0; e < ne; ++e) {
-        if (alive >> e & 1ull) {
-          const int p = a + lane + 64 * e;
-          const float4 bj = s_box[p];
-          const float ovr = soft_overlap(bk, ak, bj, box_area(bj));
-          if (!soft) {
-            if (ovr > iou_thr) alive &= ~(1ull << e);  // (a NaN overlap compares false: kept)
-          } else {
-            float sj = s_score[p];
-            if (ovr >= iou_thr) {
-              sj = sj * (linear ? 1.f - ovr : 0.f);
-              s_score[p] = sj;
-            }
-            if (sj < min_score) alive &= ~(1ull << e);
-          }
-        }
-      }
-    }
-  }
+  run_segments<unsigned long long, true, false>(s_seg, S, s_box, nullptr, s_score, s_idx, s_out, !soft,
+                                                mode == CODETR_TTA_NMS_SOFT_LINEAR, iou_thr, min_score, lane, wave);
   __syncthreads();
-
-  // 5. order the emitted detections by (score, 2^32 - 1 - c), cut, round once to T
-  tta_bitonic_desc_u64(s_out, P, tid);
+  bitonic_desc<kTtaMaxC>(ScoreKeys{s_out}, P, tid);
   int nout = 0;
-  for (int p = tid; p < P; p += kTtaThreads) nout += s_out[p] != 0ull ? 1 : 0;
-  const int E = tta_block_sum(nout, s_wave, lane, wave);
+  for (int p = tid; p < P; p += kNmsThreads) nout += s_out[p] != 0ull ? 1 : 0;
+  const int E = block_sum(nout, s_wave, lane, wave);
   const int M = (max_keep > 0 && max_keep < E) ? max_keep : E;
+
+  // 5. cut, round once to T
   T* bo = boxes_out + (size_t)n * K * 4;
   T* so = scores_out + (size_t)n * K;
   int64_t* lo = labels_out + (size_t)n * K;
   int* io = index_out + (size_t)n * K;
-  for (int r = tid; r < K; r += kTtaThreads) {
+  for (int r = tid; r < K; r += kNmsThreads) {
     if (r < M) {
-      const unsigned c = 0xffffffffu - (unsigned)s_out[r];
+      const unsigned c = inv_index((unsigned)s_out[r]);
       const int p = s_pos[c];
       int v;
-      const size_t e = at((int)c, v);
-      const float4 b = s_box[p];
-      bo[4 * r] = from_f32<T>(b.x);
-      bo[4 * r + 1] = from_f32<T>(b.y);
-      bo[4 * r + 2] = from_f32<T>(b.z);
-      bo[4 * r + 3] = from_f32<T>(b.w);
-      so[r] = from_f32<T>(s_score[p]);
-      lo[r] = labels[e];
-      io[r] = (int)c;
+      write_row(bo, so, lo, io, r, s_box[p], from_f32<T>(s_score[p]), labels[at((int)c, v)], (int)c);
     } else {
-      const T z = from_f32<T>(0.f);
-      bo[4 * r] = z;
-      bo[4 * r + 1] = z;
-      bo[4 * r + 2] = z;
-      bo[4 * r + 3] = z;
-      so[r] = z;
-      lo[r] = 0;
-      io[r] = 0;
+      zero_row(bo, so, lo, io, r);
     }
   }
   if (tid == 0) count_out[n] = M;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+
+// what a launch returns: 0, or the HIP error it left
+int launched() {
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
 }
 
 template <class OutT>
@@ -818,8 +788,7 @@ int launch_pre(void* stream, const void* src, int64_t Hs, int64_t Ws, int64_t Hr
                      static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), (int)Hs, (int)Ws, (int)Hr,
                      (int)Wr, (int)Hp, (int)Wp, mean[0], mean[1], mean[2], stdv[0], stdv[1], stdv[2], pad[0], pad[1],
                      pad[2], static_cast<OutT*>(dst), static_cast<OutT*>(mask));
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return launched();
 }
 
 // the checks of a batched preprocess call and its kernel arguments; `cols` = 7 (codetr_preprocess_batch_u8_*) or 8
@@ -852,36 +821,26 @@ int pre_batch_args(const void* src, int64_t src_bytes, int64_t N, const int64_t*
   return 0;
 }
 
+// cols = 7: preprocess_batch_kernel; 8: preprocess_views_kernel
 template <class OutT>
-int launch_pre_batch(void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int64_t H,
-                     int64_t W, const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst,
-                     void* mask) {
+int launch_pre_rows(int cols, void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int64_t H,
+                    int64_t W, const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst,
+                    void* mask) {
   BatchTable tab = {};
   BatchNorm nm;
   unsigned flips;
-  if (const int rc = pre_batch_args(src, src_bytes, N, images, 7, H, W, mean, stdv, pad, pad_fill, dst, tab, nm, flips))
+  if (const int rc = pre_batch_args(src, src_bytes, N, images, cols, H, W, mean, stdv, pad, pad_fill, dst, tab, nm, flips))
     return rc;
-  hipLaunchKernelGGL((preprocess_batch_kernel<OutT>), dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N),
-                     dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), tab, nm,
-                     (int)H, (int)W, static_cast<OutT*>(dst), static_cast<OutT*>(mask));
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
-}
-
-template <class OutT>
-int launch_pre_views(void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int64_t H,
-                     int64_t W, const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst,
-                     void* mask) {
-  BatchTable tab = {};
-  BatchNorm nm;
-  unsigned flips;
-  if (const int rc = pre_batch_args(src, src_bytes, N, images, 8, H, W, mean, stdv, pad, pad_fill, dst, tab, nm, flips))
-    return rc;
-  hipLaunchKernelGGL((preprocess_views_kernel<OutT>), dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N),
-                     dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), tab, flips,
-                     nm, (int)H, (int)W, static_cast<OutT*>(dst), static_cast<OutT*>(mask));
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  const dim3 grid((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N);
+  const auto s = static_cast<hipStream_t>(stream);
+  const auto in = static_cast<const unsigned char*>(src);
+  if (cols == 8)
+    hipLaunchKernelGGL((preprocess_views_kernel<OutT>), grid, dim3(256), 0, s, in, tab, flips, nm, (int)H, (int)W,
+                       static_cast<OutT*>(dst), static_cast<OutT*>(mask));
+  else
+    hipLaunchKernelGGL((preprocess_batch_kernel<OutT>), grid, dim3(256), 0, s, in, tab, nm, (int)H, (int)W,
+                       static_cast<OutT*>(dst), static_cast<OutT*>(mask));
+  return launched();
 }
 
 template <class T>
@@ -897,8 +856,7 @@ int launch_post(void* stream, const void* boxes, const void* scores, const int64
                      static_cast<const T*>(divisors), (int)Q, apply_threshold ? 1 : 0, score_threshold,
                      apply_nms ? 1 : 0, iou_threshold, static_cast<T*>(boxes_out), static_cast<T*>(scores_out),
                      labels_out, count);
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return launched();
 }
 
 template <class T>
@@ -913,13 +871,12 @@ int launch_softnms(void* stream, const void* boxes, const void* scores, const in
   if (!__builtin_isfinite(iou_threshold) || !__builtin_isfinite(min_score)) return CODETR_E_BADARG;
   if (Q > kPostMaxQ || N > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
   const int keep = max_keep <= 0 || max_keep > Q ? 0 : (int)max_keep;
-  hipLaunchKernelGGL((postprocess_softnms_kernel<T>), dim3((unsigned)N), dim3(kPostMaxQ), 0,
+  hipLaunchKernelGGL((postprocess_softnms_kernel<T>), dim3((unsigned)N), dim3(kNmsThreads), 0,
                      static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
                      labels, static_cast<const T*>(divisors), (int)Q, apply_threshold ? 1 : 0, score_threshold,
                      method == CODETR_SOFTNMS_LINEAR ? 1 : 0, iou_threshold, min_score, keep, static_cast<T*>(boxes_out),
                      static_cast<T*>(scores_out), labels_out, index_out, count);
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return launched();
 }
 
 template <class T>
@@ -942,13 +899,12 @@ int launch_tta_merge(void* stream, const void* boxes, const void* scores, const 
   while (P < C) P <<= 1;
   if (const hipError_t e = allow_large_lds<tta_merge_kernel<T>>((int)tta_lds_bytes(kTtaMaxC)); e != hipSuccess)
     return (int)e;
-  hipLaunchKernelGGL((tta_merge_kernel<T>), dim3((unsigned)N), dim3(kTtaThreads), tta_lds_bytes(P),
+  hipLaunchKernelGGL((tta_merge_kernel<T>), dim3((unsigned)N), dim3(kNmsThreads), tta_lds_bytes(P),
                      static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
                      labels, count, (int)V, (int)N, (int)Q, P, flip_mask, width, mode, iou_threshold, min_score,
                      max_keep > 0 ? (int)max_keep : 0, max_keep > 0 ? (int)max_keep : C, static_cast<T*>(boxes_out),
                      static_cast<T*>(scores_out), labels_out, index_out, count_out);
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return launched();
 }
 
 }  // namespace
@@ -978,68 +934,52 @@ int codetr_batched_nms_f32(void* stream, const float* boxes_sorted_dev, const in
   hipLaunchKernelGGL(batched_nms_kernel, dim3(1), dim3(threads), (size_t)((N + 15) / 16 * 16),
                      static_cast<hipStream_t>(stream), boxes_sorted_dev, labels_sorted_dev, (int)N, iou_threshold,
                      static_cast<unsigned char*>(keep_dev));
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return launched();
 }
 
-#define CODETR_PRE_BATCH_ENTRY(NAME, OUT_T)                                                                           \
-  int NAME(void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* images_host, int64_t H,    \
-           int64_t W, const float* mean_host, const float* std_host, const int* pad_value_host, float pad_fill,       \
-           void* dst_dev, void* mask_dev) {                                                                           \
-    return launch_pre_batch<OUT_T>(stream, src_dev, src_bytes, N, images_host, H, W, mean_host, std_host,             \
-                                   pad_value_host, pad_fill, dst_dev, mask_dev);                                      \
-  }
-CODETR_PRE_BATCH_ENTRY(codetr_preprocess_batch_u8_f16, _Float16)
-CODETR_PRE_BATCH_ENTRY(codetr_preprocess_batch_u8_bf16, Bf16)
-CODETR_PRE_BATCH_ENTRY(codetr_preprocess_batch_u8_f32, float)
+// STEM_f16 / STEM_bf16 / STEM_f32 (PARAMS) = LAUNCH<element type> ARGS
+#define CODETR_ENTRIES(STEM, LAUNCH, PARAMS, ARGS)            \
+  int STEM##_f16 PARAMS { return LAUNCH<_Float16> ARGS; }     \
+  int STEM##_bf16 PARAMS { return LAUNCH<Bf16> ARGS; }        \
+  int STEM##_f32 PARAMS { return LAUNCH<float> ARGS; }
 
-#define CODETR_POST_ENTRY(NAME, T)                                                                                    \
-  int NAME(void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,                    \
-           const void* divisor_dev, int64_t N, int64_t Q, int apply_threshold, float score_threshold, int apply_nms,  \
-           float iou_threshold, void* boxes_out_dev, void* scores_out_dev, int64_t* labels_out_dev, int* count_dev) { \
-    return launch_post<T>(stream, boxes_dev, scores_dev, labels_dev, divisor_dev, N, Q, apply_threshold,              \
-                          score_threshold, apply_nms, iou_threshold, boxes_out_dev, scores_out_dev, labels_out_dev,   \
-                          count_dev);                                                                                 \
-  }
-CODETR_POST_ENTRY(codetr_postprocess_detections_f16, _Float16)
-CODETR_POST_ENTRY(codetr_postprocess_detections_bf16, Bf16)
-CODETR_POST_ENTRY(codetr_postprocess_detections_f32, float)
+CODETR_ENTRIES(codetr_preprocess_batch_u8, launch_pre_rows,
+               (void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* images_host, int64_t H,
+                int64_t W, const float* mean_host, const float* std_host, const int* pad_value_host, float pad_fill,
+                void* dst_dev, void* mask_dev),
+               (7, stream, src_dev, src_bytes, N, images_host, H, W, mean_host, std_host, pad_value_host, pad_fill, dst_dev,
+                mask_dev))
 
-#define CODETR_SOFTNMS_ENTRY(NAME, T)                                                                                 \
-  int NAME(void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,                    \
-           const void* divisor_dev, int64_t N, int64_t Q, int apply_threshold, float score_threshold, int method,     \
-           float iou_threshold, float min_score, int64_t max_keep, void* boxes_out_dev, void* scores_out_dev,         \
-           int64_t* labels_out_dev, int* index_out_dev, int* count_dev) {                                             \
-    return launch_softnms<T>(stream, boxes_dev, scores_dev, labels_dev, divisor_dev, N, Q, apply_threshold,           \
-                             score_threshold, method, iou_threshold, min_score, max_keep, boxes_out_dev,              \
-                             scores_out_dev, labels_out_dev, index_out_dev, count_dev);                               \
-  }
-CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_f16, _Float16)
-CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_bf16, Bf16)
-CODETR_SOFTNMS_ENTRY(codetr_postprocess_softnms_f32, float)
+CODETR_ENTRIES(codetr_preprocess_views_u8, launch_pre_rows,
+               (void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* images_host, int64_t H,
+                int64_t W, const float* mean_host, const float* std_host, const int* pad_value_host, float pad_fill,
+                void* dst_dev, void* mask_dev),
+               (8, stream, src_dev, src_bytes, N, images_host, H, W, mean_host, std_host, pad_value_host, pad_fill, dst_dev,
+                mask_dev))
 
-#define CODETR_PRE_VIEWS_ENTRY(NAME, OUT_T)                                                                           \
-  int NAME(void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* images_host, int64_t H,    \
-           int64_t W, const float* mean_host, const float* std_host, const int* pad_value_host, float pad_fill,       \
-           void* dst_dev, void* mask_dev) {                                                                           \
-    return launch_pre_views<OUT_T>(stream, src_dev, src_bytes, N, images_host, H, W, mean_host, std_host,             \
-                                   pad_value_host, pad_fill, dst_dev, mask_dev);                                      \
-  }
-CODETR_PRE_VIEWS_ENTRY(codetr_preprocess_views_u8_f16, _Float16)
-CODETR_PRE_VIEWS_ENTRY(codetr_preprocess_views_u8_bf16, Bf16)
-CODETR_PRE_VIEWS_ENTRY(codetr_preprocess_views_u8_f32, float)
+CODETR_ENTRIES(codetr_postprocess_detections, launch_post,
+               (void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,
+                const void* divisor_dev, int64_t N, int64_t Q, int apply_threshold, float score_threshold, int apply_nms,
+                float iou_threshold, void* boxes_out_dev, void* scores_out_dev, int64_t* labels_out_dev, int* count_dev),
+               (stream, boxes_dev, scores_dev, labels_dev, divisor_dev, N, Q, apply_threshold, score_threshold, apply_nms,
+                iou_threshold, boxes_out_dev, scores_out_dev, labels_out_dev, count_dev))
 
-#define CODETR_TTA_MERGE_ENTRY(NAME, T)                                                                               \
-  int NAME(void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,                    \
-           const int* count_dev, int64_t V, int64_t N, int64_t Q, uint32_t flip_mask, const float* width_dev,         \
-           int mode, float iou_threshold, float min_score, int64_t max_keep, void* boxes_out_dev,                     \
-           void* scores_out_dev, int64_t* labels_out_dev, int* index_out_dev, int* count_out_dev) {                   \
-    return launch_tta_merge<T>(stream, boxes_dev, scores_dev, labels_dev, count_dev, V, N, Q, flip_mask, width_dev,   \
-                               mode, iou_threshold, min_score, max_keep, boxes_out_dev, scores_out_dev,               \
-                               labels_out_dev, index_out_dev, count_out_dev);                                         \
-  }
-CODETR_TTA_MERGE_ENTRY(codetr_tta_merge_f16, _Float16)
-CODETR_TTA_MERGE_ENTRY(codetr_tta_merge_bf16, Bf16)
-CODETR_TTA_MERGE_ENTRY(codetr_tta_merge_f32, float)
+CODETR_ENTRIES(codetr_postprocess_softnms, launch_softnms,
+               (void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,
+                const void* divisor_dev, int64_t N, int64_t Q, int apply_threshold, float score_threshold, int method,
+                float iou_threshold, float min_score, int64_t max_keep, void* boxes_out_dev, void* scores_out_dev,
+                int64_t* labels_out_dev, int* index_out_dev, int* count_dev),
+               (stream, boxes_dev, scores_dev, labels_dev, divisor_dev, N, Q, apply_threshold, score_threshold, method,
+                iou_threshold, min_score, max_keep, boxes_out_dev, scores_out_dev, labels_out_dev, index_out_dev,
+                count_dev))
+
+CODETR_ENTRIES(codetr_tta_merge, launch_tta_merge,
+               (void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,
+                const int* count_dev, int64_t V, int64_t N, int64_t Q, uint32_t flip_mask, const float* width_dev,
+                int mode, float iou_threshold, float min_score, int64_t max_keep, void* boxes_out_dev,
+                void* scores_out_dev, int64_t* labels_out_dev, int* index_out_dev, int* count_out_dev),
+               (stream, boxes_dev, scores_dev, labels_dev, count_dev, V, N, Q, flip_mask, width_dev, mode, iou_threshold,
+                min_score, max_keep, boxes_out_dev, scores_out_dev, labels_out_dev, index_out_dev, count_out_dev))
+#undef CODETR_ENTRIES
 
 }  // extern "C"

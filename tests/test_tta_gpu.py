@@ -247,6 +247,40 @@ def test_unflip_tie_and_threshold_rules_on_the_gpu():
     assert run([[0, 0, 2, 2], [5, 5, 6, 6]], [0.5, 0.5], [False, False], 10.0, hard)[0] == [0, 1]
 
 
+ONE_VIEW = [(dt, Q, False) for dt in DTYPES for Q in (1, 65, 300)] + [(torch.float32, 1024, True)]
+
+
+@pytest.mark.parametrize("method", ["linear", "naive"])
+@pytest.mark.parametrize("dtype,Q,one_label", ONE_VIEW)
+def test_one_view_merge_equals_the_soft_postprocess(dtype, Q, one_label, method):
+    """GPU against GPU: the merge of ONE unflipped view with every row a candidate is the soft-NMS post-processing of
+    that view with unit divisors and no score threshold -- both kernels are their own front end followed by the same
+    sort, segment, chain and row-writing code.  count and all Q rows of index, labels, scores and boxes, bit for bit.
+    Q = 1024 under one label is 16 positions per lane in both (a 32-bit mask in one, a 64-bit mask in the other)."""
+    from codetr import hip_ops
+    from test_softnms_gpu import _image
+
+    N, t = 2, 0.8 if one_label else 0.5
+    rng = np.random.default_rng(1200 + Q)
+    layouts = ("one", "one") if one_label else ("one", "mixed")      # ties, zero scores, zero-area pairs; no NaN
+    images = [_image(rng, Q, layout, one_label or i == 0, dtype) for i, layout in enumerate(layouts)]
+    boxes = torch.stack([im[0] for im in images]).to(DEV)
+    scores = torch.stack([im[1] for im in images]).to(DEV)
+    labels = torch.from_numpy(np.stack([im[2] for im in images])).to(DEV)
+    view = hip_ops.Detections(boxes, scores, labels, torch.full((N,), Q, dtype=torch.int32, device=DEV), None)
+    merged = hip_ops.detections_to_host(hip_ops.tta_merge(
+        [view], [False], [1000.0] * N, dict(type="soft_nms", iou_threshold=t, method=method, min_score=1e-3), None))
+    soft = hip_ops.detections_to_host(hip_ops.postprocess_detections_soft(
+        boxes, scores, labels, torch.ones((N, 4), dtype=dtype, device=DEV), None, t, method, 1e-3, None))
+    print(f"{dtype} Q={Q} {method}: counts {merged.count.tolist()} / {soft.count.tolist()}")
+    assert merged.scores.shape == soft.scores.shape == (N, Q)
+    assert merged.count.tolist() == soft.count.tolist()
+    if Q >= 65:
+        assert all(0 < c < Q for c in soft.count.tolist())             # something was picked, something left
+    assert torch.equal(merged.index, soft.index) and torch.equal(merged.labels, soft.labels)
+    assert torch.equal(_bits(merged.scores), _bits(soft.scores)) and torch.equal(_bits(merged.boxes), _bits(soft.boxes))
+
+
 def test_tta_merge_host_side_limits():
     from codetr import hip_ops
 
