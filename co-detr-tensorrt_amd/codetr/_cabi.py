@@ -126,6 +126,13 @@ SIGNATURES = {
                                      ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_tta_merge_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
                                     ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_draw_font": (_i32, [_vp]),
+    "codetr_draw_detections_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
+                                          ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
+    "codetr_draw_detections_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
+                                           ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
+    "codetr_draw_detections_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
+                                          ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
     "codetr_patch_merge_layernorm_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_patch_merge_layernorm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
     "codetr_mask_pyramid": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32]),
@@ -194,7 +201,7 @@ CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 
          "sine_pos_tokens": 0, "ffn_fused": 0, "ffn_oproj_fused": 0, "linear_splitk": 0, "linear_sk": 0, "mask_pyramid": 0,
          "query_sine_embed": 0, "encoder_geometry": 0, "row_max": 0, "preprocess": 0, "batched_nms": 0,
          "preprocess_batch": 0, "postprocess_detections": 0, "postprocess_softnms": 0,
-         "preprocess_views": 0, "tta_merge": 0,
+         "preprocess_views": 0, "tta_merge": 0, "draw_detections": 0,
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
@@ -213,7 +220,7 @@ _QUERIES = {"codetr_hip_abi_version", "codetr_hip_strerror", "codetr_msda_varian
             "codetr_linear_pp_supported", "codetr_linear_pp_preferred", "codetr_msda_op4_supported", "codetr_swin_mlp_supported",
             "codetr_msda_encoder_packed_lds_bytes", "codetr_msda_pack_projection_index", "codetr_window_attention_bias_index",
             "codetr_mx_scale_bytes", "codetr_decoder_layer_supported",
-            "codetr_decoder_layer_blob_halfs"}
+            "codetr_decoder_layer_blob_halfs", "codetr_draw_font"}
 
 
 class _RecordingLib:
@@ -630,6 +637,35 @@ def tta_merge(boxes, scores, labels, count, flip_mask, width, mode, iou_threshol
         V, N, Q, int(flip_mask), width.data_ptr(), int(mode), float(iou_threshold), float(min_score), int(max_keep),
         boxes_out.data_ptr(), scores_out.data_ptr(), labels_out.data_ptr(), index_out.data_ptr(), count_out.data_ptr())
     check(rc, "codetr_tta_merge")
+
+
+DRAW_MAX_Q = 4096              # CODETR_DRAW_MAX_Q: detection rows per image of codetr_draw_detections_*
+DRAW_MAX_SIDE = 16384          # CODETR_DRAW_MAX_SIDE
+DRAW_FONT_BYTES = 665          # CODETR_DRAW_FONT_BYTES: 95 glyphs (ASCII 32..126) x 7 rows
+_DRAW_BY_DTYPE = {torch.float16: "codetr_draw_detections_f16", torch.bfloat16: "codetr_draw_detections_bf16",
+                  torch.float32: "codetr_draw_detections_f32"}
+
+
+def draw_font() -> bytes:
+    """the library's 5x7 font (host only, no GPU): 95 x 7 bytes, top row first, bit 4 = the leftmost pixel"""
+    out = (ctypes.c_ubyte * DRAW_FONT_BYTES)()
+    check(load().codetr_draw_font(out), "codetr_draw_font")
+    return bytes(out)
+
+
+def draw_detections(buf, rows, boxes, scores, labels, count, palette, names, line_width, alpha, score_thr, text_rgb,
+                    font_scale, draw_labels):
+    """buf: flat uint8 device buffer, drawn on in place; rows: <= PREPROCESS_BATCH_MAX (offset, H, W); boxes [N,Q,4] /
+    scores [N,Q] in one dtype, labels [N,Q] int64, count [N] int32; palette [C,3] / names [C,24] uint8 on the device;
+    text_rgb = 0xRRGGBB (include/codetr_hip.h states the rendering)"""
+    CALLS["draw_detections"] += 1
+    N, Q = scores.shape
+    table = (ctypes.c_int64 * (3 * N))(*[int(v) for row in rows for v in row])
+    rc = getattr(load(), _DRAW_BY_DTYPE[scores.dtype])(
+        current_stream_ptr(buf.device), buf.data_ptr(), buf.numel(), N, table, boxes.data_ptr(), scores.data_ptr(),
+        labels.data_ptr(), count.data_ptr(), Q, palette.data_ptr(), names.data_ptr(), palette.shape[0], int(line_width),
+        float(alpha), float(score_thr), int(text_rgb), int(font_scale), 1 if draw_labels else 0)
+    check(rc, "codetr_draw_detections")
 
 
 def mask_pyramid(img_masks, shapes):

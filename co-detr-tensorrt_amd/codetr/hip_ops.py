@@ -740,6 +740,107 @@ def tta_merge(view_dets, flips, widths, nms=None, max_per_img=None):
     return out
 
 
+DRAW_MAX_Q = _cabi.DRAW_MAX_Q
+DRAW_MAX_SIDE = _cabi.DRAW_MAX_SIDE
+DRAW_NAME_ROW = 24    # bytes per row of the names table: the length, then up to 23 characters
+# the defaults of mmdet's DetLocalVisualizer (line_width, alpha, text_color) and of the Inferencer's pred_score_thr
+DRAW_STYLE = dict(line_width=3, alpha=0.8, score_thr=0.3, text_color=(200, 200, 200), font_scale=1, draw_labels=True)
+
+
+def draw_style(style=None):
+    """the style of draw_detections, validated: the keys of DRAW_STYLE (missing ones take its values) -> a new dict.
+    ValueError for an unknown key, line_width outside 1..15, alpha outside [0, 1], font_scale outside 1..4, a
+    text_color that is not three values in 0..255, a score_thr that is not a number."""
+    st = dict(DRAW_STYLE)
+    style = dict(style or {})
+    unknown = set(style) - set(st)
+    if unknown:
+        raise ValueError(f"draw style: unknown key(s) {sorted(unknown)}; known: {sorted(st)}")
+    st.update(style)
+
+    def whole(key, lo, hi):
+        v = st[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or int(v) != v or not lo <= v <= hi:
+            raise ValueError(f"draw style: {key} must be an integer in {lo}..{hi}, got {v!r}")
+        return int(v)
+
+    st["line_width"] = whole("line_width", 1, 15)
+    st["font_scale"] = whole("font_scale", 1, 4)
+    if isinstance(st["alpha"], bool) or not isinstance(st["alpha"], (int, float)) or not 0.0 <= st["alpha"] <= 1.0:
+        raise ValueError(f"draw style: alpha must be in [0, 1], got {st['alpha']!r}")
+    thr = st["score_thr"]
+    if isinstance(thr, bool) or not isinstance(thr, (int, float)) or thr != thr:
+        raise ValueError(f"draw style: score_thr must be a number, got {thr!r}")
+    tc = st["text_color"]
+    if not isinstance(tc, (tuple, list)) or len(tc) != 3 or any(int(v) != v or not 0 <= v <= 255 for v in tc):
+        raise ValueError(f"draw style: text_color must be three values in 0..255, got {tc!r}")
+    st["alpha"], st["score_thr"], st["text_color"] = float(st["alpha"]), float(thr), tuple(int(v) for v in tc)
+    st["draw_labels"] = bool(st["draw_labels"])
+    return st
+
+
+def draw_names_table(classes):
+    """class names -> the [C, 24] uint8 table draw_detections reads (a CPU tensor): byte 0 of a row is the length, the
+    name truncated to 23 characters; a character outside ASCII 32..126 becomes '?'"""
+    rows = []
+    for name in classes:
+        text = "".join(ch if 32 <= ord(ch) <= 126 else "?" for ch in str(name))[:DRAW_NAME_ROW - 1]
+        rows.append(bytes([len(text)]) + text.encode("ascii") + bytes(DRAW_NAME_ROW - 1 - len(text)))
+    return torch.frombuffer(bytearray(b"".join(rows)), dtype=torch.uint8).view(len(rows), DRAW_NAME_ROW)
+
+
+def draw_detections(buf_u8, rows, dets, names, palette, style=None):
+    """The Inferencer's visualisation in one launch per PREPROCESS_BATCH_MAX images (csrc/draw.hip; the rendering is
+    stated in include/codetr_hip.h): per detection with a score above style['score_thr'] a box outline in its class
+    colour and, after all outlines, "<name>: <percent>" on a darkened patch at the box's top-left corner.  In place.
+      buf_u8    one flat uint8 device buffer holding RGB HWC images (Inferencer.upload's)
+      rows      (offset, H, W) per image
+      dets      Detections / SoftDetections over [N, Q] rows, N = len(rows), Q <= 4096, boxes in image coordinates
+      names     [C, 24] uint8 on the device (draw_names_table); palette [C, 3] uint8 on the device
+      style     the keys of DRAW_STYLE
+    -> buf_u8.  ValueError for Q > 4096, a bad style value, a wrong dtype or shape, CPU tensors.  Nothing is launched
+    when N == 0 or Q == 0."""
+    st = draw_style(style)
+    tensors = dict(buf=buf_u8, names=names, palette=palette, boxes=dets.boxes, scores=dets.scores, labels=dets.labels,
+                   count=dets.count)
+    for key, t in tensors.items():
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != buf_u8.device:
+            raise ValueError(f"draw_detections: {key} must be a tensor on the image buffer's GPU")
+    if buf_u8.dtype != torch.uint8 or buf_u8.dim() != 1 or not buf_u8.is_contiguous():
+        raise ValueError("draw_detections: expected one contiguous flat uint8 buffer")
+    C = palette.shape[0] if palette.dim() == 2 else 0
+    if names.dtype != torch.uint8 or palette.dtype != torch.uint8 or C == 0 or tuple(palette.shape) != (C, 3) or \
+            tuple(names.shape) != (C, DRAW_NAME_ROW):
+        raise ValueError("draw_detections: names [C, 24] and palette [C, 3] in uint8, C > 0")
+    dtype = dets.scores.dtype
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32) or dets.boxes.dtype != dtype or \
+            dets.labels.dtype != torch.int64 or dets.count.dtype != torch.int32:
+        raise ValueError("draw_detections: boxes and scores in one dtype of f16 / bf16 / f32, labels int64, count int32")
+    rows = [tuple(int(v) for v in r) for r in rows]
+    N = len(rows)
+    if dets.scores.dim() != 2 or dets.scores.shape[0] != N or tuple(dets.boxes.shape) != tuple(dets.scores.shape) + (4,) \
+            or dets.labels.shape != dets.scores.shape or tuple(dets.count.shape) != (N,):
+        raise ValueError("draw_detections: boxes [N,Q,4], scores [N,Q], labels [N,Q], count [N], N = len(rows)")
+    Q = dets.scores.shape[1]
+    if Q > DRAW_MAX_Q:
+        raise ValueError(f"draw_detections: at most {DRAW_MAX_Q} detection rows per image, got {Q}")
+    for off, H, W in rows:
+        if not (1 <= H <= DRAW_MAX_SIDE and 1 <= W <= DRAW_MAX_SIDE) or off < 0 or off + H * W * 3 > buf_u8.numel():
+            raise ValueError(f"draw_detections: image (offset {off}, {H}x{W}) outside the buffer or larger than "
+                             f"{DRAW_MAX_SIDE} a side")
+    if N == 0 or Q == 0:
+        return buf_u8
+    boxes, scores, labels, count = (t.contiguous() for t in (dets.boxes, dets.scores, dets.labels, dets.count))
+    tc = st["text_color"]
+    with torch.cuda.device(buf_u8.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            _cabi.draw_detections(buf_u8, rows[i:j], boxes[i:j], scores[i:j], labels[i:j], count[i:j],
+                                  palette.contiguous(), names.contiguous(), st["line_width"], st["alpha"], st["score_thr"],
+                                  (tc[0] << 16) | (tc[1] << 8) | tc[2], st["font_scale"], st["draw_labels"])
+    return buf_u8
+
+
 def mask_pyramid(img_masks, shapes):
     """img_masks [B,H,W] (float 0/1, bool or uint8; non-zero = padding) + level shapes [(H_l, W_l)] ->
     (mask_flat [B,S] bool, ycum, xcum, valid_counts [B,L,2] fp32): the level masks (nearest resize), their running

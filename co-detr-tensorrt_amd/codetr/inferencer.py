@@ -1,14 +1,15 @@
 """``Inferencer`` -- the reference's image-in / detections-out wrapper (reference codetr/inferencer.py:27-499), with
 its pre- and post-processing on the GPU.
 
-Same constructor and call signature for the parts that do not need mmengine's visualiser:
+Same constructor and call signature:
 ``Inferencer(model, model_file, dataset_meta, score_threshold=None, iou_threshold=None)`` reads ``score_thr`` /
 ``nms.iou_threshold`` from ``cfg.model.test_cfg[0]`` (reference :60-70), the mean / std of
 ``cfg.model.data_preprocessor`` (:72-76) and the ``Resize`` / ``Pad`` steps of the test pipeline (:95-101);
 ``__call__(images, ..., device, dtype)`` takes RGB ``np.ndarray`` images and returns
 ``{"predictions": [{"labels", "scores", "bboxes"}, ...], "visualization": []}`` (reference :402-485, ``pred2dict``
-:303-341).  Visualisation (mmengine ``Visualizer``, cv2) is outside the scope of this build: ``return_vis`` /
-``show`` raise.
+:303-341).  ``no_save_pred=False`` with an ``out_dir`` writes ``out_dir/preds/{num_predicted_imgs}.json`` per image, as
+``pred2dict`` does.  Without a ``visualizer`` (below) ``return_vis`` raises; ``show`` and ``return_datasamples`` (a
+window, mmengine's ``DetDataSample``) always do.
 
 Per image (reference :441-452, :343-378): upload the uint8 image, one kernel for resize + pad + normalise + mask
 (``hip_ops.preprocess_image``), ``model(batch_inputs, img_masks)``, score threshold, per-class NMS
@@ -41,7 +42,29 @@ step, which mmdet's TTA pipelines do not have), one forward and one of the post-
 view's own scale factors as divisors; then one ``hip_ops.tta_merge`` launch and one download.  At most 16 views and
 ``views * num_queries <= 4096``.  Parity with mmdet / mmcv is unpinned (neither is installed here); as in the soft-NMS
 kernel classes are told apart by comparing labels, ties go to the lowest index and the IoU arithmetic is the project's.
+
+``visualizer`` (the reference builds mmdet's ``DetLocalVisualizer`` from ``cfg.visualizer``, :125-146, and draws in
+``visualize``, :163-235): ``None``, the default, changes nothing.  A dict with any of ``line_width`` (1..15, default 3),
+``alpha`` (0.8), ``text_color`` ((200, 200, 200)), ``font_scale`` (1..4), ``draw_labels``, ``palette`` and ``classes`` --
+or ``"config"``, which reads ``line_width`` / ``alpha`` / ``text_color`` from ``cfg.visualizer`` and is a ``ValueError``
+for a config without that entry -- turns the drawing on: ``__call__(..., return_vis=True)`` returns one ``[H, W, 3]``
+uint8 array per image in ``results_dict["visualization"]``, and ``out_dir`` without ``no_save_vis`` writes
+``out_dir/vis/%08d.png`` (PNG through stdlib ``zlib``, where the reference writes ``.jpg`` through cv2).
+``pred_score_thr`` is the drawing's score threshold; ``draw_pred=False`` returns the original images.  Class names:
+``visualizer["classes"]``, else ``dataset_meta["classes"]``, else ``str(label)``; cut to 23 characters, a non-ASCII
+character becomes ``?``.  Palette: RGB triples from the same two places; for a name such as ``"coco"`` or nothing, a
+generated table (``generated_palette``: mmdet's named palettes are not part of this build).  A visualising call takes
+the chunked path; per chunk one ``hip_ops.draw_detections`` launch draws every image's final detections (plain, soft
+or the TTA merge's, cut to ``max_per_img``) on the buffer the chunk's one upload filled, in place and after the last
+preprocessing launch on the stream, and one more device-to-host copy fetches that buffer.  The rendering is the
+project's own, modelled on ``DetLocalVisualizer``'s defaults and stated pixel by pixel in ``include/codetr_hip.h``.
+Parity with mmdet's visualiser is unpinned (neither mmdet nor matplotlib is installed here).
 """
+import colorsys
+import json
+import os
+import struct
+import zlib
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -145,9 +168,85 @@ def tta_settings(cfg, tta):
                 views=views)
 
 
+def generated_palette(n):
+    """n RGB triples for classes without a palette of their own: the hue steps by the golden ratio (neighbouring
+    labels get distant colours), fixed saturation and value; the same table on every call"""
+    out = []
+    for i in range(n):
+        r, g, b = colorsys.hsv_to_rgb((i * 0.6180339887498949) % 1.0, 0.75, 1.0)
+        out.append((int(r * 255 + 0.5), int(g * 255 + 0.5), int(b * 255 + 0.5)))
+    return out
+
+
+VISUALIZER_KEYS = ("line_width", "alpha", "text_color", "font_scale", "draw_labels", "palette", "classes")
+
+
+def _meta(dataset_meta, key):
+    if dataset_meta is None:
+        return None
+    return dataset_meta.get(key) if isinstance(dataset_meta, dict) else getattr(dataset_meta, key, None)
+
+
+def visualizer_settings(cfg, visualizer, dataset_meta=None):
+    """How `Inferencer(..., visualizer=...)` reads its argument: None -> None; a dict with keys of VISUALIZER_KEYS (the
+    style of hip_ops.draw_detections without score_thr, which is the call's pred_score_thr, plus `palette` and
+    `classes`) is validated; "config" takes line_width / alpha / text_color from `cfg.visualizer` (ValueError when the
+    config has no such entry, the case in which the reference raises).  Class names: visualizer['classes'], else
+    dataset_meta['classes'], else str(label) for the query head's num_classes labels.  Palette: a list of RGB triples
+    from the same two places; for a name such as 'coco', or nothing, `generated_palette`.
+    -> dict(style, classes [str], palette [(r, g, b)], names: the [C, 24] uint8 table, colors: [C, 3] uint8)"""
+    if visualizer is None:
+        return None
+    if visualizer == "config":
+        entry = cfg.get("visualizer")
+        if entry is None:
+            raise ValueError('visualizer="config": the config has no "visualizer" entry')
+        visualizer = {k: entry[k] for k in ("line_width", "alpha", "text_color") if k in entry}
+    if not isinstance(visualizer, dict):
+        raise ValueError(f"visualizer must be None, 'config' or a dict with keys of {VISUALIZER_KEYS}")
+    unknown = set(visualizer) - set(VISUALIZER_KEYS)
+    if unknown:
+        raise ValueError(f"visualizer: unknown key(s) {sorted(unknown)}; known: {list(VISUALIZER_KEYS)}")
+    style = hip_ops.draw_style({k: v for k, v in visualizer.items() if k not in ("palette", "classes")})
+    classes = visualizer.get("classes")
+    if classes is None:
+        classes = _meta(dataset_meta, "classes")
+    if classes is None:
+        head = cfg.model.get("query_head") or {}
+        classes = [str(i) for i in range(int(head.get("num_classes", 80)))]
+    classes = [str(c) for c in classes]
+    if not classes:
+        raise ValueError("visualizer: no classes")
+    palette = visualizer.get("palette")
+    if palette is None:
+        palette = _meta(dataset_meta, "palette")
+    if palette is None or isinstance(palette, str):
+        palette = generated_palette(len(classes))   # (mmdet's named palettes are not part of this build)
+    palette = [tuple(int(v) for v in c) for c in palette]
+    if len(palette) != len(classes) or any(len(c) != 3 or min(c) < 0 or max(c) > 255 for c in palette):
+        raise ValueError("visualizer: the palette needs one RGB triple in 0..255 per class")
+    return dict(style=style, classes=classes, palette=palette, names=hip_ops.draw_names_table(classes),
+                colors=torch.tensor(palette, dtype=torch.uint8).view(-1, 3))
+
+
+def write_png(path, image):
+    """an RGB uint8 image [H, W, 3] as an 8-bit truecolour PNG: filter 0 on every row, one IDAT at a low zlib level"""
+    image = np.ascontiguousarray(image, np.uint8)
+    H, W = image.shape[:2]
+    rows = np.zeros((H, 1 + 3 * W), np.uint8)
+    rows[:, 1:] = image.reshape(H, 3 * W)
+
+    def chunk(tag, data):
+        return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", W, H, 8, 2, 0, 0, 0))
+                + chunk(b"IDAT", zlib.compress(rows.tobytes(), 1)) + chunk(b"IEND", b""))
+
+
 class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
-                 iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None):
+                 iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -191,7 +290,10 @@ class Inferencer:
         if self.scale is None:
             raise ValueError("Resize is not found in the test pipeline")
         self.tta = tta_settings(self.cfg, tta)
+        self.visualizer = visualizer_settings(self.cfg, visualizer, dataset_meta)
+        self._vis_tables = {}   # device -> (names, colors) on it: uploaded on the first visualising call there
         self.num_predicted_imgs = 0
+        self.num_visualized_imgs = 0
 
     # ---- pre ------------------------------------------------------------------------------------------
     def preprocess(self, image: np.ndarray, device="cuda:0", dtype=torch.float32):
@@ -223,6 +325,10 @@ class Inferencer:
         arithmetic of `preprocess`, stacked as mmdet's DetDataPreprocessor does (H, W = the largest Pad shape rounded
         up to pad_size_divisor; beyond an image's Pad region pad_value, mask 1).  One host-to-device copy, one launch
         per 32 images; dtype f16, bf16 or f32."""
+        return self._preprocess_chunk(images, device, dtype)[:3]
+
+    def _preprocess_chunk(self, images, device, dtype):
+        """preprocess_batch + the uploaded buffer and every image's (offset, H, W) in it, for the visualisation"""
         rows, metas, offset = [], [], 0
         d = self.pad_size_divisor
         for image in images:
@@ -249,7 +355,7 @@ class Inferencer:
             host[row[0]:row[0] + image.size] = np.ascontiguousarray(image).reshape(-1)
         src = staging.to(device, non_blocking=True)
         x, m = hip_ops.preprocess_batch(src, rows, (Hb, Wb), self.mean, self.std, self.pad_val, self.pad_value, dtype)
-        return x, m, metas
+        return x, m, metas, src, [r[:3] for r in rows]
 
     # ---- post -----------------------------------------------------------------------------------------
     def postprocess_predictions(self, batch_boxes, batch_scores, batch_labels):
@@ -304,7 +410,12 @@ class Inferencer:
         """the model's (boxes [N,Q,4], scores [N,Q], labels [N,Q]) -> one result dict per image ({"labels", "scores",
         "bboxes"} as Python lists, what `__call__` returns): score threshold, per-class NMS and / scale_factor of
         `run_inference` for the whole batch in one launch, then one device-to-host copy"""
-        host = hip_ops.detections_to_host(self.postprocess_device(predictions, metas))
+        return self._postprocess_chunk(predictions, metas)[0]
+
+    def _postprocess_chunk(self, predictions, metas):
+        """postprocess_batch + the detections it fetched, still on the device"""
+        dets = self.postprocess_device(predictions, metas)
+        host = hip_ops.detections_to_host(dets)
         out = []
         for i in range(len(metas)):
             c = int(host.count[i])
@@ -312,7 +423,7 @@ class Inferencer:
                 c = min(c, self.max_per_img)
             out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
                         "bboxes": host.boxes[i, :c].float().tolist()})
-        return out
+        return out, dets
 
     # ---- test-time augmentation ---------------------------------------------------------------------------
     def upload(self, images: List[np.ndarray], device="cuda:0", tail: Optional[torch.Tensor] = None):
@@ -362,6 +473,10 @@ class Inferencer:
     def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32):
         """one chunk through every view and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor."""
+        return self._tta_chunk(images, device, dtype)[0]
+
+    def _tta_chunk(self, images, device, dtype):
+        """tta_batch + the uploaded images, every image's (offset, H, W) and the merged detections on the device"""
         t = self.tta
         flips = (False, True) if t["flip"] else (False,)
         shapes = [im.shape[:2] for im in images]
@@ -392,20 +507,51 @@ class Inferencer:
             c = int(host.count[i])
             out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
                         "bboxes": host.boxes[i, :c].float().tolist()})
-        return out
+        return out, src, [(o, H, W) for o, (H, W) in zip(offsets, shapes)], dets
+
+    # ---- visualisation and files --------------------------------------------------------------------------
+    def draw_chunk(self, src, rows, dets, pred_score_thr):
+        """the chunk's predictions drawn on its uploaded images: one hip_ops.draw_detections launch on the buffer the
+        preprocessing read (in place, after it on the same stream) and one device-to-host copy of that buffer -> one
+        [H, W, 3] uint8 array per image"""
+        v = self.visualizer
+        key = str(src.device)
+        if key not in self._vis_tables:
+            self._vis_tables[key] = (v["names"].to(src.device), v["colors"].to(src.device))
+        names, colors = self._vis_tables[key]
+        if self.max_per_img is not None and not self.soft and self.tta is None:
+            # the hard path cuts to max_per_img on the host (postprocess_batch): the kernel gets the clamped count
+            dets = dets._replace(count=dets.count.clamp(max=self.max_per_img))
+        hip_ops.draw_detections(src, rows, dets, names, colors, dict(v["style"], score_thr=float(pred_score_thr)))
+        host = src.cpu().numpy()
+        return [host[o:o + H * W * 3].reshape(H, W, 3).copy() for o, H, W in rows]
+
+    def save_outputs(self, pred, vis, out_dir, no_save_pred):
+        """the files of one image (reference pred2dict :303-341, visualize :214-219; PNG, not JPEG)"""
+        if out_dir == "":
+            return
+        if not no_save_pred:
+            os.makedirs(os.path.join(out_dir, "preds"), exist_ok=True)
+            with open(os.path.join(out_dir, "preds", f"{self.num_predicted_imgs}.json"), "w") as f:
+                json.dump(pred, f)
+        if vis is not None:
+            os.makedirs(os.path.join(out_dir, "vis"), exist_ok=True)
+            write_png(os.path.join(out_dir, "vis", "%08d.png" % self.num_visualized_imgs), vis)
 
     def __call__(self, images: List[np.ndarray], return_vis: bool = False, show: bool = False, wait_time: int = 0,
                  no_save_vis: bool = False, draw_pred: bool = True, pred_score_thr: float = 0.3,
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
                  batch_size: int = 1) -> Dict:
-        if return_vis or show or not no_save_pred or return_datasamples:
+        if show or return_datasamples or (return_vis and self.visualizer is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
         batch_size = int(batch_size)
         results_dict = {"predictions": [], "visualization": []}
-        if batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None:
+        save_vis = out_dir != "" and not no_save_vis
+        visualise = self.visualizer is not None and (return_vis or save_vis)
+        if batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None and not visualise:
             for image in images:
                 with torch.no_grad():
                     x, m, meta = self.preprocess(image, device, dtype)
@@ -414,6 +560,7 @@ class Inferencer:
                         "bboxes": res["bboxes"].float().tolist()}
                 if print_result:
                     print(pred)
+                self.save_outputs(pred, None, out_dir, no_save_pred)
                 self.num_predicted_imgs += 1
                 results_dict["predictions"].append(pred)
             return results_dict
@@ -421,13 +568,21 @@ class Inferencer:
             chunk = images[start:start + batch_size]
             with torch.no_grad():
                 if self.tta is not None:
-                    preds = self.tta_batch(chunk, device, dtype)
+                    preds, src, rows, dets = self._tta_chunk(chunk, device, dtype)
                 else:
-                    x, m, metas = self.preprocess_batch(chunk, device, dtype)
-                    preds = self.postprocess_batch(self.model(x, m), metas)
-            for pred in preds:
+                    x, m, metas, src, rows = self._preprocess_chunk(chunk, device, dtype)
+                    preds, dets = self._postprocess_chunk(self.model(x, m), metas)
+                drawn = [None] * len(chunk)
+                if visualise:   # (draw_pred=False: the originals, as mmdet returns the undrawn image; nothing launched)
+                    drawn = self.draw_chunk(src, rows, dets, pred_score_thr) if draw_pred else [im.copy() for im in chunk]
+            for pred, vis in zip(preds, drawn):
                 if print_result:
                     print(pred)
+                self.save_outputs(pred, vis if save_vis else None, out_dir, no_save_pred)
                 self.num_predicted_imgs += 1
+                if vis is not None:
+                    self.num_visualized_imgs += 1
+                    if return_vis:
+                        results_dict["visualization"].append(vis)
                 results_dict["predictions"].append(pred)
         return results_dict

@@ -870,6 +870,75 @@ int codetr_tta_merge_f32(void *stream, const void *boxes_dev, const void *scores
                          int *count_out_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Visualisation: the predictions drawn on the original images, in place, one launch for a chunk.
+ *
+ * Replaces DetLocalVisualizer.add_datasample / _draw_instances as the reference's Inferencer.visualize drives them
+ * (codetr/inferencer.py:163-235; the call at :458-470): per detection above pred_score_thr a box outline in the colour of
+ * its class and, on a dark patch at the box's top-left corner, "<class name>: <score in percent>".  mmdet rasterises
+ * through matplotlib; this library defines its own rendering, modelled on DetLocalVisualizer's defaults (line_width 3,
+ * alpha 0.8, text colour (200, 200, 200), all boxes first and all texts after them, a text size that grows with the box
+ * area), and states it here in integer pixel arithmetic.  Parity with mmdet's visualiser is unpinned (neither mmdet nor
+ * matplotlib is installed where this is tested).
+ *
+ * codetr_draw_detections_*: N <= CODETR_PREPROCESS_BATCH_MAX images (the caller splits).
+ *   Inputs, per image n:
+ *     buf_dev            one flat byte buffer, buf_bytes long; image n is RGB uint8 HWC at byte offset images_host[3n],
+ *                        images_host HOST [N][3] int64: offset, H, W; 1 <= H, W <= CODETR_DRAW_MAX_SIDE; the images must
+ *                        lie inside the buffer and must not overlap.  No alignment is asked of offsets or row pitches.
+ *     boxes_dev [N, Q, 4] xyxy in original-image coordinates, scores_dev [N, Q] in T; labels_dev [N, Q] int64;
+ *     count_dev [N] int32: rows j < count[n] (clamped to 0..Q) are image n's detections, in the order the
+ *                        post-processing kernels emit them; Q <= CODETR_DRAW_MAX_Q.
+ *   Style: line_width lw in 1..15; alpha in [0, 1], A = (int)(alpha * 256.0f + 0.5f) in 0..256 (fp32); score_thr (fp32);
+ *     text_rgb = 0xRRGGBB; font_scale in 1..4; draw_labels 0 / 1.
+ *   Tables: palette_dev [C, 3] uint8; names_dev [C, 24] bytes: byte 0 of a row is the name's length <= 23, bytes 1.. are
+ *     ASCII 32..126 (a longer length reads as 23, any other byte draws as '?').
+ *   Drawn set: row j is drawn when its score widened to fp32 is > score_thr (strict; a NaN fails), its label is in
+ *     [0, C), its four coordinates are finite and, with every coordinate clamped in fp32 to [-16384, 16383] and
+ *     xi = (int)floorf(x + 0.5f) (one fp32 rounding in the sum), x2i >= x1i and y2i >= y1i.
+ *   blend(p, c) = (p * (256 - A) + c * A + 128) >> 8 per channel.
+ *   Layer 1, box edges, for j ascending: with a = lw / 2 and b = (lw - 1) / 2 (integer divisions), pixel (x, y) is on j's
+ *     edge iff it lies in [x1i - a, x2i + a] x [y1i - a, y2i + a] and not in [x1i + b + 1, x2i - b - 1] x
+ *     [y1i + b + 1, y2i - b - 1] (an empty inner rectangle: the box is filled); an edge pixel p becomes
+ *     blend(p, palette[label]).
+ *   Layer 2, labels, after every edge of the image, for j ascending (draw_labels = 1):
+ *     text = names[label] + ": " + score text.  v = score * 1000.0f + 0.5f with one fp32 rounding after the multiply and
+ *     one after the add (never an fma); n = 0 if !(v > 0), 1000 if v >= 1000, else (int)v; the score text is the decimal
+ *     of n / 10, ".", the digit n % 10: 87.3, 5.0, 100.0.
+ *     s = font_scale * (1 + ((x2i - x1i) * (y2i - y1i) >= 15400)): 15400 is the midpoint of mmdet's 800..30000 ramp.
+ *     The text grid has 6 * len + 1 columns and 9 rows of font pixels, each s x s image pixels, its top-left image pixel
+ *     at (x1i + lw, y1i + lw); character k fills grid columns 1 + 6k .. 5 + 6k and rows 1..7 from the 5x7 font below.
+ *     A grid pixel whose font bit is set becomes text_rgb, opaque; every other grid pixel p becomes blend(p, black).
+ *   Everything is clipped to the image; nothing is shifted or wrapped.  A pixel is written only if a layer changed it.
+ *   One 256-thread workgroup per 64x16 tile (csrc/draw.hip); no workspace.  CODETR_E_BADARG for a null pointer, N, Q or
+ *   C <= 0, an inconsistent row, a style value outside its range, a NaN score_thr; CODETR_E_TOO_LARGE for
+ *   N > CODETR_PREPROCESS_BATCH_MAX, Q > CODETR_DRAW_MAX_Q, a side > CODETR_DRAW_MAX_SIDE, C > 65536.  All checks run
+ *   before any HIP call.
+ *
+ * codetr_draw_font: HOST only -- copies the library's 5x7 font (authored for this library) to out_host: 95 glyphs, ASCII
+ *   32..126, 7 bytes each, top row first; bit 4 of a byte is the leftmost of the row's 5 pixels, bits 5..7 are zero.
+ *   The kernel reads the same table from __constant__ memory.  Returns 0, CODETR_E_BADARG for a null pointer.
+ * ------------------------------------------------------------------------------------------ */
+#define CODETR_DRAW_MAX_Q 4096
+#define CODETR_DRAW_MAX_SIDE 16384
+#define CODETR_DRAW_FONT_BYTES 665
+int codetr_draw_font(unsigned char *out_host);
+int codetr_draw_detections_f16(void *stream, void *buf_dev, int64_t buf_bytes, int64_t N, const int64_t *images_host,
+                               const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                               const int *count_dev, int64_t Q, const unsigned char *palette_dev,
+                               const unsigned char *names_dev, int64_t C, int line_width, float alpha, float score_thr,
+                               uint32_t text_rgb, int font_scale, int draw_labels);
+int codetr_draw_detections_bf16(void *stream, void *buf_dev, int64_t buf_bytes, int64_t N, const int64_t *images_host,
+                                const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                                const int *count_dev, int64_t Q, const unsigned char *palette_dev,
+                                const unsigned char *names_dev, int64_t C, int line_width, float alpha, float score_thr,
+                                uint32_t text_rgb, int font_scale, int draw_labels);
+int codetr_draw_detections_f32(void *stream, void *buf_dev, int64_t buf_bytes, int64_t N, const int64_t *images_host,
+                               const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                               const int *count_dev, int64_t Q, const unsigned char *palette_dev,
+                               const unsigned char *names_dev, int64_t C, int line_width, float alpha, float score_thr,
+                               uint32_t text_rgb, int font_scale, int draw_labels);
+
+/* ------------------------------------------------------------------------------------------
  * Backward of multi-scale deformable attention (training path).
  *
  * Replaces ms_deformable_col2im_cuda<T> / ms_deform_attn_backward (codetr/csrc/ms_deform_attn.cu:781-897, 975-1028;

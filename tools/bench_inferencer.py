@@ -24,7 +24,12 @@ the feature --; and the two TTA kernels alone, HIP events as above: tta_merge at
 both label layouts, preprocess_views beside preprocess_batch on the same 8 images resized into (1152, 768) (twice the rows: each
 image plain and mirrored).
 
-    python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta]      -> one JSON line
+`--vis` adds a `vis` sub-record (the visualisation, fp16): images/s of `Inferencer(visualizer={})` at batch_size 8 with
+`return_vis` on (pred_score_thr 0: every detection is drawn) and off; draw_detections_kernel alone, HIP events as above,
+on 8 images of 1920x1280 with 300 and with 20 drawn detections each; and the device-to-host copy of that buffer, the
+one extra transfer a visualising chunk makes.
+
+    python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis]   -> one JSON line
 """
 import argparse
 import csv
@@ -206,6 +211,62 @@ def tta_record(inf, n_images, repeats, bs=4):
     return rec
 
 
+def draw_kernel_times(N=8, H=1280, W=1920, Q=300):
+    """us per launch of draw_detections_kernel on N images of W x H with Q and with 20 drawn detections each (fp16,
+    default style, 80 classes), and the device-to-host copy of the buffer"""
+    from codetr import hip_ops
+    from codetr.inferencer import generated_palette
+
+    g = torch.Generator().manual_seed(0)
+    c = torch.rand(N, Q, 2, generator=g) * torch.tensor([W, H])
+    wh = torch.rand(N, Q, 2, generator=g) * torch.tensor([W / 3, H / 3]) + 8
+    boxes = torch.cat((c - wh / 2, c + wh / 2), -1).half().to(DEV)
+    scores = (torch.rand(N, Q, generator=g) * 0.6 + 0.35).half().to(DEV)
+    labels = torch.randint(0, 80, (N, Q), generator=g).to(DEV)
+    buf = torch.randint(0, 256, (N * H * W * 3,), dtype=torch.uint8, generator=g).to(DEV)
+    rows = [(n * H * W * 3, H, W) for n in range(N)]
+    names = hip_ops.draw_names_table([f"class {i}" for i in range(80)]).to(DEV)
+    colors = torch.tensor(generated_palette(80), dtype=torch.uint8, device=DEV)
+    out = {"images": N, "image_wh": [W, H], "buffer_bytes": buf.numel()}
+    for drawn in (Q, 20):
+        dets = hip_ops.Detections(boxes, scores, labels, torch.full((N,), drawn, dtype=torch.int32, device=DEV), None)
+        out[f"draw_detections_kernel_{drawn}_drawn_us"] = _event_us(
+            lambda: hip_ops.draw_detections(buf, rows, dets, names, colors), launches=50, warmup=5)
+    buf.cpu()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(5):
+        t0 = time.perf_counter()
+        buf.cpu()
+        times.append(time.perf_counter() - t0)
+    out["download_ms"] = round(min(times) * 1e3, 3)
+    out["download_gb_per_s"] = round(buf.numel() / min(times) / 1e9, 2)
+    return out
+
+
+def vis_record(inf, images, repeats, bs=8):
+    import bench
+    from codetr.inferencer import Inferencer
+
+    v = Inferencer(inf.model, bench.CFG, dataset_meta=None, visualizer={})
+    rec = {"batch_size": bs, "images": len(images), "repeats": repeats, "dtype": "fp16", "pred_score_thr": 0.0}
+    for name, on in (("return_vis_off", False), ("return_vis_on", True), ("return_vis_off_again", False),
+                     ("return_vis_on_again", True)):
+        with torch.no_grad():
+            v(images[:bs], return_vis=on, pred_score_thr=0.0, device=DEV, dtype=torch.float16, batch_size=bs)
+            times = []
+            for _ in range(repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = v(images, return_vis=on, pred_score_thr=0.0, device=DEV, dtype=torch.float16, batch_size=bs)
+                times.append(time.perf_counter() - t0)
+        rec[name] = {"images_per_s": round(len(images) / min(times), 2), "pass_s": [round(t, 4) for t in times]}
+    rec["detections_per_image"] = round(sum(len(p["labels"]) for p in out["predictions"]) / len(images), 1)
+    rec["image_bytes_per_pass"] = int(sum(im.size for im in images))
+    rec["kernels"] = draw_kernel_times()
+    return rec
+
+
 def soft_inferencer(inf):
     """the same model behind the post-processing its config specifies (soft-NMS, max_per_img)"""
     import bench
@@ -276,6 +337,8 @@ def main():
     ap.add_argument("--tta", action="store_true", help="add the test-time-augmentation sub-record")
     ap.add_argument("--tta-images", type=int, default=8)
     ap.add_argument("--tta-only", action="store_true", help="only the tta sub-record (implies --tta)")
+    ap.add_argument("--vis", action="store_true", help="add the visualisation sub-record")
+    ap.add_argument("--vis-only", action="store_true", help="only the vis sub-record (implies --vis)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -291,6 +354,11 @@ def main():
         print(json.dumps({"metric": "Inferencer test-time augmentation (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass",
                           "tta": tta_record(infs["fp16"], a.tta_images, a.repeats)}))
+        return
+    if a.vis_only:
+        print(json.dumps({"metric": "Inferencer visualisation (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass",
+                          "vis": vis_record(infs["fp16"], images, a.repeats)}))
         return
     infs["fp16_soft_nms"] = soft_inferencer(infs["fp16"])
     for name, inf in infs.items():
@@ -318,6 +386,8 @@ def main():
     line["postprocess_launch_us"] = post_kernel_times()
     if a.tta:
         line["tta"] = tta_record(infs["fp16"], a.tta_images, a.repeats)
+    if a.vis:
+        line["vis"] = vis_record(infs["fp16"], images, a.repeats)
     if not a.no_profile:
         line["kernel_times"] = profile()
     print(json.dumps(line))
