@@ -366,16 +366,37 @@ def linear(x2d, weight, bias, residual2d, act, out2d, row_mask=None, hm_rows=0, 
     return out2d
 
 
-_SK_PREFERRED = {}
+_PERSIST_PREFERRED = {}
+
+
+def _persist_preferred(which, M, N, K, act, has_residual) -> bool:
+    """the library's own rule for one of the two persistent GEMMs (which: 'sk' | 'pp'), asked once per problem"""
+    key = (which, M, N, K, act, bool(has_residual))
+    v = _PERSIST_PREFERRED.get(key)
+    if v is None:
+        fn = getattr(load(), f"codetr_linear_{which}_preferred")
+        v = _PERSIST_PREFERRED[key] = bool(fn(M, N, K, _ACT[act], 1 if has_residual else 0))
+    return v
+
+
+def _persist_launch(which, x2d, weight, bias, residual2d, act, out2d, *tail):
+    """marshals the operands both persistent GEMMs take; tail: what follows `act` in the entry's signature"""
+    lib = load()
+    CALLS["linear"] += 1
+    CALLS["linear_" + which] += 1
+    M, K = x2d.shape
+    fn = getattr(lib, f"codetr_linear_{which}_{'f16' if x2d.dtype == torch.float16 else 'bf16'}")
+    rc = fn(current_stream_ptr(x2d.device), x2d.data_ptr(), weight.data_ptr(),
+            bias.data_ptr() if bias is not None else None,
+            residual2d.data_ptr() if residual2d is not None else None, out2d.data_ptr(), M, weight.shape[0], K, _ACT[act],
+            *tail)
+    check(rc, "codetr_linear_" + which)
+    return out2d
 
 
 def linear_sk_preferred(M, N, K, act=None, has_residual=False) -> bool:
     """True where the persistent GEMM (csrc/gemm_sk.hip) measured faster than codetr_linear_* (the library's own rule)"""
-    key = (M, N, K, act, bool(has_residual))
-    v = _SK_PREFERRED.get(key)
-    if v is None:
-        v = _SK_PREFERRED[key] = bool(load().codetr_linear_sk_preferred(M, N, K, _ACT[act], 1 if has_residual else 0))
-    return v
+    return _persist_preferred("sk", M, N, K, act, has_residual)
 
 
 _SK_WORKSPACE = {}
@@ -394,19 +415,9 @@ def linear_sk_workspace(device):
 def linear_sk(x2d, weight, bias, residual2d, act, out2d, flags=0):
     """y = act(x @ w.T + b) (+ r) by the persistent 256-tile GEMM; flags as in include/codetr_hip.h (0 = default;
     0x40 = stream-K split of the left-over tiles, which needs the workspace)"""
-    lib = load()
-    CALLS["linear"] += 1
-    CALLS["linear_sk"] += 1
-    M, K = x2d.shape
-    N = weight.shape[0]
     ws = linear_sk_workspace(x2d.device) if flags & 0x40 else None
-    fn = lib.codetr_linear_sk_f16 if x2d.dtype == torch.float16 else lib.codetr_linear_sk_bf16
-    rc = fn(current_stream_ptr(x2d.device), x2d.data_ptr(), weight.data_ptr(),
-            bias.data_ptr() if bias is not None else None,
-            residual2d.data_ptr() if residual2d is not None else None, out2d.data_ptr(), M, N, K, _ACT[act],
-            ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, flags)
-    check(rc, "codetr_linear_sk")
-    return out2d
+    return _persist_launch("sk", x2d, weight, bias, residual2d, act, out2d,
+                           ws.data_ptr() if ws is not None else None, ws.numel() if ws is not None else 0, flags)
 
 
 def swin_mlp(x2d, ln_w, ln_b, eps, w1, b1, w2_packed, b2, out2d):
@@ -420,31 +431,14 @@ def swin_mlp(x2d, ln_w, ln_b, eps, w1, b1, w2_packed, b2, out2d):
     return out2d
 
 
-_PP_PREFERRED = {}
-
-
 def linear_pp_preferred(M, N, K, act=None, has_residual=False) -> bool:
     """True where the ping-pong GEMM (csrc/gemm_pp.hip) measured faster than the other two (the library's own rule)"""
-    key = (M, N, K, act, bool(has_residual))
-    v = _PP_PREFERRED.get(key)
-    if v is None:
-        v = _PP_PREFERRED[key] = bool(load().codetr_linear_pp_preferred(M, N, K, _ACT[act], 1 if has_residual else 0))
-    return v
+    return _persist_preferred("pp", M, N, K, act, has_residual)
 
 
 def linear_pp(x2d, weight, bias, residual2d, act, out2d, flags=0):
     """y = act(x @ w.T + b) (+ r) by the ping-pong persistent GEMM; flags as in include/codetr_hip.h"""
-    lib = load()
-    CALLS["linear"] += 1
-    CALLS["linear_pp"] += 1
-    M, K = x2d.shape
-    N = weight.shape[0]
-    fn = lib.codetr_linear_pp_f16 if x2d.dtype == torch.float16 else lib.codetr_linear_pp_bf16
-    rc = fn(current_stream_ptr(x2d.device), x2d.data_ptr(), weight.data_ptr(),
-            bias.data_ptr() if bias is not None else None,
-            residual2d.data_ptr() if residual2d is not None else None, out2d.data_ptr(), M, N, K, _ACT[act], flags)
-    check(rc, "codetr_linear_pp")
-    return out2d
+    return _persist_launch("pp", x2d, weight, bias, residual2d, act, out2d, flags)
 
 
 def query_sine_embed(ref, valid_ratios, pos_feat, temperature=10000.0, apply_sigmoid=True, valid_ratios32=None):

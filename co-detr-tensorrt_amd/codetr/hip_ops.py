@@ -60,6 +60,21 @@ def _timed(name, meta, launch, device):
     return r
 
 
+def _timed_linear(launch, device, M, N, K, *tag):
+    """run `launch()`; when bench.py has armed LINEAR_PROFILE, bracket it with HIP events on the launch stream and append
+    (start, end, flops, M, N, K, *tag) -- unless launch() returned False: a launch the library did not accept"""
+    if LINEAR_PROFILE is None:
+        return launch()
+    st = torch.cuda.current_stream(device)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(st)
+    r = launch()
+    e1.record(st)
+    if r is not False:
+        LINEAR_PROFILE.append((e0, e1, 2.0 * M * N * K, M, N, K) + tag)
+    return r
+
+
 def _gpu(x, what):
     if not x.is_cuda:
         raise RuntimeError(
@@ -131,15 +146,7 @@ def linear(x, weight, bias=None, act=None, residual=None, row_mask=None, head_ma
                     launch = lambda: _cabi.linear_sk(x2, w, bias, r2, act, out)  # noqa: E731
                 else:
                     launch = lambda: _cabi.linear(x2, w, bias, r2, act, out, mk, hm_rows, hm_hd)  # noqa: E731
-                if LINEAR_PROFILE is None:
-                    launch()
-                else:
-                    st = torch.cuda.current_stream(x.device)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record(st)
-                    launch()
-                    e1.record(st)
-                    LINEAR_PROFILE.append((e0, e1, 2.0 * x2.shape[0] * N * K, x2.shape[0], N, K))
+                _timed_linear(launch, x.device, x2.shape[0], N, K)
         if head_major:
             return out.view(x.shape[0], N // hm_hd, hm_rows, hm_hd)
         return out.view(*x.shape[:-1], N)
@@ -184,23 +191,10 @@ def linear_ln(x, norm_weight, norm_bias, eps, weight, bias=None, act=None):
         x2 = x2 if x2.is_contiguous() else x2.contiguous()
         w = weight if weight.is_contiguous() else weight.contiguous()
         out = torch.empty((x2.shape[0], N), dtype=x.dtype, device=x.device)
-        ok = [False]
-
-        def launch():
-            ok[0] = _cabi.linear_ln(x2, norm_weight, norm_bias, eps, w, bias, act, out)
-
         with torch.cuda.device(x.device):
-            if LINEAR_PROFILE is None:
-                launch()
-            else:
-                st = torch.cuda.current_stream(x.device)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st)
-                launch()
-                e1.record(st)
-                if ok[0]:
-                    LINEAR_PROFILE.append((e0, e1, 2.0 * x2.shape[0] * N * K, x2.shape[0], N, K))
-        if ok[0]:
+            ok = _timed_linear(lambda: _cabi.linear_ln(x2, norm_weight, norm_bias, eps, w, bias, act, out),
+                               x.device, x2.shape[0], N, K)
+        if ok:
             return out.view(*x.shape[:-1], N)
     return linear(layer_norm(x, norm_weight, norm_bias, eps), weight, bias, act=act)
 
@@ -233,23 +227,9 @@ def linear_xadd(x, x_add, weight, bias=None):
         a2 = a2 if a2.is_contiguous() else a2.contiguous()
         w = weight if weight.is_contiguous() else weight.contiguous()
         out = torch.empty((x2.shape[0], N), dtype=x.dtype, device=x.device)
-        ok = [False]
-
-        def launch():
-            ok[0] = _cabi.linear_xadd(x2, a2, w, bias, out)
-
         with torch.cuda.device(x.device):
-            if LINEAR_PROFILE is None:
-                launch()
-            else:
-                st = torch.cuda.current_stream(x.device)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(st)
-                launch()
-                e1.record(st)
-                if ok[0]:
-                    LINEAR_PROFILE.append((e0, e1, 2.0 * x2.shape[0] * N * K, x2.shape[0], N, K))
-        if ok[0]:
+            ok = _timed_linear(lambda: _cabi.linear_xadd(x2, a2, w, bias, out), x.device, x2.shape[0], N, K)
+        if ok:
             return out.view(*x.shape[:-1], N)
     return linear(x + x_add, weight, bias)
 
@@ -1223,30 +1203,19 @@ def encoder_projections(x, pos, w_cat, b_cat, row_mask, n_value, head_dim):
         mk = mk.contiguous()
     value = torch.empty((B * S, n_value), dtype=torch.float16, device=x.device)
     packed = torch.empty((B * S, n_packed), dtype=x.dtype, device=x.device)
-    ok = [False]
     gen = getattr(pos, "_codetr_posgen", None) if ENC_POSGEN else None   # (set by the producer of `pos`: co_dino_head.py)
 
     def launch():
         if gen is not None and gen["S"] == S and gen["B"] == B:
-            ok[0] = _cabi.encoder_projections_posgen(x2, S, gen["cums"], gen["shapes"], gen["level_embed"], gen["temperature"],
-                                                     gen["scale"], gen["eps"], gen["offset"], gen["normalize"], w_cat, b_cat,
-                                                     mk, value, packed, S, int(head_dim))
-            if ok[0]:
-                return
-        ok[0] = _cabi.encoder_projections(x2, p2, w_cat, b_cat, mk, value, packed, S, int(head_dim))
+            if _cabi.encoder_projections_posgen(x2, S, gen["cums"], gen["shapes"], gen["level_embed"], gen["temperature"],
+                                                gen["scale"], gen["eps"], gen["offset"], gen["normalize"], w_cat, b_cat,
+                                                mk, value, packed, S, int(head_dim)):
+                return True
+        return _cabi.encoder_projections(x2, p2, w_cat, b_cat, mk, value, packed, S, int(head_dim))
 
     with torch.cuda.device(x.device):
-        if LINEAR_PROFILE is None:
-            launch()
-        else:
-            st = torch.cuda.current_stream(x.device)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            launch()
-            e1.record(st)
-            if ok[0]:
-                LINEAR_PROFILE.append((e0, e1, 2.0 * B * S * (n_value + n_packed) * K, B * S, n_value + n_packed, K))
-    if not ok[0]:
+        ok = _timed_linear(launch, x.device, B * S, n_value + n_packed, K)
+    if not ok:
         return None
     return value.view(B, n_value // head_dim, S, head_dim), packed.view(B, S, n_packed)
 
@@ -1435,15 +1404,7 @@ def linear_fp8(x8, x_scale, weight, bias=None, act=None, residual=None, out_scal
     out = torch.empty((x2.shape[0], N), dtype=FP8 if out_scale is not None else torch.float16, device=x8.device)
     with torch.cuda.device(x8.device):
         launch = lambda: _cabi.linear_fp8(x2, w8, ws, x_scale, bias, r2, act, out, out_scale or 0.0)  # noqa: E731
-        if LINEAR_PROFILE is None:
-            launch()
-        else:
-            st = torch.cuda.current_stream(x8.device)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            launch()
-            e1.record(st)
-            LINEAR_PROFILE.append((e0, e1, 2.0 * x2.shape[0] * N * K, x2.shape[0], N, K, "fp8"))
+        _timed_linear(launch, x8.device, x2.shape[0], N, K, "fp8")
     return out.view(*x8.shape[:-1], N)
 
 
@@ -1459,15 +1420,7 @@ def linear_fp8mx(x8, x_scales, weight, bias=None, act=None, residual=None, out_m
     sy = torch.empty(_cabi.mx_scale_bytes(x2.shape[0], N), dtype=torch.uint8, device=x8.device) if out_mx else None
     with torch.cuda.device(x8.device):
         launch = lambda: _cabi.linear_fp8mx(x2, x_scales, w8, ws, bias, r2, act, out, sy)  # noqa: E731
-        if LINEAR_PROFILE is None:
-            launch()
-        else:
-            st = torch.cuda.current_stream(x8.device)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(st)
-            launch()
-            e1.record(st)
-            LINEAR_PROFILE.append((e0, e1, 2.0 * x2.shape[0] * N * K, x2.shape[0], N, K, "fp8"))
+        _timed_linear(launch, x8.device, x2.shape[0], N, K, "fp8")
     out = out.view(*x8.shape[:-1], N)
     return (out, sy) if out_mx else out
 

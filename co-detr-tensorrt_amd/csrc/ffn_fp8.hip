@@ -25,6 +25,7 @@
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "large_lds.h"
 
 namespace {
 
@@ -515,9 +516,7 @@ int codetr_ffn_fp8(void* stream, const void* x_f16_dev, const void* w1q_dev, con
     return CODETR_E_BADARG;
   if (M > 0x7fffffffLL - 256) return CODETR_E_TOO_LARGE;
   const int ntiles = (int)((M + 127) / 128);
-  int cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  const int cus = device_cus();
   const unsigned blocks = (unsigned)(ntiles < cus ? ntiles : cus);   // persistent: one workgroup per CU
   hipLaunchKernelGGL(ffn_fp8_kernel, dim3(blocks), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
                      static_cast<const unsigned short*>(x_f16_dev), static_cast<const unsigned char*>(w1q_dev), w1_scale_dev,

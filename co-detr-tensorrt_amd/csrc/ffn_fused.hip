@@ -32,6 +32,7 @@
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "large_lds.h"
 
 // diagnostic builds only (tools/micro/ffn_ablate.hip -DCODETR_FFN_ABL=mask; WRONG results by construction, never shipped):
 // 1 = no LDS-DMA inside the chunk loop, 2 = no MFMAs, 4 = no W fragment reads inside the chunk loop, 8 = no waits / barriers in the
@@ -617,9 +618,7 @@ int ffn_entry(void* stream, const void* x_dev, const void* w1_dev, const void* b
   // Persistent grid: one workgroup per CU.  A left-over partial round that fills at most half of the CUs (1 599 tiles on
   // 256 CUs at one 1920x1280 image: 63 tiles in a 7th round) is served by a second launch with 64-row tiles instead:
   // twice the workgroups, half the MFMA time per tile -- half a round instead of a whole one.
-  int cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
+  const int cus = device_cus();
   const int64_t ntiles_all = (M + 127) / 128;
   const int64_t left = ntiles_all % cus;
   const bool split = left > 0 && 2 * left <= cus;

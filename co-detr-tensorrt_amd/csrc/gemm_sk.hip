@@ -37,56 +37,39 @@
 //     was 40 % of the first version's time.  For the same reason the bias sits in LDS behind the ring, and the fragments
 //     of the next tile's first half-stage are dropped over the epilogue and re-read behind it (one barrier).
 //
+// The ring producer, the fragment offsets, the bias in LDS, the epilogue and the host-side checks are those of
+// csrc/gemm_persist.h, shared with the ping-pong kernel of csrc/gemm_pp.hip.
+//
 // Requirements: K % 64 == 0, K >= 128, N % 8 == 0, N <= 16384, dense row-major operands, 16-byte aligned bases; M, N
 // otherwise arbitrary (edge tiles clamp their loads and mask their stores).  No row mask / head-major output
 // (gemm_f16.hip serves those).  The workspace (codetr_linear_sk_workspace_bytes) must be zero-filled once; every launch
 // leaves its counters at zero.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "codetr_hip.h"
-#include "device_prims.h"
-
-namespace {
 
 // diagnostic builds only (tools/micro: -DCODETR_SK_ABL=mask gives WRONG results by construction): 1 = no LDS-DMA inside the
 // main loop, 2 = no MFMAs, 4 = no fragment reads, 8 = no wait + barrier per phase, 16 = no output stores
 #ifndef CODETR_SK_ABL
 #define CODETR_SK_ABL 0
 #endif
+namespace {
 constexpr int kAbl = CODETR_SK_ABL;
-typedef unsigned u32x2v __attribute__((__vector_size__(2 * sizeof(unsigned))));
+}
 
-constexpr int kSlot = 32768;     // one half-stage: W[256][64 B] then X[256][64 B]
-constexpr int kOpBytes = 16384;
+#include "gemm_persist.h"
+
+namespace {
+
 constexpr int kMaxParts = 4;     // stream-K: most parts a tile is cut into
 constexpr int kWaves = 8;
-constexpr int kBiasBytes = 32768;     // bias in LDS: N <= 16384
 constexpr int kSlabFloats = 8192;    // one wave's 128 x 64 fp32 accumulators
 
-struct SkArgs {
-  const unsigned char* X;
-  const unsigned char* W;
-  const unsigned short* bias;
-  const unsigned short* R;
-  unsigned short* Y;
+struct SkArgs : PersistArgs {
   float* slabs;        // [G][2][8 waves][8192] fp32: slab 0 = a part that starts inside its tile, slab 1 = one that starts it
   unsigned* counters;  // [stream-K tiles][8 waves]
-  int M, N, K;
-  int tiles_n, T, nk;  // nk = K / 64
-  int G;               // workgroups (a multiple of 8)
   int D;               // tiles of the data-parallel rounds (a multiple of G); tiles D .. T-1 are the stream-K region
   int S;               // stream-K units (64-deep k-tiles): (T - D) * nk
   int Gs;              // workgroups that take part in the stream-K region (0 .. Gs-1)
   int np;              // 1: one workgroup per tile (G == T == D), XCD-aware order
 };
-
-// swizzle key of a 64-byte LDS row (4 chunks of 16 B): {0, 3, 2, 1}[(row >> 2) & 3] -- conflict-free under
-// ds_read_b128's lane groups (tests/test_lds_bank_model.py)
-__device__ __forceinline__ int key64(int row) {
-  const int q = (row >> 2) & 3;
-  return q ^ ((q & 1) << 1);
-}
 
 // ---- the work list of one workgroup: stream-K range first, then the data-parallel rounds ----
 struct Cursor {
@@ -172,7 +155,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave & 1, wn = wave >> 1;   // 2 x 4 waves: rows wm*128, columns wn*64
   const int wg = blockIdx.x;
-  const int K = a.K, K2 = K * 2;
   const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) unsigned char*)lds);
 
   Cursor cc;   // consumer side
@@ -180,68 +162,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   if (cc.mode == 2) return;   // nothing to do (fewer k-tiles in the problem than workgroups)
   Cursor pc = cc;             // producer side: NS half-stages ahead
 
-  // ---- producer: this wave's 2 + 2 pieces of a half-stage ----
-  // piece P = wave + 8 q covers LDS rows P*16 .. P*16+15 (64 B each): lane -> row P*16 + (lane >> 2), position lane & 3,
-  // which holds source chunk (lane & 3) ^ key64(row).  W rows are permuted: LDS row q*64 + i*16 + c holds weight row
-  // q*64 + 4 c + i of the tile (see the epilogue).
-  unsigned voffW[2], voffX[2];
-  const unsigned char* Wp = a.W;
-  const unsigned char* Xp = a.X;
-  int pk2 = 0;   // next half-stage (32-deep) of the producer's item
-  auto prod_set_tile = [&]() {
-    const int tm = pc.tile / a.tiles_n, tn = pc.tile - tm * a.tiles_n;
-    const int m0 = tm * 256, n0 = tn * 256;
-    const int nmax = a.N - 1 - n0, mmax = a.M - 1 - m0;   // edge tiles: the last row again (its outputs are never stored)
-    // (recomputed from the lane id at every tile switch: kept in registers across the main loop these constants were
-    // spilled, and a scratch reload is a vector-memory operation that queues behind every LDS-DMA piece in flight)
-    int ln = lane;
-    asm volatile("" : "+v"(ln));
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int r = (wave + 8 * q) * 16 + (ln >> 2);
-      const int rw = (r & 192) + 4 * (r & 15) + ((r >> 4) & 3);
-      const unsigned co = (unsigned)((((ln & 3) ^ key64(r)) * 16));
-      const int rn = rw < nmax ? rw : nmax, rm = r < mmax ? r : mmax;
-      voffW[q] = (unsigned)rn * (unsigned)K2 + co;
-      voffX[q] = (unsigned)rm * (unsigned)K2 + co;
-    }
-    Wp = a.W + ((size_t)n0 * K + (size_t)pc.kb * 64) * 2;
-    Xp = a.X + ((size_t)m0 * K + (size_t)pc.kb * 64) * 2;
-    pk2 = 2 * pc.kb;
-  };
-  prod_set_tile();
-  // one piece (g = 0, 1: W; 2, 3: X) of the producer's current half-stage into ring slot `slot`
-  auto produce_piece = [&](int g, int slot) {
-    const unsigned dst = lds0 + (unsigned)slot * kSlot + (unsigned)wave * 1024u;
-    if (g < 2) lds_dma16(Wp, voffW[g], dst + (unsigned)g * 8192u);
-    else lds_dma16(Xp, voffX[g - 2], dst + kOpBytes + (unsigned)(g - 2) * 8192u);
-  };
-  // past the end of the list the producer re-fetches its last half-stage (nobody reads it): the counted waits stay uniform
+  // ---- producer: NS half-stages ahead, through this workgroup's items and their k ranges ----
+  RingProducer prod;
+  prod.set_item(a, wave, lane, pc.tile, pc.kb);
+  auto produce_piece = [&](int g, int slot) { prod.piece(g, slot, lds0, wave); };
   auto produce_advance = [&]() {
-    if (pc.mode == 2) return;
-    ++pk2;
-    if (pk2 < 2 * pc.ke) {
-      Wp += 64;
-      Xp += 64;
-      return;
-    }
+    if (pc.mode == 2 || prod.step(pc.ke)) return;
     cursor_next(pc, a, wg);
-    if (pc.mode != 2) prod_set_tile();
+    if (pc.mode != 2) prod.set_item(a, wave, lane, pc.tile, pc.kb);
   };
 
-  // ---- consumer: fragment addresses ----
-  // fragment i of an operand = LDS rows base + i*16 + (lane & 15), chunk (lane >> 4) ^ key64(row)
-  const int fa = lane & 15, fc = lane >> 4;
-  const unsigned offA = (unsigned)((wn * 64 + fa) * 64 + ((fc ^ key64(fa)) * 16));
-  const unsigned offB = (unsigned)(kOpBytes + (wm * 128 + fa) * 64 + ((fc ^ key64(fa)) * 16));
+  const unsigned offA = frag_offset(0, wn * 64, lane), offB = frag_offset(kOpBytes, wm * 128, lane);
 
   f32x4 acc[4][8];   // [n-tile][m-tile]
   Frags<T> F0 = {}, F1 = {};
 
-  if (HAS_BIAS) {   // visible to everybody behind the prologue's barriers
-    for (int i = tid; i * 8 < a.N; i += 512)
-      *reinterpret_cast<u32x4*>(lds + NS * kSlot + i * 16) = *reinterpret_cast<const u32x4*>(a.bias + i * 8);
-  }
+  if (HAS_BIAS) stage_bias(lds + NS * kSlot, a.bias, a.N, tid);
   // ---- prologue: NS half-stages in flight, fragments of half-stage 0 in F0 ----
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
@@ -308,29 +244,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       SK_PHASE(F1, F0, false)
     }
 
-    const int tm = cc.tile / a.tiles_n, tn = cc.tile - tm * a.tiles_n;
-    const int m0 = tm * 256 + wm * 128, n0 = tn * 256 + wn * 64;   // this wave's corner
-    const int g = lane >> 4, nl = 4 * fa;
-    const int mleft = a.M - m0, nleft = a.N - n0;   // rows / columns of the piece that exist
-    const unsigned rowb = (unsigned)a.N * 2u;
-    const unsigned span = (mleft > 0 && nleft > 0) ? (unsigned)(mleft < 128 ? mleft : 128) * rowb : 0u;
-    // lanes whose columns do not exist get an offset outside every descriptor (loads return 0, stores are dropped)
-    const unsigned voff = nl < nleft ? (unsigned)(4 * g) * rowb + (unsigned)nl * 2u : 0x80000000u;
-    const int mrem = mleft - 4 * g;   // row j*16 + r of this lane exists iff j*16 + r < mrem (a constant against one register)
-    const __amdgpu_buffer_rsrc_t rres = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<unsigned char*>(reinterpret_cast<const unsigned char*>(a.R)) + ((size_t)m0 * a.N + n0) * 2, 0,
-        HAS_RES ? span : 0u, 0x00020000);
-    uint2 rr[8][4];
-    auto load_res = [&](int j0, int j1) {
-#pragma unroll
-      for (int j = j0; j < j1; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const u32x2v t2 = __builtin_amdgcn_raw_buffer_load_b64(rres, j * 16 + r < mrem ? voff : 0x80000000u,
-                                                                   (unsigned)(j * 16 + r) * rowb, 0);
-          rr[j][r] = uint2{t2[0], t2[1]};
-        }
-    };
     bool finish = true;
     if (SK && (cc.kb != 0 || cc.ke != a.nk)) {
       // ---- a part of a stream-K tile: publish the partial sums, the last arriver (per wave) continues ----
@@ -388,60 +301,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (lane == 0) __hip_atomic_store(a.counters + t * kWaves + wave, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    // wave-uniform: did this wave issue the epilogue's 32 output stores?  (a piece wholly outside the matrix -- e.g. waves 6, 7
-    // of every tile at N = 192 -- and a non-finishing stream-K part store nothing)
-    const bool stored = finish && a.M > m0 && a.N > n0;
-    if (stored) {
-      // ---- epilogue of this wave's 128 x 64 piece, straight from the accumulators ----
-      // acc[i][j][r]: output row m0 + j*16 + 4 (lane >> 4) + r, column n0 + 4 (lane & 15) + i: the four n-tiles give the
-      // lane 4 consecutive columns = 8 bytes, lanes 0-15 one 128-byte line, a store instruction 4 whole lines
-      float bias4[4] = {0.f, 0.f, 0.f, 0.f};
-      if (HAS_BIAS) {
-        const int nb = n0 + nl < a.N ? n0 + nl : 0;
-        const uint2 b2 = *reinterpret_cast<const uint2*>(lds + NS * kSlot + nb * 2);
-        bias4[0] = T::to_f32((unsigned short)(b2.x & 0xffffu));
-        bias4[1] = T::to_f32((unsigned short)(b2.x >> 16));
-        bias4[2] = T::to_f32((unsigned short)(b2.y & 0xffffu));
-        bias4[3] = T::to_f32((unsigned short)(b2.y >> 16));
-      }
-      // buffer descriptors on the piece's corner (wave-uniform) + ONE 32-bit lane offset; the row of a store goes into the
-      // scalar offset.  (Per-lane 64-bit addresses were hoisted and spilled by the compiler: 32 stores, each behind a
-      // scratch reload and `wait_vmcnt<0>()` -- every store waited for the one before and for the DMA pieces in flight.)
-      const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(
-          reinterpret_cast<unsigned char*>(a.Y) + ((size_t)m0 * a.N + n0) * 2, 0, span, 0x00020000);
-      if (HAS_RES) load_res(0, 4);   // residual rows: four row sets in flight, the other four requested two row sets later
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        if (HAS_RES && j == 2) load_res(4, 8);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float x[4];
-#pragma unroll
-          for (int i = 0; i < 4; ++i) x[i] = acc[i][j][r] + bias4[i];
-          if (ACT == 1) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[i] = x[i] < 0.f ? 0.f : x[i];   // NaN-propagating, like torch.relu
-          }
-          if (ACT == 2) {
-            const f32x2 g01 = gelu_erf2(f32x2{x[0], x[1]}), g23 = gelu_erf2(f32x2{x[2], x[3]});
-            x[0] = g01.x; x[1] = g01.y; x[2] = g23.x; x[3] = g23.y;
-          }
-          uint2 o = {T::pack2(x[0], x[1]), T::pack2(x[2], x[3])};
-          if (HAS_RES) {
-            // fp16(fp16(linear) + residual): the two roundings of `identity + linear(x)` in the reference's fp16 path
-            const uint2 q = rr[j][r];
-            const float y0 = T::to_f32((unsigned short)(o.x & 0xffffu)) + T::to_f32((unsigned short)(q.x & 0xffffu));
-            const float y1 = T::to_f32((unsigned short)(o.x >> 16)) + T::to_f32((unsigned short)(q.x >> 16));
-            const float y2 = T::to_f32((unsigned short)(o.y & 0xffffu)) + T::to_f32((unsigned short)(q.y & 0xffffu));
-            const float y3 = T::to_f32((unsigned short)(o.y >> 16)) + T::to_f32((unsigned short)(q.y >> 16));
-            o = uint2{T::pack2(y0, y1), T::pack2(y2, y3)};
-          }
-          if (!(kAbl & 16))
-            __builtin_amdgcn_raw_buffer_store_b64(u32x2v{o.x, o.y}, ry, j * 16 + r < mrem ? voff : 0x80000000u,
-                                                  (unsigned)(j * 16 + r) * rowb, 0);
-        }
-      }
-    }
+    // a non-finishing stream-K part stores nothing
+    const bool stored = finish && tile_epilogue<T, ACT, HAS_BIAS, HAS_RES>(acc, a, cc.tile, wm, wn, lane, lds + NS * kSlot);
     // The fragments of the next item's first half-stage (read in the last phase) are dropped over the epilogue, which needs
     // their registers (kept live, the compiler spilled around every store -- and a scratch access is a vector-memory
     // operation that waits for every LDS-DMA piece in flight).  They are read again here; the barrier keeps a wave that is
@@ -453,8 +314,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    // the relaxed wait (VMN + 32) is only sound behind 32 stores that were really issued: a wave without them has nothing
-    // but LDS-DMA pieces in its queue, and vmcnt(VMN + 32) would let it past pieces the next phases read
     post = stored && !(kAbl & 16) ? NS - 2 : 0;
     cursor_next(cc, a, wg);
   }
@@ -463,41 +322,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 }
 
 // ---- host side ----
-int device_cus() {
-  static int cus[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
-
-bool sk_supported(int64_t M, int64_t N, int64_t K) {
-  return M > 0 && N > 0 && K >= 128 && K % 64 == 0 && N % 8 == 0 && M <= 0x7fffffffLL && N <= 16384 &&
-         255 * K * 2 + 64 < 0x7fffffffLL;
-}
-
-// plan of one launch; returns false when the problem has no work
-bool sk_plan(int64_t M, int64_t N, int64_t K, int G, int flags, SkArgs& a) {
-  const int64_t tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256, T = tiles_m * tiles_n;
-  if (T > 0x3fffffff) return false;
-  a.M = (int)M; a.N = (int)N; a.K = (int)K;
-  a.tiles_n = (int)tiles_n; a.T = (int)T; a.nk = (int)(K / 64);
-  a.G = G;
+// the work list of a launch whose common fields are filled in
+void sk_plan(int flags, SkArgs& a) {
+  const int G = a.G, T = a.T;
   a.np = 0;
   if (flags & 0x20) {   // one workgroup per tile
-    a.G = (int)T; a.D = (int)T; a.S = 0; a.Gs = 0; a.np = 1;
-    return true;
+    a.G = T; a.D = T; a.S = 0; a.Gs = 0; a.np = 1;
+    return;
   }
   const bool no_sk = (flags & 0x40) == 0;   // stream-K split of the left-over tiles only on request (see the header)
-  int rounds = (int)(T / G);
-  int rem = (int)(T - (int64_t)rounds * G);
+  const int rounds = T / G;
+  const int rem = T - rounds * G;
   if (no_sk && rem > 0) {   // data-parallel only (A/B): the left-over tiles are whole items of the first `rem` workgroups
     a.D = rounds * G; a.S = rem * a.nk; a.Gs = rem;
-    return true;
+    return;
   }
   a.D = rounds * G;
   a.S = rem * a.nk;
@@ -506,65 +344,43 @@ bool sk_plan(int64_t M, int64_t N, int64_t K, int G, int flags, SkArgs& a) {
   if ((int64_t)rem * kMaxParts < gs) gs = rem * kMaxParts;
   if (gs > a.S) gs = a.S;
   a.Gs = gs;
-  return true;
 }
 
 int64_t sk_slab_bytes(int G) { return (int64_t)G * 2 * kWaves * kSlabFloats * 4; }
 int64_t sk_workspace_bytes(int G) { return sk_slab_bytes(G) + (int64_t)G * kWaves * 4; }
 
-template <class T, int ACT, int NS, bool SK>
-int launch_sk_act(hipStream_t st, const SkArgs& a, bool has_bias, bool has_res) {
-  const dim3 grid((unsigned)a.G), block(512);
-#define CODETR_SK(HB, HR) hipLaunchKernelGGL((linear_sk_kernel<T, ACT, HB, HR, NS, SK>), grid, block, 0, st, a)
-  if (has_bias && has_res) CODETR_SK(true, true);
-  else if (has_bias) CODETR_SK(true, false);
-  else if (has_res) CODETR_SK(false, true);
-  else CODETR_SK(false, false);
-#undef CODETR_SK
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
-}
-
 template <class T>
 int launch_sk(hipStream_t st, const void* X, const void* W, const void* bias, const void* R, void* Y, int64_t M, int64_t N,
               int64_t K, int act, void* ws, int64_t ws_bytes, int flags) {
-  if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0) return CODETR_E_BADARG;
-  if (act < 0 || act > 2 || !sk_supported(M, N, K)) return CODETR_E_UNSUPPORTED;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(Y) |
-       reinterpret_cast<uintptr_t>(R) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(ws)) & 15)
-    return CODETR_E_BADARG;
-  const int G = device_cus() / 8 * 8;
-  if (G <= 0) return CODETR_E_BADARG;
+  if (const int rc = persist_check(X, W, bias, R, Y, ws, M, N, K, act)) return rc;
+  const int G = persist_grid();
   // the workspace is only touched by the stream-K split
   if ((flags & 0x40) && (!ws || ws_bytes < sk_workspace_bytes(G))) return CODETR_E_BADARG;
   SkArgs a;
-  if (!sk_plan(M, N, K, G, flags, a)) return CODETR_E_TOO_LARGE;
-  a.X = static_cast<const unsigned char*>(X);
-  a.W = static_cast<const unsigned char*>(W);
-  a.bias = static_cast<const unsigned short*>(bias);
-  a.R = static_cast<const unsigned short*>(R);
-  a.Y = static_cast<unsigned short*>(Y);
+  if (const int rc = persist_fill(a, X, W, bias, R, Y, M, N, K, G)) return rc;
+  sk_plan(flags, a);
   a.slabs = static_cast<float*>(ws);
   a.counters = ws ? reinterpret_cast<unsigned*>(static_cast<unsigned char*>(ws) + sk_slab_bytes(G)) : nullptr;
-  const bool hb = bias != nullptr, hr = R != nullptr;
   // a plan whose left-over tiles are whole items (no split) runs the instantiation without the partial-tile path
   const bool split = a.Gs > 0 && a.S != a.Gs * a.nk;
-#define CODETR_SK_NS(ACT) return split ? launch_sk_act<T, ACT, 4, true>(st, a, hb, hr) : launch_sk_act<T, ACT, 4, false>(st, a, hb, hr)
+#define CODETR_SK_ACT(ACT)                                                                                              \
+  return split ? persist_launch(st, a, [](auto hb, auto hr) { return &linear_sk_kernel<T, ACT, hb(), hr(), 4, true>; })  \
+               : persist_launch(st, a, [](auto hb, auto hr) { return &linear_sk_kernel<T, ACT, hb(), hr(), 4, false>; })
   switch (act) {
-    case 0: CODETR_SK_NS(0);
-    case 1: CODETR_SK_NS(1);
-    default: CODETR_SK_NS(2);
+    case 0: CODETR_SK_ACT(0);
+    case 1: CODETR_SK_ACT(1);
+    default: CODETR_SK_ACT(2);
   }
-#undef CODETR_SK_NS
+#undef CODETR_SK_ACT
 }
 
 }  // namespace
 
 extern "C" {
 
-int64_t codetr_linear_sk_workspace_bytes(void) { return sk_workspace_bytes(device_cus() / 8 * 8); }
+int64_t codetr_linear_sk_workspace_bytes(void) { return sk_workspace_bytes(persist_grid()); }
 
-int codetr_linear_sk_supported(int64_t M, int64_t N, int64_t K) { return sk_supported(M, N, K) ? 1 : 0; }
+int codetr_linear_sk_supported(int64_t M, int64_t N, int64_t K) { return persist_supported(M, N, K) ? 1 : 0; }
 
 // Where the persistent kernel measured faster than the 256-tile kernel of gemm_f16.hip (tools/micro/gemm_sk_bench on the
 // 4- and 8-image Swin-L shapes, profiles/r04_gemm_sk.txt): K < 1536 with at least a tile per CU: -2 ... -25 %; at K = 1536 it
@@ -573,7 +389,7 @@ int codetr_linear_sk_supported(int64_t M, int64_t N, int64_t K) { return sk_supp
 int codetr_linear_sk_preferred(int64_t M, int64_t N, int64_t K, int act, int has_residual) {
   (void)act;
   (void)has_residual;
-  if (!sk_supported(M, N, K) || K >= 1536) return 0;
+  if (!persist_supported(M, N, K) || K >= 1536) return 0;
   const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
   const int64_t tn = (N + 255) / 256;
   // little of the 256-wide tile wasted (the rule of the 256-tile kernel)

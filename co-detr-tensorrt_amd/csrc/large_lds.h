@@ -1,4 +1,5 @@
-// Host side of a kernel that needs more than 64 KB of dynamic LDS: the opt-in every such launch needs, said once.
+// Host helpers the kernels' launchers share, each said once: the opt-in of a kernel that needs more than 64 KB of dynamic
+// LDS, and the CU count of the current device (the grid of every persistent kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,19 @@ hipError_t allow_large_lds(int bytes) {
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   if (e == hipSuccess) done[dev].store(true, std::memory_order_release);
   return e;
+}
+
+// compute units of the current device, asked once per device; 256 (an MI355X) where the runtime does not say
+int device_cus() {
+  static int cus[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  if (cus[dev] == 0) {
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+    cus[dev] = n;
+  }
+  return cus[dev];
 }
 
 }  // namespace

@@ -31,6 +31,7 @@
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "large_lds.h"
 
 namespace {
 
@@ -331,18 +332,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(WPE, W
     }
   }
   wait_vmcnt<0>();   // the redundant pieces fetched during the last chunk
-}
-
-int device_cus() {
-  static int cus[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
-  }
-  return cus[dev];
 }
 
 template <class ET>

@@ -69,6 +69,29 @@ def test_linear_pp_epilogues(bias, act, res):
     _run(70000, 384, 384, torch.float16, bias, act, res, seed=3)   # 274 x 2 tiles: two rounds and a left-over round
 
 
+EPILOGUES = [(False, None, False), (True, "relu", False), (True, "gelu", False), (True, None, True), (False, "relu", True),
+             (True, "gelu", True)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("M,N,K", [(300, 200, 128), (1000, 520, 192)])
+def test_both_persistent_kernels_give_the_same_bits(M, N, K, dtype):
+    """one epilogue (csrc/gemm_persist.h) behind two main loops that run the same 32-deep MFMA steps in the same order into
+    the same accumulator layout: the persistent kernel of csrc/gemm_sk.hip -- resident workgroups (flags 0) and one workgroup
+    per tile (0x20) -- and the ping-pong kernel agree bit for bit on one ragged tile and on several with K = 3 k-tiles"""
+    from codetr import _cabi
+
+    for case, (bias, act, res) in enumerate(EPILOGUES):
+        x, w, b, r = _inputs(M, N, K, dtype, bias, res, seed=40 + case)
+        y_pp = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
+        _cabi.linear_pp(x, w, b, r, act, y_pp)
+        assert not y_pp.isnan().any()
+        for flags in (0, 0x20):
+            y_sk = torch.full((M, N), float("nan"), dtype=dtype, device=DEV)
+            _cabi.linear_sk(x, w, b, r, act, y_sk, flags=flags)
+            assert torch.equal(y_sk, y_pp), (bias, act, res, flags, int((y_sk != y_pp).sum()))
+
+
 def test_waves_without_an_epilogue_keep_the_protocol():
     """N = 192 (one column tile): the strips 3 of every tile store nothing, and with M % 256 in 1 .. 128 neither does group 1
     of the last tile row -- such a wave must not take the relaxed wait of the LOAD segments behind an epilogue."""
