@@ -126,6 +126,15 @@ SIGNATURES = {
                                      ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_tta_merge_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
                                     ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_preprocess_tiles_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_preprocess_tiles_u8_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_preprocess_tiles_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
+    "codetr_slice_merge_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32,
+                                      ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_slice_merge_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32,
+                                       ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "codetr_slice_merge_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32,
+                                      ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_draw_font": (_i32, [_vp]),
     "codetr_draw_detections_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
                                           ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
@@ -201,7 +210,7 @@ CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 
          "sine_pos_tokens": 0, "ffn_fused": 0, "ffn_oproj_fused": 0, "linear_splitk": 0, "linear_sk": 0, "mask_pyramid": 0,
          "query_sine_embed": 0, "encoder_geometry": 0, "row_max": 0, "preprocess": 0, "batched_nms": 0,
          "preprocess_batch": 0, "postprocess_detections": 0, "postprocess_softnms": 0,
-         "preprocess_views": 0, "tta_merge": 0, "draw_detections": 0,
+         "preprocess_views": 0, "tta_merge": 0, "draw_detections": 0, "preprocess_tiles": 0, "slice_merge": 0,
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
@@ -631,6 +640,47 @@ def tta_merge(boxes, scores, labels, count, flip_mask, width, mode, iou_threshol
         V, N, Q, int(flip_mask), width.data_ptr(), int(mode), float(iou_threshold), float(min_score), int(max_keep),
         boxes_out.data_ptr(), scores_out.data_ptr(), labels_out.data_ptr(), index_out.data_ptr(), count_out.data_ptr())
     check(rc, "codetr_tta_merge")
+
+
+SLICE_MAX_VIEWS = 64           # CODETR_SLICE_MAX_VIEWS: views (tiles + the whole image) per image of codetr_slice_merge_*
+SLICE_METRICS = {"iou": 0, "ios": 1}   # CODETR_SLICE_IOU / CODETR_SLICE_IOS
+SLICE_MODES = {"nms": 0, "nmm": 1}     # CODETR_SLICE_NMS / CODETR_SLICE_NMM
+_PRE_TILES_BY_DTYPE = {torch.float16: "codetr_preprocess_tiles_u8_f16", torch.bfloat16: "codetr_preprocess_tiles_u8_bf16",
+                       torch.float32: "codetr_preprocess_tiles_u8_f32"}
+_SLICE_MERGE_BY_DTYPE = {torch.float16: "codetr_slice_merge_f16", torch.bfloat16: "codetr_slice_merge_bf16",
+                         torch.float32: "codetr_slice_merge_f32"}
+
+
+def preprocess_tiles_u8(src, rows, batch_hw, mean, std, pad_value, pad_fill, dst, mask):
+    """preprocess_batch_u8 with eleven values per row: (src_offset, H_img, W_img, y0, x0, H_crop, W_crop, H_resized,
+    W_resized, H_pad, W_pad) -- the row's source is that crop of the image, resized as an image of its own; rows may
+    share a src_offset"""
+    CALLS["preprocess_tiles"] += 1
+    N = len(rows)
+    H, W = batch_hw
+    table = (ctypes.c_int64 * (11 * N))(*[int(v) for row in rows for v in row])
+    f3 = ctypes.c_float * 3
+    rc = getattr(load(), _PRE_TILES_BY_DTYPE[dst.dtype])(
+        current_stream_ptr(src.device), src.data_ptr(), src.numel(), N, table, H, W, f3(*[float(v) for v in mean]),
+        f3(*[float(v) for v in std]), (ctypes.c_int * 3)(*[int(v) for v in pad_value]), float(pad_fill), dst.data_ptr(),
+        mask.data_ptr() if mask is not None else None)
+    check(rc, "codetr_preprocess_tiles_u8")
+
+
+def slice_merge(boxes, scores, labels, count, rows, origin, size, metric, mode, threshold, class_agnostic, max_keep,
+                boxes_out, scores_out, labels_out, index_out, count_out):
+    """boxes [R,Q,4] / scores [R,Q] in one dtype, labels [R,Q] int64, count [R] int32, rows [N,V] int32, origin [R,2] /
+    size [N,2] fp32; metric / mode: values of SLICE_METRICS / SLICE_MODES; outputs [N,K,..] with K = max_keep, or V*Q
+    when max_keep <= 0 (include/codetr_hip.h)"""
+    CALLS["slice_merge"] += 1
+    R, Q = scores.shape
+    N, V = rows.shape
+    rc = getattr(load(), _SLICE_MERGE_BY_DTYPE[scores.dtype])(
+        current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(),
+        rows.data_ptr(), origin.data_ptr(), size.data_ptr(), R, N, V, Q, int(metric), int(mode), float(threshold),
+        1 if class_agnostic else 0, int(max_keep), boxes_out.data_ptr(), scores_out.data_ptr(), labels_out.data_ptr(),
+        index_out.data_ptr(), count_out.data_ptr())
+    check(rc, "codetr_slice_merge")
 
 
 DRAW_MAX_Q = 4096              # CODETR_DRAW_MAX_Q: detection rows per image of codetr_draw_detections_*

@@ -12,6 +12,7 @@ formulation of the model lives in oracle/ and is test infrastructure).
 """
 
 import collections
+import math
 
 import torch
 import torch.nn.functional as F
@@ -531,6 +532,21 @@ def preprocess_views(src_u8, rows8, batch_hw, mean, std, pad_val=(0, 0, 0), pad_
                             pad_value, dtype, with_mask)
 
 
+def preprocess_tiles(src_u8, rows11, batch_hw, mean, std, pad_val=(0, 0, 0), pad_value=0.0, dtype=torch.float16,
+                     with_mask=True):
+    """preprocess_batch for sliced inference's tiles: rows11 has one row per TILE, (src_offset, H_img, W_img, y0, x0,
+    H_crop, W_crop, H_resized, W_resized, H_pad, W_pad).  A row is, bit for bit, what preprocess_batch writes for a
+    contiguous copy of the H_crop x W_crop window at (y0, x0) of its image: the tile is resized as an image of its own
+    and never reads a pixel outside the crop.  Rows may share a src_offset, so the tiles of an image read its one
+    uploaded copy.  -> (batch_inputs [N, 3, H, W], img_masks [N, H, W] or None), N = len(rows11); one launch per
+    PREPROCESS_BATCH_MAX rows."""
+    if any(len(r) != 11 for r in rows11):
+        raise ValueError("preprocess_tiles: eleven values per row (src_offset, H_img, W_img, y0, x0, H_crop, W_crop, "
+                         "H_resized, W_resized, H_pad, W_pad)")
+    return _preprocess_rows("preprocess_tiles", _cabi.preprocess_tiles_u8, src_u8, rows11, batch_hw, mean, std, pad_val,
+                            pad_value, dtype, with_mask)
+
+
 # postprocess_detections' result: boxes [N,Q,4] / scores [N,Q] (input dtype), labels [N,Q] int64, count [N] int32 --
 # image i's detections are rows [:count[i]] -- all four views of the one byte buffer `packed`
 Detections = collections.namedtuple("Detections", "boxes scores labels count packed")
@@ -717,6 +733,82 @@ def tta_merge(view_dets, flips, widths, nms=None, max_per_img=None):
         _cabi.tta_merge(boxes.view(V, N, Q, 4), scores.view(V, N, Q), labels.view(V, N, Q), count.view(V, N),
                         sum(1 << v for v, f in enumerate(flips) if f), widths.to(dev, torch.float32).contiguous(), mode,
                         iou, min_score, keep, out.boxes, out.scores, out.labels, out.index, out.count)
+    return out
+
+
+SLICE_MAX_VIEWS = _cabi.SLICE_MAX_VIEWS
+SLICE_MERGE = dict(type="nmm", metric="ios", threshold=0.5, class_agnostic=False)   # SAHI's defaults
+
+
+def slice_merge_settings(merge=None):
+    """the `merge` dict of sliced inference, validated and completed from SLICE_MERGE -> dict(type 'nmm' | 'nms',
+    metric 'ios' | 'iou', threshold, class_agnostic)"""
+    out = dict(SLICE_MERGE)
+    unknown = set(merge or {}) - set(out)
+    if unknown:
+        raise ValueError(f"slice merge: unknown key(s) {sorted(unknown)}; known: {sorted(out)}")
+    out.update(merge or {})
+    if out["type"] not in _cabi.SLICE_MODES:
+        raise ValueError(f"slice merge type must be 'nmm' or 'nms', got {out['type']!r}")
+    if out["metric"] not in _cabi.SLICE_METRICS:
+        raise ValueError(f"slice merge metric must be 'ios' or 'iou', got {out['metric']!r}")
+    out["threshold"] = float(out["threshold"])
+    if not math.isfinite(out["threshold"]):
+        raise ValueError("slice merge threshold must be finite")
+    out["class_agnostic"] = bool(out["class_agnostic"])
+    return out
+
+
+def slice_merge(dets, rows, origins, sizes, merge=None, max_per_img=None):
+    """The fusion of sliced inference's per-tile detections for N images in one launch (csrc/prepost.hip; semantics:
+    include/codetr_hip.h): every row's boxes shifted by its tile's origin and clipped to the image, then per label (or
+    over all labels) greedy NMS, or greedy non-maximum merging in which a pick absorbs what it retires into the box
+    around them, under IoU or IoS (intersection over the smaller area); the best max_per_img kept.
+      dets         the results of postprocess_detections / postprocess_detections_soft over R rows (one entry, or a
+                   list concatenated in order), boxes in each crop's own pixel coordinates
+      rows         [N, V] int32: the row of image n's v-th view; a value outside [0, R) is an absent view
+      origins      [R, 2] fp32 (x0, y0) of every row's crop;  sizes  [N, 2] fp32 (W, H) of the original images
+                   (tensors on the device, or nested lists)
+      merge        dict(type 'nmm' | 'nms', metric 'ios' | 'iou', threshold, class_agnostic); None: SLICE_MERGE
+      max_per_img  None: all
+    -> SoftDetections over [N, K] rows (K = max_per_img, or V * Q): `index` is c = v * Q + j of every row (of the pick, in
+    'nmm'); `detections_to_host` fetches all of it in one copy."""
+    m = slice_merge_settings(merge)
+    dets = list(dets) if isinstance(dets, (list, tuple)) and not hasattr(dets, "scores") else [dets]
+    if not dets:
+        raise ValueError("slice_merge: no detections")
+    scores0 = dets[0].scores
+    _gpu(scores0, "slice_merge")
+    dtype, dev, Q = scores0.dtype, scores0.device, scores0.shape[-1]
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError("slice_merge: detections in f16, bf16 or f32")
+    if any(d.scores.dim() != 2 or d.scores.shape[1] != Q or d.scores.dtype != dtype for d in dets):
+        raise ValueError("slice_merge: every entry [rows, Q] detections of one dtype")
+    R = sum(d.scores.shape[0] for d in dets)
+    rows = torch.as_tensor(rows, dtype=torch.int32)
+    origins = torch.as_tensor(origins, dtype=torch.float32)
+    sizes = torch.as_tensor(sizes, dtype=torch.float32)
+    if rows.dim() != 2 or rows.numel() == 0 or tuple(origins.shape) != (R, 2) or tuple(sizes.shape) != (rows.shape[0], 2):
+        raise ValueError("slice_merge: rows [N, V], origins [R, 2], sizes [N, 2] with N, V > 0")
+    N, V = rows.shape
+    if V > SLICE_MAX_VIEWS or V * Q > TTA_MAX_CANDIDATES:
+        raise ValueError(f"slice_merge: at most {SLICE_MAX_VIEWS} views and {TTA_MAX_CANDIDATES} candidates per image, "
+                         f"got {V} views of {Q}")
+    one = len(dets) == 1
+    boxes = (dets[0].boxes if one else torch.cat([d.boxes for d in dets])).contiguous()
+    scores = (dets[0].scores if one else torch.cat([d.scores for d in dets])).contiguous()
+    labels = (dets[0].labels if one else torch.cat([d.labels for d in dets])).contiguous()
+    count = (dets[0].count if one else torch.cat([d.count for d in dets])).contiguous()
+    keep = 0 if max_per_img is None else int(max_per_img)
+    K = keep if keep > 0 else V * Q
+    out = _new_detections(N, K, dtype, dev, True, Q == 0 or R == 0)
+    if Q == 0 or R == 0:
+        return out
+    with torch.cuda.device(dev):
+        _cabi.slice_merge(boxes, scores, labels, count, rows.to(dev).contiguous(), origins.to(dev).contiguous(),
+                          sizes.to(dev).contiguous(), _cabi.SLICE_METRICS[m["metric"]], _cabi.SLICE_MODES[m["type"]],
+                          m["threshold"], m["class_agnostic"], keep, out.boxes, out.scores, out.labels, out.index,
+                          out.count)
     return out
 
 

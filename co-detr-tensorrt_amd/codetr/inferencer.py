@@ -43,6 +43,21 @@ view's own scale factors as divisors; then one ``hip_ops.tta_merge`` launch and 
 ``views * num_queries <= 4096``.  Parity with mmdet / mmcv is unpinned (neither is installed here); as in the soft-NMS
 kernel classes are told apart by comparing labels, ties go to the lowest index and the IoU arithmetic is the project's.
 
+``slicing`` (beyond the reference; sliced inference as in SAHI): ``None``, the default, changes nothing.  A dict
+``dict(tile=(w, h), overlap=0.2 | (ox, oy), full_image=True, merge=dict(type='nmm' | 'nms', metric='ios' | 'iou',
+threshold=0.5, class_agnostic=False), max_per_img=300, tile_batch=8)`` (the defaults shown; only ``tile`` is required)
+cuts every image into overlapping tiles (``slice_grid``; y-major, then x; with ``full_image`` the whole image is the
+last view), runs every tile as an image of its own -- the keep-ratio resize into the config's ``scale``, divisor
+padding, no fixed-size ``Pad`` step, as a TTA view -- and fuses the views' detections on the device.  Per chunk of
+``batch_size`` images: one pinned staging copy and one upload (the images, every view's origin and rescale divisor, the
+image sizes and the view table), one ``preprocess_tiles`` launch per 32 rows (every row a crop of the uploaded image),
+``ceil(rows / tile_batch)`` forwards each followed by the configured post-processing launch (hard, soft or none) with
+the rows' own scale factors as divisors, then one ``hip_ops.slice_merge`` launch -- boxes shifted by the tile origin,
+clipped to the image, greedy NMS or greedy non-maximum merging under IoU or IoS, cut to ``max_per_img`` -- and one
+download.  At most 64 views per image and ``views * num_queries <= 4096``; not combined with ``tta``.  Parity with SAHI
+is unpinned (it is not installed here): ties, label comparison and the overlap arithmetic are the project's, stated in
+``include/codetr_hip.h``.
+
 ``visualizer`` (the reference builds mmdet's ``DetLocalVisualizer`` from ``cfg.visualizer``, :125-146, and draws in
 ``visualize``, :163-235): ``None``, the default, changes nothing.  A dict with any of ``line_width`` (1..15, default 3),
 ``alpha`` (0.8), ``text_color`` ((200, 200, 200)), ``font_scale`` (1..4), ``draw_labels``, ``palette`` and ``classes`` --
@@ -55,7 +70,7 @@ uint8 array per image in ``results_dict["visualization"]``, and ``out_dir`` with
 character becomes ``?``.  Palette: RGB triples from the same two places; for a name such as ``"coco"`` or nothing, a
 generated table (``generated_palette``: mmdet's named palettes are not part of this build).  A visualising call takes
 the chunked path; per chunk one ``hip_ops.draw_detections`` launch draws every image's final detections (plain, soft
-or the TTA merge's, cut to ``max_per_img``) on the buffer the chunk's one upload filled, in place and after the last
+the TTA merge's or the slice merge's, cut to ``max_per_img``) on the buffer the chunk's one upload filled, in place and after the last
 preprocessing launch on the stream, and one more device-to-host copy fetches that buffer.  The rendering is the
 project's own, modelled on ``DetLocalVisualizer``'s defaults and stated pixel by pixel in ``include/codetr_hip.h``.
 Parity with mmdet's visualiser is unpinned (neither mmdet nor matplotlib is installed here).
@@ -168,6 +183,33 @@ def tta_settings(cfg, tta):
                 views=views)
 
 
+SLICING_KEYS = ("tile", "overlap", "full_image", "merge", "max_per_img", "tile_batch")
+
+
+def slicing_settings(slicing):
+    """How `Inferencer(..., slicing=...)` reads its argument: None -> None; a dict with keys of SLICING_KEYS is
+    validated and completed -> dict(tile (w, h), overlap (ox, oy), full_image, merge (hip_ops.slice_merge_settings),
+    max_per_img or None, tile_batch)."""
+    if slicing is None:
+        return None
+    if not isinstance(slicing, dict) or set(slicing) - set(SLICING_KEYS) or "tile" not in slicing:
+        raise ValueError(f"slicing must be None or a dict with 'tile' and keys of {SLICING_KEYS}")
+    tile = tuple(slicing["tile"])
+    if len(tile) != 2 or any(int(t) != t or t < 1 for t in tile):
+        raise ValueError("slicing tile: (width, height), positive integers")
+    overlap = slicing.get("overlap", 0.2)
+    overlap = tuple(overlap) if isinstance(overlap, (tuple, list)) else (overlap, overlap)
+    if len(overlap) != 2 or any(not 0 <= float(o) < 1 for o in overlap):
+        raise ValueError("slicing overlap: a ratio, or (ox, oy), each in [0, 1)")
+    mpi = slicing.get("max_per_img", 300)
+    tile_batch = slicing.get("tile_batch", 8)
+    if int(tile_batch) != tile_batch or tile_batch < 1:
+        raise ValueError(f"slicing tile_batch must be a positive integer, got {tile_batch}")
+    return dict(tile=(int(tile[0]), int(tile[1])), overlap=(float(overlap[0]), float(overlap[1])),
+                full_image=bool(slicing.get("full_image", True)), merge=hip_ops.slice_merge_settings(slicing.get("merge")),
+                max_per_img=int(mpi) if mpi is not None and mpi > 0 else None, tile_batch=int(tile_batch))
+
+
 def generated_palette(n):
     """n RGB triples for classes without a palette of their own: the hue steps by the golden ratio (neighbouring
     labels get distant colours), fixed saturation and value; the same table on every call"""
@@ -246,7 +288,8 @@ def write_png(path, image):
 
 class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
-                 iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None):
+                 iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
+                 slicing=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -290,6 +333,9 @@ class Inferencer:
         if self.scale is None:
             raise ValueError("Resize is not found in the test pipeline")
         self.tta = tta_settings(self.cfg, tta)
+        self.slicing = slicing_settings(slicing)
+        if self.slicing is not None and self.tta is not None:
+            raise NotImplementedError("slicing together with tta is not built: one or the other")
         self.visualizer = visualizer_settings(self.cfg, visualizer, dataset_meta)
         self._vis_tables = {}   # device -> (names, colors) on it: uploaded on the first visualising call there
         self.num_predicted_imgs = 0
@@ -509,6 +555,102 @@ class Inferencer:
                         "bboxes": host.boxes[i, :c].float().tolist()})
         return out, src, [(o, H, W) for o, (H, W) in zip(offsets, shapes)], dets
 
+    # ---- sliced inference -------------------------------------------------------------------------------------
+    @staticmethod
+    def slice_grid(H, W, tile, overlap):
+        """the tiles of an H x W image: `tile` (w, h), `overlap` a ratio or (ox, oy), each in [0, 1).  Per axis of length
+        L with tile t and overlap o the step is t - int(o * t) (at least 1); tiles start at 0, step, 2 step, ... up to
+        and including the first that reaches L, which is moved back to end at L (an axis shorter than t: one tile of
+        length L).  -> [(y0, x0, h, w)], y-major, then x"""
+        ox, oy = tuple(overlap) if isinstance(overlap, (tuple, list)) else (overlap, overlap)
+
+        def axis(L, t, o):
+            if not 0 <= o < 1 or t < 1 or L < 1:
+                raise ValueError("slice_grid: positive sizes and an overlap in [0, 1)")
+            step, starts, p = max(1, t - int(o * t)), [], 0
+            while p + t < L:
+                starts.append(p)
+                p += step
+            return starts + [max(0, L - t)], min(t, L)
+
+        (xs, w), (ys, h) = axis(int(W), int(tile[0]), ox), axis(int(H), int(tile[1]), oy)
+        return [(y, x, h, w) for y in ys for x in xs]
+
+    @staticmethod
+    def slice_limits(views, Q=None):
+        """the merge kernel's limits: `views` of one image (tiles + the whole image), Q detections per view once known"""
+        if views > hip_ops.SLICE_MAX_VIEWS:
+            raise ValueError(f"slicing: {views} views of an image, at most {hip_ops.SLICE_MAX_VIEWS} (tiles + the whole "
+                             "image) are merged: use larger tiles")
+        if Q is not None and views * Q > hip_ops.TTA_MAX_CANDIDATES:
+            raise ValueError(f"slicing: {views} views of {Q} detections exceed the merge kernel's "
+                             f"{hip_ops.TTA_MAX_CANDIDATES} candidates per image")
+
+    def slice_rows(self, offsets, shapes):
+        """The rows of a chunk: every image of `shapes` (H, W) at byte `offsets` as its tiles (and, with full_image, the
+        whole image last), each resized keep-ratio into the config's scale as `view_rows` treats an image, padded to
+        pad_size_divisor and stacked; image-major.  -> (rows for hip_ops.preprocess_tiles, metas per row with `origin`
+        (x0, y0), the [N, V] view table (-1: no such view), (H, W) of the batch)"""
+        s, d = self.slicing, self.pad_size_divisor
+        rows, metas, table = [], [], []
+        for o, (H, W) in zip(offsets, shapes):
+            views = self.slice_grid(H, W, s["tile"], s["overlap"]) + ([(0, 0, H, W)] if s["full_image"] else [])
+            self.slice_limits(len(views))
+            table.append(list(range(len(rows), len(rows) + len(views))))
+            for y0, x0, h, w in views:
+                nh, nw = rescale_size(h, w, self.scale)
+                rows.append((o, H, W, y0, x0, h, w, nh, nw, nh, nw))
+                pad_shape = (-(-nh // d) * d, -(-nw // d) * d) if d > 1 else (nh, nw)
+                metas.append(dict(ori_shape=(h, w), img_shape=(nh, nw), img_unpadded_shape=(nh, nw), pad_shape=pad_shape,
+                                  scale_factor=(nw / w, nh / h), origin=(x0, y0)))
+        Hb, Wb = max(m["pad_shape"][0] for m in metas), max(m["pad_shape"][1] for m in metas)
+        for m in metas:
+            m["batch_input_shape"] = (Hb, Wb)
+        V = max(len(t) for t in table)
+        return rows, metas, [t + [-1] * (V - len(t)) for t in table], (Hb, Wb)
+
+    def slice_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32):
+        """one chunk through every tile and the merge -> one result dict per image (see the module docstring).  The
+        chunk's one upload carries the images, every row's origin and rescale divisor, the image sizes and the view table."""
+        return self._slice_chunk(images, device, dtype)[0]
+
+    def _slice_chunk(self, images, device, dtype):
+        """slice_batch + the uploaded images, every image's (offset, H, W) and the merged detections on the device"""
+        s = self.slicing
+        shapes = [im.shape[:2] for im in images]
+        N, offsets, offset = len(images), [], 0
+        for im in images:
+            offsets.append(offset)
+            offset += im.size
+        rows, metas, table, batch_hw = self.slice_rows(offsets, shapes)
+        R, V = len(rows), len(table[0])
+        origins = torch.tensor([m["origin"] for m in metas], dtype=torch.float32)            # [R, 2] (x0, y0)
+        sizes = torch.tensor([[float(W), float(H)] for H, W in shapes], dtype=torch.float32)  # [N, 2] (W, H)
+        view_rows = torch.tensor(table, dtype=torch.int32)                                    # [N, V]
+        div = self.divisors(metas, dtype)                                                     # [R, 4]
+        tail = torch.cat([t.view(-1).view(torch.uint8) for t in (origins, sizes, view_rows, div)])
+        src, _, tail = self.upload(images, device, tail)
+        origins = tail[:8 * R].view(torch.float32).view(R, 2)
+        sizes = tail[8 * R:8 * (R + N)].view(torch.float32).view(N, 2)
+        view_rows = tail[8 * (R + N):8 * (R + N) + 4 * N * V].view(torch.int32).view(N, V)
+        div = tail[8 * (R + N) + 4 * N * V:].view(dtype).view(R, 4)
+        x, m = hip_ops.preprocess_tiles(src, rows, batch_hw, self.mean, self.std, self.pad_val, self.pad_value, dtype)
+        row_dets = []
+        for i in range(0, R, s["tile_batch"]):
+            j = min(R, i + s["tile_batch"])
+            preds = self.model(x[i:j], m[i:j])
+            if i == 0:   # (Q is the model's: known after a forward)
+                self.slice_limits(V, preds[1].shape[1])
+            row_dets.append(self.postprocess_device(preds, metas[i:j], div[i:j]))
+        dets = hip_ops.slice_merge(row_dets, view_rows, origins, sizes, s["merge"], s["max_per_img"])
+        host = hip_ops.detections_to_host(dets)
+        out = []
+        for i in range(N):
+            c = int(host.count[i])
+            out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
+                        "bboxes": host.boxes[i, :c].float().tolist()})
+        return out, src, [(o, H, W) for o, (H, W) in zip(offsets, shapes)], dets
+
     # ---- visualisation and files --------------------------------------------------------------------------
     def draw_chunk(self, src, rows, dets, pred_score_thr):
         """the chunk's predictions drawn on its uploaded images: one hip_ops.draw_detections launch on the buffer the
@@ -519,7 +661,7 @@ class Inferencer:
         if key not in self._vis_tables:
             self._vis_tables[key] = (v["names"].to(src.device), v["colors"].to(src.device))
         names, colors = self._vis_tables[key]
-        if self.max_per_img is not None and not self.soft and self.tta is None:
+        if self.max_per_img is not None and not self.soft and self.tta is None and self.slicing is None:
             # the hard path cuts to max_per_img on the host (postprocess_batch): the kernel gets the clamped count
             dets = dets._replace(count=dets.count.clamp(max=self.max_per_img))
         hip_ops.draw_detections(src, rows, dets, names, colors, dict(v["style"], score_thr=float(pred_score_thr)))
@@ -551,7 +693,8 @@ class Inferencer:
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
         visualise = self.visualizer is not None and (return_vis or save_vis)
-        if batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None and not visualise:
+        if (batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None and self.slicing is None
+                and not visualise):
             for image in images:
                 with torch.no_grad():
                     x, m, meta = self.preprocess(image, device, dtype)
@@ -569,6 +712,8 @@ class Inferencer:
             with torch.no_grad():
                 if self.tta is not None:
                     preds, src, rows, dets = self._tta_chunk(chunk, device, dtype)
+                elif self.slicing is not None:
+                    preds, src, rows, dets = self._slice_chunk(chunk, device, dtype)
                 else:
                     x, m, metas, src, rows = self._preprocess_chunk(chunk, device, dtype)
                     preds, dets = self._postprocess_chunk(self.model(x, m), metas)

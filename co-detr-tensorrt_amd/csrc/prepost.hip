@@ -27,7 +27,12 @@
 // tta_merge_kernel    mmdet DetTTAModel._merge_single_sample for up to 4096 candidates per image: the views' detections
 //                     un-flipped and concatenated, per-class hard or soft NMS (label segments, one wave per chain, 64
 //                     positions per lane), sorted by score, cut to max_per_img.
-// The last two kernels are their own front ends over ONE set of device functions: pack_key (the tie rule), bitonic_desc
+// preprocess_tiles_kernel  preprocess_batch_kernel with a crop rectangle per row: sliced inference's tiles (SAHI's slicing:
+//                     every tile of an image is resized as an image of its own); rows read windows of one uploaded image.
+// slice_merge_kernel  the fusion of the tiles' detections, up to 4096 candidates per image: shifted by the tile's origin,
+//                     clipped to the image, then greedy per-label (or class-agnostic) NMS or non-maximum merging under
+//                     IoU or IoS (intersection over the smaller area), sorted by score, cut to max_per_img.
+// The merge and soft-NMS kernels are their own front ends over ONE set of device functions: pack_key (the tie rule), bitonic_desc
 // (either key layout), block_scan / block_sum / block_max_u64, segment_starts, run_segments (the greedy chain with both
 // threshold rules) and write_row / zero_row.  postprocess_kernel and the kernels above it are on the Inferencer's default
 // path, whose machine code is pinned: postprocess_kernel keeps its own sort, scan and epilogue.
@@ -82,16 +87,17 @@ __device__ __forceinline__ void coeff(int d, ResizeAxis ax, int& s, int& a1) {
   a1 = (int)rintf(f * 2048.0f);  // round half to even, as cvRound
 }
 
-// pixel (y, x) of the cv2-resized image (y < Hr, x < Wr) of a uint8 HWC RGB image [Hs, Ws, 3] -> v[3] in 0..255
-__device__ __forceinline__ void resized_pixel(const unsigned char* __restrict__ src, int Hs, int Ws, int Hr, int Wr,
-                                              int y, int x, int v[3]) {
+// pixel (y, x) of the cv2-resized image (y < Hr, x < Wr) of a uint8 HWC RGB image [Hs, Ws, 3] whose rows are `pitch`
+// pixels apart (a window of a wider image: its neighbours are clamped to the window) -> v[3] in 0..255
+__device__ __forceinline__ void resized_pixel(const unsigned char* __restrict__ src, int Hs, int Ws, int pitch, int Hr,
+                                              int Wr, int y, int x, int v[3]) {
   int sy, b1, sx, a1;
   coeff(y, ResizeAxis{0.f, Hs, Hr}, sy, b1);
   coeff(x, ResizeAxis{0.f, Ws, Wr}, sx, a1);
   const int sy1 = min(sy + 1, Hs - 1), sx1 = min(sx + 1, Ws - 1);
   const int a0 = 2048 - a1, b0 = 2048 - b1;
-  const unsigned char* r0 = src + ((size_t)sy * Ws) * 3;
-  const unsigned char* r1 = src + ((size_t)sy1 * Ws) * 3;
+  const unsigned char* r0 = src + ((size_t)sy * pitch) * 3;
+  const unsigned char* r1 = src + ((size_t)sy1 * pitch) * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int top = a0 * r0[sx * 3 + c] + a1 * r0[sx1 * 3 + c];
@@ -100,6 +106,11 @@ __device__ __forceinline__ void resized_pixel(const unsigned char* __restrict__ 
     int q = (int)(acc >> 22);
     v[c] = q < 0 ? 0 : (q > 255 ? 255 : q);
   }
+}
+// ... of a contiguous image
+__device__ __forceinline__ void resized_pixel(const unsigned char* __restrict__ src, int Hs, int Ws, int Hr, int Wr,
+                                              int y, int x, int v[3]) {
+  resized_pixel(src, Hs, Ws, Ws, Hr, Wr, y, x, v);
 }
 
 // DetDataPreprocessor's (x - mean) / std of a 0..255 value: one fp32 subtract, one IEEE divide
@@ -180,6 +191,41 @@ __global__ __launch_bounds__(256) void preprocess_views_kernel(const unsigned ch
   if (y < im.Hp && x < im.Wp) {
     int v[3] = {nm.pad[0], nm.pad[1], nm.pad[2]};
     if (inside) resized_pixel(src + im.src_offset, im.Hs, im.Ws, im.Hr, im.Wr, y, (flips >> n & 1u) ? im.Wr - 1 - x : x, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c] = normalise(v[c], nm.mean[c], nm.stdv[c]);
+  }
+  const size_t plane = (size_t)H * W, p = (size_t)y * W + x;
+  OutT* d = dst + (size_t)n * 3 * plane;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) d[c * plane + p] = from_f32<OutT>(o[c]);
+  if (mask) mask[(size_t)n * plane + p] = from_f32<OutT>(inside ? 0.f : 1.f);
+}
+
+// one row of a tiles launch: the (Hs, Ws) window whose first byte is src + src_offset, inside an image `pitch` pixels wide
+struct TileImage {
+  int64_t src_offset;
+  int pitch, Hs, Ws, Hr, Wr, Hp, Wp;
+};
+struct TileTable {
+  TileImage img[kPreBatchMax];
+};
+
+// preprocess_batch_kernel with a crop per row: the row's source is a window of an uploaded image, resized as the
+// contiguous copy of that window would be; rows may read windows of the same image.  (Its own body, as the views kernel's.)
+template <class OutT>
+__global__ __launch_bounds__(256) void preprocess_tiles_kernel(const unsigned char* __restrict__ src, TileTable tab,
+                                                               BatchNorm nm, int H, int W, OutT* __restrict__ dst,
+                                                               OutT* __restrict__ mask) {
+  const int x = blockIdx.x * 256 + threadIdx.x;
+  const int y = blockIdx.y;
+  const int n = blockIdx.z;
+  if (x >= W) return;
+  const TileImage im = tab.img[n];
+  const bool inside = y < im.Hr && x < im.Wr;
+  float o[3] = {nm.fill, nm.fill, nm.fill};
+  if (y < im.Hp && x < im.Wp) {
+    int v[3] = {nm.pad[0], nm.pad[1], nm.pad[2]};
+    if (inside) resized_pixel(src + im.src_offset, im.Hs, im.Ws, im.pitch, im.Hr, im.Wr, y, x, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[c] = normalise(v[c], nm.mean[c], nm.stdv[c]);
   }
@@ -488,6 +534,24 @@ __device__ __forceinline__ float soft_overlap(float4 bk, float ak, float4 bj, fl
   const float uni = ak + aj;
   return inter / (uni - inter);
 }
+// intersection over the smaller area (SAHI's IOS), the same rounded intersection; NaN when the smaller area is 0
+__device__ __forceinline__ float ios_overlap(float4 bk, float ak, float4 bj, float aj) {
+#pragma clang fp contract(off)
+  const float w = fmaxf(0.f, fminf(bk.z, bj.z) - fmaxf(bk.x, bj.x));
+  const float h = fmaxf(0.f, fminf(bk.w, bj.w) - fmaxf(bk.y, bj.y));
+  const float inter = w * h;
+  return inter / fminf(ak, aj);
+}
+// the box around two boxes: min and max only, so exact and free of the order the boxes come in
+__device__ __forceinline__ float4 box_union(float4 a, float4 b) {
+  return make_float4(fminf(a.x, b.x), fminf(a.y, b.y), fmaxf(a.z, b.z), fmaxf(a.w, b.w));
+}
+__device__ __forceinline__ float4 wave_box_union(float4 v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1)
+    v = box_union(v, make_float4(__shfl_xor(v.x, m, 64), __shfl_xor(v.y, m, 64), __shfl_xor(v.z, m, 64), __shfl_xor(v.w, m, 64)));
+  return v;
+}
 
 // after the (label, index) sort of V live candidates: s_seg[0 .. S) = the first position of every label segment,
 // s_seg[S] = V -> S.  kMaxP / 1024 positions per thread, a round each; with one round s_wave must be free at the call.
@@ -518,10 +582,15 @@ __device__ __forceinline__ int segment_starts(const unsigned long long* s_lab, i
 //   soft                        overlap >= iou_thr: score * (1 - overlap), or * 0 unless `linear`; score < min_score: gone
 // kStoredArea: the areas are read from s_area (next to s_score in LDS, so that one instruction reads both), else
 // computed again (s_area unused).  No workgroup barrier in here: a position's score is read and written by its own lane only.
-template <class Mask, bool kHardToo, bool kStoredArea>
-__device__ __forceinline__ void run_segments(const unsigned short* s_seg, int S, const float4* s_box, const float* s_area,
+// kSlice (the slice merge, hard only) adds two switches: `ios` measures the overlap as intersection over the smaller area,
+// and `nmm` (non-maximum merging) has the pick absorb what it retires -- every lane gathers the box around its retired
+// positions, a wave reduction joins them with k's and the owner stores the result in s_box[k], which no later round reads
+// (k is retired; every overlap of this round was measured against the bk read before).
+template <class Mask, bool kHardToo, bool kStoredArea, bool kSlice = false>
+__device__ __forceinline__ void run_segments(const unsigned short* s_seg, int S, float4* s_box, const float* s_area,
                                              float* s_score, const unsigned* s_idx, unsigned long long* s_out, bool hard,
-                                             bool linear, float iou_thr, float min_score, int lane, int wave) {
+                                             bool linear, float iou_thr, float min_score, int lane, int wave,
+                                             bool ios = false, bool nmm = false) {
   constexpr Mask kOne = 1;
   for (int seg = wave; seg < S; seg += kNmsWaves) {
     const int a = s_seg[seg], b = s_seg[seg + 1];
@@ -546,13 +615,18 @@ __device__ __forceinline__ void run_segments(const unsigned short* s_seg, int S,
       }
       const float4 bk = s_box[k];
       const float ak = kStoredArea ? s_area[k] : box_area(bk);
+      float4 grown = bk;  // (kSlice && nmm) k and what this lane's positions gave up to it
       for (int e = 0; e < ne; ++e) {
         if (alive >> e & kOne) {
           const int p = a + lane + 64 * e;
           const float4 bj = s_box[p];
-          const float ovr = soft_overlap(bk, ak, bj, kStoredArea ? s_area[p] : box_area(bj));
+          const float aj = kStoredArea ? s_area[p] : box_area(bj);
+          const float ovr = (kSlice && ios) ? ios_overlap(bk, ak, bj, aj) : soft_overlap(bk, ak, bj, aj);
           if (kHardToo && hard) {
-            if (ovr > iou_thr) alive &= ~(kOne << e);
+            if (ovr > iou_thr) {
+              alive &= ~(kOne << e);
+              if (kSlice && nmm) grown = box_union(grown, bj);
+            }
           } else {
             float sj = s_score[p];
             if (ovr >= iou_thr) {  // (a NaN overlap compares false: weight 1)
@@ -562,6 +636,10 @@ __device__ __forceinline__ void run_segments(const unsigned short* s_seg, int S,
             if (sj < min_score) alive &= ~(kOne << e);
           }
         }
+      }
+      if (kSlice && nmm) {
+        grown = wave_box_union(grown);
+        if (((k - a) & 63) == lane) s_box[k] = grown;
       }
     }
   }
@@ -768,6 +846,114 @@ __global__ __launch_bounds__(kNmsThreads) void tta_merge_kernel(
   if (tid == 0) count_out[n] = M;
 }
 
+constexpr int kSliceMaxV = CODETR_SLICE_MAX_VIEWS;
+
+// grid N, 1024 threads: the detections of image n's V views (tile rows of the stacked [R, Q] inputs, rows[n, v]; a row
+// outside [0, R) is an absent view; candidate c = v Q + j for j < count[row]) shifted by the row's origin and clipped to the
+// image -> the fused detections in output order, cut to max_keep, count_out[n] of them; rows [count_out, K) are zero.
+// tta_merge_kernel's LDS layout and steps with a front end of its own; P = the power of two >= V Q.
+// metric: CODETR_SLICE_IOU / _IOS, mode: CODETR_SLICE_NMS / _NMM.
+template <class T>
+__global__ __launch_bounds__(kNmsThreads) void slice_merge_kernel(
+    const T* __restrict__ boxes, const T* __restrict__ scores, const int64_t* __restrict__ labels,
+    const int* __restrict__ count, const int* __restrict__ rows, const float* __restrict__ origin,
+    const float* __restrict__ size, int R, int V, int Q, int P, int metric, int mode, float thr, int agnostic,
+    int max_keep, int K, T* __restrict__ boxes_out, T* __restrict__ scores_out, int64_t* __restrict__ labels_out,
+    int* __restrict__ index_out, int* __restrict__ count_out) {
+  extern __shared__ __align__(16) unsigned char slice_lds[];
+  float4* s_box = reinterpret_cast<float4*>(slice_lds);  // by position after sort 1; a pick's box becomes its union (NMM)
+  unsigned long long* s_lab = reinterpret_cast<unsigned long long*>(slice_lds + (size_t)16 * P);  // sort 1, major key
+  unsigned long long* s_out = s_lab;  // (after the segments are found) emitted: pack_key(score, c); else 0
+  float* s_score = reinterpret_cast<float*>(slice_lds + (size_t)24 * P);
+  unsigned* s_idx = reinterpret_cast<unsigned*>(slice_lds + (size_t)28 * P);  // sort 1, minor key: inv_index(c); 0 = none
+  unsigned short* s_pos = reinterpret_cast<unsigned short*>(slice_lds + (size_t)32 * P);  // c -> position
+  unsigned short* s_seg = reinterpret_cast<unsigned short*>(slice_lds + (size_t)34 * P);  // segment starts, then Vn
+  __shared__ int s_row[kSliceMaxV];  // the row of view v, its candidates (0 for an absent view)
+  __shared__ int s_cnt[kSliceMaxV];
+  __shared__ int s_wave[kNmsWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = blockIdx.x;
+  const int C = V * Q;
+  if (tid < V) {
+    const int r = rows[(size_t)n * V + tid];
+    const bool present = r >= 0 && r < R;
+    s_row[tid] = present ? r : 0;
+    s_cnt[tid] = present ? count[r] : 0;
+  }
+  __syncthreads();
+  // element (row of view v, j) of the stacked inputs
+  auto at = [&](int c) -> size_t {
+    const int v = c / Q;
+    return (size_t)s_row[v] * Q + (size_t)(c - v * Q);
+  };
+
+  // front end: the sort keys of the candidates, (label, c) -- or (0, c): one segment -- everything else 0
+  int nlive = 0;
+  for (int c = tid; c < P; c += kNmsThreads) {
+    bool live = false;
+    unsigned long long lab = 0;
+    if (c < C) {
+      const int v = c / Q;
+      if (c - v * Q < s_cnt[v]) {
+        live = true;
+        lab = agnostic ? 0ull : (unsigned long long)labels[at(c)];
+      }
+    }
+    s_lab[c] = lab;
+    s_idx[c] = live ? inv_index((unsigned)c) : 0u;
+    nlive += live ? 1 : 0;
+  }
+  const int Vn = block_sum(nlive, s_wave, lane, wave);  // (its barriers: the sort keys are complete)
+
+  // 1. by (label, c), descending: every label a contiguous segment in ascending c, empty slots last; boxes moved to the
+  //    image's coordinates and clipped to it (fmaxf first: a NaN coordinate becomes 0)
+  bitonic_desc<kTtaMaxC>(LabelIndexKeys{s_lab, s_idx}, P, tid);
+  const float Wimg = size[2 * n], Himg = size[2 * n + 1];
+  for (int p = tid; p < Vn; p += kNmsThreads) {
+    const unsigned c = inv_index(s_idx[p]);
+    const size_t e = at((int)c);
+    const int r = s_row[c / Q];
+    const float x0 = origin[2 * r], y0 = origin[2 * r + 1];
+    s_box[p] = make_float4(fminf(fmaxf(to_f32(boxes[4 * e]) + x0, 0.f), Wimg), fminf(fmaxf(to_f32(boxes[4 * e + 1]) + y0, 0.f), Himg),
+                           fminf(fmaxf(to_f32(boxes[4 * e + 2]) + x0, 0.f), Wimg), fminf(fmaxf(to_f32(boxes[4 * e + 3]) + y0, 0.f), Himg));
+    s_score[p] = to_f32(scores[e]);
+    s_pos[c] = (unsigned short)p;
+  }
+  // 2. - 4. as tta_merge_kernel; up to 1024 slots a lane holds at most 16 positions of a segment: the 32-bit mask
+  const int S = segment_starts<kTtaMaxC>(s_lab, Vn, s_seg, s_wave, tid);
+  for (int p = tid; p < P; p += kNmsThreads) s_out[p] = 0ull;
+  __syncthreads();
+  const bool ios = metric == CODETR_SLICE_IOS, nmm = mode == CODETR_SLICE_NMM;
+  if (P <= kNmsThreads)
+    run_segments<unsigned, true, false, true>(s_seg, S, s_box, nullptr, s_score, s_idx, s_out, true, false, thr, 0.f, lane, wave,
+                                              ios, nmm);
+  else
+    run_segments<unsigned long long, true, false, true>(s_seg, S, s_box, nullptr, s_score, s_idx, s_out, true, false, thr, 0.f,
+                                                        lane, wave, ios, nmm);
+  __syncthreads();
+  bitonic_desc<kTtaMaxC>(ScoreKeys{s_out}, P, tid);
+  int nout = 0;
+  for (int p = tid; p < P; p += kNmsThreads) nout += s_out[p] != 0ull ? 1 : 0;
+  const int E = block_sum(nout, s_wave, lane, wave);
+  const int M = (max_keep > 0 && max_keep < E) ? max_keep : E;
+
+  // 5. cut, round once to T
+  T* bo = boxes_out + (size_t)n * K * 4;
+  T* so = scores_out + (size_t)n * K;
+  int64_t* lo = labels_out + (size_t)n * K;
+  int* io = index_out + (size_t)n * K;
+  for (int r = tid; r < K; r += kNmsThreads) {
+    if (r < M) {
+      const unsigned c = inv_index((unsigned)s_out[r]);
+      const int p = s_pos[c];
+      write_row(bo, so, lo, io, r, s_box[p], from_f32<T>(s_score[p]), labels[at((int)c)], (int)c);
+    } else {
+      zero_row(bo, so, lo, io, r);
+    }
+  }
+  if (tid == 0) count_out[n] = M;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 // what a launch returns: 0, or the HIP error it left
@@ -791,6 +977,18 @@ int launch_pre(void* stream, const void* src, int64_t Hs, int64_t Ws, int64_t Hr
   return launched();
 }
 
+// the normalisation of a batched preprocess call, checked
+int pre_norm_args(const float* mean, const float* stdv, const int* pad, float pad_fill, BatchNorm& nm) {
+  for (int c = 0; c < 3; ++c) {
+    if (stdv[c] == 0.f || pad[c] < 0 || pad[c] > 255) return CODETR_E_BADARG;
+    nm.mean[c] = mean[c];
+    nm.stdv[c] = stdv[c];
+    nm.pad[c] = pad[c];
+  }
+  nm.fill = pad_fill;
+  return 0;
+}
+
 // the checks of a batched preprocess call and its kernel arguments; `cols` = 7 (codetr_preprocess_batch_u8_*) or 8
 // (codetr_preprocess_views_u8_*: the eighth value of a row is its flip, gathered into `flips`)
 int pre_batch_args(const void* src, int64_t src_bytes, int64_t N, const int64_t* images, int cols, int64_t H, int64_t W,
@@ -799,13 +997,7 @@ int pre_batch_args(const void* src, int64_t src_bytes, int64_t N, const int64_t*
   if (!src || !images || !mean || !stdv || !pad || !dst || src_bytes <= 0 || N <= 0 || H <= 0 || W <= 0)
     return CODETR_E_BADARG;
   if (N > kPreBatchMax || H > 65535 || W > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
-  for (int c = 0; c < 3; ++c) {
-    if (stdv[c] == 0.f || pad[c] < 0 || pad[c] > 255) return CODETR_E_BADARG;
-    nm.mean[c] = mean[c];
-    nm.stdv[c] = stdv[c];
-    nm.pad[c] = pad[c];
-  }
-  nm.fill = pad_fill;
+  if (const int rc = pre_norm_args(mean, stdv, pad, pad_fill, nm)) return rc;
   flips = 0;
   for (int64_t n = 0; n < N; ++n) {
     const int64_t* r = images + cols * n;  // src_offset, H_src, W_src, H_resized, W_resized, H_pad, W_pad[, flip]
@@ -840,6 +1032,34 @@ int launch_pre_rows(int cols, void* stream, const void* src, int64_t src_bytes, 
   else
     hipLaunchKernelGGL((preprocess_batch_kernel<OutT>), grid, dim3(256), 0, s, in, tab, nm, (int)H, (int)W,
                        static_cast<OutT*>(dst), static_cast<OutT*>(mask));
+  return launched();
+}
+
+// codetr_preprocess_tiles_u8_*: the batch entry's checks with a crop per row, then preprocess_tiles_kernel
+template <class OutT>
+int launch_pre_tiles(void* stream, const void* src, int64_t src_bytes, int64_t N, const int64_t* tiles, int64_t H, int64_t W,
+                     const float* mean, const float* stdv, const int* pad, float pad_fill, void* dst, void* mask) {
+  if (!src || !tiles || !mean || !stdv || !pad || !dst || src_bytes <= 0 || N <= 0 || H <= 0 || W <= 0)
+    return CODETR_E_BADARG;
+  if (N > kPreBatchMax || H > 65535 || W > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
+  TileTable tab = {};
+  BatchNorm nm;
+  if (const int rc = pre_norm_args(mean, stdv, pad, pad_fill, nm)) return rc;
+  for (int64_t n = 0; n < N; ++n) {
+    const int64_t* r = tiles + 11 * n;  // src_offset, H_img, W_img, y0, x0, H_crop, W_crop, H_resized, W_resized, H_pad, W_pad
+    const int64_t off = r[0], Hi = r[1], Wi = r[2], y0 = r[3], x0 = r[4], Hc = r[5], Wc = r[6], Hr = r[7], Wr = r[8],
+                  Hp = r[9], Wp = r[10];
+    if (off < 0 || Hi <= 0 || Wi <= 0 || y0 < 0 || x0 < 0 || Hc <= 0 || Wc <= 0 || Hr <= 0 || Wr <= 0 || Hp < Hr ||
+        Wp < Wr || Hp > H || Wp > W)
+      return CODETR_E_BADARG;
+    if (Hi > 32767 || Wi > 32767) return CODETR_E_TOO_LARGE;
+    if (y0 > Hi || Hc > Hi - y0 || x0 > Wi || Wc > Wi - x0) return CODETR_E_BADARG;  // the crop must lie in the image,
+    if (off > src_bytes || Hi * Wi * 3 > src_bytes - off) return CODETR_E_BADARG;    // the image in the buffer
+    tab.img[n] = TileImage{off + (y0 * Wi + x0) * 3, (int)Wi, (int)Hc, (int)Wc, (int)Hr, (int)Wr, (int)Hp, (int)Wp};
+  }
+  hipLaunchKernelGGL((preprocess_tiles_kernel<OutT>), dim3((unsigned)((W + 255) / 256), (unsigned)H, (unsigned)N), dim3(256),
+                     0, static_cast<hipStream_t>(stream), static_cast<const unsigned char*>(src), tab, nm, (int)H, (int)W,
+                     static_cast<OutT*>(dst), static_cast<OutT*>(mask));
   return launched();
 }
 
@@ -904,6 +1124,33 @@ int launch_tta_merge(void* stream, const void* boxes, const void* scores, const 
                      labels, count, (int)V, (int)N, (int)Q, P, flip_mask, width, mode, iou_threshold, min_score,
                      max_keep > 0 ? (int)max_keep : 0, max_keep > 0 ? (int)max_keep : C, static_cast<T*>(boxes_out),
                      static_cast<T*>(scores_out), labels_out, index_out, count_out);
+  return launched();
+}
+
+template <class T>
+int launch_slice_merge(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count,
+                       const int* rows, const float* origin, const float* size, int64_t R, int64_t N, int64_t V, int64_t Q,
+                       int metric, int mode, float threshold, int class_agnostic, int64_t max_keep, void* boxes_out,
+                       void* scores_out, int64_t* labels_out, int* index_out, int* count_out) {
+  if (!boxes || !scores || !labels || !count || !rows || !origin || !size || !boxes_out || !scores_out || !labels_out ||
+      !index_out || !count_out || R <= 0 || N <= 0 || V <= 0 || Q <= 0)
+    return CODETR_E_BADARG;
+  if (metric != CODETR_SLICE_IOU && metric != CODETR_SLICE_IOS) return CODETR_E_BADARG;
+  if (mode != CODETR_SLICE_NMS && mode != CODETR_SLICE_NMM) return CODETR_E_BADARG;
+  if (!__builtin_isfinite(threshold)) return CODETR_E_BADARG;
+  if (V > kSliceMaxV || Q > kTtaMaxC || V * Q > kTtaMaxC || N > 0x7fffffffLL / kTtaMaxC || R > 0x7fffffffLL / kTtaMaxC ||
+      max_keep > 0x7fffffffLL)
+    return CODETR_E_TOO_LARGE;
+  const int C = (int)(V * Q);
+  int P = 1;
+  while (P < C) P <<= 1;
+  if (const hipError_t e = allow_large_lds<slice_merge_kernel<T>>((int)tta_lds_bytes(kTtaMaxC)); e != hipSuccess)
+    return (int)e;
+  hipLaunchKernelGGL((slice_merge_kernel<T>), dim3((unsigned)N), dim3(kNmsThreads), tta_lds_bytes(P),
+                     static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                     labels, count, rows, origin, size, (int)R, (int)V, (int)Q, P, metric, mode, threshold,
+                     class_agnostic ? 1 : 0, max_keep > 0 ? (int)max_keep : 0, max_keep > 0 ? (int)max_keep : C,
+                     static_cast<T*>(boxes_out), static_cast<T*>(scores_out), labels_out, index_out, count_out);
   return launched();
 }
 
@@ -980,6 +1227,23 @@ CODETR_ENTRIES(codetr_tta_merge, launch_tta_merge,
                 void* scores_out_dev, int64_t* labels_out_dev, int* index_out_dev, int* count_out_dev),
                (stream, boxes_dev, scores_dev, labels_dev, count_dev, V, N, Q, flip_mask, width_dev, mode, iou_threshold,
                 min_score, max_keep, boxes_out_dev, scores_out_dev, labels_out_dev, index_out_dev, count_out_dev))
+
+CODETR_ENTRIES(codetr_preprocess_tiles_u8, launch_pre_tiles,
+               (void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* tiles_host, int64_t H,
+                int64_t W, const float* mean_host, const float* std_host, const int* pad_value_host, float pad_fill,
+                void* dst_dev, void* mask_dev),
+               (stream, src_dev, src_bytes, N, tiles_host, H, W, mean_host, std_host, pad_value_host, pad_fill, dst_dev,
+                mask_dev))
+
+CODETR_ENTRIES(codetr_slice_merge, launch_slice_merge,
+               (void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,
+                const int* count_dev, const int* rows_dev, const float* origin_dev, const float* size_dev, int64_t R,
+                int64_t N, int64_t V, int64_t Q, int metric, int mode, float threshold, int class_agnostic,
+                int64_t max_keep, void* boxes_out_dev, void* scores_out_dev, int64_t* labels_out_dev,
+                int* index_out_dev, int* count_out_dev),
+               (stream, boxes_dev, scores_dev, labels_dev, count_dev, rows_dev, origin_dev, size_dev, R, N, V, Q, metric,
+                mode, threshold, class_agnostic, max_keep, boxes_out_dev, scores_out_dev, labels_out_dev, index_out_dev,
+                count_out_dev))
 #undef CODETR_ENTRIES
 
 }  // extern "C"

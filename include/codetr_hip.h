@@ -870,6 +870,91 @@ int codetr_tta_merge_f32(void *stream, const void *boxes_dev, const void *scores
                          int *count_out_dev);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliced inference (SAHI's slicing, beyond the reference): one image as overlapping tiles, each run as an image of its
+ * own, optionally next to the whole image, and the fusion of their detections, both on the device.
+ *
+ * codetr_preprocess_tiles_u8_*: codetr_preprocess_batch_u8_* with a crop rectangle per row,
+ *     tiles_host         HOST [N][11] int64: src_offset, H_img, W_img, y0, x0, H_crop, W_crop, H_resized, W_resized,
+ *                        H_pad, W_pad
+ *   A row's source is the H_crop x W_crop window whose top-left pixel is (y0, x0) of the H_img x W_img image at
+ *   src_offset (its rows W_img * 3 bytes apart).  The output row is, bit for bit, what codetr_preprocess_batch_u8_* writes
+ *   for a contiguous copy of that window: the resize coefficients come from the crop's size, the sy + 1 / sx + 1
+ *   neighbour is clamped to the crop (a pixel outside it is never read), and the Pad region, the divisor padding, pad_fill
+ *   and the mask are the batch entry's.  Rows may name the same src_offset: the tiles of an image read its one uploaded
+ *   copy.  Limits and error codes are codetr_preprocess_batch_u8_*'s, with the side limit on H_img and W_img, plus
+ *   CODETR_E_BADARG for y0 < 0, x0 < 0, H_crop <= 0, W_crop <= 0, y0 + H_crop > H_img or x0 + W_crop > W_img.  All checks
+ *   run before any HIP call.
+ *
+ * codetr_slice_merge_*: the fusion of the views' detections (SAHI's postprocess: greedy NMS or greedy non-maximum
+ *   merging, under IoU or IoS) for N images of up to V views, one workgroup per image.  The operands are the stacked
+ *   outputs of the per-row codetr_postprocess_* launches, in each crop's own pixel coordinates:
+ *     boxes_dev [R, Q, 4], scores_dev [R, Q] in T; labels_dev [R, Q] int64; count_dev [R] int32: rows j < count[r] of
+ *     row r are candidates; rows_dev [N, V] int32: the row of image n's v-th view, a value outside [0, R) = the view is
+ *     absent; origin_dev [R, 2] fp32: (x0, y0) of row r's crop in its image; size_dev [N, 2] fp32: (W, H) of the
+ *     original image.  The candidate index is c = v * Q + j.  Everything below is fp32 with one rounding per
+ *     operation, never contracted.
+ *     1. boxes and scores convert to fp32 (exact); each coordinate gets + x0 or + y0 (one rounding) and is clipped to
+ *        the image with fminf(fmaxf(v, 0), W or H) -- a NaN coordinate becomes 0; area_c = (x2 - x1) * (y2 - y1) of the
+ *        clipped box, one rounded product;
+ *     2. "highest score" and ties are codetr_tta_merge_*'s: -0 equals +0, a NaN with the sign bit clear above +inf; ties
+ *        go to the lowest c;
+ *     3. the overlap of pick k and candidate c: w = max(0, min(x2) - max(x1)), h likewise, inter = w * h, then
+ *        metric CODETR_SLICE_IOU: inter / (area_k + area_c - inter), codetr_postprocess_softnms_*'s ovr;
+ *        metric CODETR_SLICE_IOS: inter / fminf(area_k, area_c), the intersection over the smaller area.
+ *        A NaN overlap (0 / 0: a box of no area) compares false;
+ *     4. segments: the candidates of one label; with class_agnostic != 0 all candidates of the image form one segment;
+ *     5. mode CODETR_SLICE_NMS, per segment, while a candidate of it is alive: pick the alive k with the highest score,
+ *        emit (box_k, score_k, label_k), retire k and every alive c of the segment with overlap > threshold;
+ *     6. mode CODETR_SLICE_NMM (greedy non-maximum merging): the same pick and the same retirement, but the retired c
+ *        are absorbed: the emitted box is (min x1, min y1, max x2, max y2) over k and the boxes it absorbed -- min and
+ *        max only, hence exact and free of any order --, the emitted score and label are k's.  Overlaps are always
+ *        measured against k's original box, never a grown one, and an absorbed box absorbs nothing itself;
+ *     7. the emitted detections are sorted by score descending, ties by ascending c; the first max_keep stay
+ *        (max_keep <= 0: all).
+ *   Outputs exactly as codetr_tta_merge_*, K = max_keep (V * Q when max_keep <= 0): boxes_out_dev [N, K, 4],
+ *   scores_out_dev [N, K] in T (rounded once), labels_out_dev [N, K] int64, index_out_dev [N, K] int32 = the c of every
+ *   row (in NMM mode the c of the pick), count_out_dev [N] int32; rows beyond count_out[n] are zero.  Parity with SAHI is
+ *   unpinned (it is not installed where this is tested); ties, label comparison and the overlap arithmetic are this
+ *   library's, and SAHI's non-greedy NMM variant is not provided.
+ *   LDS as codetr_tta_merge_* (36 bytes per slot of the power of two >= V * Q): no workspace operand.  CODETR_E_BADARG
+ *   for a null pointer, R, N, V or Q <= 0, a metric or mode other than those below, a threshold that is not finite;
+ *   CODETR_E_TOO_LARGE for V > CODETR_SLICE_MAX_VIEWS or V * Q > CODETR_TTA_MAX_CANDIDATES.  All checks run before any
+ *   HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define CODETR_SLICE_MAX_VIEWS 64
+#define CODETR_SLICE_IOU 0
+#define CODETR_SLICE_IOS 1
+#define CODETR_SLICE_NMS 0
+#define CODETR_SLICE_NMM 1
+int codetr_preprocess_tiles_u8_f16(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                   const int64_t *tiles_host, int64_t H, int64_t W, const float *mean_host,
+                                   const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                   void *mask_dev);
+int codetr_preprocess_tiles_u8_bf16(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                   const int64_t *tiles_host, int64_t H, int64_t W, const float *mean_host,
+                                   const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                   void *mask_dev);
+int codetr_preprocess_tiles_u8_f32(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                                   const int64_t *tiles_host, int64_t H, int64_t W, const float *mean_host,
+                                   const float *std_host, const int *pad_value_host, float pad_fill, void *dst_dev,
+                                   void *mask_dev);
+int codetr_slice_merge_f16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                           const int *count_dev, const int *rows_dev, const float *origin_dev, const float *size_dev,
+                           int64_t R, int64_t N, int64_t V, int64_t Q, int metric, int mode, float threshold,
+                           int class_agnostic, int64_t max_keep, void *boxes_out_dev, void *scores_out_dev,
+                           int64_t *labels_out_dev, int *index_out_dev, int *count_out_dev);
+int codetr_slice_merge_bf16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                           const int *count_dev, const int *rows_dev, const float *origin_dev, const float *size_dev,
+                           int64_t R, int64_t N, int64_t V, int64_t Q, int metric, int mode, float threshold,
+                           int class_agnostic, int64_t max_keep, void *boxes_out_dev, void *scores_out_dev,
+                           int64_t *labels_out_dev, int *index_out_dev, int *count_out_dev);
+int codetr_slice_merge_f32(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                           const int *count_dev, const int *rows_dev, const float *origin_dev, const float *size_dev,
+                           int64_t R, int64_t N, int64_t V, int64_t Q, int metric, int mode, float threshold,
+                           int class_agnostic, int64_t max_keep, void *boxes_out_dev, void *scores_out_dev,
+                           int64_t *labels_out_dev, int *index_out_dev, int *count_out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Visualisation: the predictions drawn on the original images, in place, one launch for a chunk.
  *
  * Replaces DetLocalVisualizer.add_datasample / _draw_instances as the reference's Inferencer.visualize drives them

@@ -29,7 +29,14 @@ image plain and mirrored).
 on 8 images of 1920x1280 with 300 and with 20 drawn detections each; and the device-to-host copy of that buffer, the
 one extra transfer a visualising chunk makes.
 
-    python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis]   -> one JSON line
+`--slice` adds a `slice` sub-record (sliced inference, fp16): images/s of `Inferencer(slicing=dict(tile=(1280, 1280),
+overlap=0.2, full_image=True))` at batch_size 2 over --slice-images synthetic 3840x2160 images (8 tiles + the image: 9
+views each), beside the host composition it replaces on the same images -- per image the tiles cropped on the host, one
+plain `Inferencer` call over the image's 9 crops at batch_size = tile_batch (no fixed Pad step, as the sliced path), the
+detections shifted and fused in numpy (tests/slice_ref.py) --; and the two slicing kernels alone, HIP events as above:
+preprocess_tiles on the 9 rows of one such image, slice_merge at N = 2, V = 9, Q = 300 for both merge types.
+
+    python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis] [--slice]   -> one JSON line
 """
 import argparse
 import csv
@@ -211,6 +218,93 @@ def tta_record(inf, n_images, repeats, bs=4):
     return rec
 
 
+SLICE = dict(tile=(1280, 1280), overlap=0.2, full_image=True, tile_batch=8, max_per_img=300)
+SLICE_WH = (3840, 2160)
+
+
+def slice_kernel_times(image):
+    """us per launch of preprocess_tiles_kernel (the 9 rows of one 3840x2160 image into the (1152, 768) scale, fp16) and of
+    slice_merge_kernel (N = 2, V = 9, Q = 300, fp16, 80 classes; nmm / ios and nms / iou at 0.5)"""
+    from codetr import hip_ops
+    from codetr.inferencer import Inferencer, rescale_size
+
+    H, W = image.shape[:2]
+    views = Inferencer.slice_grid(H, W, SLICE["tile"], SLICE["overlap"]) + [(0, 0, H, W)]
+    rows = [(0, H, W, y, x, h, w) + rescale_size(h, w, (1152, 768)) * 2 for y, x, h, w in views]
+    src = torch.from_numpy(image.reshape(-1)).to(DEV)
+    hw = (max(r[7] for r in rows), max(r[8] for r in rows))
+    mean, std = (123.675, 116.28, 103.53), (58.395, 57.12, 57.375)
+    out = {"preprocess_tiles_kernel_9_rows_us": _event_us(
+        lambda: hip_ops.preprocess_tiles(src, rows, hw, mean, std, dtype=torch.float16), launches=50, warmup=5),
+        "preprocess_tiles_batch_hw": list(hw), "slice_merge_kernel": {}}
+    g = torch.Generator().manual_seed(0)
+    N, V, Q = 2, len(views), 300
+    c = torch.rand(N, Q, 2, generator=g) * torch.tensor([W, H])
+    wh = torch.rand(N, Q, 2, generator=g) * 300 + 8
+    base = torch.cat((c - wh / 2, c + wh / 2), -1)
+    origins = torch.tensor([[float(x), float(y)] for y, x, _, _ in views] * N)
+    boxes = (base[:, None] + (torch.rand(N, V, Q, 4, generator=g) - 0.5) * 6).view(N * V, Q, 4) - origins.repeat(1, 2)[:, None]
+    dets = hip_ops.Detections(boxes.half().to(DEV), torch.rand(N * V, Q, generator=g).half().to(DEV),
+                              torch.randint(0, 80, (N, 1, Q), generator=g).expand(N, V, Q).reshape(N * V, Q).to(DEV),
+                              torch.full((N * V,), Q, dtype=torch.int32, device=DEV), None)
+    table = torch.arange(N * V, dtype=torch.int32, device=DEV).view(N, V)
+    sizes = torch.tensor([[float(W), float(H)]] * N, device=DEV)
+    origins = origins.to(DEV)
+    for name, merge in (("nmm_ios", dict(type="nmm", metric="ios", threshold=0.5)),
+                        ("nms_iou", dict(type="nms", metric="iou", threshold=0.5))):
+        call = lambda: hip_ops.slice_merge(dets, table, origins, sizes, merge, 300)  # noqa: E731
+        out["slice_merge_kernel"][name] = {"us_per_launch": _event_us(call), "detections": int(call().count.sum())}
+    return out
+
+
+def slice_record(inf, n_images, repeats, bs=2):
+    import bench
+    from codetr.inferencer import Inferencer
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import slice_ref
+
+    rng = np.random.default_rng(5)
+    images = [rng.integers(0, 256, (SLICE_WH[1], SLICE_WH[0], 3), dtype=np.uint8) for _ in range(n_images)]
+    rec = {"slicing": SLICE, "image_wh": SLICE_WH, "batch_size": bs, "images": n_images, "repeats": repeats, "dtype": "fp16"}
+    sliced = Inferencer(inf.model, bench.CFG, dataset_meta=None, slicing=SLICE)
+    times = _passes(sliced, images, bs, repeats)
+    rec["views_per_image"] = len(sliced.slice_rows([0], [images[0].shape[:2]])[0])
+    rec["sliced"] = {"images_per_s": round(n_images / min(times), 3), "pass_s": [round(v, 4) for v in times]}
+    plain = Inferencer(inf.model, bench.CFG, dataset_meta=None)
+    plain.pad_size = None
+    merge = sliced.slicing["merge"]
+
+    def composed(image):
+        H, W = image.shape[:2]
+        views = slice_ref.grid(H, W, SLICE["tile"], (SLICE["overlap"],) * 2) + [(0, 0, H, W)]
+        crops = [np.ascontiguousarray(image[y:y + h, x:x + w]) for y, x, h, w in views]
+        preds = plain(crops, device=DEV, dtype=torch.float16, batch_size=SLICE["tile_batch"])["predictions"]
+        Q = max(1, max(len(p["labels"]) for p in preds))
+        boxes, scores = np.zeros((len(views), Q, 4), np.float32), np.zeros((len(views), Q), np.float32)
+        labels, count = np.zeros((len(views), Q), np.int64), np.zeros(len(views), np.int64)
+        for r, p in enumerate(preds):
+            n = count[r] = len(p["labels"])
+            boxes[r, :n], scores[r, :n], labels[r, :n] = np.asarray(p["bboxes"]).reshape(n, 4), p["scores"], p["labels"]
+        return slice_ref.merge(boxes, scores, labels, count, range(len(views)), [(x, y) for y, x, _, _ in views], (W, H),
+                               metric=merge["metric"], mode=merge["type"], threshold=merge["threshold"],
+                               class_agnostic=merge["class_agnostic"], max_keep=SLICE["max_per_img"])
+
+    with torch.no_grad():
+        composed(images[0])
+        times = []
+        for _ in range(repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for image in images:
+                composed(image)
+            times.append(time.perf_counter() - t0)
+    rec["host_composition"] = {"images_per_s": round(n_images / min(times), 3), "pass_s": [round(v, 4) for v in times]}
+    rec["speedup"] = round(rec["sliced"]["images_per_s"] / rec["host_composition"]["images_per_s"], 3)
+    rec["kernels_us"] = slice_kernel_times(images[0])
+    return rec
+
+
 def draw_kernel_times(N=8, H=1280, W=1920, Q=300):
     """us per launch of draw_detections_kernel on N images of W x H with Q and with 20 drawn detections each (fp16,
     default style, 80 classes), and the device-to-host copy of the buffer"""
@@ -339,6 +433,9 @@ def main():
     ap.add_argument("--tta-only", action="store_true", help="only the tta sub-record (implies --tta)")
     ap.add_argument("--vis", action="store_true", help="add the visualisation sub-record")
     ap.add_argument("--vis-only", action="store_true", help="only the vis sub-record (implies --vis)")
+    ap.add_argument("--slice", action="store_true", help="add the sliced-inference sub-record")
+    ap.add_argument("--slice-images", type=int, default=4)
+    ap.add_argument("--slice-only", action="store_true", help="only the slice sub-record (implies --slice)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -359,6 +456,11 @@ def main():
         print(json.dumps({"metric": "Inferencer visualisation (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass",
                           "vis": vis_record(infs["fp16"], images, a.repeats)}))
+        return
+    if a.slice_only:
+        print(json.dumps({"metric": "Inferencer sliced inference (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass",
+                          "slice": slice_record(infs["fp16"], a.slice_images, a.repeats)}))
         return
     infs["fp16_soft_nms"] = soft_inferencer(infs["fp16"])
     for name, inf in infs.items():
@@ -388,6 +490,8 @@ def main():
         line["tta"] = tta_record(infs["fp16"], a.tta_images, a.repeats)
     if a.vis:
         line["vis"] = vis_record(infs["fp16"], images, a.repeats)
+    if a.slice:
+        line["slice"] = slice_record(infs["fp16"], a.slice_images, a.repeats)
     if not a.no_profile:
         line["kernel_times"] = profile()
     print(json.dumps(line))

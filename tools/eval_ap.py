@@ -210,6 +210,21 @@ def parse_tta(text):
     return dict(scales=scales, flip=len(parts) == 2, nms=dict(type="nms", iou_threshold=0.6), max_per_img=100)
 
 
+def parse_slice(text):
+    """--slice WxH,overlap[,full]: e.g. '640x640,0.2,full' -> the Inferencer's slicing dict; the tiles (with `full`, and
+    the whole image) are fused with the Inferencer's defaults -- greedy non-maximum merging at IoS 0.5 -- and cut to 100
+    detections per image"""
+    parts = text.split(",")
+    try:
+        w, h = (int(v) for v in parts[0].lower().split("x"))
+        overlap = float(parts[1])
+    except (ValueError, IndexError):
+        raise SystemExit(f"--slice {text!r}: expected WxH,overlap[,full], e.g. 640x640,0.2,full")
+    if len(parts) > 3 or (len(parts) == 3 and parts[2] != "full"):
+        raise SystemExit(f"--slice {text!r}: expected WxH,overlap[,full], e.g. 640x640,0.2,full")
+    return dict(tile=(w, h), overlap=overlap, full_image=len(parts) == 3, max_per_img=100)
+
+
 def run_coco(args):
     for p in (os.path.join(ROOT, "co-detr-tensorrt_amd"),):
         if p not in sys.path:
@@ -233,7 +248,7 @@ def run_coco(args):
     # --nms config: the post-processing the config specifies (soft-NMS + max_per_img, what the published AP was
     # produced with); hard: the reference Inferencer's hard NMS at the config's IoU threshold, no cut
     inf = Inferencer(model, args.config, meta, score_threshold=0.0, nms_type="config" if args.nms == "config" else None,
-                     tta=parse_tta(args.tta) if args.tta else None)
+                     tta=parse_tta(args.tta) if args.tta else None, slicing=parse_slice(args.slice) if args.slice else None)
     dets, gts = [], []
     images = ann["images"][:args.limit] if args.limit else ann["images"]
     for im in images:
@@ -268,6 +283,9 @@ def main():
     c.add_argument("--tta", default=None, metavar="SCALES[,flip]",
                    help="test-time augmentation: scales as LONGxSHORT joined by '+', e.g. 1333x800+2000x1200,flip; the "
                         "views are merged with hard NMS at IoU 0.6, 100 detections per image")
+    c.add_argument("--slice", default=None, metavar="WxH,overlap[,full]",
+                   help="sliced inference: tile size and overlap ratio, e.g. 640x640,0.2,full (full: the whole image is a "
+                        "view too); fused by greedy non-maximum merging at IoS 0.5, 100 detections per image")
     a = ap.parse_args()
     (run_proxy if a.mode == "proxy" else run_coco)(a)
 
