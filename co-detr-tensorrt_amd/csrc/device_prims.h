@@ -39,6 +39,22 @@ __device__ __forceinline__ unsigned short bf16_from_f32(float v) {
   return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
+// ---- ReLU on eight packed 16-bit floats, x < 0 ? 0 : x with a NaN of either sign kept (the contract of every epilogue;
+// v_pk_max_f16(x, 0) returns 0 for a NaN, v_pk_max_i16(x, 0) for a NaN with the sign bit set).  Sign-magnitude floats
+// read as int16: the negative numbers, -0 and -inf are exactly the values <= kNegInf (the bits of -inf), the NaNs with the
+// sign bit set lie above it.  kNegInf - x (saturating) is negative exactly for the values to keep: arithmetic shift, and --
+// three packed operations per two values; -0 -> +0.
+template <class F, short kNegInf>
+__device__ __forceinline__ F relu_bits16(F x) {
+  s16x8 i;
+  __builtin_memcpy(&i, &x, 16);
+  u32x4 keep = __builtin_bit_cast(u32x4, __builtin_elementwise_sub_sat((s16x8)kNegInf, i) >> 15);
+  asm("" : "+v"(keep));   // (keeps the mask a mask: the compiler otherwise rewrites this as a compare + select per value)
+  i = __builtin_bit_cast(s16x8, __builtin_bit_cast(u32x4, i) & keep);
+  __builtin_memcpy(&x, &i, 16);
+  return x;
+}
+
 // ---- element types: fp16 / bf16 storage, fp32 accumulation on the matrix cores either way
 struct HalfT {
   using elem = _Float16;
@@ -69,11 +85,7 @@ struct HalfT {
     __builtin_memcpy(&o, &h, 8);
     return o;
   }
-  // v_pk_max_f16: one op per two values
-  __device__ static frag relu(frag x) {
-    const frag z = {0, 0, 0, 0, 0, 0, 0, 0};
-    return __builtin_elementwise_max(x, z);
-  }
+  __device__ static frag relu(frag x) { return relu_bits16<frag, (short)0xfc00>(x); }
 };
 struct BFloatT {
   using elem = __bf16;
@@ -95,22 +107,18 @@ struct BFloatT {
     const bf16x4 h = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
     return __builtin_bit_cast(s16x4, h);
   }
-  // sign-magnitude 16-bit floats order like int16 on the non-negative side: v_pk_max_i16(x, 0) is ReLU (-0 -> +0)
-  __device__ static frag relu(frag x) {
-    s16x8 i;
-    __builtin_memcpy(&i, &x, 16);
-    const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
-    i = __builtin_elementwise_max(i, z);
-    __builtin_memcpy(&x, &i, 16);
-    return x;
-  }
+  __device__ static frag relu(frag x) { return relu_bits16<frag, (short)0xff80>(x); }
 };
 
 // ---- nn.GELU (erf form): 0.5 x (1 + erf(x / sqrt 2)).  libm's erff costs ~50 VALU ops per element and made the GELU
-// epilogues VALU-bound; erf is evaluated with Abramowitz-Stegun 7.1.26 instead (|erf error| <= 1.5e-7, i.e. < 2^-22
-// relative on the output: three orders of magnitude below the fp16 / bf16 rounding of the result).
+// epilogues VALU-bound; erf is evaluated with Abramowitz-Stegun 7.1.26 instead (|erf error| <= 1.5e-7).
 //   0.5 x (1 + erf(x / sqrt 2)) = 0.5 x + |x| (0.5 - (0.5 p(t) t) exp(-x^2 / 2)),  t = 1 / (1 + 0.3275911 |x| / sqrt 2):
 // the sign of erf folds into |x|, the halves into the coefficients -- 11 plain operations + v_rcp + v_exp.
+// What that is worth (tests/test_epilogue_exact_cpu.py emulates the formula over every fp16 / bf16 input, the GPU test
+// runs it through the kernels): the error is ABSOLUTE, at most 2.4e-7 |x| for the formula in fp32 and at most 4.8e-7 |x|
+// with the two 1-ulp hardware operations -- far below the fp16 / bf16 rounding of the result wherever |gelu(x)| is of
+// the order of |x|, but not a relative bound: for -6 < x < -3 the fp16 result is up to 2 ulp from the correctly rounded
+// one, and in the far tail (x < -5, |gelu(x)| < 1e-6) the relative error reaches 100 % and the sign is not preserved.
 __device__ __forceinline__ float gelu_erf(float x) {
   const float u = fabsf(x);
   const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752f, u, 1.0f));
@@ -123,7 +131,10 @@ __device__ __forceinline__ float gelu_erf(float x) {
 }
 // the same function on two values at once: the 11 plain operations as 6 packed ones (v_pk_fma_f32 / v_pk_mul_f32 are full
 // rate on gfx950 when no MFMA competes for the issue slot -- an epilogue), v_rcp / v_exp per element.  Same operations in
-// the same order as gelu_erf, so the results are bit-identical.
+// the same order as gelu_erf, so the fp32 results are bit-identical.  The STORED value need not be: where gelu_erf's result
+// goes straight to fp16 the compiler fuses the last fma with the conversion (v_fma_mix{lo,hi}_f16: one rounding), while
+// the packed form rounds to fp32 and then to fp16 -- the last fp16 bit differs on a few inputs (4 of the 184 326 of the
+// exact-epilogue test); bf16 has no such instruction and is identical.
 __device__ __forceinline__ f32x2 gelu_erf2(f32x2 x) {
   const f32x2 u = {fabsf(x.x), fabsf(x.y)};
   const f32x2 d = __builtin_elementwise_fma(f32x2{0.3275911f * 0.70710678118654752f, 0.3275911f * 0.70710678118654752f}, u,

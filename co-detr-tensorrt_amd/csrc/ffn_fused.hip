@@ -422,8 +422,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
           for (int h = 0; h < 2; ++h)
 #pragma unroll
             for (int r = 0; r < 4; ++r) pf[s][mt][h * 4 + r] = (E)hacc[2 * s + h][mt][r];
-      // ReLU on the packed halves (one op per two values).  max(NaN, 0) = 0 drops a NaN of the hidden unit, but a NaN
-      // there can only come from a NaN / inf in this row of X, which the residual add puts back.
+      // ReLU on the packed halves (relu_bits16: three packed ops per two values; a NaN of the hidden unit stays a NaN)
       if (!(CODETR_FFN_ABL_MASK & 16))
 #pragma unroll
       for (int s = 0; s < 2; ++s)
