@@ -136,6 +136,7 @@ SIGNATURES = {
     "codetr_slice_merge_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32,
                                       ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_draw_font": (_i32, [_vp]),
+    "codetr_frames_to_rgb_u8": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _i64]),
     "codetr_draw_detections_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
                                           ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
     "codetr_draw_detections_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
@@ -211,6 +212,7 @@ CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 
          "query_sine_embed": 0, "encoder_geometry": 0, "row_max": 0, "preprocess": 0, "batched_nms": 0,
          "preprocess_batch": 0, "postprocess_detections": 0, "postprocess_softnms": 0,
          "preprocess_views": 0, "tta_merge": 0, "draw_detections": 0, "preprocess_tiles": 0, "slice_merge": 0,
+         "frames_to_rgb": 0,
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
@@ -710,6 +712,24 @@ def draw_detections(buf, rows, boxes, scores, labels, count, palette, names, lin
         labels.data_ptr(), count.data_ptr(), Q, palette.data_ptr(), names.data_ptr(), palette.shape[0], int(line_width),
         float(alpha), float(score_thr), int(text_rgb), int(font_scale), 1 if draw_labels else 0)
     check(rc, "codetr_draw_detections")
+
+
+FRAME_FORMATS = {"rgb": 0, "bgr": 1, "rgba": 2, "bgra": 3, "gray": 4, "nv12": 5, "nv21": 6, "i420": 7}   # CODETR_FRAME_*
+FRAME_MAX_SIDE = 32767         # CODETR_FRAME_MAX_SIDE
+COLOR_MATRICES = {"bt601": 0, "bt709": 1}                       # CODETR_COLOR_BT601 / _BT709
+COLOR_RANGES = {"limited": 0, "full": 1}                        # CODETR_COLOR_LIMITED / _FULL
+
+
+def frames_to_rgb(src, rows, matrix, range_, dst):
+    """src / dst: flat uint8 device buffers; rows: <= PREPROCESS_BATCH_MAX of (format, H, W, plane0_offset, plane0_pitch,
+    plane1_offset, plane1_pitch, plane2_offset, plane2_pitch, dst_offset); matrix / range_: the CODETR_COLOR_* codes
+    (include/codetr_hip.h states the conversion)"""
+    CALLS["frames_to_rgb"] += 1
+    N = len(rows)
+    table = (ctypes.c_int64 * (10 * N))(*[int(v) for row in rows for v in row])
+    rc = load().codetr_frames_to_rgb_u8(current_stream_ptr(dst.device), src.data_ptr(), src.numel(), N, table,
+                                        int(matrix), int(range_), dst.data_ptr(), dst.numel())
+    check(rc, "codetr_frames_to_rgb_u8")
 
 
 def mask_pyramid(img_masks, shapes):

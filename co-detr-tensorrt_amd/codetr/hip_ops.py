@@ -913,6 +913,52 @@ def draw_detections(buf_u8, rows, dets, names, palette, style=None):
     return buf_u8
 
 
+FRAME_FORMATS = _cabi.FRAME_FORMATS
+FRAME_COLOR = dict(matrix="bt601", range="limited")   # what OpenCV's cvtColor(..., COLOR_YUV2RGB_NV12) computes
+_range = range    # (frames_to_rgb has a parameter of that name)
+
+
+def frames_to_rgb(src_u8, rows10, dst_bytes, matrix="bt601", range="limited", out=None):
+    """Frames as decoders hand them out -> packed RGB HWC images in one new flat uint8 device buffer of `dst_bytes`
+    bytes, one launch per PREPROCESS_BATCH_MAX frames (csrc/frames.hip; include/codetr_hip.h states the conversion).
+      src_u8    one flat contiguous uint8 device buffer that holds every plane
+      rows10    per frame (format, H, W, plane0_offset, plane0_pitch, plane1_offset, plane1_pitch, plane2_offset,
+                plane2_pitch, dst_offset); format a name of FRAME_FORMATS or its code, offsets in bytes, the columns of
+                a plane the format does not have 0
+      matrix    'bt601' | 'bt709'; range 'limited' | 'full' (the YUV formats; ignored by the others)
+      out       a flat uint8 buffer of dst_bytes on src_u8's GPU to write into instead of a new one (the frames of a
+                chunk that lie in several source buffers: one call per source)
+    -> the buffer; bytes outside the frames' images are not written.  ValueError for an unknown format, matrix or range
+    and for a wrong dtype or shape; whatever else is inconsistent the entry point rejects before it launches."""
+    _gpu(src_u8, "frames_to_rgb")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
+        raise ValueError("frames_to_rgb: expected one contiguous flat uint8 buffer")
+    if matrix not in _cabi.COLOR_MATRICES or range not in _cabi.COLOR_RANGES:
+        raise ValueError(f"frames_to_rgb: matrix one of {sorted(_cabi.COLOR_MATRICES)} and range one of "
+                         f"{sorted(_cabi.COLOR_RANGES)}, got {matrix!r} / {range!r}")
+    rows = []
+    for r in rows10:
+        if len(r) != 10:
+            raise ValueError("frames_to_rgb: ten values per row (format, H, W, three (offset, pitch) pairs, dst_offset)")
+        fmt = FRAME_FORMATS.get(r[0], r[0]) if isinstance(r[0], str) else r[0]
+        if isinstance(fmt, str) or int(fmt) not in FRAME_FORMATS.values():
+            raise ValueError(f"frames_to_rgb: unknown frame format {r[0]!r}; known: {sorted(FRAME_FORMATS)}")
+        rows.append((int(fmt),) + tuple(int(v) for v in r[1:]))
+    if not rows or int(dst_bytes) <= 0:
+        raise ValueError("frames_to_rgb: no frames")
+    if out is None:
+        out = torch.empty((int(dst_bytes),), dtype=torch.uint8, device=src_u8.device)
+    elif (not torch.is_tensor(out) or out.device != src_u8.device or out.dtype != torch.uint8 or out.dim() != 1
+          or not out.is_contiguous() or out.numel() != int(dst_bytes)):
+        raise ValueError("frames_to_rgb: out must be a contiguous flat uint8 buffer of dst_bytes on the source's GPU")
+    dst = out
+    with torch.cuda.device(src_u8.device):
+        for i in _range(0, len(rows), PREPROCESS_BATCH_MAX):
+            _cabi.frames_to_rgb(src_u8, rows[i:i + PREPROCESS_BATCH_MAX], _cabi.COLOR_MATRICES[matrix],
+                                _cabi.COLOR_RANGES[range], dst)
+    return dst
+
+
 def mask_pyramid(img_masks, shapes):
     """img_masks [B,H,W] (float 0/1, bool or uint8; non-zero = padding) + level shapes [(H_l, W_l)] ->
     (mask_flat [B,S] bool, ycum, xcum, valid_counts [B,L,2] fp32): the level masks (nearest resize), their running

@@ -74,7 +74,20 @@ the TTA merge's or the slice merge's, cut to ``max_per_img``) on the buffer the 
 preprocessing launch on the stream, and one more device-to-host copy fetches that buffer.  The rendering is the
 project's own, modelled on ``DetLocalVisualizer``'s defaults and stated pixel by pixel in ``include/codetr_hip.h``.
 Parity with mmdet's visualiser is unpinned (neither mmdet nor matplotlib is installed here).
+
+``input_format`` / ``color`` of ``__call__`` (beyond the reference, which takes host RGB arrays): ``"rgb"``, the default,
+with numpy arrays changes nothing.  ``"bgr"``, ``"rgba"``, ``"bgra"``, ``"gray"``, ``"nv12"``, ``"nv21"`` and ``"i420"``
+take frames as decoders and capture libraries hand them out -- numpy arrays or ``torch.uint8`` tensors, on the host or
+already on the GPU; for the YUV formats the 2-D ``[H * 3 / 2, W]`` array or a tuple of planes (``parse_frame``).
+``color`` = ``dict(matrix='bt601' | 'bt709', range='limited' | 'full')``, default BT.601 limited, is the YUV matrix.
+Such a call takes the chunked path; per chunk ``stage_chunk`` uploads the raw planes (1.5 bytes per pixel of NV12 /
+I420 instead of 3) in the one pinned staging copy and one ``hip_ops.frames_to_rgb`` launch writes them as the packed
+RGB buffer every other kernel reads; GPU-resident frames -- pitched views of a decoder surface among them -- are not
+uploaded at all: one launch per group of frames that share a storage reads them where they lie.  The visualisation draws
+on, and returns, the converted RGB frames.  The conversion is stated in integer arithmetic in ``include/codetr_hip.h``;
+parity with OpenCV's ``cvtColor`` is unpinned (cv2 is not installed here).
 """
+import collections
 import colorsys
 import json
 import os
@@ -208,6 +221,114 @@ def slicing_settings(slicing):
     return dict(tile=(int(tile[0]), int(tile[1])), overlap=(float(overlap[0]), float(overlap[1])),
                 full_image=bool(slicing.get("full_image", True)), merge=hip_ops.slice_merge_settings(slicing.get("merge")),
                 max_per_img=int(mpi) if mpi is not None and mpi > 0 else None, tile_batch=int(tile_batch))
+
+
+FRAME_COLOR_KEYS = ("matrix", "range")
+
+
+def frame_settings(input_format="rgb", color=None):
+    """How `__call__(..., input_format=..., color=...)` reads its arguments: `input_format` a name of
+    hip_ops.FRAME_FORMATS ('rgb', 'bgr', 'rgba', 'bgra', 'gray', 'nv12', 'nv21', 'i420'); `color` None or a dict with any
+    of `matrix` ('bt601' | 'bt709') and `range` ('limited' | 'full'), completed from hip_ops.FRAME_COLOR (BT.601,
+    limited range: what OpenCV's cvtColor computes) -- only the YUV formats read it.
+    -> dict(format, matrix, range)"""
+    if not isinstance(input_format, str) or input_format not in hip_ops.FRAME_FORMATS:
+        raise ValueError(f"input_format must be one of {sorted(hip_ops.FRAME_FORMATS)}, got {input_format!r}")
+    if color is not None and (not isinstance(color, dict) or set(color) - set(FRAME_COLOR_KEYS)):
+        raise ValueError(f"color must be None or a dict with keys of {FRAME_COLOR_KEYS}, got {color!r}")
+    out = dict(hip_ops.FRAME_COLOR, **(color or {}))
+    if out["matrix"] not in ("bt601", "bt709"):
+        raise ValueError(f"color matrix must be 'bt601' or 'bt709', got {out['matrix']!r}")
+    if out["range"] not in ("limited", "full"):
+        raise ValueError(f"color range must be 'limited' or 'full', got {out['range']!r}")
+    return dict(format=input_format, matrix=out["matrix"], range=out["range"])
+
+
+# one frame of a chunk: the format's code, its size, its planes as 2-D byte arrays [rows, row bytes] -- numpy on the host,
+# torch tensors with strides (pitch, 1) on the GPU -- and whether they are on the GPU
+Frame = collections.namedtuple("Frame", "code H W planes resident")
+
+_FRAME_SHAPES = dict(rgb="(H, W, 3)", bgr="(H, W, 3)", rgba="(H, W, 4)", bgra="(H, W, 4)", gray="(H, W)",
+                     nv12="(H * 3 / 2, W) with even H and W, or planes (y (H, W), uv (ceil(H / 2), ceil(W / 2), 2))",
+                     nv21="(H * 3 / 2, W) with even H and W, or planes (y (H, W), vu (ceil(H / 2), ceil(W / 2), 2))",
+                     i420="(H * 3 / 2, W) with even H and W, or planes (y (H, W), u, v (ceil(H / 2), ceil(W / 2)))")
+
+
+def parse_frame(item, input_format="rgb"):
+    """One chunk item -> Frame.  `item`: a numpy array or a torch tensor, uint8, on the host or on the GPU, of the
+    format's shape (_FRAME_SHAPES); for nv12 / nv21 / i420 either the 2-D array decoders hand out or a tuple of planes.
+    A host plane may have any strides (it is copied row by row into the staging buffer); a GPU-resident plane is read
+    where it lies and needs unit innermost stride and a positive row stride of at least the row's bytes, which becomes
+    its pitch -- a crop of a wider surface, say.  Anything else is a ValueError that names the format."""
+    fmt = input_format
+
+    def bad(why):
+        return ValueError(f"input_format={fmt!r}: expected uint8 frames of shape {_FRAME_SHAPES[fmt]}; {why}")
+
+    def array(a):
+        if torch.is_tensor(a):
+            if a.dtype != torch.uint8:
+                raise bad(f"got a tensor of {a.dtype}")
+            return a if a.is_cuda else a.detach().numpy()
+        if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+            raise bad(f"got {type(a).__name__}" + (f" of {a.dtype}" if isinstance(a, np.ndarray) else ""))
+        return a
+
+    def rows2d(a):
+        """[R, W] or [R, W, C] -> the byte rows [R, W * C]"""
+        R, B = a.shape[0], int(np.prod(a.shape[1:]))
+        if isinstance(a, np.ndarray):
+            return a.reshape(R, B)          # (a copy where the strides do not allow a view: host planes are copied anyway)
+        inner, unit = [], 1
+        for size, stride in zip(reversed(a.shape[1:]), reversed(a.stride()[1:])):
+            inner.append(size == 1 or stride == unit)
+            unit *= size
+        if not all(inner) or (R > 1 and a.stride(0) < B):
+            raise bad(f"a GPU-resident plane needs unit innermost stride and a row stride of at least the row's bytes, "
+                      f"got strides {tuple(a.stride())} for shape {tuple(a.shape)}")
+        return a.as_strided((R, B), (a.stride(0) if R > 1 else B, 1))
+
+    if isinstance(item, (tuple, list)):
+        if fmt not in ("nv12", "nv21", "i420"):
+            raise bad("got a tuple of planes")
+        parts = [array(a) for a in item]
+        if len(parts) != (3 if fmt == "i420" else 2) or parts[0].ndim != 2 or min(parts[0].shape) < 1:
+            raise bad(f"got {len(parts)} plane(s)" + (f", y of shape {tuple(parts[0].shape)}" if parts else ""))
+        H, W = (int(v) for v in parts[0].shape)
+        chroma = ((H + 1) // 2, (W + 1) // 2) + ((2,) if fmt != "i420" else ())
+        for a in parts[1:]:
+            if tuple(a.shape) != chroma:
+                raise bad(f"got a chroma plane of shape {tuple(a.shape)} for a {H} x {W} frame, expected {chroma}")
+        planes = [rows2d(a) for a in parts]
+    else:
+        a = array(item)
+        if fmt in ("nv12", "nv21", "i420"):
+            if a.ndim != 2 or a.shape[0] % 3 or (a.shape[0] * 2 // 3) % 2 or a.shape[1] % 2 or min(a.shape) < 1:
+                raise bad(f"got shape {tuple(a.shape)}")
+            H, W = int(a.shape[0]) * 2 // 3, int(a.shape[1])
+            if fmt != "i420":
+                planes = [rows2d(a[:H]), rows2d(a[H:])]
+            else:   # two chroma rows lie in every row of the lower third: only an unpitched array splits into planes
+                if isinstance(a, np.ndarray):
+                    c = np.ascontiguousarray(a[H:])
+                elif a.stride(1) == 1 and a.stride(0) == W:
+                    c = a[H:]
+                else:
+                    raise bad(f"a GPU-resident 2-D i420 frame must be contiguous (strides {tuple(a.stride())}): pass the "
+                              "planes (y, u, v) of a pitched surface")
+                c = c.reshape(2, H // 2, W // 2)
+                planes = [rows2d(a[:H]), rows2d(c[0]), rows2d(c[1])]
+        else:
+            C = dict(rgb=3, bgr=3, rgba=4, bgra=4, gray=0)[fmt]
+            if a.ndim != (3 if C else 2) or (C and a.shape[2] != C) or min(a.shape) < 1:
+                raise bad(f"got shape {tuple(a.shape)}")
+            H, W = int(a.shape[0]), int(a.shape[1])
+            planes = [rows2d(a)]
+    on_gpu = [torch.is_tensor(p) for p in planes]
+    if any(on_gpu):
+        if not all(on_gpu) or len({p.untyped_storage().data_ptr() for p in planes}) != 1:
+            raise bad("the planes of a GPU-resident frame must share one storage (views of one surface)")
+    return Frame(hip_ops.FRAME_FORMATS[fmt], H, W, planes, all(on_gpu))
 
 
 def generated_palette(n):
@@ -366,42 +487,36 @@ class Inferencer:
                     scale_factor=(nw / W, nh / H))
         return x[None], m[None], meta
 
-    def preprocess_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32):
+    def preprocess_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
+                         color=None):
         """RGB uint8 images [H_i, W_i, 3] -> (batch_inputs [N,3,H,W], img_masks [N,H,W], metas): per image the
         arithmetic of `preprocess`, stacked as mmdet's DetDataPreprocessor does (H, W = the largest Pad shape rounded
         up to pad_size_divisor; beyond an image's Pad region pad_value, mask 1).  One host-to-device copy, one launch
-        per 32 images; dtype f16, bf16 or f32."""
-        return self._preprocess_chunk(images, device, dtype)[:3]
+        per 32 images; dtype f16, bf16 or f32.  `input_format` / `color`: frames of another format or already on the
+        GPU (`frame_settings`, `stage_chunk`)."""
+        return self._preprocess_chunk(images, device, dtype, frame_settings(input_format, color))[:3]
 
-    def _preprocess_chunk(self, images, device, dtype):
-        """preprocess_batch + the uploaded buffer and every image's (offset, H, W) in it, for the visualisation"""
-        rows, metas, offset = [], [], 0
+    def _preprocess_chunk(self, images, device, dtype, frames=None):
+        """preprocess_batch + the RGB buffer on the device and every image's (offset, H, W) in it, for the visualisation"""
+        if not len(images):
+            raise ValueError("preprocess_batch: no images")
+        src, staged, _ = self.stage_chunk(images, device, frames)
+        rows, metas = [], []
         d = self.pad_size_divisor
-        for image in images:
-            if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
-                raise ValueError("expected RGB uint8 images of shape (H, W, 3)")
-            H, W = image.shape[:2]
+        for offset, H, W in staged:
             nh, nw = rescale_size(H, W, self.scale)
             Hp, Wp = nh, nw
             if self.pad_size is not None:
                 Wp, Hp = max(self.pad_size[0], nw), max(self.pad_size[1], nh)
             rows.append((offset, H, W, nh, nw, Hp, Wp))
-            offset += H * W * 3
             pad_shape = (-(-Hp // d) * d, -(-Wp // d) * d) if d > 1 else (Hp, Wp)
             metas.append(dict(ori_shape=(H, W), img_shape=(nh, nw), img_unpadded_shape=(nh, nw), pad_shape=pad_shape,
                               scale_factor=(nw / W, nh / H)))
-        if not rows:
-            raise ValueError("preprocess_batch: no images")
         Hb, Wb = max(m["pad_shape"][0] for m in metas), max(m["pad_shape"][1] for m in metas)
         for m in metas:
             m["batch_input_shape"] = (Hb, Wb)
-        staging = torch.empty((offset,), dtype=torch.uint8, pin_memory=True)
-        host = staging.numpy()
-        for image, row in zip(images, rows):
-            host[row[0]:row[0] + image.size] = np.ascontiguousarray(image).reshape(-1)
-        src = staging.to(device, non_blocking=True)
         x, m = hip_ops.preprocess_batch(src, rows, (Hb, Wb), self.mean, self.std, self.pad_val, self.pad_value, dtype)
-        return x, m, metas, src, [r[:3] for r in rows]
+        return x, m, metas, src, staged
 
     # ---- post -----------------------------------------------------------------------------------------
     def postprocess_predictions(self, batch_boxes, batch_scores, batch_labels):
@@ -497,6 +612,89 @@ class Inferencer:
         dev = staging.to(device, non_blocking=True)
         return dev[:offset], offsets, (dev[tail_at:].view(tail.dtype).view(tail.shape) if tail is not None else None)
 
+    @staticmethod
+    def host_rgb(images, frames=None):
+        """whether a chunk is what the reference's Inferencer takes: RGB frames, every one a host numpy array"""
+        return (frames is None or frames["format"] == "rgb") and all(isinstance(im, np.ndarray) for im in images)
+
+    def stage_chunk(self, images, device="cuda:0", frames=None, tail=None):
+        """The chunk's frames as packed RGB HWC images in one flat uint8 buffer on the device
+        -> (the buffer, [(offset, H, W)] per image, `tail` on the device).
+        `frames`: `frame_settings(...)`, None for RGB.  `tail`: a small host tensor that rides in the chunk's one
+        host-to-device copy, or a function of the [(offset, H, W)] list that returns one (the TTA and slicing tails
+        depend on the frame sizes).
+          * host RGB arrays: `upload` -- the images back to back in one pinned staging buffer, one copy, no launch;
+          * any other host frame: its raw planes, rows packed, each plane 16-byte aligned, in the one pinned staging
+            buffer (1.5 bytes per pixel of NV12 / I420 instead of 3) and one `hip_ops.frames_to_rgb` launch behind the
+            copy;
+          * GPU-resident frames: no upload; one launch per group of frames that share a storage, which read the planes
+            where they lie (offsets relative to the storage, pitches from the strides).  With no host frame in the chunk
+            the tail is a small copy of its own.
+        Host and GPU frames may be mixed.  The images of a converted chunk start at multiples of 16 bytes."""
+        if not len(images):
+            raise ValueError("stage_chunk: no images")
+        if self.host_rgb(images, frames):
+            shapes = []
+            for image in images:
+                if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+                    raise ValueError("expected RGB uint8 images of shape (H, W, 3)")
+                shapes.append(image.shape[:2])
+            offsets = np.cumsum([0] + [H * W * 3 for H, W in shapes]).tolist()
+            staged = [(o, H, W) for o, (H, W) in zip(offsets, shapes)]
+            src, _, tail = self.upload(images, device, tail(staged) if callable(tail) else tail)
+            return src, staged, tail
+        frames = frames or frame_settings()
+        items = [parse_frame(im, frames["format"]) for im in images]
+        staged, dst_bytes = [], 0
+        for it in items:
+            staged.append((dst_bytes, it.H, it.W))
+            dst_bytes = -(-(dst_bytes + it.H * it.W * 3) // 16) * 16
+        if callable(tail):
+            tail = tail(staged)
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        host_rows, copies, groups, pos = [], [], {}, 0   # groups: storage address -> (its bytes as a flat tensor, rows)
+        for it, (dst, H, W) in zip(items, staged):
+            cols = []
+            for plane in it.planes:
+                if it.resident:
+                    cols += [plane.storage_offset(), plane.stride(0)]
+                else:
+                    pos = -(-pos // 16) * 16
+                    copies.append((pos, plane))
+                    cols += [pos, plane.shape[1]]
+                    pos += plane.size
+            row = (it.code, H, W) + tuple(cols) + (0,) * (6 - len(cols)) + (dst,)
+            if not it.resident:
+                host_rows.append(row)
+                continue
+            if it.planes[0].device != dev:
+                raise ValueError(f"a GPU-resident frame on {it.planes[0].device} in a call for {dev}")
+            storage = it.planes[0].untyped_storage()
+            if storage.data_ptr() not in groups:
+                flat = torch.empty((0,), dtype=torch.uint8, device=dev).set_(storage, 0, (storage.nbytes(),), (1,))
+                groups[storage.data_ptr()] = (flat, [])
+            groups[storage.data_ptr()][1].append(row)
+        tail_at = -(-pos // 16) * 16
+        tail_bytes = tail.contiguous().view(-1).view(torch.uint8) if tail is not None else None
+        total = pos if tail is None else tail_at + tail_bytes.numel()
+        up = None
+        if total:
+            staging = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+            host = staging.numpy()
+            for at, plane in copies:
+                host[at:at + plane.size].reshape(plane.shape)[...] = plane
+            if tail is not None:
+                staging[tail_at:] = tail_bytes
+            up = staging.to(dev, non_blocking=True)
+        src = torch.empty((dst_bytes,), dtype=torch.uint8, device=dev)
+        if host_rows:
+            hip_ops.frames_to_rgb(up[:pos], host_rows, dst_bytes, frames["matrix"], frames["range"], out=src)
+        for flat, rows in groups.values():
+            hip_ops.frames_to_rgb(flat, rows, dst_bytes, frames["matrix"], frames["range"], out=src)
+        return src, staged, (up[tail_at:].view(tail.dtype).view(tail.shape) if tail is not None else None)
+
     def view_rows(self, offsets, shapes, scale, flips):
         """One TTA scale of a chunk: images of `shapes` (H, W) at byte `offsets`, resized keep-ratio into `scale`, once
         per entry of `flips` (False / True: mirrored), padded to pad_size_divisor and stacked.  Rows are flip-major --
@@ -516,25 +714,25 @@ class Inferencer:
             m["batch_input_shape"] = (Hb, Wb)
         return rows, metas, (Hb, Wb)
 
-    def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32):
+    def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb", color=None):
         """one chunk through every view and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor."""
-        return self._tta_chunk(images, device, dtype)[0]
+        return self._tta_chunk(images, device, dtype, frame_settings(input_format, color))[0]
 
-    def _tta_chunk(self, images, device, dtype):
-        """tta_batch + the uploaded images, every image's (offset, H, W) and the merged detections on the device"""
+    def _tta_chunk(self, images, device, dtype, frames=None):
+        """tta_batch + the RGB buffer on the device, every image's (offset, H, W) and the merged detections on the device"""
         t = self.tta
         flips = (False, True) if t["flip"] else (False,)
-        shapes = [im.shape[:2] for im in images]
-        N, offsets, offset = len(images), [], 0
-        for im in images:
-            offsets.append(offset)
-            offset += im.size
-        plans = [self.view_rows(offsets, shapes, scale, flips) for scale in t["scales"]]
-        widths = torch.tensor([float(w) for _, w in shapes], dtype=torch.float32)
-        div = torch.cat([self.divisors(metas, dtype) for _, metas, _ in plans])      # [S * F * N, 4]
-        tail = torch.cat((widths.view(torch.uint8), div.view(-1).view(torch.uint8)))
-        src, _, tail = self.upload(images, device, tail)
+        N, plans = len(images), []
+
+        def tail_of(staged):
+            shapes = [(H, W) for _, H, W in staged]
+            plans.extend(self.view_rows([o for o, _, _ in staged], shapes, scale, flips) for scale in t["scales"])
+            widths = torch.tensor([float(w) for _, w in shapes], dtype=torch.float32)
+            div = torch.cat([self.divisors(metas, dtype) for _, metas, _ in plans])      # [S * F * N, 4]
+            return torch.cat((widths.view(torch.uint8), div.view(-1).view(torch.uint8)))
+
+        src, staged, tail = self.stage_chunk(images, device, frames, tail_of)
         widths = tail[:4 * N].view(torch.float32)
         div = tail[4 * N:].view(dtype).view(len(plans), len(flips) * N, 4)
         view_dets = []
@@ -553,7 +751,7 @@ class Inferencer:
             c = int(host.count[i])
             out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
                         "bboxes": host.boxes[i, :c].float().tolist()})
-        return out, src, [(o, H, W) for o, (H, W) in zip(offsets, shapes)], dets
+        return out, src, staged, dets
 
     # ---- sliced inference -------------------------------------------------------------------------------------
     @staticmethod
@@ -609,27 +807,30 @@ class Inferencer:
         V = max(len(t) for t in table)
         return rows, metas, [t + [-1] * (V - len(t)) for t in table], (Hb, Wb)
 
-    def slice_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32):
+    def slice_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
+                    color=None):
         """one chunk through every tile and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, every row's origin and rescale divisor, the image sizes and the view table."""
-        return self._slice_chunk(images, device, dtype)[0]
+        return self._slice_chunk(images, device, dtype, frame_settings(input_format, color))[0]
 
-    def _slice_chunk(self, images, device, dtype):
-        """slice_batch + the uploaded images, every image's (offset, H, W) and the merged detections on the device"""
+    def _slice_chunk(self, images, device, dtype, frames=None):
+        """slice_batch + the RGB buffer on the device, every image's (offset, H, W) and the merged detections on the device"""
         s = self.slicing
-        shapes = [im.shape[:2] for im in images]
-        N, offsets, offset = len(images), [], 0
-        for im in images:
-            offsets.append(offset)
-            offset += im.size
-        rows, metas, table, batch_hw = self.slice_rows(offsets, shapes)
+        N, plan = len(images), []
+
+        def tail_of(staged):
+            shapes = [(H, W) for _, H, W in staged]
+            plan.extend(self.slice_rows([o for o, _, _ in staged], shapes))
+            metas, table = plan[1], plan[2]
+            origins = torch.tensor([m["origin"] for m in metas], dtype=torch.float32)            # [R, 2] (x0, y0)
+            sizes = torch.tensor([[float(W), float(H)] for H, W in shapes], dtype=torch.float32)  # [N, 2] (W, H)
+            view_rows = torch.tensor(table, dtype=torch.int32)                                    # [N, V]
+            div = self.divisors(metas, dtype)                                                     # [R, 4]
+            return torch.cat([t.view(-1).view(torch.uint8) for t in (origins, sizes, view_rows, div)])
+
+        src, staged, tail = self.stage_chunk(images, device, frames, tail_of)
+        rows, metas, table, batch_hw = plan
         R, V = len(rows), len(table[0])
-        origins = torch.tensor([m["origin"] for m in metas], dtype=torch.float32)            # [R, 2] (x0, y0)
-        sizes = torch.tensor([[float(W), float(H)] for H, W in shapes], dtype=torch.float32)  # [N, 2] (W, H)
-        view_rows = torch.tensor(table, dtype=torch.int32)                                    # [N, V]
-        div = self.divisors(metas, dtype)                                                     # [R, 4]
-        tail = torch.cat([t.view(-1).view(torch.uint8) for t in (origins, sizes, view_rows, div)])
-        src, _, tail = self.upload(images, device, tail)
         origins = tail[:8 * R].view(torch.float32).view(R, 2)
         sizes = tail[8 * R:8 * (R + N)].view(torch.float32).view(N, 2)
         view_rows = tail[8 * (R + N):8 * (R + N) + 4 * N * V].view(torch.int32).view(N, V)
@@ -649,7 +850,7 @@ class Inferencer:
             c = int(host.count[i])
             out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
                         "bboxes": host.boxes[i, :c].float().tolist()})
-        return out, src, [(o, H, W) for o, (H, W) in zip(offsets, shapes)], dets
+        return out, src, staged, dets
 
     # ---- visualisation and files --------------------------------------------------------------------------
     def draw_chunk(self, src, rows, dets, pred_score_thr):
@@ -684,17 +885,19 @@ class Inferencer:
                  no_save_vis: bool = False, draw_pred: bool = True, pred_score_thr: float = 0.3,
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
-                 batch_size: int = 1) -> Dict:
+                 batch_size: int = 1, input_format: str = "rgb", color=None) -> Dict:
         if show or return_datasamples or (return_vis and self.visualizer is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
         batch_size = int(batch_size)
+        frames = frame_settings(input_format, color)
+        plain = self.host_rgb(images, frames)   # what the reference takes; everything else is staged per chunk
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
         visualise = self.visualizer is not None and (return_vis or save_vis)
         if (batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None and self.slicing is None
-                and not visualise):
+                and not visualise and plain):
             for image in images:
                 with torch.no_grad():
                     x, m, meta = self.preprocess(image, device, dtype)
@@ -711,15 +914,20 @@ class Inferencer:
             chunk = images[start:start + batch_size]
             with torch.no_grad():
                 if self.tta is not None:
-                    preds, src, rows, dets = self._tta_chunk(chunk, device, dtype)
+                    preds, src, rows, dets = self._tta_chunk(chunk, device, dtype, frames)
                 elif self.slicing is not None:
-                    preds, src, rows, dets = self._slice_chunk(chunk, device, dtype)
+                    preds, src, rows, dets = self._slice_chunk(chunk, device, dtype, frames)
                 else:
-                    x, m, metas, src, rows = self._preprocess_chunk(chunk, device, dtype)
+                    x, m, metas, src, rows = self._preprocess_chunk(chunk, device, dtype, frames)
                     preds, dets = self._postprocess_chunk(self.model(x, m), metas)
                 drawn = [None] * len(chunk)
-                if visualise:   # (draw_pred=False: the originals, as mmdet returns the undrawn image; nothing launched)
-                    drawn = self.draw_chunk(src, rows, dets, pred_score_thr) if draw_pred else [im.copy() for im in chunk]
+                if visualise and draw_pred:
+                    drawn = self.draw_chunk(src, rows, dets, pred_score_thr)
+                elif visualise and plain:   # the originals, as mmdet returns the undrawn image; nothing launched
+                    drawn = [im.copy() for im in chunk]
+                elif visualise:             # the undrawn converted frames: one download of the chunk's RGB buffer
+                    host = src.cpu().numpy()
+                    drawn = [host[o:o + H * W * 3].reshape(H, W, 3).copy() for o, H, W in rows]
             for pred, vis in zip(preds, drawn):
                 if print_result:
                     print(pred)

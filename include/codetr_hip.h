@@ -1024,6 +1024,73 @@ int codetr_draw_detections_f32(void *stream, void *buf_dev, int64_t buf_bytes, i
                                uint32_t text_rgb, int font_scale, int draw_labels);
 
 /* ------------------------------------------------------------------------------------------
+ * Frames: what decoders and capture libraries hand out -> the packed RGB images the kernels above read, one launch for a
+ * chunk.  Beyond the reference, whose Inferencer takes host RGB arrays only (codetr/inferencer.py:402-452).
+ *
+ * codetr_frames_to_rgb_u8: N <= CODETR_PREPROCESS_BATCH_MAX frames (the caller splits).
+ *     src_dev            one flat byte buffer, src_bytes long, holding every plane of every frame
+ *     frames_host        HOST [N][10] int64: format, H, W, plane0_offset, plane0_pitch, plane1_offset, plane1_pitch,
+ *                        plane2_offset, plane2_pitch, dst_offset.  Offsets are bytes from src_dev (dst_offset: from
+ *                        dst_dev), a pitch is the distance in bytes between two rows of its plane and is at least the
+ *                        row's bytes; the columns of a plane the format does not have are 0 and never read.
+ *     dst_dev            dst_bytes long; frame n becomes RGB uint8 HWC, H * W * 3 bytes at dst_offset, its rows W * 3 bytes
+ *                        apart (the layout codetr_preprocess_batch_u8_* and codetr_draw_detections_* take)
+ *   Formats (ch = ceil(H / 2), cw = ceil(W / 2); odd H and W are allowed):
+ *     CODETR_FRAME_RGB  0   one plane, H rows of 3 W bytes: R, G, B.  With a pitch: a pitched-to-packed copy
+ *     CODETR_FRAME_BGR  1   one plane, H rows of 3 W bytes: B, G, R
+ *     CODETR_FRAME_RGBA 2   one plane, H rows of 4 W bytes: R, G, B, A; alpha is ignored
+ *     CODETR_FRAME_BGRA 3   one plane, H rows of 4 W bytes: B, G, R, A; alpha is ignored
+ *     CODETR_FRAME_GRAY 4   one plane, H rows of W bytes; R = G = B = the byte, no range expansion
+ *     CODETR_FRAME_NV12 5   plane 0: Y, H rows of W bytes; plane 1: ch rows of cw interleaved pairs U, V (2 cw bytes)
+ *     CODETR_FRAME_NV21 6   as NV12, the pairs V, U
+ *     CODETR_FRAME_I420 7   plane 0: Y; plane 1: U, ch rows of cw bytes; plane 2: V, the same shape
+ *   Chroma is taken nearest: pixel (y, x) uses chroma sample (y >> 1, x >> 1), as OpenCV's
+ *   cvtColor(..., COLOR_YUV2RGB_NV12) does.
+ *   YUV -> RGB, per launch a matrix (CODETR_COLOR_BT601 0, CODETR_COLOR_BT709 1) and a range (CODETR_COLOR_LIMITED 0,
+ *   CODETR_COLOR_FULL 1).  With c = max(0, Y - y0), d = U - 128, e = V - 128, y0 = 16 for limited and 0 for full range:
+ *       R = clamp255((CY * c           + CRV * e + (1 << 19)) >> 20)
+ *       G = clamp255((CY * c + CGU * d + CGV * e + (1 << 19)) >> 20)
+ *       B = clamp255((CY * c + CBU * d           + (1 << 19)) >> 20)
+ *   in signed 32-bit arithmetic (the largest magnitude is below 2^30), >> an arithmetic shift, clamp255 to 0..255.
+ *   The constants are round(k * 2^20), {CY, CRV, CGU, CGV, CBU} below.  BT.601 limited takes OpenCV's published
+ *   three-decimal coefficients k = 1.164, 1.596, -0.391, -0.813, 2.018 -- the default, because it is what a caller's
+ *   cvtColor does today.  The other three sets come from the exact matrices evaluated in double: with (Kr, Kb) =
+ *   (0.299, 0.114) for BT.601 and (0.2126, 0.0722) for BT.709 and Kg = 1 - Kr - Kb, full range is CY = 1, CRV = 2 (1 - Kr),
+ *   CBU = 2 (1 - Kb), CGU = -2 Kb (1 - Kb) / Kg, CGV = -2 Kr (1 - Kr) / Kg; limited range multiplies CY by 255 / 219 and
+ *   the chroma terms by 255 / 224.  Parity with OpenCV is unpinned (cv2 is not installed where this is tested): the
+ *   formula above is the contract.
+ *   Reads: no byte outside a declared plane row [offset + r * pitch, offset + r * pitch + row bytes) is read, by a
+ *   vector load either; whatever lies between the rows of a pitched plane does not matter.  Writes: no byte outside an
+ *   output image is written.  Offsets and pitches need no alignment; rows whose addresses are multiples of 4 move as
+ *   dwords (csrc/frames.hip) with the same result.
+ *   The table travels in the kernel arguments: no staging copy, capturable.  CODETR_E_BADARG for a null pointer,
+ *   N <= 0, src_bytes or dst_bytes <= 0, an unknown format, matrix or range, H or W <= 0, a negative offset, a pitch
+ *   smaller than the row's bytes, a plane row not inside [0, src_bytes), an output image not inside [0, dst_bytes), two
+ *   output images that overlap; CODETR_E_TOO_LARGE for N > CODETR_PREPROCESS_BATCH_MAX or a side above
+ *   CODETR_FRAME_MAX_SIDE (the source-side limit of codetr_preprocess_batch_u8_*).  All checks run before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define CODETR_FRAME_RGB 0
+#define CODETR_FRAME_BGR 1
+#define CODETR_FRAME_RGBA 2
+#define CODETR_FRAME_BGRA 3
+#define CODETR_FRAME_GRAY 4
+#define CODETR_FRAME_NV12 5
+#define CODETR_FRAME_NV21 6
+#define CODETR_FRAME_I420 7
+#define CODETR_FRAME_MAX_SIDE 32767
+#define CODETR_COLOR_BT601 0
+#define CODETR_COLOR_BT709 1
+#define CODETR_COLOR_LIMITED 0
+#define CODETR_COLOR_FULL 1
+/*                                   CY       CRV      CGU      CGV      CBU  */
+#define CODETR_YUV_BT601_LIMITED {1220542, 1673527, -409993, -852492, 2116026}
+#define CODETR_YUV_BT601_FULL    {1048576, 1470104, -360853, -748826, 1858077}
+#define CODETR_YUV_BT709_LIMITED {1220945, 1879825, -223607, -558796, 2215014}
+#define CODETR_YUV_BT709_FULL    {1048576, 1651297, -196424, -490864, 1945738}
+int codetr_frames_to_rgb_u8(void *stream, const void *src_dev, int64_t src_bytes, int64_t N,
+                            const int64_t *frames_host, int matrix, int range, void *dst_dev, int64_t dst_bytes);
+
+/* ------------------------------------------------------------------------------------------
  * Backward of multi-scale deformable attention (training path).
  *
  * Replaces ms_deformable_col2im_cuda<T> / ms_deform_attn_backward (codetr/csrc/ms_deform_attn.cu:781-897, 975-1028;

@@ -36,7 +36,15 @@ plain `Inferencer` call over the image's 9 crops at batch_size = tile_batch (no 
 detections shifted and fused in numpy (tests/slice_ref.py) --; and the two slicing kernels alone, HIP events as above:
 preprocess_tiles on the 9 rows of one such image, slice_merge at N = 2, V = 9, Q = 300 for both merge types.
 
+`--frames nv12|i420|bgr [--resident]` prints only a `frames` record (decoder frames, fp16): frames_to_rgb_kernel alone
+on eight 1920x1080 frames of the format -- a HIP event pair around each of 200 launches, the median in microseconds
+and the achieved GB/s of (bytes read + bytes written) beside a torch device-to-device copy of the same byte count in the same run --; and images/s of
+the Inferencer at batch_size 8 over --images frames of 1920x1080 fed as host frames of the format, (with --resident)
+as GPU-resident tensors, and as host RGB arrays converted beforehand (the conversion is not timed: the fairest thing
+the RGB-only route can do), the three in turn, three times.
+
     python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis] [--slice]   -> one JSON line
+    python tools/bench_inferencer.py --frames nv12 --resident
 """
 import argparse
 import csv
@@ -361,6 +369,94 @@ def vis_record(inf, images, repeats, bs=8):
     return rec
 
 
+FRAME_WH = (1920, 1080)
+
+
+def frame_items(fmt, n, seed=7):
+    """n random 1920x1080 frames of the format as decoders hand them out, and their RGB conversion (tests/frames_ref.py)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import frames_ref
+
+    rng = np.random.default_rng(seed)
+    W, H = FRAME_WH
+    items = [frames_ref.item(fmt, H, W, frames_ref.random_planes(fmt, H, W, rng)) for _ in range(n)]
+    return items, [frames_ref.to_rgb(it, fmt) for it in items]
+
+
+def _event_us_each(call, launches=200, warmup=20):
+    """median us of one launch, an event pair around each: what the GPU spends on it, whatever the host takes to enqueue"""
+    for _ in range(warmup):
+        call()
+    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)]
+    torch.cuda.synchronize()
+    for t0, t1 in pairs:
+        t0.record()
+        call()
+        t1.record()
+    torch.cuda.synchronize()
+    return round(float(np.median([t0.elapsed_time(t1) for t0, t1 in pairs])) * 1e3, 2)
+
+
+def frames_kernel_times(fmt, N=8):
+    """us per launch of frames_to_rgb_kernel on N 1920x1080 frames (planes packed, 16-byte aligned, as stage_chunk lays
+    them out) and of a device-to-device copy of as many bytes as the kernel reads and writes together"""
+    from codetr import hip_ops
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import frames_ref
+
+    W, H = FRAME_WH
+    rows, at, dst = [], 0, 0
+    for _ in range(N):
+        cols = []
+        for r, rb in frames_ref.plane_shapes(fmt, H, W):
+            at = -(-at // 16) * 16
+            cols += [at, rb]
+            at += r * rb
+        rows.append((fmt, H, W) + tuple(cols) + (0,) * (6 - len(cols)) + (dst,))
+        dst = -(-(dst + H * W * 3) // 16) * 16
+    g = torch.Generator().manual_seed(0)
+    src = torch.randint(0, 256, (at,), dtype=torch.uint8, generator=g).to(DEV)
+    out = torch.empty((dst,), dtype=torch.uint8, device=DEV)
+    moved = at + N * H * W * 3
+    a, b = torch.randint(0, 256, (moved // 2,), dtype=torch.uint8, generator=g).to(DEV), torch.empty((moved // 2,),
+                                                                                                   dtype=torch.uint8, device=DEV)
+    rec = {"frames": N, "frame_wh": list(FRAME_WH), "format": fmt, "bytes_read": at, "bytes_written": N * H * W * 3}
+    for name, call in (("frames_to_rgb_kernel", lambda: hip_ops.frames_to_rgb(src, rows, dst, out=out)),
+                       ("torch_copy_same_bytes", lambda: b.copy_(a)),
+                       ("frames_to_rgb_kernel_again", lambda: hip_ops.frames_to_rgb(src, rows, dst, out=out)),
+                       ("torch_copy_same_bytes_again", lambda: b.copy_(a))):
+        us = _event_us_each(call)
+        rec[name] = {"us_per_launch_median": us, "gb_per_s": round(moved / us / 1e3, 1)}
+    return rec
+
+
+def frames_record(inf, fmt, n_images, repeats, resident, bs=8):
+    items, rgb = frame_items(fmt, n_images)
+    rec = {"format": fmt, "batch_size": bs, "images": n_images, "frame_wh": list(FRAME_WH), "repeats": repeats,
+           "dtype": "fp16", "kernel": frames_kernel_times(fmt)}
+    arms = {f"{fmt}_from_host": (items, fmt), "rgb_preconverted_from_host": (rgb, "rgb")}
+    if resident:
+        on_gpu = [torch.from_numpy(np.ascontiguousarray(it)).to(DEV) for it in items]   # (1920x1080: one array per frame)
+        arms[f"{fmt}_gpu_resident"] = (on_gpu, fmt)
+    for name in arms:
+        rec[name] = {"pass_s": []}
+    with torch.no_grad():
+        for frames, f in arms.values():
+            inf(frames[:bs], device=DEV, dtype=torch.float16, batch_size=bs, input_format=f)     # warm-up
+        for _ in range(3):                                                                        # the arms in turn
+            for name, (frames, f) in arms.items():
+                for _ in range(repeats):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    inf(frames, device=DEV, dtype=torch.float16, batch_size=bs, input_format=f)
+                    rec[name]["pass_s"].append(round(time.perf_counter() - t0, 4))
+    for name in arms:
+        rec[name]["images_per_s"] = round(n_images / min(rec[name]["pass_s"]), 2)
+        rec[name]["images_per_s_median"] = round(n_images / float(np.median(rec[name]["pass_s"])), 2)
+    return rec
+
+
 def soft_inferencer(inf):
     """the same model behind the post-processing its config specifies (soft-NMS, max_per_img)"""
     import bench
@@ -436,6 +532,8 @@ def main():
     ap.add_argument("--slice", action="store_true", help="add the sliced-inference sub-record")
     ap.add_argument("--slice-images", type=int, default=4)
     ap.add_argument("--slice-only", action="store_true", help="only the slice sub-record (implies --slice)")
+    ap.add_argument("--frames", choices=("nv12", "i420", "bgr"), help="only the frames record, for frames of this format")
+    ap.add_argument("--resident", action="store_true", help="with --frames: also feed the frames as GPU-resident tensors")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -447,6 +545,11 @@ def main():
     bss = [int(v) for v in a.batch_sizes.split(",")]
     res = {}
     infs = inferencers()
+    if a.frames:
+        print(json.dumps({"metric": "Inferencer on decoder frames (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the kernel",
+                          "frames": frames_record(infs["fp16"], a.frames, a.images, a.repeats, a.resident)}))
+        return
     if a.tta_only:
         print(json.dumps({"metric": "Inferencer test-time augmentation (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass",
