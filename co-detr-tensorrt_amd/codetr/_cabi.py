@@ -137,6 +137,10 @@ SIGNATURES = {
                                       ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "codetr_draw_font": (_i32, [_vp]),
     "codetr_frames_to_rgb_u8": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _i64]),
+    "codetr_track_state_bytes": (_i64, [_i64]),
+    "codetr_track_update_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
+    "codetr_track_update_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
+    "codetr_track_update_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
     "codetr_draw_detections_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
                                           ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
     "codetr_draw_detections_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
@@ -212,7 +216,7 @@ CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 
          "query_sine_embed": 0, "encoder_geometry": 0, "row_max": 0, "preprocess": 0, "batched_nms": 0,
          "preprocess_batch": 0, "postprocess_detections": 0, "postprocess_softnms": 0,
          "preprocess_views": 0, "tta_merge": 0, "draw_detections": 0, "preprocess_tiles": 0, "slice_merge": 0,
-         "frames_to_rgb": 0,
+         "frames_to_rgb": 0, "track_update": 0,
          "msda_backward": 0, "patch_merge_layernorm": 0, "msda_encoder": 0, "msda_encoder_packed": 0, "patch_im2col": 0, "mha_attention": 0, "topk": 0,
          # which kernel behind codetr_linear_* served a launch (codetr_linear_variant), and the two fused operand loads
          "linear_pp": 0, "swin_mlp": 0, "linear_tile128": 0, "linear_tile256": 0, "linear_xs": 0, "linear_ln": 0, "linear_xadd": 0, "encoder_projections": 0,
@@ -231,7 +235,7 @@ _QUERIES = {"codetr_hip_abi_version", "codetr_hip_strerror", "codetr_msda_varian
             "codetr_linear_pp_supported", "codetr_linear_pp_preferred", "codetr_msda_op4_supported", "codetr_swin_mlp_supported",
             "codetr_msda_encoder_packed_lds_bytes", "codetr_msda_pack_projection_index", "codetr_window_attention_bias_index",
             "codetr_mx_scale_bytes", "codetr_decoder_layer_supported",
-            "codetr_decoder_layer_blob_halfs", "codetr_draw_font"}
+            "codetr_decoder_layer_blob_halfs", "codetr_draw_font", "codetr_track_state_bytes"}
 
 
 class _RecordingLib:
@@ -730,6 +734,35 @@ def frames_to_rgb(src, rows, matrix, range_, dst):
     rc = load().codetr_frames_to_rgb_u8(current_stream_ptr(dst.device), src.data_ptr(), src.numel(), N, table,
                                         int(matrix), int(range_), dst.data_ptr(), dst.numel())
     check(rc, "codetr_frames_to_rgb_u8")
+
+
+TRACK_MAX_TRACKS = 512         # CODETR_TRACK_MAX_TRACKS: track slots per stream of codetr_track_update_*
+_TRACK_BY_DTYPE = {torch.float16: "codetr_track_update_f16", torch.bfloat16: "codetr_track_update_bf16",
+                   torch.float32: "codetr_track_update_f32"}
+
+
+def track_state_bytes(max_tracks) -> int:
+    """bytes of one stream's track state (host only, no GPU); include/codetr_hip.h states the layout"""
+    n = load().codetr_track_state_bytes(int(max_tracks))
+    if n < 0:
+        check(n, "codetr_track_state_bytes")
+    return n
+
+
+def track_update(boxes, scores, labels, count, streams, state, max_tracks, thresholds, retain, tentatives, weight_iou,
+                 ids_out):
+    """boxes [N,Q,4] / scores [N,Q] in one dtype, labels [N,Q] int64, count [N] int32, N <= PREPROCESS_BATCH_MAX;
+    streams: the state index of every row; state: [S, track_state_bytes(max_tracks)] uint8 on the device; thresholds:
+    (obj high, obj low, init, match high, match low, match tentative); ids_out [N,Q] int32 (include/codetr_hip.h states
+    the rule)"""
+    CALLS["track_update"] += 1
+    N, Q = scores.shape
+    rc = getattr(load(), _TRACK_BY_DTYPE[scores.dtype])(
+        current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
+        (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
+        (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
+        ids_out.data_ptr())
+    check(rc, "codetr_track_update")
 
 
 def mask_pyramid(img_masks, shapes):

@@ -14,6 +14,7 @@ formulation of the model lives in oracle/ and is test infrastructure).
 import collections
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -957,6 +958,149 @@ def frames_to_rgb(src_u8, rows10, dst_bytes, matrix="bt601", range="limited", ou
             _cabi.frames_to_rgb(src_u8, rows[i:i + PREPROCESS_BATCH_MAX], _cabi.COLOR_MATRICES[matrix],
                                 _cabi.COLOR_RANGES[range], dst)
     return dst
+
+
+TRACK_MAX_TRACKS = _cabi.TRACK_MAX_TRACKS
+# this build's defaults: mmdet's ByteTracker config values as recalled (unpinned: mmdet is not installed here); max_tracks
+# is this build's own
+TRACKER = dict(obj_score_thrs=dict(high=0.6, low=0.1), init_track_thr=0.7, weight_iou_with_det_scores=True,
+               match_iou_thrs=dict(high=0.1, low=0.5, tentative=0.3), num_frames_retain=30, num_tentatives=3,
+               max_tracks=256)
+TrackState = collections.namedtuple("TrackState", "f next_id refused id label hits tentative last mean cov")
+
+
+def track_settings(settings=None):
+    """the settings of track_update, validated and completed from TRACKER (a partial obj_score_thrs / match_iou_thrs
+    dict keeps the other defaults) -> a new dict.  ValueError for an unknown key, a threshold that is not a finite
+    number, obj_score_thrs.low > high, num_frames_retain or num_tentatives < 1 or not an integer, max_tracks outside
+    1..TRACK_MAX_TRACKS."""
+    out = {k: dict(v) if isinstance(v, dict) else v for k, v in TRACKER.items()}
+    settings = dict(settings or {})
+    unknown = set(settings) - set(out)
+    if unknown:
+        raise ValueError(f"tracker: unknown key(s) {sorted(unknown)}; known: {sorted(out)}")
+
+    def number(name, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"tracker {name} must be a finite number, got {v!r}")
+        return float(v)
+
+    for key in ("obj_score_thrs", "match_iou_thrs"):
+        if key in settings:
+            given = settings[key]
+            if not isinstance(given, dict) or set(given) - set(out[key]):
+                raise ValueError(f"tracker {key}: a dict with keys of {sorted(out[key])}")
+            out[key].update(given)
+        out[key] = {k: number(f"{key}.{k}", v) for k, v in out[key].items()}
+    if out["obj_score_thrs"]["low"] > out["obj_score_thrs"]["high"]:
+        raise ValueError("tracker obj_score_thrs: low must not exceed high")
+    out["init_track_thr"] = number("init_track_thr", settings.get("init_track_thr", out["init_track_thr"]))
+    out["weight_iou_with_det_scores"] = bool(settings.get("weight_iou_with_det_scores", out["weight_iou_with_det_scores"]))
+    for key, hi in (("num_frames_retain", 2 ** 31 - 1), ("num_tentatives", 2 ** 31 - 1), ("max_tracks", TRACK_MAX_TRACKS)):
+        v = settings.get(key, out[key])
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= hi:
+            raise ValueError(f"tracker {key} must be an integer in 1..{hi}, got {v!r}")
+        out[key] = v
+    return out
+
+
+def new_track_state(S, max_tracks, device):
+    """the states of S fresh streams of max_tracks slots each: zeros [S, 16 + 104 max_tracks] uint8 on `device`
+    (include/codetr_hip.h states the layout; track_state_to_host decodes it)"""
+    if int(S) < 1:
+        raise ValueError(f"new_track_state: at least one stream, got {S}")
+    if not 1 <= int(max_tracks) <= TRACK_MAX_TRACKS:
+        raise ValueError(f"new_track_state: max_tracks in 1..{TRACK_MAX_TRACKS}, got {max_tracks}")
+    return torch.zeros((int(S), _cabi.track_state_bytes(max_tracks)), dtype=torch.uint8, device=device)
+
+
+def _track_slots(state):
+    if not torch.is_tensor(state) or state.dtype != torch.uint8 or state.dim() != 2 or not state.is_contiguous() or \
+            state.shape[0] < 1 or state.shape[1] < 120 or (state.shape[1] - 16) % 104:
+        raise ValueError("track state: a contiguous [S, 16 + 104 max_tracks] uint8 tensor (new_track_state)")
+    return (state.shape[1] - 16) // 104
+
+
+def track_state_to_host(state):
+    """the states of new_track_state / track_update decoded on the host (one device-to-host copy) -> TrackState of numpy
+    arrays: f, next_id, refused [S]; id, hits, tentative, last (int32) and label (int64) [S, T]; mean [S, T, 4, 2] (p, v of
+    cx, cy, a, h) and cov [S, T, 4, 3] (A, B, C) float32"""
+    T = _track_slots(state)
+    raw = state.cpu().numpy()
+    S = raw.shape[0]
+    hdr = raw[:, :16].copy().view(np.int32)
+    o = 16
+    label = raw[:, o:o + 8 * T].copy().view(np.int64)
+    o += 8 * T
+    ints = raw[:, o:o + 16 * T].copy().view(np.int32).reshape(S, 4, T)
+    o += 16 * T
+    mean = raw[:, o:o + 32 * T].copy().view(np.float32).reshape(S, 4, 2, T).transpose(0, 3, 1, 2).copy()
+    o += 32 * T
+    cov = raw[:, o:o + 48 * T].copy().view(np.float32).reshape(S, 4, 3, T).transpose(0, 3, 1, 2).copy()
+    return TrackState(hdr[:, 0].copy(), hdr[:, 1] + 1, hdr[:, 2].copy(), ints[:, 0].copy(), label, ints[:, 1].copy(),
+                      ints[:, 2].copy(), ints[:, 3].copy(), mean, cov)
+
+
+def track_update(dets, state, streams=None, settings=None):
+    """Tracking-by-detection for the frames of a chunk in one launch per PREPROCESS_BATCH_MAX rows (csrc/track.hip; the
+    rule, modelled on mmdet's ByteTracker, is stated in include/codetr_hip.h): the three greedy associations, the Kalman
+    filters, retirement and track starts of every stream on the device.
+      dets      Detections / SoftDetections over [N, Q] rows, Q <= 1024: whatever the chunk's last launch produced
+      state     new_track_state's tensor, updated in place; it stays on the device between calls
+      streams   the state index in [0, S) of every row: one int for all rows, or one per row; None: 0.  The rows of a
+                stream are its consecutive frames in row order (and from call to call)
+      settings  the keys of TRACKER (track_settings); max_tracks must be the state's
+    -> [N, Q] int32 on the device: the id of the track each row updated or started, negated while the track is
+    tentative, 0 for no track and beyond count."""
+    cfg = track_settings(settings)
+    scores = dets.scores
+    _gpu(scores, "track_update")
+    T = _track_slots(state)
+    if state.device != scores.device:
+        raise ValueError("track_update: the state lives on another device than the detections")
+    if settings is not None and "max_tracks" in settings and cfg["max_tracks"] != T:
+        raise ValueError(f"track_update: max_tracks {cfg['max_tracks']} but the state has {T} slots")
+    if scores.dtype not in (torch.float16, torch.bfloat16, torch.float32) or dets.boxes.dtype != scores.dtype:
+        raise ValueError("track_update: detections in f16, bf16 or f32")
+    if scores.dim() != 2 or tuple(dets.boxes.shape) != tuple(scores.shape) + (4,):
+        raise ValueError("track_update: boxes [N,Q,4], scores [N,Q], labels [N,Q], count [N]")
+    N, Q = scores.shape
+    streams = track_streams(streams, N)
+    if any(v >= state.shape[0] for v in streams):
+        raise ValueError(f"track_update: a stream index outside the state's {state.shape[0]} streams")
+    if Q > _cabi.POSTPROCESS_MAX_Q:
+        raise ValueError(f"track_update: at most {_cabi.POSTPROCESS_MAX_Q} detection rows per frame, got {Q}")
+    ids = torch.zeros((N, Q), dtype=torch.int32, device=scores.device) if N == 0 or Q == 0 else \
+        torch.empty((N, Q), dtype=torch.int32, device=scores.device)
+    if N == 0 or Q == 0:
+        return ids
+    boxes, scores = dets.boxes.contiguous(), scores.contiguous()
+    labels, count = dets.labels.contiguous(), dets.count.contiguous()
+    thr = (cfg["obj_score_thrs"]["high"], cfg["obj_score_thrs"]["low"], cfg["init_track_thr"],
+           cfg["match_iou_thrs"]["high"], cfg["match_iou_thrs"]["low"], cfg["match_iou_thrs"]["tentative"])
+    with torch.cuda.device(scores.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            _cabi.track_update(boxes[i:j], scores[i:j], labels[i:j], count[i:j], streams[i:j], state, T, thr,
+                               cfg["num_frames_retain"], cfg["num_tentatives"], cfg["weight_iou_with_det_scores"], ids[i:j])
+    return ids
+
+
+def track_streams(streams, N):
+    """the `streams` argument of track_update and Inferencer.__call__ -> a list of N non-negative ints: None is stream 0
+    for every row, one int is that stream for every row; ValueError for anything else"""
+    def one(v):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError(f"streams: non-negative integers, got {v!r}")
+        return int(v)
+
+    if streams is None:
+        return [0] * N
+    if isinstance(streams, (int, np.integer)):
+        return [one(streams)] * N
+    if not isinstance(streams, (list, tuple, np.ndarray)) or len(streams) != N:
+        raise ValueError(f"streams: one non-negative integer, or one per frame ({N})")
+    return [one(v) for v in streams]
 
 
 def mask_pyramid(img_masks, shapes):

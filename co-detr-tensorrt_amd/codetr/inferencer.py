@@ -86,6 +86,21 @@ RGB buffer every other kernel reads; GPU-resident frames -- pitched views of a d
 uploaded at all: one launch per group of frames that share a storage reads them where they lie.  The visualisation draws
 on, and returns, the converted RGB frames.  The conversion is stated in integer arithmetic in ``include/codetr_hip.h``;
 parity with OpenCV's ``cvtColor`` is unpinned (cv2 is not installed here).
+
+``tracker`` (beyond the reference; tracking-by-detection modelled on mmdet's ``ByteTracker``): ``None``, the default,
+changes nothing -- no new key, no new launch, the per-image route as it is.  A dict with any of the keys of
+``hip_ops.TRACKER`` (``obj_score_thrs``, ``init_track_thr``, ``weight_iou_with_det_scores``, ``match_iou_thrs``,
+``num_frames_retain``, ``num_tentatives``, ``max_tracks``) -- or ``"config"``, which reads a ``tracker`` entry of the config
+-- turns it on: every result dict gains ``"track_ids"``, one int per detection: the id of its track, negated while the
+track is tentative, 0 for none.  ``__call__(..., streams=...)`` names the stream (camera) of every frame, one
+non-negative int or one per frame, default 0; the frames of a stream are in temporal order within and across calls, a
+stream's state is created on its first frame and ``reset_tracks(stream=None)`` zeroes one or all.  A tracked call takes
+the chunked path; after the chunk's final detections one ``hip_ops.track_update`` launch (one workgroup per stream, the
+stream's frames walked in order) and one more device-to-host copy of ``[N, Q]`` int32; the states stay on the device.
+The ids are cut as the detections are, the hard path's host-side ``max_per_img`` cut included (the tracker itself
+sees every row of the launch's result).  The rule is stated in
+``include/codetr_hip.h``; parity with mmdet is unpinned (it is not installed here): the association is greedy, labels
+are compared and ties go to the lowest slot and row.
 """
 import collections
 import colorsys
@@ -221,6 +236,24 @@ def slicing_settings(slicing):
     return dict(tile=(int(tile[0]), int(tile[1])), overlap=(float(overlap[0]), float(overlap[1])),
                 full_image=bool(slicing.get("full_image", True)), merge=hip_ops.slice_merge_settings(slicing.get("merge")),
                 max_per_img=int(mpi) if mpi is not None and mpi > 0 else None, tile_batch=int(tile_batch))
+
+
+def tracker_settings(tracker, cfg=None):
+    """How `Inferencer(..., tracker=...)` reads its argument: None -> None; a dict with keys of hip_ops.TRACKER is
+    validated and completed from it (hip_ops.track_settings: ValueError for an unknown key or a value out of range);
+    "config" takes the `tracker` entry of the config `cfg` (its `type` key dropped; ValueError when the config has
+    none)."""
+    if tracker is None:
+        return None
+    if isinstance(tracker, str):
+        entry = cfg.get("tracker") if tracker == "config" and cfg is not None else None
+        if entry is None:
+            raise ValueError("tracker='config': the config has no tracker entry" if tracker == "config"
+                             else f"tracker must be None, 'config' or a dict, got {tracker!r}")
+        tracker = {k: v for k, v in dict(entry).items() if k != "type"}
+    if not isinstance(tracker, dict):
+        raise ValueError(f"tracker must be None, 'config' or a dict with keys of {sorted(hip_ops.TRACKER)}")
+    return hip_ops.track_settings(tracker)
 
 
 FRAME_COLOR_KEYS = ("matrix", "range")
@@ -410,7 +443,7 @@ def write_png(path, image):
 class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
-                 slicing=None):
+                 slicing=None, tracker=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -459,6 +492,9 @@ class Inferencer:
             raise NotImplementedError("slicing together with tta is not built: one or the other")
         self.visualizer = visualizer_settings(self.cfg, visualizer, dataset_meta)
         self._vis_tables = {}   # device -> (names, colors) on it: uploaded on the first visualising call there
+        self.tracker = tracker_settings(tracker, self.cfg)
+        self._track_state = None   # [rows, state bytes] uint8 on the device of the first tracked call
+        self._track_rows = {}      # stream -> its row of _track_state
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -852,6 +888,32 @@ class Inferencer:
                         "bboxes": host.boxes[i, :c].float().tolist()})
         return out, src, staged, dets
 
+    # ---- tracking ---------------------------------------------------------------------------------------------
+    def reset_tracks(self, stream=None):
+        """forget the tracks of one stream, or of all (None): its state is zeroed, ids start at 1 again"""
+        if stream is None:
+            self._track_state, self._track_rows = None, {}
+        elif hip_ops.track_streams(stream, 1)[0] in self._track_rows:
+            self._track_state[self._track_rows[int(stream)]].zero_()
+
+    def track_chunk(self, dets, streams):
+        """the track ids of a chunk's final detections: one hip_ops.track_update launch on the states kept on the device
+        and one device-to-host copy -> [N, Q] int32 numpy.  A stream's state is created on its first frame."""
+        dev = dets.scores.device
+        T = self.tracker["max_tracks"]
+        if self._track_state is not None and self._track_state.device != dev:
+            raise ValueError(f"the track states live on {self._track_state.device}: reset_tracks() before a call on {dev}")
+        for s in streams:
+            self._track_rows.setdefault(s, len(self._track_rows))
+        have = 0 if self._track_state is None else self._track_state.shape[0]
+        if len(self._track_rows) > have:   # (grows by doubling: a new camera is rare)
+            grown = hip_ops.new_track_state(max(len(self._track_rows), 2 * have), T, dev)
+            if have:
+                grown[:have].copy_(self._track_state)
+            self._track_state = grown
+        ids = hip_ops.track_update(dets, self._track_state, [self._track_rows[s] for s in streams], self.tracker)
+        return ids.cpu().numpy()
+
     # ---- visualisation and files --------------------------------------------------------------------------
     def draw_chunk(self, src, rows, dets, pred_score_thr):
         """the chunk's predictions drawn on its uploaded images: one hip_ops.draw_detections launch on the buffer the
@@ -885,7 +947,7 @@ class Inferencer:
                  no_save_vis: bool = False, draw_pred: bool = True, pred_score_thr: float = 0.3,
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
-                 batch_size: int = 1, input_format: str = "rgb", color=None) -> Dict:
+                 batch_size: int = 1, input_format: str = "rgb", color=None, streams=None) -> Dict:
         if show or return_datasamples or (return_vis and self.visualizer is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
@@ -896,8 +958,12 @@ class Inferencer:
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
         visualise = self.visualizer is not None and (return_vis or save_vis)
+        if self.tracker is not None:
+            streams = hip_ops.track_streams(streams, len(images))
+        elif streams is not None:
+            raise ValueError("streams without a tracker: Inferencer(..., tracker=dict(...)) turns tracking on")
         if (batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None and self.slicing is None
-                and not visualise and plain):
+                and not visualise and plain and self.tracker is None):
             for image in images:
                 with torch.no_grad():
                     x, m, meta = self.preprocess(image, device, dtype)
@@ -920,6 +986,10 @@ class Inferencer:
                 else:
                     x, m, metas, src, rows = self._preprocess_chunk(chunk, device, dtype, frames)
                     preds, dets = self._postprocess_chunk(self.model(x, m), metas)
+                if self.tracker is not None:   # the ids of the rows the predictions kept (a host-side cut included)
+                    ids = self.track_chunk(dets, streams[start:start + batch_size])
+                    for pred, row in zip(preds, ids):
+                        pred["track_ids"] = row[:len(pred["labels"])].tolist()
                 drawn = [None] * len(chunk)
                 if visualise and draw_pred:
                     drawn = self.draw_chunk(src, rows, dets, pred_score_thr)

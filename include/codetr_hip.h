@@ -1091,6 +1091,99 @@ int codetr_frames_to_rgb_u8(void *stream, const void *src_dev, int64_t src_bytes
                             const int64_t *frames_host, int matrix, int range, void *dst_dev, int64_t dst_bytes);
 
 /* ------------------------------------------------------------------------------------------
+ * Tracking: track ids for the detections of consecutive frames, association and Kalman filtering in one launch per chunk,
+ * the state of every stream (camera) kept on the device.  Beyond the reference, whose Inferencer treats every image as
+ * unrelated.  The rule is modelled on mmdet 3.x ByteTracker with its KalmanFilter and is this library's own where stated;
+ * parity with mmdet is unpinned (mmdet is not installed where this is tested): the text below is the contract.
+ *
+ * codetr_track_update_{f16,bf16,f32}: N <= CODETR_PREPROCESS_BATCH_MAX rows (frames) of Q <= CODETR_POSTPROCESS_MAX_Q
+ * detections, exactly the (boxes [N,Q,4], scores [N,Q], labels [N,Q] int64, count [N] int32) a
+ * codetr_postprocess_detections_* / _softnms_* / codetr_tta_merge_* / codetr_slice_merge_* launch wrote.
+ *     stream_of_row_host  HOST [N] int: the stream s in [0, S) every row belongs to.  The rows of one stream are its
+ *                         consecutive frames in row order; they are walked in that order inside the one launch (one
+ *                         workgroup per stream).  The table travels in the kernel arguments: no staging copy, capturable.
+ *     state_dev           [S] states of codetr_track_state_bytes(max_tracks) bytes each, read and written back once per
+ *                         launch; the state of a stream without a row is not touched.  A zero-filled state is a fresh
+ *                         stream.  8-byte aligned.
+ *     settings_host       HOST [6] float: obj_score_thrs.high, obj_score_thrs.low, init_track_thr, match_iou_thrs.high,
+ *                         match_iou_thrs.low, match_iou_thrs.tentative
+ *     retain, tentatives  num_frames_retain, num_tentatives (>= 1); weight_iou: weight_iou_with_det_scores (0 / 1)
+ *     track_id_out_dev    [N, Q] int32, every element written: the id of the track a row updated or started, negated
+ *                         while that track is tentative, 0 for no track and for rows >= count[n]
+ *   This build's defaults (mmdet's ByteTracker config values as recalled; they cannot be checked where mmdet is absent):
+ *   obj_score_thrs high 0.6 low 0.1, init_track_thr 0.7, weight_iou_with_det_scores on, match_iou_thrs high 0.1 low 0.5
+ *   tentative 0.3, num_frames_retain 30, num_tentatives 3; max_tracks 256 is this build's own.
+ *
+ *   State of a stream with T = max_tracks slots, 16 + 104 T bytes, a struct of arrays in this order:
+ *       int32 f, issued, refused, 0      the frame counter, the ids given out so far (next_id = issued + 1: ids start at
+ *                                        1), the track starts refused for lack of a free slot
+ *       int64 label[T]
+ *       int32 id[T]                      0: the slot is free, and then every other field of the slot is 0
+ *       int32 hits[T], tentative[T], last[T]     frames matched, 1 while tentative, the frame of the last match
+ *       float mean[8][T]                 row 2 c + i: coordinate c of (cx, cy, a = w / h, h), i = 0 position p, 1 velocity v
+ *       float cov[12][T]                 row 3 c + i: coordinate c, i = 0, 1, 2 the A, B, C of its covariance [[A, B], [B, C]]
+ *
+ *   Arithmetic: fp32, one rounding per operation in the order written (nothing is contracted into an FMA), divisions are
+ *   IEEE.  Boxes and scores are widened to fp32 exactly.  wp = 1.0f / 20.0f, wv = 1.0f / 160.0f.
+ *   The filter: mmdet's 8x8 Kalman filter has diagonal noise and initial covariance and a constant-velocity transition,
+ *   so it is exactly four independent two-state filters, one per coordinate.  For coordinate c at height h the position
+ *   standard deviation is s_p = wp * h (c = a: 1e-2f), the velocity standard deviation s_v = wv * h (a: 1e-5f).
+ *     initiate from z = (cx, cy, a, h):  p = z_c, v = 0, B = 0;  t = 2.0f * (wp * z_h), A = t * t;
+ *                         u = 10.0f * (wv * z_h), C = u * u;  for a: A = 1e-2f * 1e-2f, C = 1e-5f * 1e-5f
+ *     predict (h = the p of coordinate h before the step, the same h for all four coordinates):
+ *                         p' = p + v;  A' = ((A + 2.0f * B) + C) + s_p * s_p;  B' = B + C;  C' = C + s_v * s_v
+ *     update with z (h = the predicted p of coordinate h, read before any coordinate is updated): r = s_p * s_p
+ *                         (a: 1e-1f * 1e-1f);  S = A + r;  k0 = A / S;  k1 = B / S;  y = z_c - p;
+ *                         p' = p + k0 * y;  v' = v + k1 * y;  A' = A - k0 * A;  B' = B - k0 * B;  C' = C - k1 * B
+ *   A detection's measurement: cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f, h = y2 - y1, a = (x2 - x1) / h.
+ *   A track's box: w = a * h, hw = w * 0.5f, hh = h * 0.5f, (cx - hw, cy - hh, cx + hw, cy + hh) of the predicted mean.
+ *   Overlap of a track's box k and a candidate c: the IoU of the soft-NMS kernel above -- area = (x2 - x1) * (y2 - y1) of
+ *   the box's corners, one rounded product; iw = max(0, min(x2k, x2c) - max(x1k, x1c)), ih likewise, inter = iw * ih,
+ *   inter / ((area_k + area_c) - inter).  A NaN overlap or value compares false: the pair is not eligible.
+ *
+ *   Per frame (row) of a stream, in this order, f the stream's frame counter:
+ *   1. Candidates are rows j < clamp(count[n], 0, Q).  A row with a non-finite coordinate or score, x2 - x1 <= 0 or
+ *      y2 - y1 <= 0 takes no part and gets id 0.  `high`: score > obj high;  `low`: obj low < score <= obj high.
+ *   2. Every live track with last != f - 1 gets the v of coordinate h set to 0; then every live track is predicted.
+ *   3. Match A: the confirmed (not tentative) tracks, lost ones included, against the high candidates.  The value of a
+ *      pair is iou * score (one rounded product) with weight_iou, else iou; the pair is eligible when the labels are
+ *      equal (classes are told apart by comparing labels, as everywhere in this library) and value >= match high.
+ *      The matching is GREEDY: repeatedly the eligible pair of the highest value among the tracks and candidates not yet
+ *      matched is taken, ties to the lowest slot, then the lowest j.  (mmdet solves an assignment problem with `lap`;
+ *      greedy is this library's deliberate deviation, as ties and label comparison are.)
+ *   4. Match B: the tentative tracks against the high candidates still free, the same value, threshold match tentative.
+ *   5. Match C: the confirmed tracks still unmatched with last == f - 1 against the low candidates; the value is plain
+ *      iou, never weighted; threshold match low.
+ *   6. Every matched track: the filter update with its candidate's measurement; last = f, hits += 1, the label becomes the
+ *      candidate's; a tentative track is confirmed once hits >= num_tentatives.
+ *   7. An unmatched tentative track is freed; an unmatched confirmed track with f - last >= num_frames_retain is freed.
+ *   8. The free high candidates with score > init_track_thr start tracks, in ascending j, each in the lowest free slot
+ *      (slots freed in step 7 included): id = ++issued, hits = 1, last = f, the candidate's label, the filter initiated
+ *      from its measurement; confirmed when f == 0, tentative otherwise.  Without a free slot the candidate gets id 0 and
+ *      `refused` goes up by one.
+ *   9. Output as described at track_id_out_dev (the track's state after this frame decides the sign); then f += 1.
+ *
+ * codetr_track_state_bytes: host only; 16 + 104 max_tracks, CODETR_E_BADARG outside [1, CODETR_TRACK_MAX_TRACKS].
+ * CODETR_E_BADARG for a null pointer, N, Q, S or max_tracks <= 0, a stream index outside [0, S), a setting that is not
+ * finite, retain or tentatives < 1; CODETR_E_TOO_LARGE for N > CODETR_PREPROCESS_BATCH_MAX, Q > CODETR_POSTPROCESS_MAX_Q
+ * or max_tracks > CODETR_TRACK_MAX_TRACKS.  All checks run before any HIP call.
+ * ------------------------------------------------------------------------------------------ */
+#define CODETR_TRACK_MAX_TRACKS 512
+int64_t codetr_track_state_bytes(int64_t max_tracks);
+int codetr_track_update_f16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                            const int *count_dev, int64_t N, int64_t Q, const int *stream_of_row_host, int64_t S,
+                            void *state_dev, int64_t max_tracks, const float *settings_host, int64_t retain,
+                            int64_t tentatives, int weight_iou, int *track_id_out_dev);
+int codetr_track_update_bf16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                             const int *count_dev, int64_t N, int64_t Q, const int *stream_of_row_host, int64_t S,
+                             void *state_dev, int64_t max_tracks, const float *settings_host, int64_t retain,
+                             int64_t tentatives, int weight_iou, int *track_id_out_dev);
+int codetr_track_update_f32(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                            const int *count_dev, int64_t N, int64_t Q, const int *stream_of_row_host, int64_t S,
+                            void *state_dev, int64_t max_tracks, const float *settings_host, int64_t retain,
+                            int64_t tentatives, int weight_iou, int *track_id_out_dev);
+
+/* ------------------------------------------------------------------------------------------
  * Backward of multi-scale deformable attention (training path).
  *
  * Replaces ms_deformable_col2im_cuda<T> / ms_deform_attn_backward (codetr/csrc/ms_deform_attn.cu:781-897, 975-1028;

@@ -43,8 +43,15 @@ the Inferencer at batch_size 8 over --images frames of 1920x1080 fed as host fra
 as GPU-resident tensors, and as host RGB arrays converted beforehand (the conversion is not timed: the fairest thing
 the RGB-only route can do), the three in turn, three times.
 
+`--track` prints only a `track` record (tracking, fp16): track_update_kernel alone on 300 detection rows of which 100 are
+moving objects -- HIP event pairs as above, 8 frames of one stream in a launch and one frame of each of 8 streams --;
+and images/s of the Inferencer at batch_size 8 over --images images taken as the frames of one stream with
+`tracker={}`, without a tracker, and with the host composition the tracker replaces (the untracked call's predictions
+through tests/track_ref.py frame by frame, the state on the host), the three in turn, three times.
+
     python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis] [--slice]   -> one JSON line
     python tools/bench_inferencer.py --frames nv12 --resident
+    python tools/bench_inferencer.py --track
 """
 import argparse
 import csv
@@ -457,6 +464,99 @@ def frames_record(inf, fmt, n_images, repeats, resident, bs=8):
     return rec
 
 
+def track_detections(frames, Q=300, objects=100, seed=5):
+    """`frames` frames of Q fp16 detection rows: `objects` boxes on slow straight paths with jitter (score 0.75..0.95, five
+    labels), the other rows clutter of score 0.15..0.55 -> hip_ops.Detections on the device"""
+    from codetr import hip_ops
+
+    rng = np.random.default_rng(seed)
+    c0, wh = rng.uniform(60, 1800, (objects, 2)), rng.uniform(40, 120, (objects, 2))
+    v = rng.uniform(-1.5, 1.5, (objects, 2))
+    boxes, scores = np.zeros((frames, Q, 4), np.float32), np.zeros((frames, Q), np.float32)
+    for f in range(frames):
+        c = c0 + v * f + rng.uniform(-1, 1, (objects, 2))
+        boxes[f, :objects] = np.concatenate((c - wh / 2, c + wh / 2), 1)
+        scores[f, :objects] = rng.uniform(0.75, 0.95, objects)
+        cc, cw = rng.uniform(0, 1900, (Q - objects, 2)), rng.uniform(10, 80, (Q - objects, 2))
+        boxes[f, objects:] = np.concatenate((cc, cc + cw), 1)
+        scores[f, objects:] = rng.uniform(0.15, 0.55, Q - objects)
+    labels = np.tile(np.arange(Q) % 5, (frames, 1))
+    return hip_ops.Detections(torch.tensor(boxes).half().to(DEV), torch.tensor(scores).half().to(DEV),
+                              torch.tensor(labels).to(DEV), torch.full((frames,), Q, dtype=torch.int32, device=DEV), None)
+
+
+def track_kernel_times(Q=300, objects=100):
+    """us per launch of track_update_kernel: 8 frames of one stream, and one frame of each of 8 streams; the states hold
+    about `objects` live tracks (8 frames are walked before the clock starts)"""
+    from codetr import hip_ops
+
+    dets = track_detections(8, Q, objects)
+    rec = {"Q": Q, "objects": objects}
+    for name, streams in (("8_frames_of_1_stream", [0] * 8), ("1_frame_of_8_streams", list(range(8)))):
+        state = hip_ops.new_track_state(8, hip_ops.TRACKER["max_tracks"], DEV)
+        for _ in range(8 if len(set(streams)) > 1 else 1):
+            hip_ops.track_update(dets, state, streams)
+        us = _event_us_each(lambda: hip_ops.track_update(dets, state, streams), launches=100, warmup=5)
+        host = hip_ops.track_state_to_host(state)
+        rec[name] = {"us_per_launch_median": us, "live_tracks_per_stream": int((host.id[0] != 0).sum())}
+    return rec
+
+
+def track_record(inf, images, repeats, bs=8):
+    """images/s of the Inferencer on `images` as one stream: with the tracker, without it, and with the host composition
+    the tracker replaces -- the untracked call's predictions through tests/track_ref.py frame by frame, state on the host"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import track_ref
+    from codetr.inferencer import Inferencer
+
+    tracked = Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={})
+    rec = {"batch_size": bs, "images": len(images), "repeats": repeats, "dtype": "fp16", "kernel": track_kernel_times()}
+    host_ref = [None]
+
+    def with_tracker():
+        tracked.reset_tracks()
+        return tracked(images, device=DEV, dtype=torch.float16, batch_size=bs)["predictions"]
+
+    def without():
+        return inf(images, device=DEV, dtype=torch.float16, batch_size=bs)["predictions"]
+
+    def host_composition():
+        host_ref[0] = ref = track_ref.TrackRef()
+        preds = without()
+        for p in preds:
+            n = len(p["labels"])
+            p["track_ids"] = ref.update(np.asarray(p["bboxes"], np.float32).reshape(n, 4), np.asarray(p["scores"], np.float32),
+                                        np.asarray(p["labels"], np.int64)).tolist()
+        return preds
+
+    arms = {"with_tracker": with_tracker, "without_tracker": without, "host_composition": host_composition}
+    for name in arms:
+        rec[name] = {"pass_s": []}
+    with torch.no_grad():
+        got = {name: call() for name, call in arms.items()}                                   # warm-up
+        rec["ids_equal_host_composition"] = [p["track_ids"] for p in got["with_tracker"]] == \
+            [p["track_ids"] for p in got["host_composition"]]
+        rec["detections_per_image"] = round(float(np.mean([len(p["labels"]) for p in got["without_tracker"]])), 1)
+        rec["tracks_started"] = int(host_ref[0].state().next_id - 1)
+        for _ in range(3):                                                                    # the arms in turn
+            for name, call in arms.items():
+                for _ in range(repeats):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    call()
+                    rec[name]["pass_s"].append(round(time.perf_counter() - t0, 4))
+    for name in arms:
+        rec[name]["images_per_s"] = round(len(images) / min(rec[name]["pass_s"]), 2)
+        rec[name]["images_per_s_median"] = round(len(images) / float(np.median(rec[name]["pass_s"])), 2)
+    return rec
+
+
+def bench_cfg():
+    import bench
+
+    return bench.CFG
+
+
 def soft_inferencer(inf):
     """the same model behind the post-processing its config specifies (soft-NMS, max_per_img)"""
     import bench
@@ -534,6 +634,7 @@ def main():
     ap.add_argument("--slice-only", action="store_true", help="only the slice sub-record (implies --slice)")
     ap.add_argument("--frames", choices=("nv12", "i420", "bgr"), help="only the frames record, for frames of this format")
     ap.add_argument("--resident", action="store_true", help="with --frames: also feed the frames as GPU-resident tensors")
+    ap.add_argument("--track", action="store_true", help="only the tracking record: the images as one stream")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -549,6 +650,11 @@ def main():
         print(json.dumps({"metric": "Inferencer on decoder frames (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the kernel",
                           "frames": frames_record(infs["fp16"], a.frames, a.images, a.repeats, a.resident)}))
+        return
+    if a.track:
+        print(json.dumps({"metric": "Inferencer tracking (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the kernel",
+                          "track": track_record(infs["fp16"], images, a.repeats)}))
         return
     if a.tta_only:
         print(json.dumps({"metric": "Inferencer test-time augmentation (Swin-L config, random weights)",
