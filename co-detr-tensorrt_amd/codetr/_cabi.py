@@ -1,6 +1,8 @@
 """ctypes binding of libcodetr_hip.so (C ABI: include/codetr_hip.h).
 
-This is the only place the Python host crosses into native code.  The library is built
+This is the only place the Python host crosses into native code.  The header is the one written copy of the ABI:
+the signature table, the launch / query split and every CODETR_* constant below are read from it (codetr/_cheader.py),
+so a new entry point needs its declaration there and its wrapper here, nothing in between.  The library is built
 in-tree next to this file (``make -C co-detr-tensorrt_amd/csrc`` or ``__graft_entry__.build()``)
 and, like the reference's ``codetr/__init__.py:8-12`` does for its CUDA extension, a missing
 ``.so`` is an ImportError -- there is no CPU or PyTorch fallback behind these calls.
@@ -10,202 +12,27 @@ import os
 
 import torch
 
+from . import _cheader
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libcodetr_hip.so")
-ABI_VERSION = 54
+_D = _cheader.defines
+ABI_VERSION = _D["CODETR_HIP_ABI_VERSION"]
+E_IM2COL_STEP = _D["CODETR_E_IM2COL_STEP"]
+E_UNSUPPORTED = _D["CODETR_E_UNSUPPORTED"]
 
 _i64, _i32, _vp, _cp = ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_char_p
+_CTYPE = {"p": _vp, "i": _i32, "l": _i64, "u": ctypes.c_uint32, "f": ctypes.c_float, "s": _cp}
 
-# name -> (restype, argtypes); mirrors include/codetr_hip.h line by line
-_MSDA_ARGS = [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i32, _i64, _vp]
-SIGNATURES = {
-    "codetr_hip_abi_version": (_i32, []),
-    "codetr_hip_strerror": (_cp, [_i32]),
-    "codetr_msda_forward_f16": (_i32, _MSDA_ARGS),
-    "codetr_msda_forward_bf16": (_i32, _MSDA_ARGS),
-    "codetr_msda_forward_f32": (_i32, _MSDA_ARGS),
-    "codetr_msda_forward_f64": (_i32, _MSDA_ARGS),
-    "codetr_msda_backward_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i32, _i64,
-                                        _vp, _vp, _vp]),
-    "codetr_msda_backward_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i32, _i64,
-                                        _vp, _vp, _vp]),
-    "codetr_msda_backward_f64": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i32, _i64,
-                                        _vp, _vp, _vp]),
-    "codetr_msda_variant": (_cp, [_i32, _i32, _i32, _i32, _i32]),
-    "codetr_msda_fused_forward_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _i64,
-                                             _i32, _i32, _i32, _i64, _i32, _vp]),
-    "codetr_msda_fused_forward_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _i64,
-                                              _i32, _i32, _i32, _i64, _i32, _vp]),
-    "codetr_msda_fused_forward_ref32_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _i64,
-                                                   _i32, _i32, _i32, _i64, _i32, _vp]),
-    "codetr_msda_fused_forward_ref32_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i64, _i64,
-                                                    _i32, _i32, _i32, _i64, _i32, _vp]),
-    "codetr_msda_encoder_forward_packed_f16": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
-                                                      _vp, _i32, _i32, _i32, _i32, _vp]),
-    "codetr_msda_encoder_forward_packed_bf16": (_i32, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32,
-                                                       _vp, _i32, _i32, _i32, _i32, _vp]),
-    "codetr_linear_bf16_f16out": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32]),
-    "codetr_encoder_projections_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32]),
-    "codetr_encoder_projections_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32]),
-    "codetr_encoder_projections_posgen_f16": (_i32, [_vp, _vp] + [_vp] * 10 + [_vp, _i32, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                              ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32]),
-    "codetr_encoder_projections_posgen_bf16": (_i32, [_vp, _vp] + [_vp] * 10 + [_vp, _i32, _vp, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                                              ctypes.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i32]),
-    "codetr_msda_encoder_packed_lds_bytes": (_i64, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32]),
-    "codetr_msda_pack_projection_index": (_i32, [_i32, _i32, _i32, _vp]),
-    "codetr_mx_scale_bytes": (_i64, [_i64, _i64]),
-    "codetr_linear_fp8mx": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32]),
-    "codetr_cast_fp8mx_f16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64]),
-    "codetr_layernorm_fp8mx_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float]),
-    "codetr_window_attention_fp8mx_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32]),
-    "codetr_mha_attention_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i64, _i64, _i64, _i64]),
-    "codetr_mha_attention_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i64, _i64, _i64, _i64]),
-    "codetr_linear_ln_f16": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _i64, _i32]),
-    "codetr_linear_ln_bf16": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _i64, _i64, _i64, _i32]),
-    "codetr_linear_xadd_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64]),
-    "codetr_linear_xadd_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64]),
-    "codetr_im2col_tokens_b16": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp]),
-    "codetr_conv_tokens_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32]),
-    "codetr_conv_tokens_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32]),
-    "codetr_conv_im2col_nchw_b16": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "codetr_maxpool_tokens_b16": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "codetr_topk_chunks": (_i64, [_i64, _i32, _i64, _vp]),
-    "codetr_topk_chunked_f16": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64]),
-    "codetr_topk_chunked_bf16": (_i32, [_vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i64]),
-    "codetr_topk_f16": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
-    "codetr_topk_bf16": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
-    "codetr_patch_im2col_b16": (_i32, [_vp, _vp, _i64, _i32, _i64, _i64, _i32, _i32, _vp]),
-    "codetr_linear_variant": (_cp, [_i64, _i64, _i64, _i32, _i32, _i32]),
-    "codetr_add_f16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64]),
-    "codetr_add_bf16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64]),
-    "codetr_sigmoid_f16": (_i32, [_vp, _vp, _vp, _i64]),
-    "codetr_sigmoid_bf16": (_i32, [_vp, _vp, _vp, _i64]),
-    "codetr_gather_rows_b16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64]),
-    "codetr_decode_boxes_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, ctypes.c_float, ctypes.c_float]),
-    "codetr_decode_boxes_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, ctypes.c_float, ctypes.c_float]),
-    "codetr_valid_ratios_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32]),
-    "codetr_valid_ratios_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32]),
-    "codetr_linear_fp8": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _i32, ctypes.c_float, _i64, _i64, _i64,
-                                 _i32]),
-    "codetr_cast_fp8_f16": (_i32, [_vp, _vp, _vp, _i64, ctypes.c_float]),
-    "codetr_layernorm_fp8_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float, ctypes.c_float]),
-    "codetr_linear_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32]),
-    "codetr_linear_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i64, _i32]),
-    "codetr_query_sine_embed_f16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, _i32, _vp, _vp,
-                                           _vp]),
-    "codetr_query_sine_embed_bf16": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, _i32, _vp, _vp,
-                                           _vp]),
-    "codetr_encoder_geometry_f16": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_encoder_geometry_bf16": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_row_max_f16": (_i32, [_vp, _vp, _vp, _i64, _i64]),
-    "codetr_row_max_bf16": (_i32, [_vp, _vp, _vp, _i64, _i64]),
-    "codetr_preprocess_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_preprocess_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_batched_nms_f32": (_i32, [_vp, _vp, _vp, _i64, ctypes.c_float, _vp]),
-    "codetr_preprocess_batch_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_preprocess_batch_u8_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_preprocess_batch_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_postprocess_detections_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
-                                                 ctypes.c_float, _vp, _vp, _vp, _vp]),
-    "codetr_postprocess_detections_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
-                                                  ctypes.c_float, _vp, _vp, _vp, _vp]),
-    "codetr_postprocess_detections_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
-                                                 ctypes.c_float, _vp, _vp, _vp, _vp]),
-    "codetr_postprocess_softnms_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
-                                              ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_postprocess_softnms_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
-                                               ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_postprocess_softnms_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, ctypes.c_float, _i32,
-                                              ctypes.c_float, ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_preprocess_views_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_preprocess_views_u8_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_preprocess_views_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_tta_merge_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
-                                    ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_tta_merge_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
-                                     ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_tta_merge_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_uint32, _vp, _i32, ctypes.c_float,
-                                    ctypes.c_float, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_preprocess_tiles_u8_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_preprocess_tiles_u8_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_preprocess_tiles_u8_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_slice_merge_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32,
-                                      ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_slice_merge_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32,
-                                       ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_slice_merge_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32,
-                                      ctypes.c_float, _i32, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "codetr_draw_font": (_i32, [_vp]),
-    "codetr_frames_to_rgb_u8": (_i32, [_vp, _vp, _i64, _i64, _vp, _i32, _i32, _vp, _i64]),
-    "codetr_track_state_bytes": (_i64, [_i64]),
-    "codetr_track_update_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
-    "codetr_track_update_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
-    "codetr_track_update_f32": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
-    "codetr_draw_detections_f16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
-                                          ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
-    "codetr_draw_detections_bf16": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
-                                           ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
-    "codetr_draw_detections_f32": (_i32, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32,
-                                          ctypes.c_float, ctypes.c_float, ctypes.c_uint32, _i32, _i32]),
-    "codetr_patch_merge_layernorm_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
-    "codetr_patch_merge_layernorm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_float]),
-    "codetr_mask_pyramid": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i32]),
-    "codetr_linear_splitk_plan": (_i32, [_i64, _i64, _i64, _vp]),
-    "codetr_linear_splitk_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64]),
-    "codetr_linear_splitk_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64]),
-    "codetr_linear_sk_workspace_bytes": (_i64, []),
-    "codetr_linear_sk_supported": (_i32, [_i64, _i64, _i64]),
-    "codetr_linear_sk_preferred": (_i32, [_i64, _i64, _i64, _i32, _i32]),
-    "codetr_linear_sk_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i32]),
-    "codetr_msda_op4_supported": (_i32, [_i32, _i64, _i64, _i32, _i32, _i32, _i64, _i32]),
-    "codetr_msda_op4_forward_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i32, _vp]),
-    "codetr_msda_op4_forward_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i64, _i32, _vp]),
-    "codetr_swin_mlp_supported": (_i32, [_i64, _i64, _i64]),
-    "codetr_swin_mlp_f16": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
-    "codetr_swin_mlp_bf16": (_i32, [_vp, _vp, _vp, _vp, ctypes.c_float, _vp, _vp, _vp, _vp, _vp, _i64, _i64]),
-    "codetr_linear_pp_supported": (_i32, [_i64, _i64, _i64]),
-    "codetr_linear_pp_preferred": (_i32, [_i64, _i64, _i64, _i32, _i32]),
-    "codetr_linear_pp_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32]),
-    "codetr_linear_pp_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32]),
-    "codetr_linear_sk_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _vp, _i64, _i32]),
-    "codetr_decoder_layer_supported": (_i32, [_i32] * 7),
-    "codetr_decoder_layer_blob_halfs": (_i64, [_i32] * 4),
-    "codetr_decoder_layer_f16": (_i32, [_vp] * 18 + [_i64, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, ctypes.c_float]),
-    "codetr_decoder_layer_bf16": (_i32, [_vp] * 18 + [_i64, _i64, _i64, _i32, _i32, _i32, ctypes.c_float, ctypes.c_float]),
-    "codetr_layernorm_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float]),
-    "codetr_layernorm_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_float]),
-    "codetr_groupnorm_tokens_workspace_bytes": (_i64, [_i64, _i64, _i64]),
-    "codetr_groupnorm_tokens_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32,
-                                           ctypes.c_float]),
-    "codetr_groupnorm_tokens_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i32,
-                                           ctypes.c_float]),
-    "codetr_sine_pos_tokens_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, ctypes.c_float,
-                                          ctypes.c_float, ctypes.c_float, ctypes.c_float, _i32]),
-    "codetr_sine_pos_tokens_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, ctypes.c_float,
-                                          ctypes.c_float, ctypes.c_float, ctypes.c_float, _i32]),
-    "codetr_ffn_relu_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64]),
-    "codetr_ffn_relu_ln_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_float,
-                                      _vp, _vp]),
-    "codetr_ffn_relu_ln2_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_float,
-                                       _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_ffn_relu_ln2_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, ctypes.c_float,
-                                       _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_ffn_pack_w2_f16": (_i32, [_vp, _vp, _vp, _i64, _i64]),
-    "codetr_ffn_oproj_relu_ln2_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
-                                             ctypes.c_float, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_ffn_oproj_relu_ln2_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
-                                              ctypes.c_float, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_ffn_oproj_w1_index": (_i32, [_i64, _vp]),
-    "codetr_ffn_fp8": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float,
-                              _vp, _vp, ctypes.c_float, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "codetr_window_attention_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32]),
-    "codetr_window_attention_bf16": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32]),
-    "codetr_window_attention_ex": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i64, _i64, _i64, _i32, _i32, _i32, _i32,
-                                          _i32, _i32, _i32]),
-    "codetr_window_attention_bias_index": (_i32, [_i32, _vp]),
-    "codetr_window_attention_fp8out_f16": (_i32, [_vp, _vp, _vp, _vp, _vp, ctypes.c_float, _i64, _i64, _i64, _i32, _i32,
-                                                  _i32, _i32]),
-}
+def _codes(prefix, names, keys=None):
+    """{key: CODETR_<prefix>_<NAME>} for the header's enumerated codes; the keys default to the names in lower case"""
+    names = names.split()
+    return {k: _D[f"CODETR_{prefix}_{n}"] for k, n in zip(keys.split() if keys else [n.lower() for n in names], names)}
+
+
+# name -> (restype, argtypes) of every prototype the header declares, in its order
+SIGNATURES = {name: (_CTYPE[_cheader.kind(ret, returned=True)], [_CTYPE[_cheader.kind(t)] for t, _ in params])
+              for name, (ret, params) in _cheader.functions.items()}
 
 _lib = None
 
@@ -227,15 +54,10 @@ CALLS = {"encoder_projections_posgen": 0, "msda": 0, "msda_fused": 0, "linear": 
 
 # Launch recording (codetr/export.py): while RECORDER is a list, every launch-type entry point called through `load()`
 # appends (name, args) -- the raw ctypes-level arguments: ints (device pointers, sizes), floats, None, ctypes arrays
-# (host data such as level shapes).  Pure host queries (plans, variants, workspace sizes) are not launches.
+# (host data such as level shapes).  Pure host queries (plans, variants, workspace sizes, index tables) are not launches:
+# a launch returns int and takes `void *stream` first (_cheader.is_launch).
 RECORDER = None
-_QUERIES = {"codetr_hip_abi_version", "codetr_hip_strerror", "codetr_msda_variant", "codetr_linear_variant",
-            "codetr_topk_chunks", "codetr_linear_splitk_plan", "codetr_groupnorm_tokens_workspace_bytes",
-            "codetr_linear_sk_workspace_bytes", "codetr_linear_sk_supported", "codetr_linear_sk_preferred",
-            "codetr_linear_pp_supported", "codetr_linear_pp_preferred", "codetr_msda_op4_supported", "codetr_swin_mlp_supported",
-            "codetr_msda_encoder_packed_lds_bytes", "codetr_msda_pack_projection_index", "codetr_window_attention_bias_index",
-            "codetr_mx_scale_bytes", "codetr_decoder_layer_supported",
-            "codetr_decoder_layer_blob_halfs", "codetr_draw_font", "codetr_track_state_bytes"}
+_QUERIES = {name for name in SIGNATURES if not _cheader.is_launch(name)}
 
 
 class _RecordingLib:
@@ -304,16 +126,20 @@ def current_stream_ptr(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-_MSDA_BY_DTYPE = {
-    torch.float16: ("codetr_msda_forward_f16", 2),
-    torch.bfloat16: ("codetr_msda_forward_bf16", 2),
-    torch.float32: ("codetr_msda_forward_f32", 4),
-    torch.float64: ("codetr_msda_forward_f64", 8),
-}
+_SUFFIX = {torch.float16: "f16", torch.bfloat16: "bf16", torch.float32: "f32", torch.float64: "f64"}
+_B16 = (torch.float16, torch.bfloat16)
+
+
+def _entry(stem, dtype):
+    """the entry point `<stem>_<f16|bf16|f32|f64>` for a tensor type; KeyError(dtype) where the header declares none"""
+    name = f"{stem}_{_SUFFIX[dtype]}"
+    if name not in SIGNATURES:
+        raise KeyError(dtype)
+    return name
 
 
 def msda_variant(dtype, M, D, L, P) -> str:
-    return load().codetr_msda_variant(_MSDA_BY_DTYPE[dtype][1], M, D, L, P).decode()
+    return load().codetr_msda_variant(torch.empty(0, dtype=dtype).element_size(), M, D, L, P).decode()
 
 
 def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, im2col_step, out):
@@ -321,7 +147,7 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
     contract checked in ops.py (contiguous, on one HIP device, one float dtype, int64 shapes)."""
     lib = load()
     CALLS["msda"] += 1
-    name, _ = _MSDA_BY_DTYPE[value.dtype]
+    name = _entry("codetr_msda_forward", value.dtype)
     B, S, M, D = value.shape
     Nq, L, P = sampling_loc.shape[1], sampling_loc.shape[3], sampling_loc.shape[4]
     rc = getattr(lib, name)(
@@ -330,7 +156,7 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
         sampling_loc.data_ptr(), attn_weight.data_ptr(),
         B, S, M, D, L, Nq, P, int(im2col_step), out.data_ptr(),
     )
-    if rc == -2:
+    if rc == E_IM2COL_STEP:
         # same condition and wording as the reference's AT_ASSERTM (ms_deform_attn.cu:924-926)
         raise RuntimeError(f"batch({B}) must divide im2col_step({min(B, int(im2col_step))})")
     check(rc, name)
@@ -339,12 +165,11 @@ def msda_forward(value, spatial_shapes, level_start_index, sampling_loc, attn_we
 
 # "relu_res": ReLU applied after the residual add (act 3; codetr_linear_* and codetr_conv_tokens_* only)
 _ACT = {None: 0, "relu": 1, "gelu": 2, "relu_res": 3}
-_LINEAR_BY_DTYPE = {torch.float16: "codetr_linear_f16", torch.bfloat16: "codetr_linear_bf16"}
 
 
 def linear_supported(x, weight) -> bool:
     """Shapes / dtypes the native fused linear implements (K % 64 == 0, f16 / bf16)."""
-    return x.dtype in _LINEAR_BY_DTYPE and weight.dtype == x.dtype and weight.shape[1] % 64 == 0
+    return x.dtype in _B16 and weight.dtype == x.dtype and weight.shape[1] % 64 == 0
 
 
 _VARIANTS = {}
@@ -371,7 +196,7 @@ def linear(x2d, weight, bias, residual2d, act, out2d, row_mask=None, hm_rows=0, 
     variant = linear_variant(M, N, K, act, residual2d is not None, hm_head_dim)
     if variant != "unsupported":   # (the launch below reports the unsupported shape with its own error)
         CALLS["linear_" + variant] += 1
-    rc = getattr(lib, _LINEAR_BY_DTYPE[x2d.dtype])(
+    rc = getattr(lib, _entry("codetr_linear", x2d.dtype))(
         current_stream_ptr(x2d.device), x2d.data_ptr(), weight.data_ptr(),
         bias.data_ptr() if bias is not None else None,
         residual2d.data_ptr() if residual2d is not None else None,
@@ -475,8 +300,7 @@ def query_sine_embed(ref, valid_ratios, pos_feat, temperature=10000.0, apply_sig
     return ref_in, embed, ref_in32
 
 
-_MSDA_BWD = {torch.float16: "codetr_msda_backward_f16", torch.float32: "codetr_msda_backward_f32",
-             torch.float64: "codetr_msda_backward_f64"}
+_MSDA_BWD = (torch.float16, torch.float32, torch.float64)
 
 
 def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
@@ -487,11 +311,11 @@ def msda_backward(value, spatial_shapes, level_start_index, sampling_loc, attn_w
     CALLS["msda_backward"] += 1
     B, S, M, D = value.shape
     Nq, L, P = sampling_loc.shape[1], sampling_loc.shape[3], sampling_loc.shape[4]
-    rc = getattr(load(), _MSDA_BWD[value.dtype])(
+    rc = getattr(load(), _entry("codetr_msda_backward", value.dtype))(
         current_stream_ptr(value.device), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
         sampling_loc.data_ptr(), attn_weight.data_ptr(), grad_output.data_ptr(), B, S, M, D, L, Nq, P, int(im2col_step),
         grad_value.data_ptr(), grad_sampling_loc.data_ptr(), grad_attn_weight.data_ptr())
-    if rc == -2:
+    if rc == E_IM2COL_STEP:
         step = min(B, int(im2col_step))
         raise RuntimeError(f"batch({B}) must divide im2col_step({step})")
     check(rc, "codetr_msda_backward")
@@ -555,12 +379,8 @@ def batched_nms_sorted(boxes_sorted, labels_sorted, iou_threshold):
     return keep
 
 
-PREPROCESS_BATCH_MAX = 32      # CODETR_PREPROCESS_BATCH_MAX: images per codetr_preprocess_batch_u8_* launch
-POSTPROCESS_MAX_Q = 1024       # CODETR_POSTPROCESS_MAX_Q: detections per image of codetr_postprocess_detections_*
-_PRE_BATCH_BY_DTYPE = {torch.float16: "codetr_preprocess_batch_u8_f16", torch.bfloat16: "codetr_preprocess_batch_u8_bf16",
-                       torch.float32: "codetr_preprocess_batch_u8_f32"}
-_POST_BY_DTYPE = {torch.float16: "codetr_postprocess_detections_f16", torch.bfloat16: "codetr_postprocess_detections_bf16",
-                  torch.float32: "codetr_postprocess_detections_f32"}
+PREPROCESS_BATCH_MAX = _D["CODETR_PREPROCESS_BATCH_MAX"]   # images per codetr_preprocess_batch_u8_* launch
+POSTPROCESS_MAX_Q = _D["CODETR_POSTPROCESS_MAX_Q"]   # detections per image of codetr_postprocess_detections_*
 
 
 def preprocess_batch_u8(src, images, batch_hw, mean, std, pad_value, pad_fill, dst, mask):
@@ -571,7 +391,7 @@ def preprocess_batch_u8(src, images, batch_hw, mean, std, pad_value, pad_fill, d
     H, W = batch_hw
     table = (ctypes.c_int64 * (7 * N))(*[int(v) for row in images for v in row])
     f3 = ctypes.c_float * 3
-    rc = getattr(load(), _PRE_BATCH_BY_DTYPE[dst.dtype])(
+    rc = getattr(load(), _entry("codetr_preprocess_batch_u8", dst.dtype))(
         current_stream_ptr(src.device), src.data_ptr(), src.numel(), N, table, H, W, f3(*[float(v) for v in mean]),
         f3(*[float(v) for v in std]), (ctypes.c_int * 3)(*[int(v) for v in pad_value]), float(pad_fill), dst.data_ptr(),
         mask.data_ptr() if mask is not None else None)
@@ -584,7 +404,7 @@ def postprocess_detections(boxes, scores, labels, divisors, score_threshold, iou
     int32 (include/codetr_hip.h); score_threshold None = no threshold, iou_threshold None = no NMS"""
     CALLS["postprocess_detections"] += 1
     N, Q = scores.shape
-    rc = getattr(load(), _POST_BY_DTYPE[scores.dtype])(
+    rc = getattr(load(), _entry("codetr_postprocess_detections", scores.dtype))(
         current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), divisors.data_ptr(),
         N, Q, 0 if score_threshold is None else 1, 0.0 if score_threshold is None else float(score_threshold),
         0 if iou_threshold is None else 1, 0.0 if iou_threshold is None else float(iou_threshold), boxes_out.data_ptr(),
@@ -592,9 +412,7 @@ def postprocess_detections(boxes, scores, labels, divisors, score_threshold, iou
     check(rc, "codetr_postprocess_detections")
 
 
-_SOFTNMS_BY_DTYPE = {torch.float16: "codetr_postprocess_softnms_f16", torch.bfloat16: "codetr_postprocess_softnms_bf16",
-                     torch.float32: "codetr_postprocess_softnms_f32"}
-SOFTNMS_METHODS = {"naive": 0, "linear": 1}   # CODETR_SOFTNMS_NAIVE / CODETR_SOFTNMS_LINEAR
+SOFTNMS_METHODS = _codes("SOFTNMS", "NAIVE LINEAR")
 
 
 def postprocess_softnms(boxes, scores, labels, divisors, score_threshold, method, iou_threshold, min_score, max_keep,
@@ -603,7 +421,7 @@ def postprocess_softnms(boxes, scores, labels, divisors, score_threshold, method
     (include/codetr_hip.h states the semantics)"""
     CALLS["postprocess_softnms"] += 1
     N, Q = scores.shape
-    rc = getattr(load(), _SOFTNMS_BY_DTYPE[scores.dtype])(
+    rc = getattr(load(), _entry("codetr_postprocess_softnms", scores.dtype))(
         current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), divisors.data_ptr(),
         N, Q, 0 if score_threshold is None else 1, 0.0 if score_threshold is None else float(score_threshold),
         int(method), float(iou_threshold), float(min_score), int(max_keep), boxes_out.data_ptr(), scores_out.data_ptr(),
@@ -611,13 +429,9 @@ def postprocess_softnms(boxes, scores, labels, divisors, score_threshold, method
     check(rc, "codetr_postprocess_softnms")
 
 
-TTA_MAX_VIEWS = 16             # CODETR_TTA_MAX_VIEWS: views per codetr_tta_merge_* launch
-TTA_MAX_CANDIDATES = 4096      # CODETR_TTA_MAX_CANDIDATES: views * detections per view
-TTA_NMS_MODES = {"nms": 0, "naive": 1, "linear": 2}   # CODETR_TTA_NMS_HARD / _SOFT_NAIVE / _SOFT_LINEAR
-_PRE_VIEWS_BY_DTYPE = {torch.float16: "codetr_preprocess_views_u8_f16", torch.bfloat16: "codetr_preprocess_views_u8_bf16",
-                       torch.float32: "codetr_preprocess_views_u8_f32"}
-_TTA_MERGE_BY_DTYPE = {torch.float16: "codetr_tta_merge_f16", torch.bfloat16: "codetr_tta_merge_bf16",
-                       torch.float32: "codetr_tta_merge_f32"}
+TTA_MAX_VIEWS = _D["CODETR_TTA_MAX_VIEWS"]   # views per codetr_tta_merge_* launch
+TTA_MAX_CANDIDATES = _D["CODETR_TTA_MAX_CANDIDATES"]   # views * detections per view
+TTA_NMS_MODES = _codes("TTA_NMS", "HARD SOFT_NAIVE SOFT_LINEAR", "nms naive linear")
 
 
 def preprocess_views_u8(src, rows, batch_hw, mean, std, pad_value, pad_fill, dst, mask):
@@ -628,7 +442,7 @@ def preprocess_views_u8(src, rows, batch_hw, mean, std, pad_value, pad_fill, dst
     H, W = batch_hw
     table = (ctypes.c_int64 * (8 * N))(*[int(v) for row in rows for v in row])
     f3 = ctypes.c_float * 3
-    rc = getattr(load(), _PRE_VIEWS_BY_DTYPE[dst.dtype])(
+    rc = getattr(load(), _entry("codetr_preprocess_views_u8", dst.dtype))(
         current_stream_ptr(src.device), src.data_ptr(), src.numel(), N, table, H, W, f3(*[float(v) for v in mean]),
         f3(*[float(v) for v in std]), (ctypes.c_int * 3)(*[int(v) for v in pad_value]), float(pad_fill), dst.data_ptr(),
         mask.data_ptr() if mask is not None else None)
@@ -641,20 +455,16 @@ def tta_merge(boxes, scores, labels, count, flip_mask, width, mode, iou_threshol
     value of TTA_NMS_MODES; outputs [N,K,..] with K = max_keep, or V*Q when max_keep <= 0 (include/codetr_hip.h)"""
     CALLS["tta_merge"] += 1
     V, N, Q = scores.shape
-    rc = getattr(load(), _TTA_MERGE_BY_DTYPE[scores.dtype])(
+    rc = getattr(load(), _entry("codetr_tta_merge", scores.dtype))(
         current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(),
         V, N, Q, int(flip_mask), width.data_ptr(), int(mode), float(iou_threshold), float(min_score), int(max_keep),
         boxes_out.data_ptr(), scores_out.data_ptr(), labels_out.data_ptr(), index_out.data_ptr(), count_out.data_ptr())
     check(rc, "codetr_tta_merge")
 
 
-SLICE_MAX_VIEWS = 64           # CODETR_SLICE_MAX_VIEWS: views (tiles + the whole image) per image of codetr_slice_merge_*
-SLICE_METRICS = {"iou": 0, "ios": 1}   # CODETR_SLICE_IOU / CODETR_SLICE_IOS
-SLICE_MODES = {"nms": 0, "nmm": 1}     # CODETR_SLICE_NMS / CODETR_SLICE_NMM
-_PRE_TILES_BY_DTYPE = {torch.float16: "codetr_preprocess_tiles_u8_f16", torch.bfloat16: "codetr_preprocess_tiles_u8_bf16",
-                       torch.float32: "codetr_preprocess_tiles_u8_f32"}
-_SLICE_MERGE_BY_DTYPE = {torch.float16: "codetr_slice_merge_f16", torch.bfloat16: "codetr_slice_merge_bf16",
-                         torch.float32: "codetr_slice_merge_f32"}
+SLICE_MAX_VIEWS = _D["CODETR_SLICE_MAX_VIEWS"]   # views (tiles + the whole image) per image of codetr_slice_merge_*
+SLICE_METRICS = _codes("SLICE", "IOU IOS")
+SLICE_MODES = _codes("SLICE", "NMS NMM")
 
 
 def preprocess_tiles_u8(src, rows, batch_hw, mean, std, pad_value, pad_fill, dst, mask):
@@ -666,7 +476,7 @@ def preprocess_tiles_u8(src, rows, batch_hw, mean, std, pad_value, pad_fill, dst
     H, W = batch_hw
     table = (ctypes.c_int64 * (11 * N))(*[int(v) for row in rows for v in row])
     f3 = ctypes.c_float * 3
-    rc = getattr(load(), _PRE_TILES_BY_DTYPE[dst.dtype])(
+    rc = getattr(load(), _entry("codetr_preprocess_tiles_u8", dst.dtype))(
         current_stream_ptr(src.device), src.data_ptr(), src.numel(), N, table, H, W, f3(*[float(v) for v in mean]),
         f3(*[float(v) for v in std]), (ctypes.c_int * 3)(*[int(v) for v in pad_value]), float(pad_fill), dst.data_ptr(),
         mask.data_ptr() if mask is not None else None)
@@ -681,7 +491,7 @@ def slice_merge(boxes, scores, labels, count, rows, origin, size, metric, mode, 
     CALLS["slice_merge"] += 1
     R, Q = scores.shape
     N, V = rows.shape
-    rc = getattr(load(), _SLICE_MERGE_BY_DTYPE[scores.dtype])(
+    rc = getattr(load(), _entry("codetr_slice_merge", scores.dtype))(
         current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(),
         rows.data_ptr(), origin.data_ptr(), size.data_ptr(), R, N, V, Q, int(metric), int(mode), float(threshold),
         1 if class_agnostic else 0, int(max_keep), boxes_out.data_ptr(), scores_out.data_ptr(), labels_out.data_ptr(),
@@ -689,11 +499,9 @@ def slice_merge(boxes, scores, labels, count, rows, origin, size, metric, mode, 
     check(rc, "codetr_slice_merge")
 
 
-DRAW_MAX_Q = 4096              # CODETR_DRAW_MAX_Q: detection rows per image of codetr_draw_detections_*
-DRAW_MAX_SIDE = 16384          # CODETR_DRAW_MAX_SIDE
-DRAW_FONT_BYTES = 665          # CODETR_DRAW_FONT_BYTES: 95 glyphs (ASCII 32..126) x 7 rows
-_DRAW_BY_DTYPE = {torch.float16: "codetr_draw_detections_f16", torch.bfloat16: "codetr_draw_detections_bf16",
-                  torch.float32: "codetr_draw_detections_f32"}
+DRAW_MAX_Q = _D["CODETR_DRAW_MAX_Q"]   # detection rows per image of codetr_draw_detections_*
+DRAW_MAX_SIDE = _D["CODETR_DRAW_MAX_SIDE"]
+DRAW_FONT_BYTES = _D["CODETR_DRAW_FONT_BYTES"]   # 95 glyphs (ASCII 32..126) x 7 rows
 
 
 def draw_font() -> bytes:
@@ -711,17 +519,17 @@ def draw_detections(buf, rows, boxes, scores, labels, count, palette, names, lin
     CALLS["draw_detections"] += 1
     N, Q = scores.shape
     table = (ctypes.c_int64 * (3 * N))(*[int(v) for row in rows for v in row])
-    rc = getattr(load(), _DRAW_BY_DTYPE[scores.dtype])(
+    rc = getattr(load(), _entry("codetr_draw_detections", scores.dtype))(
         current_stream_ptr(buf.device), buf.data_ptr(), buf.numel(), N, table, boxes.data_ptr(), scores.data_ptr(),
         labels.data_ptr(), count.data_ptr(), Q, palette.data_ptr(), names.data_ptr(), palette.shape[0], int(line_width),
         float(alpha), float(score_thr), int(text_rgb), int(font_scale), 1 if draw_labels else 0)
     check(rc, "codetr_draw_detections")
 
 
-FRAME_FORMATS = {"rgb": 0, "bgr": 1, "rgba": 2, "bgra": 3, "gray": 4, "nv12": 5, "nv21": 6, "i420": 7}   # CODETR_FRAME_*
-FRAME_MAX_SIDE = 32767         # CODETR_FRAME_MAX_SIDE
-COLOR_MATRICES = {"bt601": 0, "bt709": 1}                       # CODETR_COLOR_BT601 / _BT709
-COLOR_RANGES = {"limited": 0, "full": 1}                        # CODETR_COLOR_LIMITED / _FULL
+FRAME_FORMATS = _codes("FRAME", "RGB BGR RGBA BGRA GRAY NV12 NV21 I420")
+FRAME_MAX_SIDE = _D["CODETR_FRAME_MAX_SIDE"]
+COLOR_MATRICES = _codes("COLOR", "BT601 BT709")
+COLOR_RANGES = _codes("COLOR", "LIMITED FULL")
 
 
 def frames_to_rgb(src, rows, matrix, range_, dst):
@@ -736,9 +544,7 @@ def frames_to_rgb(src, rows, matrix, range_, dst):
     check(rc, "codetr_frames_to_rgb_u8")
 
 
-TRACK_MAX_TRACKS = 512         # CODETR_TRACK_MAX_TRACKS: track slots per stream of codetr_track_update_*
-_TRACK_BY_DTYPE = {torch.float16: "codetr_track_update_f16", torch.bfloat16: "codetr_track_update_bf16",
-                   torch.float32: "codetr_track_update_f32"}
+TRACK_MAX_TRACKS = _D["CODETR_TRACK_MAX_TRACKS"]   # track slots per stream of codetr_track_update_*
 
 
 def track_state_bytes(max_tracks) -> int:
@@ -757,7 +563,7 @@ def track_update(boxes, scores, labels, count, streams, state, max_tracks, thres
     the rule)"""
     CALLS["track_update"] += 1
     N, Q = scores.shape
-    rc = getattr(load(), _TRACK_BY_DTYPE[scores.dtype])(
+    rc = getattr(load(), _entry("codetr_track_update", scores.dtype))(
         current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
         (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
         (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
@@ -814,12 +620,9 @@ def linear_splitk(x2d, weight, bias, residual2d, act, out2d, splits, workspace, 
     return out2d
 
 
-_LN_BY_DTYPE = {torch.float16: "codetr_layernorm_f16", torch.bfloat16: "codetr_layernorm_bf16"}
-
-
 def layernorm_supported(x, weight) -> bool:
     C = x.shape[-1]
-    return x.dtype in _LN_BY_DTYPE and weight is not None and weight.dtype == x.dtype and C % 8 == 0 and C <= 4096
+    return x.dtype in _B16 and weight is not None and weight.dtype == x.dtype and C % 8 == 0 and C <= 4096
 
 
 def patch_merge_layernorm(x4d, weight_kkc, bias_kkc, eps):
@@ -838,7 +641,7 @@ def patch_merge_layernorm(x4d, weight_kkc, bias_kkc, eps):
 def layernorm(x2d, weight, bias, eps, out2d):
     rows, C = x2d.shape
     CALLS["layernorm"] += 1
-    rc = getattr(load(), _LN_BY_DTYPE[x2d.dtype])(
+    rc = getattr(load(), _entry("codetr_layernorm", x2d.dtype))(
         current_stream_ptr(x2d.device), x2d.data_ptr(), weight.data_ptr(), bias.data_ptr(), out2d.data_ptr(),
         rows, C, float(eps))
     check(rc, "codetr_layernorm")
@@ -918,15 +721,8 @@ def encoder_projections_posgen(x2d, S, cums, level_shapes, level_embed, temperat
     return True
 
 
-_MSDA_FUSED_BY_DTYPE = {torch.float16: "codetr_msda_fused_forward_f16", torch.bfloat16: "codetr_msda_fused_forward_bf16"}
-
-
 def msda_fused_supported(dtype, D, L, P) -> bool:
-    return dtype in _MSDA_FUSED_BY_DTYPE and D in (16, 32, 64) and L * P * (256 // (D // 8)) * 32 <= 60 * 1024
-
-
-_MSDA_FUSED_REF32_BY_DTYPE = {torch.float16: "codetr_msda_fused_forward_ref32_f16",
-                              torch.bfloat16: "codetr_msda_fused_forward_ref32_bf16"}
+    return dtype in _B16 and D in (16, 32, 64) and L * P * (256 // (D // 8)) * 32 <= 60 * 1024
 
 
 def msda_fused(value, spatial_shapes, level_start_index, proj, off_col, logit_col, ref, num_levels, num_points, out,
@@ -941,16 +737,13 @@ def msda_fused(value, spatial_shapes, level_start_index, proj, off_col, logit_co
         B, S, M, D = value.shape
     Nq, ncols = proj.shape[1], proj.shape[2]
     es = proj.element_size()
-    table = _MSDA_FUSED_REF32_BY_DTYPE if ref.dtype == torch.float32 else _MSDA_FUSED_BY_DTYPE
-    rc = getattr(lib, table[value.dtype])(
+    stem = "codetr_msda_fused_forward_ref32" if ref.dtype == torch.float32 else "codetr_msda_fused_forward"
+    rc = getattr(lib, _entry(stem, value.dtype))(
         current_stream_ptr(value.device), value.data_ptr(), spatial_shapes.data_ptr(), level_start_index.data_ptr(),
         proj.data_ptr() + off_col * es, ncols, proj.data_ptr() + logit_col * es, ncols,
         ref.data_ptr(), ref.shape[-1], 1 if head_major else 0, B, S, M, D, num_levels, Nq, num_points, out.data_ptr())
     check(rc, "codetr_msda_fused_forward")
     return out
-
-
-E_UNSUPPORTED = -4
 
 
 def _windows_array(windows, M, L):
@@ -1140,13 +933,10 @@ def im2col_tokens(x4d, k, stride, pad, out):
     return out
 
 
-_CONV_BY_DTYPE = {torch.float16: "codetr_conv_tokens_f16", torch.bfloat16: "codetr_conv_tokens_bf16"}
-
-
 def conv_tokens_supported(x4d, weight, k, stride, pad) -> bool:
     """the domain of codetr_conv_tokens_*: 16-bit token-major x [B, H, W, C], C % 64 == 0, Cout % 8 == 0, k in {1, 3},
     stride in {1, 2}, 0 <= pad < k"""
-    return (x4d.dtype in _CONV_BY_DTYPE and weight.dtype == x4d.dtype and x4d.dim() == 4 and x4d.shape[-1] % 64 == 0
+    return (x4d.dtype in _B16 and weight.dtype == x4d.dtype and x4d.dim() == 4 and x4d.shape[-1] % 64 == 0
             and weight.shape[0] % 8 == 0 and k in (1, 3) and stride in (1, 2) and 0 <= pad < k)
 
 
@@ -1156,7 +946,7 @@ def conv_tokens(x4d, weight, bias, residual, k, stride, pad, act, out):
     lib = load()
     CALLS["conv_tokens"] += 1
     B, H, W, C = x4d.shape
-    name = _CONV_BY_DTYPE[x4d.dtype]
+    name = _entry("codetr_conv_tokens", x4d.dtype)
     rc = getattr(lib, name)(
         current_stream_ptr(x4d.device), x4d.data_ptr(), weight.data_ptr(),
         bias.data_ptr() if bias is not None else None, residual.data_ptr() if residual is not None else None,
@@ -1242,7 +1032,7 @@ def groupnorm_tokens(x, gamma, beta, groups, eps, out_slice, out_batch_stride):
 
 def msda_head_major_supported(dtype, D, L, P) -> bool:
     """the head-major fused kernel: 16-bit storage, 64- or 128-byte head rows, L*P <= 4 * lanes per pair"""
-    return dtype in _MSDA_FUSED_BY_DTYPE and D in (32, 64) and L * P <= 4 * 2 * (D // 8)
+    return dtype in _B16 and D in (32, 64) and L * P <= 4 * 2 * (D // 8)
 
 
 def sine_pos_tokens(ycum, xcum, level_embed, out_slice, out_batch_stride, num_feats, temperature, scale, eps, offset,

@@ -9,6 +9,7 @@
 //
 //   codetr_runner --plan model.plan [--lib libcodetr_hip.so] [--iters N] [--no-graph]
 //                 [--input batch_inputs=file.bin] [--input img_masks=file.bin] [--out-dir DIR]
+//   codetr_runner --list-entries     the launch entries and their argument kinds as compiled in (no GPU, no library)
 //
 // Inputs default to the tensors of the recorded run (stored in the plan); outputs are written as raw little-endian
 // arrays DIR/<name>.bin; one JSON line with shapes and timing goes to stdout.
@@ -24,7 +25,11 @@
 #include <fstream>
 #include <map>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
+
+#include "codetr_hip.h"   // the prototypes only (decltype below): symbols are resolved with dlsym, the library is not linked
 
 union Arg {
   const void* p;
@@ -35,8 +40,38 @@ struct Entry {
   const char* name;
   int nargs;
   int (*call)(void* fn, const Arg* a);
+  const char* kinds;   // one letter per argument: p pointer, i / l 32- / 64-bit integer, u uint32_t, f float
 };
+
+// One typed trampoline per launch entry point, its prototype deduced from the declaration in codetr_hip.h, so that any
+// recorded function is called with the right C types (integers in GPRs, floats in XMM registers) without libffi.
+template <class T>
+constexpr char kind_of() {
+  static_assert(std::is_pointer_v<T> || std::is_same_v<T, float> || (std::is_integral_v<T> && (sizeof(T) == 4 || sizeof(T) == 8)),
+                "codetr_hip.h: a launch takes pointers, float and 32- / 64-bit integers only");
+  return std::is_pointer_v<T> ? 'p' : std::is_same_v<T, float> ? 'f' : sizeof(T) == 8 ? 'l' : std::is_unsigned_v<T> ? 'u' : 'i';
+}
+template <class T>
+T from_arg(const Arg& a) {
+  if constexpr (std::is_pointer_v<T>) return (T)a.p;
+  else if constexpr (std::is_floating_point_v<T>) return a.f;
+  else return (T)a.i;
+}
+template <class F>
+struct Trampoline;
+template <class... A>
+struct Trampoline<int(A...)> {
+  static constexpr int nargs = sizeof...(A);
+  static constexpr char kinds[] = {kind_of<A>()..., '\0'};
+  template <size_t... I>
+  static int call_at(void* fn, const Arg* a, std::index_sequence<I...>) {
+    return reinterpret_cast<int (*)(A...)>(fn)(from_arg<A>(a[I])...);
+  }
+  static int call(void* fn, const Arg* a) { return call_at(fn, a, std::index_sequence_for<A...>{}); }
+};
+#define ENTRY(name) {#name, Trampoline<decltype(name)>::nargs, Trampoline<decltype(name)>::call, Trampoline<decltype(name)>::kinds},
 #include "dispatch_gen.inc"
+static_assert(kPlanAbi == CODETR_HIP_ABI_VERSION, "regenerate: python tools/gen_runner_dispatch.py > runner/dispatch_gen.inc");
 
 #define HIP_OK(expr)                                                                                      \
   do {                                                                                                    \
@@ -125,6 +160,10 @@ int main(int argc, char** argv) {
     else if (a == "--iters") iters = atoi(next().c_str());
     else if (a == "--no-graph") use_graph = false;
     else if (a == "--out-dir") out_dir = next();
+    else if (a == "--list-entries") {
+      for (const Entry& e : kEntries) printf("%s %s\n", e.name, e.kinds);
+      return 0;
+    }
     else if (a == "--input") {
       const std::string kv = next();
       const size_t eq = kv.find('=');
@@ -288,7 +327,9 @@ int main(int argc, char** argv) {
   // ---- replay ----
   hipStream_t stream;
   HIP_OK(hipStreamCreate(&stream));
-  std::vector<Arg> av(32);
+  int max_nargs = 0;
+  for (const Entry& e : kEntries) max_nargs = std::max(max_nargs, e.nargs);
+  std::vector<Arg> av(max_nargs);
   auto replay = [&]() {
     for (const Call& c : calls) {
       for (size_t j = 0; j < c.args.size(); ++j) {

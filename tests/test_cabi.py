@@ -128,7 +128,8 @@ def test_cpu_tensors_are_rejected_not_emulated():
 
 
 def test_runner_dispatch_table_is_in_sync_with_the_signature_table():
-    """runner/dispatch_gen.inc (typed trampolines of the C++ plan runner) is generated from codetr/_cabi.py SIGNATURES"""
+    """runner/dispatch_gen.inc (the launch entries the C++ plan runner builds a trampoline for) is what the generator
+    prints from include/codetr_hip.h"""
     import subprocess
     import sys
 
@@ -138,6 +139,125 @@ def test_runner_dispatch_table_is_in_sync_with_the_signature_table():
     assert gen == open(os.path.join(root, "runner", "dispatch_gen.inc")).read(), \
         "regenerate: python tools/gen_runner_dispatch.py > runner/dispatch_gen.inc"
     assert os.access(os.path.join(root, "runner", "codetr_runner"), os.X_OK)   # built by __graft_entry__.build()
+
+
+_VP, _I32, _I64, _U32, _F32 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint32, ctypes.c_float
+_LETTER = {_VP: "p", _I32: "i", _I64: "l", _U32: "u", _F32: "f"}
+
+
+def test_signature_table_agrees_with_the_compiler_on_every_launch():
+    """the regex reader of the header (codetr/_cheader.py -> _cabi.SIGNATURES) against the C++ front end: the runner
+    prints the argument kinds it deduced from decltype(entry) for all launch prototypes; no GPU, no library"""
+    import subprocess
+
+    from codetr import _cabi, _cheader
+
+    out = subprocess.run([os.path.join(ROOT, "runner", "codetr_runner"), "--list-entries"], stdout=subprocess.PIPE, text=True,
+                         check=True).stdout
+    compiled = dict(line.split() for line in out.splitlines())
+    assert set(compiled) == {n for n in _cheader.functions if _cheader.is_launch(n)} and len(compiled) == len(out.splitlines())
+    for name, letters in compiled.items():
+        res, args = _cabi.SIGNATURES[name]
+        assert res is _I32 and "".join(_LETTER[a] for a in args) == letters, name
+
+
+def test_pinned_signatures():
+    """hand-written from include/codetr_hip.h: every type kind and shape of declaration the header has"""
+    from codetr import _cabi
+
+    expected = {
+        "codetr_hip_strerror": (ctypes.c_char_p, [_I32]),                     # char* return
+        "codetr_hip_abi_version": (_I32, []),                                 # (void), int
+        "codetr_linear_sk_workspace_bytes": (_I64, []),                       # (void), int64_t
+        "codetr_msda_pack_projection_index": (_I32, [_I32, _I32, _I32, _VP]),  # int32_t*
+        "codetr_tta_merge_f16": (_I32, [_VP] * 5 + [_I64, _I64, _I64, _U32, _VP, _I32, _F32, _F32, _I64] + [_VP] * 5),
+        "codetr_linear_fp8": (_I32, [_VP, _VP, _VP, _VP, _F32, _VP, _VP, _VP, _I32, _F32, _I64, _I64, _I64, _I32]),
+        "codetr_encoder_projections_posgen_bf16": (_I32, [_VP] * 13 + [_I32, _VP, _F32, _F32, _F32, _F32, _I32] + [_VP] * 5
+                                                   + [_I64] * 6 + [_I32]),
+        "codetr_topk_chunks": (_I64, [_I64, _I32, _I64, _VP]),                # int64_t return with an out-pointer
+    }
+    assert len(expected["codetr_encoder_projections_posgen_bf16"][1]) == 32
+    for name, (res, args) in expected.items():
+        got_res, got_args = _cabi.SIGNATURES[name]
+        assert got_res is res and len(got_args) == len(args) and all(a is b for a, b in zip(got_args, args)), name
+
+
+@pytest.mark.parametrize("decl", ["int codetr_bad(void *stream, size_t n);", "double codetr_bad(int n);",
+                                  "int codetr_bad(void *stream, struct codetr_box box);",
+                                  "int codetr_bad(void *stream, const struct codetr_box *box);",
+                                  "int codetr_bad(void *stream, int (*callback)(int));",
+                                  "int codetr_bad(const char *format, ...);", "int codetr_bad(int);",
+                                  "unsigned int codetr_bad(void);"])
+def test_header_reader_refuses_what_it_does_not_know(decl):
+    from codetr import _cheader
+
+    good = "#define CODETR_N (-7)\nint codetr_good(void *stream, const int64_t *shape, float eps);\n"
+    with pytest.raises(_cheader.HeaderError, match="codetr_bad"):
+        _cheader.parse(good + decl)
+    functions, defines = _cheader.parse(good + "/* codetr_fake(int x); */ // int codetr_fake2(int x);\n"
+                                        "#ifdef __cplusplus\nextern \"C\" {\n#endif\nint64_t codetr_q(void);\n#ifdef __cplusplus\n}\n#endif\n")
+    assert functions == {"codetr_good": ("int", [("void *", "stream"), ("const int64_t *", "shape"), ("float", "eps")]),
+                         "codetr_q": ("int64_t", [])}
+    assert defines == {"CODETR_N": -7}
+
+
+def test_constants_are_the_headers():
+    from codetr import _cabi, _cheader
+
+    assert _cabi.ABI_VERSION == _cheader.defines["CODETR_HIP_ABI_VERSION"] == _cabi.load().codetr_hip_abi_version() == 54
+    assert (_cabi.E_IM2COL_STEP, _cabi.E_UNSUPPORTED) == (-2, -4)
+    assert (_cabi.PREPROCESS_BATCH_MAX, _cabi.POSTPROCESS_MAX_Q, _cabi.TTA_MAX_VIEWS, _cabi.TTA_MAX_CANDIDATES) == (32, 1024, 16, 4096)
+    assert (_cabi.SLICE_MAX_VIEWS, _cabi.DRAW_MAX_Q, _cabi.DRAW_MAX_SIDE, _cabi.DRAW_FONT_BYTES) == (64, 4096, 16384, 665)
+    assert (_cabi.FRAME_MAX_SIDE, _cabi.TRACK_MAX_TRACKS) == (32767, 512)
+    assert _cabi.SOFTNMS_METHODS == {"naive": 0, "linear": 1}
+    assert _cabi.TTA_NMS_MODES == {"nms": 0, "naive": 1, "linear": 2}
+    assert _cabi.SLICE_METRICS == {"iou": 0, "ios": 1} and _cabi.SLICE_MODES == {"nms": 0, "nmm": 1}
+    assert _cabi.FRAME_FORMATS == {"rgb": 0, "bgr": 1, "rgba": 2, "bgra": 3, "gray": 4, "nv12": 5, "nv21": 6, "i420": 7}
+    assert _cabi.COLOR_MATRICES == {"bt601": 0, "bt709": 1} and _cabi.COLOR_RANGES == {"limited": 0, "full": 1}
+
+
+def test_host_queries_are_not_launches():
+    """a launch returns int and takes `void *stream` first; everything else is a host query and is never recorded"""
+    from codetr import _cabi, _cheader
+
+    for name in ("codetr_ffn_oproj_w1_index", "codetr_msda_pack_projection_index", "codetr_draw_font", "codetr_track_state_bytes"):
+        assert name in _cabi._QUERIES and not _cheader.is_launch(name)
+    suffixed = [n for n in _cabi.SIGNATURES if n.endswith(("_supported", "_preferred", "_plan", "_bytes", "_variant"))]
+    assert len(suffixed) >= 13 and all(n in _cabi._QUERIES for n in suffixed)
+    assert len(_cabi.SIGNATURES) - len(_cabi._QUERIES) == 122 and "codetr_linear_f16" not in _cabi._QUERIES
+    _cabi.RECORDER = []
+    try:
+        idx = (ctypes.c_int32 * 256)()
+        assert _cabi.load().codetr_ffn_oproj_w1_index(256, ctypes.cast(idx, ctypes.c_void_p)) == 0
+        assert sorted(idx) == list(range(256)) and _cabi.RECORDER == []
+    finally:
+        _cabi.RECORDER = None
+
+
+def test_entry_names_by_dtype():
+    import torch
+
+    from codetr import _cabi
+
+    f16, bf16, f32, f64 = torch.float16, torch.bfloat16, torch.float32, torch.float64
+    stems = {"codetr_msda_forward": (f16, bf16, f32, f64), "codetr_msda_backward": (f16, f32, f64),
+             "codetr_linear": (f16, bf16), "codetr_layernorm": (f16, bf16), "codetr_conv_tokens": (f16, bf16),
+             "codetr_msda_fused_forward": (f16, bf16), "codetr_msda_fused_forward_ref32": (f16, bf16)}
+    for stem in ("codetr_preprocess_batch_u8", "codetr_postprocess_detections", "codetr_postprocess_softnms",
+                 "codetr_preprocess_views_u8", "codetr_tta_merge", "codetr_preprocess_tiles_u8", "codetr_slice_merge",
+                 "codetr_draw_detections", "codetr_track_update"):
+        stems[stem] = (f16, bf16, f32)
+    suffix = {f16: "_f16", bf16: "_bf16", f32: "_f32", f64: "_f64"}
+    for stem, dtypes in stems.items():
+        for dt in (f16, bf16, f32, f64):
+            if dt in dtypes:
+                assert _cabi._entry(stem, dt) == stem + suffix[dt] and stem + suffix[dt] in _cabi.SIGNATURES
+            else:
+                with pytest.raises(KeyError):
+                    _cabi._entry(stem, dt)
+    for stem, dt in (("codetr_preprocess_u8", bf16), ("codetr_linear", torch.int32)):
+        with pytest.raises(KeyError):
+            _cabi._entry(stem, dt)
 
 
 def test_kernel_name_whitelist_matches_sources():
