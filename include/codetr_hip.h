@@ -1362,7 +1362,13 @@ int codetr_decoder_layer_bf16(void *stream, const void *x_dev, const void *attn_
  *           out_batch_stride = S*C elements between images
  *   workspace_dev: codetr_groupnorm_tokens_workspace_bytes(B, HW, C) bytes of device scratch
  *   groups must equal C/8 (8 channels = one 16-byte chunk per group: GN(32) on 256 channels)
- * fp32 partial sums per 512-row slab, fp64 final reduction, statistics over (HW x 8) per (image, group).
+ * Statistics over (HW x 8) per (image, group): fp32 partial sums of x and x^2 per 128-row slab, fp64 final reduction.
+ * fp32 partials lose about 1e-7 mean^2 / var of rstd, so the final reduction bounds that loss from the sums themselves
+ * and, where it may exceed 2^-13 (f16) / 2^-10 (bf16) of var + eps (mean^2 / var above about 4 / 39 at C = 256), the
+ * group's sums are taken again over the same grid about the pivot K = (float)mean of the first reduction:
+ * mean = K + s/n, var = q/n - (s/n)^2.  A call with such groups costs up to one more pass over x; a call without them two
+ * launches that return at once.  That the neck's activations stay below the threshold is measured with seeded random
+ * weights only, not with a trained checkpoint.
  * ------------------------------------------------------------------------------------------ */
 int64_t codetr_groupnorm_tokens_workspace_bytes(int64_t B, int64_t HW, int64_t C);
 int codetr_groupnorm_tokens_f16(void *stream, const void *x_dev, const void *gamma_dev, const void *beta_dev,
