@@ -12,6 +12,10 @@ from . import _cabi
 
 _cabi.load()  # raises ImportError if the HIP extension has not been built
 
+from . import _jpeg  # noqa: E402  (the companion header's entry points, same library)
+
+_jpeg.load()
+
 from . import ops  # noqa: E402,F401  (registers torch.ops.codetr.*)
 
 try:  # model assembly (pure-Python host code on top of the ops)

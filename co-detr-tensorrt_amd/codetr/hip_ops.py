@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _cabi
+from . import _cabi, _jpeg
 
 # ops served by hand-written HIP kernels in this build (kept in sync with include/codetr_hip.h)
 NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_window_attention(f16, head_dim 32)",
@@ -912,6 +912,99 @@ def draw_detections(buf_u8, rows, dets, names, palette, style=None):
                                   palette.contiguous(), names.contiguous(), st["line_width"], st["alpha"], st["score_thr"],
                                   (tc[0] << 16) | (tc[1] << 8) | tc[2], st["font_scale"], st["draw_labels"])
     return buf_u8
+
+
+JPEG_SETTINGS = dict(quality=90, subsampling="420")
+JPEG_DOWNLOADS = {"copies": 0, "bytes": 0}   # device-to-host copies encode_jpeg made in this process
+
+
+def jpeg_settings(settings=None):
+    """quality / subsampling of encode_jpeg, validated: the keys of JPEG_SETTINGS (missing ones take its values) -> a new
+    dict.  ValueError for an unknown key, a quality that is not an integer in 1..100, a subsampling other than '420' /
+    '444'."""
+    st = dict(JPEG_SETTINGS)
+    settings = dict(settings or {})
+    unknown = set(settings) - set(st)
+    if unknown:
+        raise ValueError(f"jpeg: unknown key(s) {sorted(unknown)}; known: {sorted(st)}")
+    st.update(settings)
+    q = st["quality"]
+    if isinstance(q, bool) or not isinstance(q, (int, float)) or int(q) != q or not 1 <= q <= 100:
+        raise ValueError(f"jpeg: quality must be an integer in 1..100, got {q!r}")
+    if st["subsampling"] not in _jpeg.SUBSAMPLINGS:
+        raise ValueError(f"jpeg: subsampling must be one of {sorted(_jpeg.SUBSAMPLINGS)}, got {st['subsampling']!r}")
+    st["quality"] = int(q)
+    return st
+
+
+def jpeg_out_stride(rows, subsampling="420"):
+    """the bytes encode_jpeg reserves per image of a launch group on its first attempt: an eighth of the largest raw image
+    plus 4 KB, never more than the proven bound of the largest scan, rounded up to 16.  (A drawn 1080p frame at quality
+    90 / 4:2:0 takes about a twentieth of its raw size; noise at quality 100 exceeds the raw size and takes the retry.)"""
+    sub = _jpeg.SUBSAMPLINGS[subsampling]
+    guess = max(H * W * 3 for _, H, W in rows) // 8 + 4096
+    bound = max(_jpeg.scan_bound(H, W, sub) for _, H, W in rows)
+    return (min(guess, bound) + 15) // 16 * 16
+
+
+def encode_jpeg(src, rows, quality=90, subsampling="420", out_stride=None):
+    """RGB images on the device -> complete baseline JPEG files, encoded on the GPU (csrc/jpeg.hip; the file is stated in
+    include/codetr_jpeg.h): the scan comes from two launches per PREPROCESS_BATCH_MAX images, the header from the
+    library's host builder.
+      src       one flat uint8 device buffer holding RGB HWC images (the buffer draw_detections drew on)
+      rows      (offset, H, W) per image
+      quality   1..100 (the IJG scale); subsampling '420' | '444'
+      out_stride  bytes reserved per image on the first attempt (default: jpeg_out_stride).  An image whose scan does not
+                fit is encoded once more with the proven worst case reserved, in one launch group with the others that
+                did not fit.
+    -> list[bytes], one file per row.  One device-to-host copy per launch group: the int32 lengths and the slots travel
+    in one buffer.  ValueError for a bad setting, a wrong dtype or shape, a CPU tensor, an image outside the buffer."""
+    st = jpeg_settings(dict(quality=quality, subsampling=subsampling))
+    if not torch.is_tensor(src) or not src.is_cuda:
+        raise ValueError("encode_jpeg: src must be a tensor on a GPU")
+    if src.dtype != torch.uint8 or src.dim() != 1 or not src.is_contiguous():
+        raise ValueError("encode_jpeg: expected one contiguous flat uint8 buffer")
+    rows = [tuple(int(v) for v in r) for r in rows]
+    for off, H, W in rows:
+        if not (1 <= H <= DRAW_MAX_SIDE and 1 <= W <= DRAW_MAX_SIDE) or off < 0 or off + H * W * 3 > src.numel():
+            raise ValueError(f"encode_jpeg: image (offset {off}, {H}x{W}) outside the buffer or larger than "
+                             f"{DRAW_MAX_SIDE} a side")
+    if out_stride is not None and (int(out_stride) != out_stride or out_stride < 1):
+        raise ValueError(f"encode_jpeg: out_stride must be a positive integer, got {out_stride!r}")
+    sub = _jpeg.SUBSAMPLINGS[st["subsampling"]]
+    scans = [None] * len(rows)
+
+    def group(index, stride):
+        """one launch group: encode rows[index] into slots of `stride` bytes -> the indices that did not fit"""
+        part = [rows[i] for i in index]
+        head = (4 * len(part) + 15) // 16 * 16   # the lengths lead the buffer, so that one copy brings both
+        out = torch.empty((head + len(part) * stride,), dtype=torch.uint8, device=src.device)
+        ws = torch.empty((_jpeg.workspace_bytes(part, sub, stride),), dtype=torch.uint8, device=src.device)
+        _jpeg.encode(src, part, st["quality"], sub, out[head:], stride, out[:head].view(torch.int32), ws)
+        host = out.cpu().numpy()
+        JPEG_DOWNLOADS["copies"] += 1
+        JPEG_DOWNLOADS["bytes"] += host.size
+        lengths = host[:head].view(np.int32)
+        missed = []
+        for k, i in enumerate(index):
+            if lengths[k] < 0:
+                missed.append(i)
+            else:
+                scans[i] = host[head + k * stride:head + k * stride + int(lengths[k])].tobytes()
+        return missed
+
+    with torch.cuda.device(src.device):
+        retry = []
+        for i in range(0, len(rows), PREPROCESS_BATCH_MAX):
+            index = list(range(i, min(len(rows), i + PREPROCESS_BATCH_MAX)))
+            stride = int(out_stride) if out_stride is not None else jpeg_out_stride([rows[k] for k in index], st["subsampling"])
+            retry += group(index, stride)
+        for i in range(0, len(retry), PREPROCESS_BATCH_MAX):
+            index = retry[i:i + PREPROCESS_BATCH_MAX]
+            bound = max(_jpeg.scan_bound(rows[k][1], rows[k][2], sub) for k in index)
+            if group(index, (bound + 15) // 16 * 16):
+                raise RuntimeError("encode_jpeg: a scan exceeded its proven bound")
+    return [_jpeg.header(H, W, st["quality"], sub) + scans[i] + b"\xff\xd9" for i, (_, H, W) in enumerate(rows)]
 
 
 FRAME_FORMATS = _cabi.FRAME_FORMATS

@@ -65,6 +65,11 @@ or ``"config"``, which reads ``line_width`` / ``alpha`` / ``text_color`` from ``
 for a config without that entry -- turns the drawing on: ``__call__(..., return_vis=True)`` returns one ``[H, W, 3]``
 uint8 array per image in ``results_dict["visualization"]``, and ``out_dir`` without ``no_save_vis`` writes
 ``out_dir/vis/%08d.png`` (PNG through stdlib ``zlib``, where the reference writes ``.jpg`` through cv2).
+``vis_format="jpeg"`` or ``dict(type="jpeg", quality=90, subsampling="420" | "444")`` writes the reference's
+``out_dir/vis/%08d.jpg`` instead: ``hip_ops.encode_jpeg`` encodes the chunk's images on the GPU where the drawing left
+them (the file is stated in ``include/codetr_jpeg.h``) and only the compressed bytes come back -- the RGB buffer is
+downloaded only when ``return_vis=True`` asks for the arrays; ``return_vis="jpeg"`` returns the files as ``bytes`` in
+``results_dict["visualization_jpeg"]``.  ``vis_format=None`` (or ``"png"``), the default, changes nothing.
 ``pred_score_thr`` is the drawing's score threshold; ``draw_pred=False`` returns the original images.  Class names:
 ``visualizer["classes"]``, else ``dataset_meta["classes"]``, else ``str(label)``; cut to 23 characters, a non-ASCII
 character becomes ``?``.  Palette: RGB triples from the same two places; for a name such as ``"coco"`` or nothing, a
@@ -425,6 +430,33 @@ def visualizer_settings(cfg, visualizer, dataset_meta=None):
                 colors=torch.tensor(palette, dtype=torch.uint8).view(-1, 3))
 
 
+VIS_FORMAT_KEYS = ("type", "quality", "subsampling")
+VIS_DOWNLOADS = {"rgb": 0}   # device-to-host copies of a chunk's whole RGB buffer made for the visualisation, this process
+
+
+def vis_format_settings(vis_format):
+    """How `Inferencer(..., vis_format=...)` reads its argument: None and "png" -> None (vis/%08d.png through zlib, as
+    before); "jpeg" or a dict with keys of VIS_FORMAT_KEYS, type "jpeg" -> dict(quality, subsampling), the validated
+    settings of hip_ops.encode_jpeg (vis/%08d.jpg, the reference's name, encoded on the GPU).  ValueError otherwise."""
+    if vis_format is None or vis_format == "png":
+        return None
+    if vis_format == "jpeg":
+        vis_format = dict(type="jpeg")
+    if not isinstance(vis_format, dict):
+        raise ValueError(f"vis_format must be None, 'png', 'jpeg' or a dict with keys of {VIS_FORMAT_KEYS}")
+    unknown = set(vis_format) - set(VIS_FORMAT_KEYS)
+    if unknown:
+        raise ValueError(f"vis_format: unknown key(s) {sorted(unknown)}; known: {list(VIS_FORMAT_KEYS)}")
+    kind = vis_format.get("type", "jpeg")
+    if kind == "png":
+        if len(vis_format) > 1:
+            raise ValueError("vis_format: type 'png' takes no settings")
+        return None
+    if kind != "jpeg":
+        raise ValueError(f"vis_format: type must be 'png' or 'jpeg', got {kind!r}")
+    return hip_ops.jpeg_settings({k: v for k, v in vis_format.items() if k != "type"})
+
+
 def write_png(path, image):
     """an RGB uint8 image [H, W, 3] as an 8-bit truecolour PNG: filter 0 on every row, one IDAT at a low zlib level"""
     image = np.ascontiguousarray(image, np.uint8)
@@ -443,7 +475,7 @@ def write_png(path, image):
 class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
-                 slicing=None, tracker=None):
+                 slicing=None, tracker=None, vis_format=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -492,6 +524,7 @@ class Inferencer:
             raise NotImplementedError("slicing together with tta is not built: one or the other")
         self.visualizer = visualizer_settings(self.cfg, visualizer, dataset_meta)
         self._vis_tables = {}   # device -> (names, colors) on it: uploaded on the first visualising call there
+        self.vis_format = vis_format_settings(vis_format)   # None: PNG files; a dict: JPEG files encoded on the GPU
         self.tracker = tracker_settings(tracker, self.cfg)
         self._track_state = None   # [rows, state bytes] uint8 on the device of the first tracked call
         self._track_rows = {}      # stream -> its row of _track_state
@@ -915,10 +948,16 @@ class Inferencer:
         return ids.cpu().numpy()
 
     # ---- visualisation and files --------------------------------------------------------------------------
-    def draw_chunk(self, src, rows, dets, pred_score_thr):
+    def download_chunk(self, src, rows):
+        """one device-to-host copy of the chunk's RGB buffer -> one [H, W, 3] uint8 array per image"""
+        VIS_DOWNLOADS["rgb"] += 1
+        host = src.cpu().numpy()
+        return [host[o:o + H * W * 3].reshape(H, W, 3).copy() for o, H, W in rows]
+
+    def draw_chunk(self, src, rows, dets, pred_score_thr, download=True):
         """the chunk's predictions drawn on its uploaded images: one hip_ops.draw_detections launch on the buffer the
         preprocessing read (in place, after it on the same stream) and one device-to-host copy of that buffer -> one
-        [H, W, 3] uint8 array per image"""
+        [H, W, 3] uint8 array per image (download=False: no copy, None per image -- the drawn images stay in `src`)"""
         v = self.visualizer
         key = str(src.device)
         if key not in self._vis_tables:
@@ -928,18 +967,22 @@ class Inferencer:
             # the hard path cuts to max_per_img on the host (postprocess_batch): the kernel gets the clamped count
             dets = dets._replace(count=dets.count.clamp(max=self.max_per_img))
         hip_ops.draw_detections(src, rows, dets, names, colors, dict(v["style"], score_thr=float(pred_score_thr)))
-        host = src.cpu().numpy()
-        return [host[o:o + H * W * 3].reshape(H, W, 3).copy() for o, H, W in rows]
+        return self.download_chunk(src, rows) if download else [None] * len(rows)
 
-    def save_outputs(self, pred, vis, out_dir, no_save_pred):
-        """the files of one image (reference pred2dict :303-341, visualize :214-219; PNG, not JPEG)"""
+    def save_outputs(self, pred, vis, out_dir, no_save_pred, jpeg=None):
+        """the files of one image (reference pred2dict :303-341, visualize :214-219): vis/%08d.png from the array `vis`,
+        or, with a JPEG vis_format, the reference's vis/%08d.jpg from the encoded file `jpeg`"""
         if out_dir == "":
             return
         if not no_save_pred:
             os.makedirs(os.path.join(out_dir, "preds"), exist_ok=True)
             with open(os.path.join(out_dir, "preds", f"{self.num_predicted_imgs}.json"), "w") as f:
                 json.dump(pred, f)
-        if vis is not None:
+        if jpeg is not None:
+            os.makedirs(os.path.join(out_dir, "vis"), exist_ok=True)
+            with open(os.path.join(out_dir, "vis", "%08d.jpg" % self.num_visualized_imgs), "wb") as f:
+                f.write(jpeg)
+        elif vis is not None:
             os.makedirs(os.path.join(out_dir, "vis"), exist_ok=True)
             write_png(os.path.join(out_dir, "vis", "%08d.png" % self.num_visualized_imgs), vis)
 
@@ -958,6 +1001,13 @@ class Inferencer:
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
         visualise = self.visualizer is not None and (return_vis or save_vis)
+        if isinstance(return_vis, str):
+            if return_vis != "jpeg" or self.vis_format is None:
+                raise ValueError('return_vis="jpeg" needs Inferencer(..., vis_format="jpeg"); otherwise pass a bool')
+            results_dict["visualization_jpeg"] = []
+        # a JPEG vis_format: the files come from the encoder, the arrays only when the caller asked for them
+        want_jpeg = visualise and self.vis_format is not None and (save_vis or return_vis == "jpeg")
+        want_arrays = visualise and (self.vis_format is None or (bool(return_vis) and return_vis != "jpeg"))
         if self.tracker is not None:
             streams = hip_ops.track_streams(streams, len(images))
         elif streams is not None:
@@ -992,20 +1042,24 @@ class Inferencer:
                         pred["track_ids"] = row[:len(pred["labels"])].tolist()
                 drawn = [None] * len(chunk)
                 if visualise and draw_pred:
-                    drawn = self.draw_chunk(src, rows, dets, pred_score_thr)
-                elif visualise and plain:   # the originals, as mmdet returns the undrawn image; nothing launched
+                    drawn = self.draw_chunk(src, rows, dets, pred_score_thr, download=want_arrays)
+                elif want_arrays and plain:   # the originals, as mmdet returns the undrawn image; nothing launched
                     drawn = [im.copy() for im in chunk]
-                elif visualise:             # the undrawn converted frames: one download of the chunk's RGB buffer
-                    host = src.cpu().numpy()
-                    drawn = [host[o:o + H * W * 3].reshape(H, W, 3).copy() for o, H, W in rows]
-            for pred, vis in zip(preds, drawn):
+                elif want_arrays:             # the undrawn converted frames: one download of the chunk's RGB buffer
+                    drawn = self.download_chunk(src, rows)
+                files = [None] * len(chunk)
+                if want_jpeg:   # on the images where the kernels left them: only the compressed bytes come back
+                    files = hip_ops.encode_jpeg(src, rows, self.vis_format["quality"], self.vis_format["subsampling"])
+            for pred, vis, jpeg in zip(preds, drawn, files):
                 if print_result:
                     print(pred)
-                self.save_outputs(pred, vis if save_vis else None, out_dir, no_save_pred)
+                self.save_outputs(pred, vis if save_vis else None, out_dir, no_save_pred, jpeg if save_vis else None)
                 self.num_predicted_imgs += 1
-                if vis is not None:
+                if vis is not None or jpeg is not None:
                     self.num_visualized_imgs += 1
-                    if return_vis:
+                    if vis is not None and return_vis and return_vis != "jpeg":
                         results_dict["visualization"].append(vis)
+                    if return_vis == "jpeg":
+                        results_dict["visualization_jpeg"].append(jpeg)
                 results_dict["predictions"].append(pred)
         return results_dict

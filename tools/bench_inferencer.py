@@ -29,6 +29,12 @@ image plain and mirrored).
 on 8 images of 1920x1280 with 300 and with 20 drawn detections each; and the device-to-host copy of that buffer, the
 one extra transfer a visualising chunk makes.
 
+`--vis png` / `--vis jpeg` print only a `vis_files` record (fp16): images/s of `Inferencer(visualizer={},
+vis_format=...)(frames, out_dir=<a tmpfs directory>)` at batch_size 8 over --images 1920x1080 frames (a gradient with +-6
+of noise), alternating with the same call of an Inferencer without a visualiser; with `jpeg` also the two encoder
+launches alone on eight of the frames (HIP events, bytes read + written per second beside a device-to-device copy of as
+many bytes) and Pillow's host encoder on one frame.
+
 `--slice` adds a `slice` sub-record (sliced inference, fp16): images/s of `Inferencer(slicing=dict(tile=(1280, 1280),
 overlap=0.2, full_image=True))` at batch_size 2 over --slice-images synthetic 3840x2160 images (8 tiles + the image: 9
 views each), beside the host composition it replaces on the same images -- per image the tiles cropped on the host, one
@@ -376,6 +382,99 @@ def vis_record(inf, images, repeats, bs=8):
     return rec
 
 
+def vis_frames(n, seed=3):
+    """n 1920x1080 RGB frames: a colour gradient with +-6 of noise per channel, a new noise field per frame (the entropy
+    of a photograph; uniform noise, which synthetic_images makes, is the worst case of any image coder)"""
+    rng = np.random.default_rng(seed)
+    H, W = 1080, 1920
+    yy, xx = np.mgrid[:H, :W]
+    base = np.stack([xx * 255 // (W - 1), yy * 255 // (H - 1), (xx + yy) * 255 // (W + H - 2)], -1).astype(np.int16)
+    return [np.clip(base + rng.integers(-6, 7, base.shape, dtype=np.int16), 0, 255).astype(np.uint8) for _ in range(n)]
+
+
+def jpeg_kernel_times(frames, quality=90, subsampling="420"):
+    """us per codetr_jpeg_encode_u8 call (both launches) on the frames, the bytes it has to read and write (the RGB
+    images and the scans) per second, beside a device-to-device copy of as many bytes, and Pillow's host encoder on one of
+    the frames where Pillow imports"""
+    from codetr import _jpeg, hip_ops
+
+    N, (H, W) = len(frames), frames[0].shape[:2]
+    src = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).to(DEV)
+    rows = [(n * H * W * 3, H, W) for n in range(N)]
+    sub = _jpeg.SUBSAMPLINGS[subsampling]
+    stride = hip_ops.jpeg_out_stride(rows, subsampling)
+    out = torch.empty((N * stride,), dtype=torch.uint8, device=DEV)
+    lengths = torch.empty((N,), dtype=torch.int32, device=DEV)
+    ws = torch.empty((_jpeg.workspace_bytes(rows, sub, stride),), dtype=torch.uint8, device=DEV)
+    _jpeg.encode(src, rows, quality, sub, out, stride, lengths, ws)
+    scan = [int(v) for v in lengths.cpu()]
+    moved = src.numel() + sum(scan)
+    a, b = torch.randint(0, 256, (moved // 2,), dtype=torch.uint8).to(DEV), torch.empty((moved // 2,), dtype=torch.uint8,
+                                                                                      device=DEV)
+    rec = {"frames": N, "frame_wh": [W, H], "quality": quality, "subsampling": subsampling, "bytes_read": src.numel(),
+           "bytes_written": sum(scan), "scan_bytes_per_frame": scan, "out_stride": stride, "workspace_bytes": ws.numel()}
+    for name, call in (("jpeg_encode_two_launches", lambda: _jpeg.encode(src, rows, quality, sub, out, stride, lengths, ws)),
+                       ("torch_copy_same_bytes", lambda: b.copy_(a)),
+                       ("jpeg_encode_two_launches_again", lambda: _jpeg.encode(src, rows, quality, sub, out, stride, lengths, ws)),
+                       ("torch_copy_same_bytes_again", lambda: b.copy_(a))):
+        us = _event_us_each(call, launches=100, warmup=10)
+        rec[name] = {"us_per_call_median": us, "gb_per_s": round(moved / us / 1e3, 1)}
+    try:
+        import io
+
+        from PIL import Image
+    except ImportError:
+        rec["pillow_host_encode_ms"] = None
+    else:
+        times = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            Image.fromarray(frames[0]).save(io.BytesIO(), "JPEG", quality=quality, subsampling=2 if subsampling == "420" else 0)
+            times.append(time.perf_counter() - t0)
+        rec["pillow_host_encode_ms"] = round(min(times) * 1e3, 2)
+    return rec
+
+
+def vis_files_record(inf, fmt, n_images, repeats, bs=8):
+    """images/s of `Inferencer(visualizer={}, vis_format=fmt)(frames, out_dir=<tmpfs>)` on 1920x1080 frames at batch_size
+    8, fp16, against the same call of an Inferencer without a visualiser, alternating; with fmt 'jpeg' also the encoder's
+    own time.  Random weights draw few boxes: the encoder's work depends on the image, not on the box count."""
+    import bench
+    from codetr.inferencer import Inferencer
+
+    frames = vis_frames(n_images)
+    plain = Inferencer(inf.model, bench.CFG, dataset_meta=None)
+    v = Inferencer(inf.model, bench.CFG, dataset_meta=None, visualizer={}, vis_format=fmt)
+    root = tempfile.mkdtemp(prefix="bench_vis_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    rec = {"vis_format": fmt, "batch_size": bs, "images": n_images, "frame_wh": [1920, 1080], "repeats": repeats,
+           "dtype": "fp16", "out_dir": "tmpfs" if root.startswith("/dev/shm") else "temporary directory"}
+    try:
+        for name, who in (("no_visualisation", plain), ("out_dir_vis", v), ("no_visualisation_again", plain),
+                          ("out_dir_vis_again", v)):
+            kw = dict(out_dir=os.path.join(root, name)) if who is v else {}
+            with torch.no_grad():
+                who(frames[:bs], device=DEV, dtype=torch.float16, batch_size=bs, **kw)   # warm-up
+                times = []
+                for _ in range(repeats):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = who(frames, device=DEV, dtype=torch.float16, batch_size=bs, **kw)
+                    times.append(time.perf_counter() - t0)
+            rec[name] = {"images_per_s": round(n_images / min(times), 2), "pass_s": [round(t, 4) for t in times]}
+            if who is v:
+                files = sorted(os.listdir(os.path.join(root, name, "vis")))
+                rec[name]["files"] = len(files)
+                rec[name]["file_bytes_mean"] = int(np.mean([os.path.getsize(os.path.join(root, name, "vis", f)) for f in files]))
+                rec[name]["first_file"] = files[0]
+        rec["detections_per_image"] = round(sum(len(p["labels"]) for p in out["predictions"]) / n_images, 1)
+        rec["drawn_above_0.3_per_image"] = round(sum(sum(s > 0.3 for s in p["scores"]) for p in out["predictions"]) / n_images, 1)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    if fmt == "jpeg":
+        rec["encoder"] = jpeg_kernel_times(frames[:8], v.vis_format["quality"], v.vis_format["subsampling"])
+    return rec
+
+
 FRAME_WH = (1920, 1080)
 
 
@@ -627,7 +726,9 @@ def main():
     ap.add_argument("--tta", action="store_true", help="add the test-time-augmentation sub-record")
     ap.add_argument("--tta-images", type=int, default=8)
     ap.add_argument("--tta-only", action="store_true", help="only the tta sub-record (implies --tta)")
-    ap.add_argument("--vis", action="store_true", help="add the visualisation sub-record")
+    ap.add_argument("--vis", nargs="?", const="on", choices=("on", "png", "jpeg"),
+                    help="alone: add the visualisation sub-record; png | jpeg: only the record of the drawn files written "
+                         "to an out_dir in that format (1920x1080 frames, batch_size 8, fp16)")
     ap.add_argument("--vis-only", action="store_true", help="only the vis sub-record (implies --vis)")
     ap.add_argument("--slice", action="store_true", help="add the sliced-inference sub-record")
     ap.add_argument("--slice-images", type=int, default=4)
@@ -660,6 +761,11 @@ def main():
         print(json.dumps({"metric": "Inferencer test-time augmentation (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass",
                           "tta": tta_record(infs["fp16"], a.tta_images, a.repeats)}))
+        return
+    if a.vis in ("png", "jpeg"):
+        print(json.dumps({"metric": "Inferencer visualisation files (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass; HIP events for the encoder",
+                          "vis_files": vis_files_record(infs["fp16"], a.vis, a.images, a.repeats)}))
         return
     if a.vis_only:
         print(json.dumps({"metric": "Inferencer visualisation (Swin-L config, random weights)",
