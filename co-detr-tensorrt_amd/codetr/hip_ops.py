@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _cabi, _jpeg
+from . import _assign, _cabi, _jpeg
 
 # ops served by hand-written HIP kernels in this build (kept in sync with include/codetr_hip.h)
 NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_window_attention(f16, head_dim 32)",
@@ -1134,7 +1134,10 @@ def track_state_to_host(state):
                       ints[:, 2].copy(), ints[:, 3].copy(), mean, cov)
 
 
-def track_update(dets, state, streams=None, settings=None):
+TRACK_ASSOCIATIONS = tuple(_assign.ASSOCIATIONS)   # "greedy" (the default, codetr_hip.h's rule) and "optimal"
+
+
+def track_update(dets, state, streams=None, settings=None, association="greedy"):
     """Tracking-by-detection for the frames of a chunk in one launch per PREPROCESS_BATCH_MAX rows (csrc/track.hip; the
     rule, modelled on mmdet's ByteTracker, is stated in include/codetr_hip.h): the three greedy associations, the Kalman
     filters, retirement and track starts of every stream on the device.
@@ -1143,9 +1146,14 @@ def track_update(dets, state, streams=None, settings=None):
       streams   the state index in [0, S) of every row: one int for all rows, or one per row; None: 0.  The rows of a
                 stream are its consecutive frames in row order (and from call to call)
       settings  the keys of TRACKER (track_settings); max_tracks must be the state's
+      association  "greedy": the three greedy associations of codetr_hip.h; "optimal": each association is an assignment
+                problem over integer gains, solved in the same launch (csrc/track_assign.hip; the rule is stated in
+                include/codetr_assign.h).  The state is the same: a stream may switch between calls
     -> [N, Q] int32 on the device: the id of the track each row updated or started, negated while the track is
     tentative, 0 for no track and beyond count."""
     cfg = track_settings(settings)
+    if not isinstance(association, str) or association not in _assign.ASSOCIATIONS:
+        raise ValueError(f"track_update: association must be one of {list(TRACK_ASSOCIATIONS)}, got {association!r}")
     scores = dets.scores
     _gpu(scores, "track_update")
     T = _track_slots(state)
@@ -1174,9 +1182,40 @@ def track_update(dets, state, streams=None, settings=None):
     with torch.cuda.device(scores.device):
         for i in range(0, N, PREPROCESS_BATCH_MAX):
             j = min(N, i + PREPROCESS_BATCH_MAX)
-            _cabi.track_update(boxes[i:j], scores[i:j], labels[i:j], count[i:j], streams[i:j], state, T, thr,
-                               cfg["num_frames_retain"], cfg["num_tentatives"], cfg["weight_iou_with_det_scores"], ids[i:j])
+            args = (boxes[i:j], scores[i:j], labels[i:j], count[i:j], streams[i:j], state, T, thr,
+                    cfg["num_frames_retain"], cfg["num_tentatives"], cfg["weight_iou_with_det_scores"], ids[i:j])
+            if association == "greedy":
+                _cabi.track_update(*args)
+            else:
+                _assign.track_update2(*args, _assign.ASSOCIATIONS[association])
     return ids
+
+
+ASSIGN_MAX_ROWS, ASSIGN_MAX_COLS, ASSIGN_MAX_GAIN = _assign.MAX_ROWS, _assign.MAX_COLS, _assign.MAX_GAIN
+
+
+def linear_assignment(gain):
+    """Maximum-weight assignment of integer gains on the GPU, one workgroup per problem in one launch (csrc/assign.hip;
+    the procedure and its tie rule are stated in include/codetr_assign.h, so the matches -- not just their total -- are
+    reproducible): the shape of a DETR matcher, up to 512 targets x 1024 queries, after the caller has turned its costs
+    into gains.
+      gain  [n, m] or [B, n, m] int32 on a GPU, n <= ASSIGN_MAX_ROWS, m <= ASSIGN_MAX_COLS; values are clamped into
+            [0, ASSIGN_MAX_GAIN]; a pair of gain 0 is never matched
+    -> (match [.., n] int32: the column of every row, -1 for unmatched; total [..] int64: the sum of the matched gains)"""
+    if not torch.is_tensor(gain) or gain.dtype != torch.int32 or gain.dim() not in (2, 3):
+        raise ValueError("linear_assignment: gain must be an int32 tensor [n, m] or [B, n, m]")
+    B, n, m = gain.shape if gain.dim() == 3 else (1,) + tuple(gain.shape)
+    if n > ASSIGN_MAX_ROWS or m > ASSIGN_MAX_COLS:
+        raise ValueError(f"linear_assignment: at most {ASSIGN_MAX_ROWS} rows x {ASSIGN_MAX_COLS} columns, got {n} x {m}")
+    _gpu(gain, "linear_assignment")
+    g = gain.contiguous().view(B, n, m)
+    match = torch.full((B, n), -1, dtype=torch.int32, device=g.device)
+    total = torch.zeros((B,), dtype=torch.int64, device=g.device)
+    if B and n and m:
+        with torch.cuda.device(g.device):
+            for i in range(0, B, 65535):
+                _assign.assign(g[i:i + 65535], match[i:i + 65535], total[i:i + 65535])
+    return (match, total) if gain.dim() == 3 else (match[0], total[0])
 
 
 def track_streams(streams, N):

@@ -106,6 +106,12 @@ The ids are cut as the detections are, the hard path's host-side ``max_per_img``
 sees every row of the launch's result).  The rule is stated in
 ``include/codetr_hip.h``; parity with mmdet is unpinned (it is not installed here): the association is greedy, labels
 are compared and ties go to the lowest slot and row.
+
+``track_association`` (with a tracker only): ``None``, the default, or ``"greedy"`` keeps that rule and its launch;
+``"optimal"`` makes each of the three associations an assignment problem over integer gains, as mmdet's ``lapjv`` call
+does, solved inside the same one launch per chunk (``include/codetr_assign.h`` states the gains, the procedure and its
+tie rule; ``csrc/track_assign.hip``).  Greedy loses an identity where two objects cross and the best single pair leaves
+the other track nothing above the threshold; the assignment keeps both.  The states are the same for both rules.
 """
 import collections
 import colorsys
@@ -434,6 +440,19 @@ VIS_FORMAT_KEYS = ("type", "quality", "subsampling")
 VIS_DOWNLOADS = {"rgb": 0}   # device-to-host copies of a chunk's whole RGB buffer made for the visualisation, this process
 
 
+def track_association_setting(track_association, tracker):
+    """How `Inferencer(..., track_association=...)` reads its argument: None -> "greedy"; a name of
+    hip_ops.TRACK_ASSOCIATIONS; ValueError for anything else, and for a name given without a tracker"""
+    if track_association is None:
+        return "greedy"
+    if not isinstance(track_association, str) or track_association not in hip_ops.TRACK_ASSOCIATIONS:
+        raise ValueError(f"track_association must be None or one of {list(hip_ops.TRACK_ASSOCIATIONS)}, "
+                         f"got {track_association!r}")
+    if tracker is None:
+        raise ValueError("track_association without a tracker: Inferencer(..., tracker=dict(...)) turns tracking on")
+    return track_association
+
+
 def vis_format_settings(vis_format):
     """How `Inferencer(..., vis_format=...)` reads its argument: None and "png" -> None (vis/%08d.png through zlib, as
     before); "jpeg" or a dict with keys of VIS_FORMAT_KEYS, type "jpeg" -> dict(quality, subsampling), the validated
@@ -475,7 +494,8 @@ def write_png(path, image):
 class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
-                 slicing=None, tracker=None, vis_format=None):
+                 slicing=None, tracker=None, vis_format=None,
+                 track_association=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -526,6 +546,7 @@ class Inferencer:
         self._vis_tables = {}   # device -> (names, colors) on it: uploaded on the first visualising call there
         self.vis_format = vis_format_settings(vis_format)   # None: PNG files; a dict: JPEG files encoded on the GPU
         self.tracker = tracker_settings(tracker, self.cfg)
+        self.track_association = track_association_setting(track_association, self.tracker)
         self._track_state = None   # [rows, state bytes] uint8 on the device of the first tracked call
         self._track_rows = {}      # stream -> its row of _track_state
         self.num_predicted_imgs = 0
@@ -944,7 +965,8 @@ class Inferencer:
             if have:
                 grown[:have].copy_(self._track_state)
             self._track_state = grown
-        ids = hip_ops.track_update(dets, self._track_state, [self._track_rows[s] for s in streams], self.tracker)
+        ids = hip_ops.track_update(dets, self._track_state, [self._track_rows[s] for s in streams], self.tracker,
+                                   self.track_association)
         return ids.cpu().numpy()
 
     # ---- visualisation and files --------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 // The Inferencer's tracking-by-detection on the GPU: a chunk's final detections (whatever post-processing or merge launch
 // produced them) -> one track id per detection row, the streams' track states kept on the device between calls.  The rule
 // -- candidates, the four two-state Kalman filters, the three greedy associations, retirement and track starts -- is
-// stated operation by operation in include/codetr_hip.h ("Tracking"); this file follows that text.
+// stated operation by operation in include/codetr_hip.h ("Tracking"); this file and track_common.h follow that text.
 //
 // track_update_kernel  one workgroup of 256 threads per stream.  The stream's rows of the launch are walked in row order
 //                     inside the one launch (a chunk of 8 frames of one camera is one launch); the state is read from the
@@ -15,235 +15,12 @@
 //                     whose best was the candidate just taken are recomputed.  Track starts take the k-th free slot for
 //                     the k-th starting candidate through two workgroup scans.
 // fp32 with one rounding per operation: contraction is off for the whole file, divisions are IEEE.
-// A separate translation unit from prepost.hip on purpose: the code of the kernels there is pinned.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "codetr_hip.h"
-#include "device_prims.h"
-#include "large_lds.h"
-
+// A separate translation unit from prepost.hip on purpose: the code of the kernels there is pinned.  The body lives in
+// track_common.h, which track_assign.hip (codetr_track_update2_*: the same walk with a choice of association) shares.
 #pragma clang fp contract(off)
+#include "track_common.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kOwn = CODETR_TRACK_MAX_TRACKS / kThreads;  // tracks a thread owns in a matching phase
-constexpr int kNone = 0x7fffffff;
-constexpr int kStaticLds = 1024;  // an upper bound of what the compiler adds for the workgroup votes (256 bytes today)
-static_assert(CODETR_TRACK_MAX_TRACKS % kThreads == 0, "a whole number of tracks per thread");
-
-struct Bf16 {
-  unsigned short bits;
-};
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
-__device__ __forceinline__ float to_f32(Bf16 v) { return bf16_to_f32(v.bits); }
-
-struct RowTable {  // a kernel argument, like prepost.hip's BatchTable: the stream of every row
-  int stream[CODETR_PREPROCESS_BATCH_MAX];
-};
-struct Settings {
-  float obj_high, obj_low, init_thr, match_high, match_low, match_tentative;
-  int retain, tentatives, weight_iou;
-};
-
-constexpr float kWp = 1.0f / 20.0f, kWv = 1.0f / 160.0f;
-
-// position / velocity standard deviation of coordinate c (0 cx, 1 cy, 2 a, 3 h) at height h
-__device__ __forceinline__ float std_p(int c, float h) { return c == 2 ? 1e-2f : kWp * h; }
-__device__ __forceinline__ float std_v(int c, float h) { return c == 2 ? 1e-5f : kWv * h; }
-
-// the workgroup's LDS, carved from one dynamic buffer
-struct Lds {
-  // the state, in the header's order
-  int* hdr;            // [4] f, issued, refused, 0
-  long long* label;    // [T]
-  int *id, *hits, *tent, *last;  // [T]
-  float* mean;         // [8][T]   (c * 2 + {p, v})
-  float* cov;          // [12][T]  (c * 3 + {A, B, C})
-  // working arrays
-  float4* tbox;        // [T] the predicted box of a live track
-  int* match;          // [T] the candidate a track took in this frame, -1: none
-  unsigned short* freelist;  // [T]
-  float4* cbox;        // [Q]
-  long long* clabel;   // [Q]
-  float* cscore;       // [Q]
-  int* out;            // [Q]
-  unsigned char* cls;  // [Q] 0: takes no part or taken, 1: high and free, 2: low and free
-  float* red_v;        // [2][kWaves]
-  int *red_t, *red_j;  // [2][kWaves]
-  int* wsum;           // [kWaves]
-};
-
-__host__ __device__ inline int64_t state_bytes_of(int64_t T) { return 16 + 104 * T; }
-__host__ __device__ inline int64_t round16(int64_t v) { return (v + 15) / 16 * 16; }
-__host__ __device__ inline int64_t lds_bytes_of(int64_t T, int64_t Q) {
-  return round16(state_bytes_of(T)) + 24 * T + 32 * Q + round16(Q) + 32 * kWaves;
-}
-
-__device__ __forceinline__ Lds carve(unsigned char* base, int T, int Q) {
-  Lds s;
-  unsigned char* p = base;
-  s.hdr = (int*)p, p += 16;
-  s.label = (long long*)p, p += 8 * T;
-  s.id = (int*)p, p += 4 * T;
-  s.hits = (int*)p, p += 4 * T;
-  s.tent = (int*)p, p += 4 * T;
-  s.last = (int*)p, p += 4 * T;
-  s.mean = (float*)p, p += 32 * T;
-  s.cov = (float*)p;
-  p = base + round16(state_bytes_of(T));  // the 16-byte items first, then 8, 4, 2 and 1
-  s.tbox = (float4*)p, p += 16 * T;
-  s.cbox = (float4*)p, p += 16 * Q;
-  s.clabel = (long long*)p, p += 8 * Q;
-  s.match = (int*)p, p += 4 * T;
-  s.cscore = (float*)p, p += 4 * Q;
-  s.out = (int*)p, p += 4 * Q;
-  s.red_v = (float*)p, p += 8 * kWaves;
-  s.red_t = (int*)p, p += 8 * kWaves;
-  s.red_j = (int*)p, p += 8 * kWaves;
-  s.wsum = (int*)p, p += 8 * kWaves;
-  s.freelist = (unsigned short*)p, p += 4 * T;  // (2 T used)
-  s.cls = p;
-  return s;
-}
-
-__device__ __forceinline__ float box_area(float4 b) {
-  const float w = b.z - b.x, h = b.w - b.y;
-  return w * h;
-}
-// the library's IoU (prepost.hip's soft_overlap): NaN for two zero-area boxes
-__device__ __forceinline__ float overlap(float4 bk, float ak, float4 bj, float aj) {
-  const float w = fmaxf(0.f, fminf(bk.z, bj.z) - fmaxf(bk.x, bj.x));
-  const float h = fmaxf(0.f, fminf(bk.w, bj.w) - fmaxf(bk.y, bj.y));
-  const float inter = w * h;
-  const float uni = ak + aj;
-  return inter / (uni - inter);
-}
-
-// (v, j) of the better of two bests: the higher value, ties to the lower j; j == kNone: no candidate
-__device__ __forceinline__ void take_better(float& v, int& j, float ov, int oj) {
-  if (oj != kNone && (j == kNone || ov > v || (ov == v && oj < j))) v = ov, j = oj;
-}
-
-// the best free candidate of class `cls` for track t, by the whole wave (t is wave-uniform): lanes stride over the
-// candidates, then one wave arg-max.  `skip`: a candidate taken so recently that its cls byte may not be visible yet.
-__device__ __forceinline__ void wave_best(const Lds& s, int t, int cnt, int cls, bool weighted, float thr, int skip,
-                                          int lane, float& best_v, int& best_j) {
-  const float4 tb = s.tbox[t];
-  const float ta = box_area(tb);
-  const long long tl = s.label[t];
-  float bv = 0.f;
-  int bj = kNone;
-  for (int j = lane; j < cnt; j += 64) {
-    if (s.cls[j] != cls || j == skip || s.clabel[j] != tl) continue;
-    const float4 cb = s.cbox[j];
-    const float iou = overlap(tb, ta, cb, box_area(cb));
-    const float val = weighted ? iou * s.cscore[j] : iou;
-    if (val >= thr && (bj == kNone || val > bv)) bv = val, bj = j;  // (a NaN compares false; ascending j: ties keep the lower)
-  }
-#pragma unroll
-  for (int m = 32; m > 0; m >>= 1) {
-    const float ov = __shfl_xor(bv, m, 64);
-    const int oj = __shfl_xor(bj, m, 64);
-    take_better(bv, bj, ov, oj);
-  }
-  best_v = bv, best_j = bj;
-}
-
-// exclusive rank of `flag` among the workgroup's threads in tid order + the total; two barriers (the second frees wsum)
-__device__ __forceinline__ int block_rank(bool flag, int* wsum, int lane, int wave, int& total) {
-  const unsigned long long b = __ballot(flag);
-  const int r = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) wsum[wave] = __popcll(b);
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    const int c = wsum[w];
-    before += w < wave ? c : 0;
-    all += c;
-  }
-  __syncthreads();
-  total = all;
-  return before + r;
-}
-
-// one greedy association (steps 3 to 5 of the rule).  kind 0: confirmed tracks, 1: tentative tracks, 2: confirmed tracks
-// matched in the previous frame.  Ends with a barrier.
-__device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f, int kind, int cls, bool weighted, float thr,
-                                            int tid) {
-  const int lane = tid & 63, wave = tid >> 6;
-  float bv[kOwn];
-  int bj[kOwn];
-  bool any = false;
-#pragma unroll
-  for (int k = 0; k < kOwn; ++k) {
-    const int t = tid + k * kThreads;
-    bool elig = false;
-    if (t < T && s.id[t] != 0 && s.match[t] < 0) {
-      const bool tent = s.tent[t] != 0;
-      elig = kind == 1 ? tent : (!tent && (kind == 0 || s.last[t] == f - 1));
-    }
-    bv[k] = 0.f, bj[k] = kNone;
-    unsigned long long need = __ballot(elig);
-    while (need) {  // (wave-uniform)
-      const int l = __ffsll((long long)need) - 1;
-      need &= need - 1;
-      float v;
-      int j;
-      wave_best(s, wave * 64 + l + k * kThreads, cnt, cls, weighted, thr, -1, lane, v, j);
-      if (lane == l) bv[k] = v, bj[k] = j;
-    }
-    any |= elig;
-  }
-  if (__syncthreads_or(any) == 0) return;
-  for (int buf = 0;; buf ^= 1) {
-    // the workgroup's best pair: the highest value, ties to the lowest slot (a track's own best is its lowest j)
-    float v = 0.f;
-    int t = kNone, j = kNone;
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k)  // (ascending slot: a tie keeps the lower)
-      if (bj[k] != kNone && (t == kNone || bv[k] > v)) v = bv[k], t = tid + k * kThreads, j = bj[k];
-#pragma unroll
-    for (int m = 32; m > 0; m >>= 1) {
-      const float ov = __shfl_xor(v, m, 64);
-      const int ot = __shfl_xor(t, m, 64), oj = __shfl_xor(j, m, 64);
-      if (ot != kNone && (t == kNone || ov > v || (ov == v && ot < t))) v = ov, t = ot, j = oj;
-    }
-    if (lane == 0) s.red_v[buf * kWaves + wave] = v, s.red_t[buf * kWaves + wave] = t, s.red_j[buf * kWaves + wave] = j;
-    __syncthreads();
-    v = 0.f, t = kNone, j = kNone;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      const float ov = s.red_v[buf * kWaves + w];
-      const int ot = s.red_t[buf * kWaves + w], oj = s.red_j[buf * kWaves + w];
-      if (ot != kNone && (t == kNone || ov > v || (ov == v && ot < t))) v = ov, t = ot, j = oj;
-    }
-    if (t == kNone) break;  // (uniform)
-#pragma unroll
-    for (int k = 0; k < kOwn; ++k) {
-      const bool mine = t == tid + k * kThreads;
-      if (mine) {
-        s.match[t] = j;
-        s.cls[j] = 0;  // taken: seen by the other waves after the next barrier, skipped by name until then
-        bj[k] = kNone;
-      }
-      unsigned long long need = __ballot(!mine && bj[k] == j);
-      while (need) {
-        const int l = __ffsll((long long)need) - 1;
-        need &= need - 1;
-        float nv;
-        int nj;
-        wave_best(s, wave * 64 + l + k * kThreads, cnt, cls, weighted, thr, j, lane, nv, nj);
-        if (lane == l) bv[k] = nv, bj[k] = nj;
-      }
-    }
-  }
-  __syncthreads();
-}
 
 template <class T>
 __global__ __launch_bounds__(kThreads) void track_update_kernel(const T* __restrict__ boxes, const T* __restrict__ scores,
@@ -252,202 +29,34 @@ __global__ __launch_bounds__(kThreads) void track_update_kernel(const T* __restr
                                                                 unsigned char* __restrict__ states, int maxT, Settings cfg,
                                                                 int* __restrict__ ids_out) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int b = blockIdx.x;
-  bool have = false;
-  for (int n = 0; n < N; ++n) have |= tab.stream[n] == b;  // (uniform)
-  if (!have) return;  // a stream without a row in this launch keeps its state bytes
-
-  const Lds s = carve(lds_raw, maxT, Q);
-  const int64_t sbytes = state_bytes_of(maxT);
-  {  // the state is one run of dwords in both places
-    const unsigned* g = reinterpret_cast<const unsigned*>(states + (int64_t)b * sbytes);
-    unsigned* l = reinterpret_cast<unsigned*>(lds_raw);
-    for (int64_t i = tid; i < sbytes / 4; i += kThreads) l[i] = g[i];
-  }
-  __syncthreads();
-  int f = s.hdr[0], issued = s.hdr[1], refused = s.hdr[2];  // (uniform, kept in registers over the frames)
-
-  for (int n = 0; n < N; ++n) {
-    if (tab.stream[n] != b) continue;  // (uniform)
-    const int cnt = min(max(count[n], 0), Q);
-
-    // 1. candidates
-    for (int j = tid; j < Q; j += kThreads) {
-      unsigned char cls = 0;
-      if (j < cnt) {
-        const T* bp = boxes + ((int64_t)n * Q + j) * 4;
-        const float4 cb = make_float4(to_f32(bp[0]), to_f32(bp[1]), to_f32(bp[2]), to_f32(bp[3]));
-        const float sc = to_f32(scores[(int64_t)n * Q + j]);
-        const bool finite = __builtin_isfinite(cb.x) && __builtin_isfinite(cb.y) && __builtin_isfinite(cb.z) &&
-                            __builtin_isfinite(cb.w) && __builtin_isfinite(sc);
-        if (finite && cb.z - cb.x > 0.f && cb.w - cb.y > 0.f) cls = sc > cfg.obj_high ? 1 : (sc > cfg.obj_low ? 2 : 0);
-        s.cbox[j] = cb;
-        s.cscore[j] = sc;
-        s.clabel[j] = labels[(int64_t)n * Q + j];
-      }
-      s.cls[j] = cls;
-      s.out[j] = 0;
-    }
-    // 2. predict
-    for (int t = tid; t < maxT; t += kThreads) {
-      s.match[t] = -1;
-      if (s.id[t] == 0) continue;
-      if (s.last[t] != f - 1) s.mean[7 * maxT + t] = 0.f;
-      const float h = s.mean[6 * maxT + t];
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float* m = s.mean + (2 * c) * maxT + t;
-        float* q = s.cov + (3 * c) * maxT + t;
-        const float A = q[0], B = q[maxT], C = q[2 * maxT];
-        const float sp = std_p(c, h), sv = std_v(c, h);
-        m[0] = m[0] + m[maxT];
-        q[0] = ((A + 2.f * B) + C) + sp * sp;
-        q[maxT] = B + C;
-        q[2 * maxT] = C + sv * sv;
-      }
-      const float cx = s.mean[t], cy = s.mean[2 * maxT + t], a = s.mean[4 * maxT + t], hh = s.mean[6 * maxT + t];
-      const float w = a * hh;
-      const float hw = w * 0.5f, hv = hh * 0.5f;
-      s.tbox[t] = make_float4(cx - hw, cy - hv, cx + hw, cy + hv);
-    }
-    __syncthreads();
-
-    // 3. to 5. the three associations
-    match_phase(s, maxT, cnt, f, 0, 1, cfg.weight_iou != 0, cfg.match_high, tid);
-    match_phase(s, maxT, cnt, f, 1, 1, cfg.weight_iou != 0, cfg.match_tentative, tid);
-    match_phase(s, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
-
-    // 6. update the matched tracks, 7. free slots
-    for (int t = tid; t < maxT; t += kThreads) {
-      const int id = s.id[t];
-      if (id == 0) continue;
-      const int j = s.match[t];
-      if (j >= 0) {
-        const float4 cb = s.cbox[j];
-        const float zh = cb.w - cb.y;
-        const float z[4] = {(cb.x + cb.z) * 0.5f, (cb.y + cb.w) * 0.5f, (cb.z - cb.x) / zh, zh};
-        const float h = s.mean[6 * maxT + t];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          float* m = s.mean + (2 * c) * maxT + t;
-          float* q = s.cov + (3 * c) * maxT + t;
-          const float A = q[0], B = q[maxT], C = q[2 * maxT];
-          const float sr = c == 2 ? 1e-1f : kWp * h;
-          const float S = A + sr * sr;
-          const float k0 = A / S, k1 = B / S;
-          const float y = z[c] - m[0];
-          m[0] = m[0] + k0 * y;
-          m[maxT] = m[maxT] + k1 * y;
-          q[0] = A - k0 * A;
-          q[maxT] = B - k0 * B;
-          q[2 * maxT] = C - k1 * B;
-        }
-        const int hits = s.hits[t] + 1;
-        s.hits[t] = hits;
-        s.last[t] = f;
-        s.label[t] = s.clabel[j];
-        int tent = s.tent[t];
-        if (tent && hits >= cfg.tentatives) s.tent[t] = tent = 0;
-        s.out[j] = tent ? -id : id;
-      } else if (s.tent[t] != 0 || f - s.last[t] >= cfg.retain) {  // a freed slot is all zero
-        s.id[t] = 0, s.hits[t] = 0, s.tent[t] = 0, s.last[t] = 0, s.label[t] = 0;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) s.mean[i * maxT + t] = 0.f;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) s.cov[i * maxT + t] = 0.f;
-      }
-    }
-    __syncthreads();
-
-    // 8. start tracks: the k-th starting candidate (ascending j) takes the k-th free slot (ascending)
-    int nfree = 0;
-    for (int base = 0; base < maxT; base += kThreads) {  // (uniform trip count)
-      const int t = base + tid;
-      const bool fr = t < maxT && s.id[t] == 0;
-      int tot;
-      const int r = nfree + block_rank(fr, s.wsum, lane, wave, tot);
-      if (fr) s.freelist[r] = (unsigned short)t;
-      nfree += tot;
-    }
-    __syncthreads();
-    int nstart = 0;
-    for (int base = 0; base < cnt; base += kThreads) {  // (uniform trip count)
-      const int j = base + tid;
-      const bool st = j < cnt && s.cls[j] == 1 && s.cscore[j] > cfg.init_thr;
-      int tot;
-      const int r = nstart + block_rank(st, s.wsum, lane, wave, tot);
-      if (st && r < nfree) {
-        const int t = s.freelist[r];
-        const float4 cb = s.cbox[j];
-        const float zh = cb.w - cb.y;
-        const float z[4] = {(cb.x + cb.z) * 0.5f, (cb.y + cb.w) * 0.5f, (cb.z - cb.x) / zh, zh};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const float sp = c == 2 ? 1e-2f : 2.f * std_p(c, zh), sv = c == 2 ? 1e-5f : 10.f * std_v(c, zh);
-          s.mean[(2 * c) * maxT + t] = z[c];
-          s.mean[(2 * c + 1) * maxT + t] = 0.f;
-          s.cov[(3 * c) * maxT + t] = sp * sp;
-          s.cov[(3 * c + 1) * maxT + t] = 0.f;
-          s.cov[(3 * c + 2) * maxT + t] = sv * sv;
-        }
-        const int id = issued + r + 1, tent = f != 0;
-        s.id[t] = id, s.hits[t] = 1, s.tent[t] = tent, s.last[t] = f, s.label[t] = s.clabel[j];
-        s.out[j] = tent ? -id : id;
-      }
-      nstart += tot;
-    }
-    issued += min(nstart, nfree);
-    refused += max(nstart - nfree, 0);
-    __syncthreads();
-
-    // 9. one id per candidate row, 0 beyond the count
-    for (int j = tid; j < Q; j += kThreads) ids_out[(int64_t)n * Q + j] = j < cnt ? s.out[j] : 0;
-    f += 1;
-    __syncthreads();
-  }
-
-  if (tid == 0) s.hdr[0] = f, s.hdr[1] = issued, s.hdr[2] = refused, s.hdr[3] = 0;
-  __syncthreads();
-  {
-    unsigned* g = reinterpret_cast<unsigned*>(states + (int64_t)b * sbytes);
-    const unsigned* l = reinterpret_cast<const unsigned*>(lds_raw);
-    for (int64_t i = tid; i < sbytes / 4; i += kThreads) g[i] = l[i];
-  }
+  const int tid = threadIdx.x;
+  track_stream(lds_raw, boxes, scores, labels, count, N, Q, tab, states, maxT, cfg, ids_out,
+               [&](const Lds& s, int cnt, int f) {  // 3. to 5. the three associations
+                 match_phase(s, maxT, cnt, f, 0, 1, cfg.weight_iou != 0, cfg.match_high, tid);
+                 match_phase(s, maxT, cnt, f, 1, 1, cfg.weight_iou != 0, cfg.match_tentative, tid);
+                 match_phase(s, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
+               });
 }
 
 template <class T>
 int launch_track(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count, int64_t N,
                  int64_t Q, const int* stream_of_row, int64_t S, void* state, int64_t max_tracks, const float* settings,
                  int64_t retain, int64_t tentatives, int weight_iou, int* ids_out) {
-  if (!boxes || !scores || !labels || !count || !stream_of_row || !state || !settings || !ids_out || N <= 0 || Q <= 0 ||
-      S <= 0 || max_tracks <= 0 || retain < 1 || tentatives < 1)
-    return CODETR_E_BADARG;
-  if (N > CODETR_PREPROCESS_BATCH_MAX || Q > CODETR_POSTPROCESS_MAX_Q || max_tracks > CODETR_TRACK_MAX_TRACKS ||
-      S > 0x7fffffffLL)
-    return CODETR_E_TOO_LARGE;
-  for (int i = 0; i < 6; ++i)
-    if (!__builtin_isfinite(settings[i])) return CODETR_E_BADARG;
-  RowTable tab = {};
-  for (int64_t n = 0; n < N; ++n) {
-    if (stream_of_row[n] < 0 || stream_of_row[n] >= S) return CODETR_E_BADARG;
-    tab.stream[n] = stream_of_row[n];
-  }
-  for (int64_t n = N; n < CODETR_PREPROCESS_BATCH_MAX; ++n) tab.stream[n] = -1;
-  const Settings cfg = {settings[0], settings[1], settings[2], settings[3], settings[4], settings[5],
-                        (int)(retain > 0x7fffffffLL ? 0x7fffffffLL : retain),
-                        (int)(tentatives > 0x7fffffffLL ? 0x7fffffffLL : tentatives), weight_iou ? 1 : 0};
-  const int64_t lds = lds_bytes_of(max_tracks, Q);
-  if (lds + kStaticLds > 64 * 1024)  // (the opt-in is needed once dynamic + static LDS pass 64 KB)
-    if (const hipError_t e = allow_large_lds<track_update_kernel<T>>(
-            (int)lds_bytes_of(CODETR_TRACK_MAX_TRACKS, CODETR_POSTPROCESS_MAX_Q));
-        e != hipSuccess)
-      return (int)e;
-  hipLaunchKernelGGL((track_update_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
-                     static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores), labels,
-                     count, (int)N, (int)Q, tab, static_cast<unsigned char*>(state), (int)max_tracks, cfg, ids_out);
-  const hipError_t err = hipGetLastError();
-  return err == hipSuccess ? 0 : (int)err;
+  return checked_track_launch(
+      boxes, scores, labels, count, N, Q, stream_of_row, S, state, max_tracks, settings, retain, tentatives, weight_iou,
+      ids_out, [&](const RowTable& tab, const Settings& cfg) -> hipError_t {
+        const int64_t lds = lds_bytes_of(max_tracks, Q);
+        if (lds + kStaticLds > 64 * 1024)  // (the opt-in is needed once dynamic + static LDS pass 64 KB)
+          if (const hipError_t e = allow_large_lds<track_update_kernel<T>>(
+                  (int)lds_bytes_of(CODETR_TRACK_MAX_TRACKS, CODETR_POSTPROCESS_MAX_Q));
+              e != hipSuccess)
+            return e;
+        hipLaunchKernelGGL((track_update_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
+                           static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                           labels, count, (int)N, (int)Q, tab, static_cast<unsigned char*>(state), (int)max_tracks, cfg,
+                           ids_out);
+        return hipSuccess;
+      });
 }
 
 }  // namespace

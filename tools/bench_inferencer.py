@@ -49,7 +49,9 @@ the Inferencer at batch_size 8 over --images frames of 1920x1080 fed as host fra
 as GPU-resident tensors, and as host RGB arrays converted beforehand (the conversion is not timed: the fairest thing
 the RGB-only route can do), the three in turn, three times.
 
-`--track` prints only a `track` record (tracking, fp16): track_update_kernel alone on 300 detection rows of which 100 are
+`--track` prints only a `track` record (tracking, fp16; the greedy and the optimal association alternating, a crowd of
+overlapping objects with the solver's rounds per frame, codetr_assign_i32 beside scipy, and a tracked-optimal arm of the
+Inferencer): the tracking kernels alone on 300 detection rows of which 100 are
 moving objects -- HIP event pairs as above, 8 frames of one stream in a launch and one frame of each of 8 streams --;
 and images/s of the Inferencer at batch_size 8 over --images images taken as the frames of one stream with
 `tracker={}`, without a tracker, and with the host composition the tracker replaces (the untracked call's predictions
@@ -584,20 +586,135 @@ def track_detections(frames, Q=300, objects=100, seed=5):
                               torch.tensor(labels).to(DEV), torch.full((frames,), Q, dtype=torch.int32, device=DEV), None)
 
 
+def crowd_detections(frames, Q=300, objects=100, seed=9, side=350.0):
+    """`frames` frames of Q fp16 rows: `objects` boxes of about 90 x 150 of ONE label wandering inside a side x side
+    square, so that every box overlaps many others (the workload on which the associations differ), the other rows
+    low-score clutter in the same square -> (hip_ops.Detections on the device, the same arrays on the host)"""
+    from codetr import hip_ops
+
+    rng = np.random.default_rng(seed)
+    c0, wh = rng.uniform(0, side, (objects, 2)), rng.uniform((80, 130), (100, 170), (objects, 2))
+    v = rng.uniform(-8, 8, (objects, 2))
+    boxes, scores = np.zeros((frames, Q, 4), np.float32), np.zeros((frames, Q), np.float32)
+    for f in range(frames):
+        c = c0 + v * f + rng.uniform(-4, 4, (objects, 2))
+        boxes[f, :objects] = np.concatenate((c - wh / 2, c + wh / 2), 1)
+        scores[f, :objects] = rng.uniform(0.75, 0.95, objects)
+        cc, cw = rng.uniform(0, side, (Q - objects, 2)), rng.uniform(40, 120, (Q - objects, 2))
+        boxes[f, objects:] = np.concatenate((cc, cc + cw), 1)
+        scores[f, objects:] = rng.uniform(0.15, 0.55, Q - objects)
+    labels = np.zeros((frames, Q), np.int64)
+    b16, s16 = torch.tensor(boxes).half(), torch.tensor(scores).half()
+    dets = hip_ops.Detections(b16.to(DEV), s16.to(DEV), torch.tensor(labels).to(DEV),
+                              torch.full((frames,), Q, dtype=torch.int32, device=DEV), None)
+    return dets, (b16, s16, labels)
+
+
 def track_kernel_times(Q=300, objects=100):
-    """us per launch of track_update_kernel: 8 frames of one stream, and one frame of each of 8 streams; the states hold
-    about `objects` live tracks (8 frames are walked before the clock starts)"""
+    """us per launch of the tracking kernels, greedy (track_update_kernel) and optimal (track_update2_kernel) alternating
+    in one session: 8 frames of one stream, one frame of each of 8 streams, and 8 frames of a crowd of overlapping
+    objects; the states hold about `objects` live tracks (8 frames are walked before the clock starts).  For the crowd
+    the restatements (tests/) give the solver's rounds per frame and the frames on which the two associations differ."""
     from codetr import hip_ops
 
     dets = track_detections(8, Q, objects)
+    crowd, crowd_host = crowd_detections(16, Q, objects)
+    first, second = [hip_ops.Detections(*(None if t is None else t[i:i + 8] for t in crowd)) for i in (0, 8)]
     rec = {"Q": Q, "objects": objects}
-    for name, streams in (("8_frames_of_1_stream", [0] * 8), ("1_frame_of_8_streams", list(range(8)))):
-        state = hip_ops.new_track_state(8, hip_ops.TRACKER["max_tracks"], DEV)
-        for _ in range(8 if len(set(streams)) > 1 else 1):
-            hip_ops.track_update(dets, state, streams)
-        us = _event_us_each(lambda: hip_ops.track_update(dets, state, streams), launches=100, warmup=5)
-        host = hip_ops.track_state_to_host(state)
-        rec[name] = {"us_per_launch_median": us, "live_tracks_per_stream": int((host.id[0] != 0).sum())}
+    # crowd_replayed: the chunk shown a second time, i.e. every object jumps back by 8 frames of its motion at once -- a
+    # cut in the video; the tracks no longer sit on their objects and the augmenting paths grow long
+    for name, streams, warm, timed in (("8_frames_of_1_stream", [0] * 8, [dets], dets),
+                                       ("1_frame_of_8_streams", list(range(8)), [dets] * 8, dets),
+                                       ("crowd_8_frames_of_1_stream", [0] * 8, [first], second),
+                                       ("crowd_replayed_8_frames_of_1_stream", [0] * 8, [first, second], second)):
+        rec[name] = {}
+        states, keeps = {}, {}
+        for association in hip_ops.TRACK_ASSOCIATIONS:
+            states[association] = state = hip_ops.new_track_state(8, hip_ops.TRACKER["max_tracks"], DEV)
+            for chunk in warm:
+                hip_ops.track_update(chunk, state, streams, association=association)
+            keeps[association] = state.clone()
+        for turn in range(2):                                                 # greedy and optimal alternating
+            for association in hip_ops.TRACK_ASSOCIATIONS:
+                state, keep = states[association], keeps[association]
+
+                def timed_call():
+                    hip_ops.track_update(timed, state, streams, association=association)
+
+                if timed is dets:         # r17's workloads: the state moves on from launch to launch, as r17 measured
+                    us = _event_us_each(timed_call, launches=100, warmup=5)
+                else:
+                    us = _track_us_restoring(state, keep, timed_call)
+                host = hip_ops.track_state_to_host(state)
+                rec[name].setdefault(association, {"us_per_launch_median": []})["us_per_launch_median"].append(us)
+                rec[name][association]["live_tracks_per_stream"] = int((host.id[0] != 0).sum())
+    # the crowd through the two restatements: rounds per frame, and where the associations part ways
+    import track_assign_ref
+    import track_ref
+    g, o = track_ref.TrackRef(), track_assign_ref.TrackAssignRef()
+    rounds, differ, before = [], 0, 0
+    for f in range(16):
+        ids_g = g.update(crowd_host[0][f], crowd_host[1][f], crowd_host[2][f])
+        ids_o = o.update(crowd_host[0][f], crowd_host[1][f], crowd_host[2][f])
+        differ += int(f >= 8 and not np.array_equal(ids_g, ids_o))
+        rounds.append(o.log["rounds"] - before)
+        before = o.log["rounds"]
+    rec["crowd_8_frames_of_1_stream"]["solver_rounds_per_frame"] = rounds[8:]
+    rec["crowd_8_frames_of_1_stream"]["frames_where_greedy_and_optimal_differ"] = differ
+    rounds = []
+    for f in range(8, 16):
+        o.update(crowd_host[0][f], crowd_host[1][f], crowd_host[2][f])
+        rounds.append(o.log["rounds"] - before)
+        before = o.log["rounds"]
+    rec["crowd_replayed_8_frames_of_1_stream"]["solver_rounds_per_frame"] = rounds
+    o2 = track_assign_ref.TrackAssignRef()
+    h = [t.cpu() if torch.is_tensor(t) else t for t in (dets.boxes, dets.scores, dets.labels)]
+    for _ in range(2):
+        before = o2.log["rounds"]
+        for f in range(8):
+            o2.update(h[0][f], h[1][f], h[2][f].numpy())
+    rec["8_frames_of_1_stream"]["solver_rounds_per_launch"] = o2.log["rounds"] - before
+    return rec
+
+
+def _track_us_restoring(state, keep, call, launches=50, warmup=3):
+    """median us of one launch that always starts from the state `keep` (restored outside the event pair)"""
+    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(launches)]
+    for i in range(warmup + launches):
+        state.copy_(keep)
+        if i >= warmup:
+            pairs[i - warmup][0].record()
+        call()
+        if i >= warmup:
+            pairs[i - warmup][1].record()
+    torch.cuda.synchronize()
+    return round(float(np.median([t0.elapsed_time(t1) for t0, t1 in pairs])) * 1e3, 2)
+
+
+def assign_times():
+    """codetr_assign_i32 beside scipy.optimize.linear_sum_assignment on this box's CPU: 100 x 900 (a DETR matcher's
+    shape; gains at 10 % density) with B = 8, and 300 x 300 dense; us per launch (event pairs, median) / per call"""
+    from scipy.optimize import linear_sum_assignment
+    from codetr import hip_ops
+    import assign_ref
+
+    rng = np.random.default_rng(1)
+    rec = {}
+    for name, (B, n, m, density) in (("100x900_B8", (8, 100, 900, 0.1)), ("100x900_B8_dense", (8, 100, 900, 1.0)),
+                                     ("300x300_dense", (1, 300, 300, 1.0))):
+        G = rng.integers(1, hip_ops.ASSIGN_MAX_GAIN + 1, (B, n, m)) * (rng.random((B, n, m)) < density)
+        dev = torch.tensor(G.astype(np.int32)).to(DEV)
+        match, total = hip_ops.linear_assignment(dev)
+        us = _event_us_each(lambda: hip_ops.linear_assignment(dev), launches=50, warmup=3)
+        t = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            want = [int(G[b][linear_sum_assignment(G[b], maximize=True)].sum()) for b in range(B)]
+            t.append(time.perf_counter() - t0)
+        rounds = [assign_ref.solve(G[b])[2] for b in range(B)]
+        rec[name] = {"gpu_us_per_launch_median": us, "scipy_us_median": round(float(np.median(t)) * 1e6, 1),
+                     "totals_equal_scipy": total.tolist() == want, "rounds_per_problem": rounds,
+                     "gpu_us_per_round_of_the_longest": round(us / max(rounds), 3)}
     return rec
 
 
@@ -609,12 +726,18 @@ def track_record(inf, images, repeats, bs=8):
     from codetr.inferencer import Inferencer
 
     tracked = Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={})
-    rec = {"batch_size": bs, "images": len(images), "repeats": repeats, "dtype": "fp16", "kernel": track_kernel_times()}
+    optimal = Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={}, track_association="optimal")
+    rec = {"batch_size": bs, "images": len(images), "repeats": repeats, "dtype": "fp16", "kernel": track_kernel_times(),
+           "assign": assign_times()}
     host_ref = [None]
 
     def with_tracker():
         tracked.reset_tracks()
         return tracked(images, device=DEV, dtype=torch.float16, batch_size=bs)["predictions"]
+
+    def with_tracker_optimal():
+        optimal.reset_tracks()
+        return optimal(images, device=DEV, dtype=torch.float16, batch_size=bs)["predictions"]
 
     def without():
         return inf(images, device=DEV, dtype=torch.float16, batch_size=bs)["predictions"]
@@ -628,7 +751,8 @@ def track_record(inf, images, repeats, bs=8):
                                         np.asarray(p["labels"], np.int64)).tolist()
         return preds
 
-    arms = {"with_tracker": with_tracker, "without_tracker": without, "host_composition": host_composition}
+    arms = {"with_tracker": with_tracker, "with_tracker_optimal": with_tracker_optimal, "without_tracker": without,
+            "host_composition": host_composition}
     for name in arms:
         rec[name] = {"pass_s": []}
     with torch.no_grad():
