@@ -34,20 +34,35 @@
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "gemm_epilogue.h"
 
 namespace {
 
 constexpr int BM = 128, BN = 128;
 constexpr int kThreads = 256;
-constexpr int kStagePitch = 64 * 2 + 16;            // epilogue staging: bytes per staged row of a wave's 64x64 quadrant
-constexpr int kStagingBytes = 4 * 64 * kStagePitch;  // 36,864 B for the 4 waves
+constexpr int kStagingBytes = 4 * 64 * kStagePitch;  // epilogue staging (gemm_epilogue.h): 36,864 B for the 4 waves
 
+// f(std::integral_constant<int, ACT>) for the run-time activation code `act` (0 .. 3, checked by the callers)
+template <class F>
+__host__ __device__ __forceinline__ auto dispatch_act(int act, F f) {
+  switch (act) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    default: return f(std::integral_constant<int, 2>{});
+  }
+}
 
-// act 3 (ReLU after the residual, the ResNet bottleneck's relu(bn3(conv3(x)) + identity)): the accumulator leaves
-// without activation, the ReLU is applied to the sum with the residual (the same two roundings as act 0 + residual,
-// then the exact ReLU); with no residual, act 3 is act 1
-template <bool ON>
-__device__ __forceinline__ float relu_if(float x) { return ON ? (x < 0.f ? 0.f : x) : x; }
+// a launcher's operands as the kernels take them
+const unsigned short* u16(const void* p) { return static_cast<const unsigned short*>(p); }
+struct Operands {
+  const unsigned short *x, *w, *b, *r;
+  unsigned short* y;
+  const unsigned char* mk;
+  Operands(const void* X, const void* W, const void* bias, const void* R, void* Y, const void* mask = nullptr)
+      : x(u16(X)), w(u16(W)), b(u16(bias)), r(u16(R)), y(static_cast<unsigned short*>(Y)),
+        mk(static_cast<const unsigned char*>(mask)) {}
+};
 
 // LDS image of one operand tile: [128 rows][CH = BKT/8 chunks of 16 B].  The DMA destination is lane-linear, so
 // the bank swizzle lives on the SOURCE address: LDS position p of row r holds source chunk p ^ sw(r), and the
@@ -290,14 +305,13 @@ __device__ __forceinline__ void linear_body(const unsigned short* __restrict__ X
     return;
   }
 
-  // ---- epilogue -------------------------------------------------------------------------------
+  // ---- epilogue: the output rule of gemm_epilogue.h ------------------------------------------------
   // accumulator layout: for MFMA tile (i, j) a lane holds n = wn*64 + i*16 + 4*(lane>>4) + r (r = 0..3),
   // m = wm*64 + j*16 + (lane&15), i.e. 8 contiguous output bytes per lane and 32-byte row segments per
   // store instruction.  Partial-line stores of that shape run at ~1 TB/s, so the tile goes through LDS
-  // once and leaves as whole 128-byte lines (16 B per lane): bias + activation in fp32 on the
-  // accumulators -> fp16 image of the wave's 64x64 quadrant in its private LDS region -> read back by
-  // rows, add the residual (fp16 + fp16 -> fp16, the same two roundings as `identity + linear(x)`
-  // in the reference's fp16 path) -> global_store_dwordx4.
+  // once and leaves as whole 128-byte lines (16 B per lane): activation in fp32 on the accumulators ->
+  // 16-bit image of the wave's 64x64 quadrant in its private LDS region -> read back by rows, row state,
+  // residual -> global_store_dwordx4.
   if (vec_n) {
     constexpr int kPitch = kStagePitch;  // bytes per staged row (+16: rows 0/8 do not share a bank pair)
     unsigned char* stage = lds + wave * (64 * kPitch);  // main loop is done with LDS (barrier above)
@@ -307,12 +321,7 @@ __device__ __forceinline__ void linear_body(const unsigned short* __restrict__ X
       for (int j = 0; j < 4; ++j) {
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float x = acc[i][j][r];
-          if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;  // NaN-propagating, like torch.relu
-          if (ACT == 2) x = gelu_erf(x);
-          v[r] = x;
-        }
+        for (int r = 0; r < 4; ++r) v[r] = epi_act<ACT, HAS_RES>(acc[i][j][r]);
         *reinterpret_cast<s16x4*>(stage + (j * 16 + frow) * kPitch + (i * 16 + ncol) * 2) = T::pack4(v);
       }
     }
@@ -327,6 +336,7 @@ __device__ __forceinline__ void linear_body(const unsigned short* __restrict__ X
       for (int it = 0; it < 8; ++it) {
         int m = m0 + wm * 64 + it * 8 + srow;
         m = m < M ? m : M - 1;
+        // epi_residual_col with the guard this kernel has always compiled (N % 8 == 0 here, so N >= 8 and the guard is dead)
         const int nn = n + 8 <= N ? n : (N >= 8 ? N - 8 : 0);
         rres[it] = *reinterpret_cast<const s16x8*>(R + (size_t)m * N + nn);
       }
@@ -338,34 +348,22 @@ __device__ __forceinline__ void linear_body(const unsigned short* __restrict__ X
       if (m < M && n < N) {
         s16x8 v = *reinterpret_cast<const s16x8*>(stage + ml * kPitch + schunk * 16);
         if (row_mask) {
+          // epi_row_state written out: through the helper this kernel's forms with a bias compiled to other instructions
           const unsigned char mk = row_mask[m];
           if (mk == 2) {
-            // the INPUT row counts as zeros (`memory * keep` ahead of enc_output): y = act(bias)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              float x = HAS_BIAS ? T::to_f32(bias[n + e]) : 0.f;
-              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
-              if (ACT == 2) x = gelu_erf(x);
-              v[e] = (short)T::from_f32(x);
-            }
+            for (int e = 0; e < 8; ++e)
+              v[e] = (short)T::from_f32(epi_act<ACT, HAS_RES>(HAS_BIAS ? T::to_f32(bias[n + e]) : 0.f));
           } else if (mk) {
-            v = s16x8{0, 0, 0, 0, 0, 0, 0, 0};  // masked_fill(mask[..., None], 0) on the linear's output
+            v = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
           }
         }
         size_t off = (size_t)m * N + n;
-        if (hm_hd > 0) {
-          // head-major destination y[b][head][position][channel]: rows m = (b, position), columns n = (head, channel);
-          // an 8-column chunk never straddles heads (hm_hd % 8 == 0), 8 consecutive rows of one head are 8*hm_hd*2
-          // contiguous bytes
-          const int bb = m / hm_rows, pos = m - bb * hm_rows;
-          const int head = n / hm_hd, ch = n - head * hm_hd;
-          off = (((size_t)bb * (N / hm_hd) + head) * hm_rows + pos) * hm_hd + ch;
-        }
+        if (hm_hd > 0) off = epi_head_major(m, n, N, hm_rows, hm_hd);
         if (HAS_RES) {
           const s16x8 rr = rres[it];
 #pragma unroll
-          for (int e = 0; e < 8; ++e)
-            v[e] = (short)T::from_f32(relu_if<ACT == 3>(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[e])));
+          for (int e = 0; e < 8; ++e) v[e] = (short)epi_residual<T, ACT>((unsigned short)v[e], (unsigned short)rr[e]);
         }
         *reinterpret_cast<s16x8*>(Y + off) = v;
       }
@@ -385,20 +383,9 @@ __device__ __forceinline__ void linear_body(const unsigned short* __restrict__ X
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         if (n + r < N) {
-          float v = acc[i][j][r];
-          if (ACT == 1 || (ACT == 3 && !HAS_RES)) v = v < 0.f ? 0.f : v;
-          if (ACT == 2) v = gelu_erf(v);
-          unsigned short h = T::from_f32(v);
-          if (row_mask && row_mask[m]) {
-            h = 0;
-            if (row_mask[m] == 2) {
-              float x = HAS_BIAS ? T::to_f32(bias[n + r]) : 0.f;
-              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
-              if (ACT == 2) x = gelu_erf(x);
-              h = T::from_f32(x);
-            }
-          }
-          if (HAS_RES) h = T::from_f32(relu_if<ACT == 3>(T::to_f32(h) + T::to_f32(R[off + r])));
+          unsigned short h = T::from_f32(epi_act<ACT, HAS_RES>(acc[i][j][r]));
+          if (row_mask) epi_row_state<T, T, ACT, HAS_RES>(h, row_mask[m], HAS_BIAS, bias, n + r);
+          if (HAS_RES) h = epi_residual<T, ACT>(h, R[off + r]);
           Y[off + r] = h;
         }
       }
@@ -452,16 +439,11 @@ int launch_cfg(hipStream_t st, const void* X, const void* W, const void* bias, c
                const void* mask, int M, int N, int K, int hm_rows, int hm_hd) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const dim3 grid((unsigned)(tiles_m * tiles_n)), block(kThreads);
-  auto x = static_cast<const unsigned short*>(X);
-  auto w = static_cast<const unsigned short*>(W);
-  auto b = static_cast<const unsigned short*>(bias);
-  auto r = static_cast<const unsigned short*>(R);
-  auto y = static_cast<unsigned short*>(Y);
-  auto mk = static_cast<const unsigned char*>(mask);
-  if (bias && R) hipLaunchKernelGGL((linear_kernel<T, ACT, true, true, BKT, STAGES, false>), grid, block, 0, st, x, w, b, r, y, mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
-  else if (bias) hipLaunchKernelGGL((linear_kernel<T, ACT, true, false, BKT, STAGES, false>), grid, block, 0, st, x, w, b, r, y, mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
-  else if (R) hipLaunchKernelGGL((linear_kernel<T, ACT, false, true, BKT, STAGES, false>), grid, block, 0, st, x, w, b, r, y, mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
-  else hipLaunchKernelGGL((linear_kernel<T, ACT, false, false, BKT, STAGES, false>), grid, block, 0, st, x, w, b, r, y, mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
+  const Operands o(X, W, bias, R, Y, mask);
+  if (bias && R) hipLaunchKernelGGL((linear_kernel<T, ACT, true, true, BKT, STAGES, false>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, o.mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
+  else if (bias) hipLaunchKernelGGL((linear_kernel<T, ACT, true, false, BKT, STAGES, false>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, o.mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
+  else if (R) hipLaunchKernelGGL((linear_kernel<T, ACT, false, true, BKT, STAGES, false>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, o.mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
+  else hipLaunchKernelGGL((linear_kernel<T, ACT, false, false, BKT, STAGES, false>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, o.mk, M, N, K, tiles_n, hm_rows, hm_hd, 0);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -494,16 +476,16 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
     }
   }
   const unsigned char mk = row_mask ? row_mask[m] : 0;
+  dispatch_act(act, [&](auto a) {   // (act <= 2: the residual plays no part in the activation)
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    if (n + r >= N) break;
-    float x = (mk == 2 ? 0.f : v[r]) + (bias ? T::to_f32(bias[n + r]) : 0.f);
-    if (act == 1) x = x < 0.f ? 0.f : x;
-    if (act == 2) x = gelu_erf(x);
-    unsigned short h = (mk != 0 && mk != 2) ? (unsigned short)0 : T::from_f32(x);
-    if (R) h = T::from_f32(T::to_f32(h) + T::to_f32(R[off + r]));
-    Y[off + r] = h;
-  }
+    for (int r = 0; r < 4; ++r) {
+      if (n + r >= N) break;
+      unsigned short h = T::from_f32(epi_act<a(), false>(v[r] + (bias ? T::to_f32(bias[n + r]) : 0.f)));
+      epi_row_state<T, T, a(), false>(h, mk, bias != nullptr, bias, n + r);
+      if (R) h = epi_residual<T, 0>(h, R[off + r]);
+      Y[off + r] = h;
+    }
+  });
 }
 
 // Split-K plan: problems whose 128x128 output tiles cannot fill the chip but whose K is long (the neck's extra
@@ -534,14 +516,12 @@ int launch_splitk(hipStream_t st, const void* X, const void* W, const void* bias
   if ((int64_t)kps * (splits - 1) >= ktiles) return CODETR_E_BADARG;  // an empty last range
   const int tiles_m = (int)((M + BM - 1) / BM), tiles_n = (int)((N + BN - 1) / BN);
   const dim3 grid((unsigned)(tiles_m * tiles_n), (unsigned)splits), block(kThreads);
-  hipLaunchKernelGGL((linear_kernel<T, 0, false, false, 64, 2, true>), grid, block, 0, st,
-                     static_cast<const unsigned short*>(X), static_cast<const unsigned short*>(W), nullptr, nullptr,
+  const Operands o(X, W, bias, R, Y, mask);
+  hipLaunchKernelGGL((linear_kernel<T, 0, false, false, 64, 2, true>), grid, block, 0, st, o.x, o.w, nullptr, nullptr,
                      static_cast<unsigned short*>(ws), nullptr, (int)M, (int)N, (int)K, tiles_n, 0, 0, kps);
   const long groups = (long)M * ((N + 3) / 4);
   hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st,
-                     static_cast<const float*>(ws), static_cast<const unsigned short*>(bias),
-                     static_cast<const unsigned short*>(R), static_cast<const unsigned char*>(mask),
-                     static_cast<unsigned short*>(Y), (int)M, (int)N, splits, act);
+                     static_cast<const float*>(ws), o.b, o.r, o.mk, o.y, (int)M, (int)N, splits, act);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -834,7 +814,8 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
   if (threadIdx.x == 0) st1 = __builtin_amdgcn_s_memtime();
 #endif
 
-  // epilogue in two 64-row halves per wave through its private staging region (64 rows x 144 B)
+  // epilogue (the output rule of gemm_epilogue.h) in two 64-row halves per wave through its private staging region
+  // (64 rows x 144 B), as in linear_body
   constexpr int kPitch = kStagePitch;
   unsigned char* stage = lds + wave * (64 * kPitch);
   const int srow = lane >> 3, schunk = lane & 7;
@@ -848,12 +829,7 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
       for (int j = 0; j < 4; ++j) {
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float x = acc[i][h * 4 + j][r];
-          if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
-          if (ACT == 2) x = gelu_erf(x);
-          v[r] = x;
-        }
+        for (int r = 0; r < 4; ++r) v[r] = epi_act<ACT, HAS_RES>(acc[i][h * 4 + j][r]);
         *reinterpret_cast<s16x4*>(stage + (j * 16 + frow) * kPitch + (i * 16 + ncol) * 2) = T::pack4(v);
       }
     __builtin_amdgcn_wave_barrier();
@@ -864,8 +840,7 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
       for (int it = 0; it < 8; ++it) {
         int m = m0 + wm * 128 + h * 64 + it * 8 + srow;
         m = m < M ? m : M - 1;
-        const int nn = n + 8 <= N ? n : N - 8;
-        rres[it] = *reinterpret_cast<const s16x8*>(R + (size_t)m * N + nn);
+        rres[it] = *reinterpret_cast<const s16x8*>(R + (size_t)m * N + epi_residual_col(n, N));
       }
     }
 #pragma unroll
@@ -875,15 +850,12 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
       if (m < M && n < N) {
         s16x8 v = *reinterpret_cast<const s16x8*>(stage + ml * kPitch + schunk * 16);
         if (row_mask) {
+          // epi_row_state written out: through the helper this kernel's forms with a bias compiled to other instructions
           const unsigned char mk = row_mask[m];
           if (mk == 2) {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              float x = HAS_BIAS ? T::to_f32(bias[n + e]) : 0.f;
-              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
-              if (ACT == 2) x = gelu_erf(x);
-              v[e] = (short)T::from_f32(x);
-            }
+            for (int e = 0; e < 8; ++e)
+              v[e] = (short)T::from_f32(epi_act<ACT, HAS_RES>(HAS_BIAS ? T::to_f32(bias[n + e]) : 0.f));
           } else if (mk) {
             v = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
           }
@@ -891,8 +863,7 @@ __global__ __launch_bounds__(512) void linear_256_kernel(const unsigned short* _
         if (HAS_RES) {
           const s16x8 rr = rres[it];
 #pragma unroll
-          for (int e = 0; e < 8; ++e)
-            v[e] = (short)T::from_f32(relu_if<ACT == 3>(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[e])));
+          for (int e = 0; e < 8; ++e) v[e] = (short)epi_residual<T, ACT>((unsigned short)v[e], (unsigned short)rr[e]);
         }
         // uniform 64-bit tile base (SGPRs) + 32-bit lane offset: the store carries half the address bytes
         const unsigned loff = ((unsigned)(wm * 128 + h * 64 + ml) * (unsigned)N + (unsigned)(wn * 64 + schunk * 8)) * 2u;
@@ -929,20 +900,15 @@ int launch_big(hipStream_t st, const void* X, const void* W, const void* bias, c
                int M, int N, int K) {
   const int tiles_m = (M + 255) / 256, tiles_n = (N + 255) / 256;
   const dim3 grid((unsigned)(tiles_m * tiles_n)), block(512);
-  auto x = static_cast<const unsigned short*>(X);
-  auto w = static_cast<const unsigned short*>(W);
-  auto b = static_cast<const unsigned short*>(bias);
-  auto r = static_cast<const unsigned short*>(R);
-  auto y = static_cast<unsigned short*>(Y);
-  auto mk = static_cast<const unsigned char*>(mask);
+  const Operands o(X, W, bias, R, Y, mask);
   // X two k-tiles ahead in a 3-slot ring (8 images: -3 ... -13 % on every Swin stage 1-3 shape); scalar-base LDS-DMA for
   // problems of more than one column tile (-1 ... -2.5 %; a single column tile -- N = 192 -- measured 6 % slower with it
   // and keeps the pointer form)
   const bool sdma = tiles_n > 1;
 #define CODETR_L256S(HB, HR) \
-  hipLaunchKernelGGL((linear_256_kernel<T, ACT, HB, HR, true, true>), grid, block, 0, st, x, w, b, r, y, mk, M, N, K, tiles_n)
+  hipLaunchKernelGGL((linear_256_kernel<T, ACT, HB, HR, true, true>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, o.mk, M, N, K, tiles_n)
 #define CODETR_L256(HB, HR) \
-  hipLaunchKernelGGL((linear_256_kernel<T, ACT, HB, HR, true, false>), grid, block, 0, st, x, w, b, r, y, mk, M, N, K, tiles_n)
+  hipLaunchKernelGGL((linear_256_kernel<T, ACT, HB, HR, true, false>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, o.mk, M, N, K, tiles_n)
   if (sdma) {
     if (bias && R) CODETR_L256S(true, true);
     else if (bias) CODETR_L256S(true, false);
@@ -1194,8 +1160,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
     for (int it = 0; it < 4; ++it) {
       int m = m0 + it * 8 + srow;
       m = m < M ? m : M - 1;
-      int n = np + schunk * 8;
-      n = n + 8 <= N ? n : N - 8;
+      const int n = epi_residual_col(np + schunk * 8, N);
       rr[it] = *reinterpret_cast<const s16x8*>(R + (size_t)m * N + n);
     }
   };
@@ -1213,31 +1178,14 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
         continue;
       }
       if (m < M && n < Ny) {  // N % 8 == 0: a chunk of 8 columns is inside or outside as a whole
-        if (row_mask) {
-          const unsigned char mk = (unsigned char)((row_states >> (8 * it)) & 0xffu);
-          if (mk == 2) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              float x = bias ? T::to_f32(sBias[n + e]) : 0.f;
-              if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
-              if (ACT == 2) x = gelu_erf(x);
-              v[e] = (short)OT::from_f32(x);
-            }
-          } else if (mk) {
-            v = s16x8{0, 0, 0, 0, 0, 0, 0, 0};
-          }
-        }
+        if (row_mask)
+          epi_row_state<T, OT, ACT, HAS_RES>(v, (unsigned char)((row_states >> (8 * it)) & 0xffu), bias != nullptr, sBias, n);
         if (HAS_RES) {
 #pragma unroll
-          for (int e = 0; e < 8; ++e)
-            v[e] = (short)T::from_f32(relu_if<ACT == 3>(T::to_f32((unsigned short)v[e]) + T::to_f32((unsigned short)rr[it][e])));
+          for (int e = 0; e < 8; ++e) v[e] = (short)epi_residual<T, ACT>((unsigned short)v[e], (unsigned short)rr[it][e]);
         }
         size_t off = (size_t)m * Ny + n;
-        if (hm_hd > 0) {  // column-block-major destination y[b][n / hm_hd][position][n % hm_hd] (hm_hd % 8 == 0: a lane's 8-column chunk lies inside one block)
-          const int bb = m / hm_rows, pos = m - bb * hm_rows;
-          const int head = n / hm_hd, ch = n - head * hm_hd;
-          off = (((size_t)bb * (Ny / hm_hd) + head) * hm_rows + pos) * hm_hd + ch;
-        }
+        if (hm_hd > 0) off = epi_head_major(m, n, Ny, hm_rows, hm_hd);
         if (!(CODETR_XS_ABL & 1) || v[0] == 0x1234) *reinterpret_cast<s16x8*>(Y + off) = v;
       }
     }
@@ -1364,12 +1312,7 @@ __global__ __launch_bounds__(256) void linear_xs_kernel(const unsigned short* __
       for (int mt = 0; mt < 2; ++mt) {
         float v[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float x = acc[nt][mt][r];
-          if (ACT == 1 || (ACT == 3 && !HAS_RES)) x = x < 0.f ? 0.f : x;
-          if (ACT == 2) x = gelu_erf(x);
-          v[r] = x;
-        }
+        for (int r = 0; r < 4; ++r) v[r] = epi_act<ACT, HAS_RES>(acc[nt][mt][r]);
         *reinterpret_cast<s16x4*>(my_stage + (mt * 16 + l15) * kXsPitch + ((c & 1) * CN + nt * 16 + grp * 4) * 2) =
             (SPLIT && c >= c1) ? T::pack4(v) : OT::pack4(v);
       }
@@ -1415,19 +1358,11 @@ int launch_xs_res(hipStream_t st, const void* X, const void* W, const void* bias
                   const void* mask, int M, int N, int hm_rows, int hm_hd, const void* X2 = nullptr,
                   const void* LNG = nullptr, const void* LNB = nullptr, float ln_eps = 0.f) {
   const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-  auto x = static_cast<const unsigned short*>(X);
-  auto x2 = static_cast<const unsigned short*>(X2);
-  auto lg = static_cast<const unsigned short*>(LNG);
-  auto lb = static_cast<const unsigned short*>(LNB);
-  auto w = static_cast<const unsigned short*>(W);
-  auto b = static_cast<const unsigned short*>(bias);
-  auto r = static_cast<const unsigned short*>(R);
-  auto y = static_cast<unsigned short*>(Y);
-  auto mk = static_cast<const unsigned char*>(mask);
+  const Operands o(X, W, bias, R, Y, mask);
   if (R && std::is_same<T, OT>::value)
-    hipLaunchKernelGGL((linear_xs_kernel<T, KS, ACT, true, T>), grid, block, 0, st, x, x2, lg, lb, ln_eps, w, b, r, y, mk, M, N, hm_rows, hm_hd);
+    hipLaunchKernelGGL((linear_xs_kernel<T, KS, ACT, true, T>), grid, block, 0, st, o.x, u16(X2), u16(LNG), u16(LNB), ln_eps, o.w, o.b, o.r, o.y, o.mk, M, N, hm_rows, hm_hd);
   else if (R) return CODETR_E_UNSUPPORTED;   // (a residual is added in the operands' type)
-  else hipLaunchKernelGGL((linear_xs_kernel<T, KS, ACT, false, OT>), grid, block, 0, st, x, x2, lg, lb, ln_eps, w, b, r, y, mk, M, N, hm_rows, hm_hd);
+  else hipLaunchKernelGGL((linear_xs_kernel<T, KS, ACT, false, OT>), grid, block, 0, st, o.x, u16(X2), u16(LNG), u16(LNB), ln_eps, o.w, o.b, o.r, o.y, o.mk, M, N, hm_rows, hm_hd);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -1435,12 +1370,7 @@ int launch_xs_res(hipStream_t st, const void* X, const void* W, const void* bias
 template <class T, int KS>
 int launch_xs_act(hipStream_t st, const void* X, const void* W, const void* bias, const void* R, void* Y,
                   const void* mask, int M, int N, int act, int hm_rows, int hm_hd) {
-  switch (act) {
-    case 0: return launch_xs_res<T, KS, 0>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
-    case 1: return launch_xs_res<T, KS, 1>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
-    case 3: return launch_xs_res<T, KS, 3>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
-    default: return launch_xs_res<T, KS, 2>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd);
-  }
+  return dispatch_act(act, [&](auto a) { return launch_xs_res<T, KS, a()>(st, X, W, bias, R, Y, mask, M, N, hm_rows, hm_hd); });
 }
 
 template <class T>
@@ -1477,22 +1407,13 @@ int launch(hipStream_t st, const void* X, const void* W, const void* bias, const
   }
   const bool io16 = (reinterpret_cast<uintptr_t>(Y) & 15) == 0 && (!R || (reinterpret_cast<uintptr_t>(R) & 15) == 0);
   const int kind = pick_kernel(M, N, K, act, R != nullptr, hm_hd, io16);
-  if (kind == kKernel256) {
-    switch (act) {
-      case 0: return launch_big<T, 0>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
-      case 1: return launch_big<T, 1>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
-      case 3: return launch_big<T, 3>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
-      default: return launch_big<T, 2>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K);
-    }
-  }
+  if (kind == kKernel256)
+    return dispatch_act(act, [&](auto a) { return launch_big<T, a()>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K); });
   if (kind == kKernelXS)
     return launch_xs<T>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, act, (int)hm_rows, hm_hd);
-  switch (act) {
-    case 0: return launch_act<T, 0>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
-    case 1: return launch_act<T, 1>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
-    case 3: return launch_act<T, 3>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
-    default: return launch_act<T, 2>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
-  }
+  return dispatch_act(act, [&](auto a) {
+    return launch_act<T, a()>(st, X, W, bias, R, Y, mask, (int)M, (int)N, (int)K, (int)hm_rows, hm_hd);
+  });
 }
 
 template <class T, int ACT, int BKT>
@@ -1500,15 +1421,11 @@ int launch_conv_cfg(hipStream_t st, const void* X, const void* W, const void* bi
                     int K, const ConvGeom& g) {
   const int tiles_m = (M + BM - 1) / BM, tiles_n = (N + BN - 1) / BN;
   const dim3 grid((unsigned)(tiles_m * tiles_n)), block(kThreads);
-  auto x = static_cast<const unsigned short*>(X);
-  auto w = static_cast<const unsigned short*>(W);
-  auto b = static_cast<const unsigned short*>(bias);
-  auto r = static_cast<const unsigned short*>(R);
-  auto y = static_cast<unsigned short*>(Y);
-  if (bias && R) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, true, true, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
-  else if (bias) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, true, false, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
-  else if (R) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, false, true, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
-  else hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, false, false, BKT, 2>), grid, block, 0, st, x, w, b, r, y, M, N, K, tiles_n, g);
+  const Operands o(X, W, bias, R, Y);
+  if (bias && R) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, true, true, BKT, 2>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, M, N, K, tiles_n, g);
+  else if (bias) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, true, false, BKT, 2>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, M, N, K, tiles_n, g);
+  else if (R) hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, false, true, BKT, 2>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, M, N, K, tiles_n, g);
+  else hipLaunchKernelGGL((conv_tokens_kernel<T, ACT, false, false, BKT, 2>), grid, block, 0, st, o.x, o.w, o.b, o.r, o.y, M, N, K, tiles_n, g);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }
@@ -1540,12 +1457,7 @@ int launch_conv(hipStream_t st, const void* X, const void* W, const void* bias, 
   if (((M + BM - 1) / BM) * ((Cout + BN - 1) / BN) > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
   if (act == 3 && !R) act = 1;
   const ConvGeom g{(int)H, (int)Wd, (int)C, (int)Wo, (int)(Ho * Wo), k, stride, pad};
-  switch (act) {
-    case 0: return launch_conv_act<T, 0>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
-    case 1: return launch_conv_act<T, 1>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
-    case 2: return launch_conv_act<T, 2>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
-    default: return launch_conv_act<T, 3>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g);
-  }
+  return dispatch_act(act, [&](auto a) { return launch_conv_act<T, a()>(st, X, W, bias, R, Y, (int)M, (int)Cout, (int)K, g); });
 }
 
 // x + x2 folded into the X-stationary kernel's operand load (act 0, no residual / mask): only where that kernel applies
@@ -1571,37 +1483,40 @@ int launch_ln(hipStream_t st, const void* X, const void* G, const void* Bt, floa
       ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(G) | reinterpret_cast<uintptr_t>(Bt) |
         reinterpret_cast<uintptr_t>(W)) & 15))
     return CODETR_E_UNSUPPORTED;
-#define CODETR_LN_CASE(KS, ACT) \
-  return launch_xs_res<T, KS, ACT>(st, X, W, bias, nullptr, Y, nullptr, (int)M, (int)N, 0, 0, nullptr, G, Bt, eps)
-  if (K == 192) {
-    if (act == 0) CODETR_LN_CASE(6, 0);
-    if (act == 1) CODETR_LN_CASE(6, 1);
-    CODETR_LN_CASE(6, 2);
-  }
-  if (act == 0) CODETR_LN_CASE(8, 0);
-  if (act == 1) CODETR_LN_CASE(8, 1);
-  CODETR_LN_CASE(8, 2);
-#undef CODETR_LN_CASE
+  return dispatch_act(act, [&](auto a) {
+    if (K == 192) return launch_xs_res<T, 6, a()>(st, X, W, bias, nullptr, Y, nullptr, (int)M, (int)N, 0, 0, nullptr, G, Bt, eps);
+    return launch_xs_res<T, 8, a()>(st, X, W, bias, nullptr, Y, nullptr, (int)M, (int)N, 0, 0, nullptr, G, Bt, eps);
+  });
 }
 
-// the encoder's two projections as one launch of the X-stationary kernel (SPLIT form): K = 256 only
-template <class T, class OT>
-int launch_split(hipStream_t st, const void* X, const void* X2, const void* W, const void* bias, const void* mask, void* Y,
-                 void* Y2, int64_t M, int64_t N1, int64_t N2, int64_t K, int64_t hm_rows, int hm_hd) {
-  if (!X || !X2 || !W || !Y || !Y2 || M <= 0 || N1 <= 0 || N2 <= 0 || K <= 0) return CODETR_E_BADARG;
+// the argument checks of the two SPLIT launchers below; 0 or a CODETR_E_ code.  second: the operand of the second product
+// that must be 16-byte aligned (X2, or the level embedding); own: the code of the caller's own range checks, which rank
+// behind the null / sign checks and ahead of everything else
+int split_check(const void* X, const void* second, const void* W, const void* bias, const void* Y, const void* Y2, int64_t M,
+                int64_t N1, int64_t N2, int64_t K, int64_t hm_rows, int hm_hd, int own = 0) {
+  if (!X || !W || !Y || !Y2 || M <= 0 || N1 <= 0 || N2 <= 0 || K <= 0) return CODETR_E_BADARG;
+  if (own) return own;
   if (M > 0x7fffffffLL) return CODETR_E_TOO_LARGE;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(X2) | reinterpret_cast<uintptr_t>(W) |
+  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(second) | reinterpret_cast<uintptr_t>(W) |
        reinterpret_cast<uintptr_t>(Y) | reinterpret_cast<uintptr_t>(Y2) | reinterpret_cast<uintptr_t>(bias)) & 15)
     return CODETR_E_BADARG;
   if (hm_hd != 0 || hm_rows != 0) {
     if (hm_hd <= 0 || hm_rows <= 0 || hm_hd % 8 != 0 || N1 % hm_hd != 0 || M % hm_rows != 0) return CODETR_E_UNSUPPORTED;
   }
   if (K != 256 || N1 % 64 != 0 || N2 % 8 != 0 || N1 + N2 > 1536 || M < 128 * 256) return CODETR_E_UNSUPPORTED;
+  return 0;
+}
+
+// the encoder's two projections as one launch of the X-stationary kernel (SPLIT form): K = 256 only
+template <class T, class OT>
+int launch_split(hipStream_t st, const void* X, const void* X2, const void* W, const void* bias, const void* mask, void* Y,
+                 void* Y2, int64_t M, int64_t N1, int64_t N2, int64_t K, int64_t hm_rows, int hm_hd) {
+  if (!X2) return CODETR_E_BADARG;
+  if (const int rc = split_check(X, X2, W, bias, Y, Y2, M, N1, N2, K, hm_rows, hm_hd)) return rc;
   const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-  hipLaunchKernelGGL((linear_xs_kernel<T, 8, 0, false, OT, true>), grid, block, 0, st, static_cast<const unsigned short*>(X),
-                     static_cast<const unsigned short*>(X2), nullptr, nullptr, 0.f, static_cast<const unsigned short*>(W),
-                     static_cast<const unsigned short*>(bias), nullptr, static_cast<unsigned short*>(Y),
-                     static_cast<const unsigned char*>(mask), (int)M, (int)(N1 + N2), (int)hm_rows, hm_hd,
+  const Operands o(X, W, bias, nullptr, Y, mask);
+  hipLaunchKernelGGL((linear_xs_kernel<T, 8, 0, false, OT, true>), grid, block, 0, st, o.x, u16(X2), nullptr, nullptr, 0.f,
+                     o.w, o.b, nullptr, o.y, o.mk, (int)M, (int)(N1 + N2), (int)hm_rows, hm_hd,
                      static_cast<unsigned short*>(Y2), (int)N1);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
@@ -1613,18 +1528,9 @@ int launch_split_pos(hipStream_t st, const void* X, const float* const* ycum, co
                      const int64_t* shapes, int L, const void* level_embed, float temperature, float scale, float eps,
                      float offset, int normalize, const void* W, const void* bias, const void* mask, void* Y, void* Y2,
                      int64_t M, int64_t S, int64_t N1, int64_t N2, int64_t K, int64_t hm_rows, int hm_hd) {
-  if (!X || !ycum || !xcum || !shapes || !W || !Y || !Y2 || M <= 0 || S <= 0 || N1 <= 0 || N2 <= 0 || K <= 0 || L <= 0 ||
-      !(temperature > 0.f))
-    return CODETR_E_BADARG;
-  if (L > 5) return CODETR_E_UNSUPPORTED;
-  if (M > 0x7fffffffLL || M % S != 0) return M % S != 0 ? CODETR_E_BADARG : CODETR_E_TOO_LARGE;
-  if ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(W) | reinterpret_cast<uintptr_t>(Y) |
-       reinterpret_cast<uintptr_t>(Y2) | reinterpret_cast<uintptr_t>(bias) | reinterpret_cast<uintptr_t>(level_embed)) & 15)
-    return CODETR_E_BADARG;
-  if (hm_hd != 0 || hm_rows != 0) {
-    if (hm_hd <= 0 || hm_rows <= 0 || hm_hd % 8 != 0 || N1 % hm_hd != 0 || M % hm_rows != 0) return CODETR_E_UNSUPPORTED;
-  }
-  if (K != 256 || N1 % 64 != 0 || N2 % 8 != 0 || N1 + N2 > 1536 || M < 128 * 256) return CODETR_E_UNSUPPORTED;
+  if (!ycum || !xcum || !shapes || S <= 0 || L <= 0 || !(temperature > 0.f)) return CODETR_E_BADARG;
+  const int own = L > 5 ? CODETR_E_UNSUPPORTED : M % S != 0 ? CODETR_E_BADARG : 0;
+  if (const int rc = split_check(X, level_embed, W, bias, Y, Y2, M, N1, N2, K, hm_rows, hm_hd, own)) return rc;
   XsPosGen pg;
   int64_t sum = 0;
   for (int l = 0; l < 5; ++l) {
@@ -1638,7 +1544,7 @@ int launch_split_pos(hipStream_t st, const void* X, const float* const* ycum, co
     if (l < L) sum += h * w;
   }
   if (sum != S) return CODETR_E_BADARG;
-  pg.level_embed = static_cast<const unsigned short*>(level_embed);
+  pg.level_embed = u16(level_embed);
   pg.L = L;
   pg.S = (int)S;
   pg.log2_temperature = log2f(temperature);
@@ -1647,10 +1553,9 @@ int launch_split_pos(hipStream_t st, const void* X, const float* const* ycum, co
   pg.offset = offset;
   pg.normalize = normalize;
   const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-  hipLaunchKernelGGL((linear_xs_kernel<T, 8, 0, false, OT, true, true>), grid, block, 0, st, static_cast<const unsigned short*>(X),
-                     nullptr, nullptr, nullptr, 0.f, static_cast<const unsigned short*>(W),
-                     static_cast<const unsigned short*>(bias), nullptr, static_cast<unsigned short*>(Y),
-                     static_cast<const unsigned char*>(mask), (int)M, (int)(N1 + N2), (int)hm_rows, hm_hd,
+  const Operands o(X, W, bias, nullptr, Y, mask);
+  hipLaunchKernelGGL((linear_xs_kernel<T, 8, 0, false, OT, true, true>), grid, block, 0, st, o.x, nullptr, nullptr, nullptr,
+                     0.f, o.w, o.b, nullptr, o.y, o.mk, (int)M, (int)(N1 + N2), (int)hm_rows, hm_hd,
                      static_cast<unsigned short*>(Y2), (int)N1, pg);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;

@@ -24,12 +24,11 @@
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "gemm_epilogue.h"
 #include "mx_scale.h"
 
 namespace {
 
-
-constexpr int kStagePitch = 64 * 2 + 16;  // epilogue staging: bytes per staged row of a wave's 64-column slice
 constexpr float kFp8Max = 448.0f;         // largest finite e4m3 (OCP e4m3fn)
 
 // XOR swizzle of the 16-byte chunk index of a 128-byte LDS row.  A lane's fragment is two ds_read_b128 (chunks 2g, 2g+1,
@@ -240,10 +239,7 @@ __global__ __launch_bounds__(512) void linear_256_fp8_kernel(const unsigned char
         f16x4 hv;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          float x = fmaf(acc[i][h * 4 + j][r], sc[i][r], bs[i][r]);
-          if (ACT == 1) x = x < 0.f ? 0.f : x;
-          if (ACT == 2) x = gelu_erf(x);
-          hv[r] = (_Float16)x;
+          hv[r] = (_Float16)epi_act<ACT, HAS_RES>(fmaf(acc[i][h * 4 + j][r], sc[i][r], bs[i][r]));
         }
         s16x4 o;
         __builtin_memcpy(&o, &hv, 8);
@@ -256,8 +252,7 @@ __global__ __launch_bounds__(512) void linear_256_fp8_kernel(const unsigned char
       for (int it = 0; it < 8; ++it) {
         int m = m0 + wm * 128 + h * 64 + it * 8 + srow;
         m = m < M ? m : M - 1;
-        const int nn = n + 8 <= N ? n : N - 8;
-        rres[it] = *reinterpret_cast<const s16x8*>(R + (size_t)m * N + nn);
+        rres[it] = *reinterpret_cast<const s16x8*>(R + (size_t)m * N + epi_residual_col(n, N));
       }
     }
 #pragma unroll
@@ -269,7 +264,7 @@ __global__ __launch_bounds__(512) void linear_256_fp8_kernel(const unsigned char
         if (HAS_RES) {
           const s16x8 rr = rres[it];
 #pragma unroll
-          for (int e = 0; e < 8; ++e) v[e] = (short)f2h(h2f((unsigned short)v[e]) + h2f((unsigned short)rr[e]));
+          for (int e = 0; e < 8; ++e) v[e] = (short)epi_residual<HalfT, ACT>((unsigned short)v[e], (unsigned short)rr[e]);
         }
         const unsigned eoff = (unsigned)(wm * 128 + h * 64 + ml) * (unsigned)N + (unsigned)(wn * 64 + schunk * 8);
         if (OUT8 && MX) {

@@ -18,6 +18,7 @@
 
 #include "codetr_hip.h"
 #include "device_prims.h"
+#include "gemm_epilogue.h"
 #include "large_lds.h"
 
 namespace {
@@ -176,20 +177,15 @@ __device__ __forceinline__ bool tile_epilogue(f32x4 (&acc)[4][8], const PersistA
       if (HAS_RES && j == 2) load_res(4, 8);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
+        // the output rule of gemm_epilogue.h (ACT 0 .. 2, no row states), on the packed GELU
         float x[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) x[i] = acc[i][j][r] + bias4[i];
-        if (ACT == 1) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) x[i] = x[i] < 0.f ? 0.f : x[i];   // NaN-propagating, like torch.relu
-        }
-        if (ACT == 2) {
-          const f32x2 g01 = gelu_erf2(f32x2{x[0], x[1]}), g23 = gelu_erf2(f32x2{x[2], x[3]});
-          x[0] = g01.x; x[1] = g01.y; x[2] = g23.x; x[3] = g23.y;
-        }
-        uint2 o = {T::pack2(x[0], x[1]), T::pack2(x[2], x[3])};
+        const f32x2 x01 = epi_act2<ACT, HAS_RES>(f32x2{x[0], x[1]}), x23 = epi_act2<ACT, HAS_RES>(f32x2{x[2], x[3]});
+        uint2 o = {T::pack2(x01.x, x01.y), T::pack2(x23.x, x23.y)};
         if (HAS_RES) {
-          // fp16(fp16(linear) + residual): the two roundings of `identity + linear(x)` in the reference's fp16 path
+          // epi_residual on the four packed values (through a helper the bf16 forms compiled to other instructions):
+          // fp16(fp16(linear) + residual), the two roundings of `identity + linear(x)` in the reference's fp16 path
           const uint2 q = rr[j][r];
           const float y0 = T::to_f32((unsigned short)(o.x & 0xffffu)) + T::to_f32((unsigned short)(q.x & 0xffffu));
           const float y1 = T::to_f32((unsigned short)(o.x >> 16)) + T::to_f32((unsigned short)(q.x >> 16));

@@ -11,9 +11,9 @@ instruction returning a sum exactly when every partial sum is fp32-representable
 
 Each copy is reached at the smallest shape its kernel accepts, asked from the library (codetr_linear_variant,
 codetr_linear_splitk_plan, codetr_linear_{sk,pp}_supported), and the kernel that served is asserted:
-the 128-tile kernel (vector and ragged-N stores, act 3, row states), the 256-tile kernel, the X-stationary kernel
-(row-major, head-major, bf16 operands -> fp16, row states), the split-K second pass, the persistent kernel (resident,
-one workgroup per tile, stream-K split), the ping-pong kernel, and the fused FFN.
+the 128-tile kernel (vector and ragged-N stores, head-major, act 3, row states), the 256-tile kernel (act 3, row states),
+the X-stationary kernel (row-major, head-major, bf16 operands -> fp16, row states), the split-K second pass (row states),
+the persistent kernel (resident, one workgroup per tile, stream-K split), the ping-pong kernel, and the fused FFN.
 
 Measured on an MI355X: zero differing bits on every None / ReLU / relu_res / row-state case of every route, every GELU
 output inside its interval.  The GELU error itself is only visible through a 16-bit output: the part of |y - gelu(z)| that
@@ -190,6 +190,44 @@ def test_relu_after_the_residual_and_row_states_xs(T):
     for act in (None, "relu", "gelu"):
         _check("xs", T, "A", act, states=True)
     _check("xs", T, "B2", None, rmode="mix", states=True)
+
+
+@pytest.mark.parametrize("T", DTYPES)
+def test_relu_after_the_residual_and_row_states_tile256(T):
+    _check("tile256", T, "B2", "relu_res", rmode="mix")
+    _check("tile256", T, "A", "relu_res")                  # no residual: act 3 is act 1
+    for act in (None, "relu", "gelu"):
+        _check("tile256", T, "A", act, states=True)
+    _check("tile256", T, "B2", None, rmode="mix", states=True)
+    _check("tile256", T, "B2", "relu_res", rmode="mix", states=True)
+
+
+@pytest.mark.parametrize("T", DTYPES)
+def test_row_states_splitk(T):
+    """the second pass takes None / relu / gelu (no act 3): row states under each, without and with a residual"""
+    for act in (None, "relu", "gelu"):
+        _check("splitk", T, "A", act, states=True)
+        _check("splitk", T, "B2", act, rmode="mix", states=True)
+
+
+@pytest.mark.parametrize("T", DTYPES)
+def test_tile128_head_major(T):
+    """the head-major destination of the 128-tile kernel (too few rows for the X-stationary one), with row states"""
+    from codetr import _cabi, hip_ops
+
+    K, hd, B, S = 64, 32, 2, 200
+    case = _case("A", T, K)
+    N = (case["w"].shape[0] + hd - 1) // hd * hd
+    case = ee.pad_columns(case, N)
+    M = B * S
+    assert M < 128 * 256 and _cabi.linear_variant(M, N, K, None, False, hd) == "tile128"
+    state = (torch.arange(M, device=DEV) % 3).to(torch.uint8)
+    before = _cabi.CALLS["linear_tile128"]
+    y = hip_ops.linear(ee.make_x(case, M).view(B, S, K), case["w"], case["b"], row_mask=state.view(B, S), head_major=hd)
+    assert _cabi.CALLS["linear_tile128"] == before + 1 and y.shape == (B, N // hd, S, hd)
+    want = ee.expected(ee.accumulators(case, M), case["b"], None, None, T, state)
+    want = want.view(B, S, N // hd, hd).permute(0, 2, 1, 3)
+    assert ee.differing(y, want.contiguous()) == 0
 
 
 def _head_major_case(T, kind, p_out=None):
