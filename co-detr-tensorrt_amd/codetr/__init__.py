@@ -16,6 +16,10 @@ from . import _jpeg  # noqa: E402  (the companion header's entry points, same li
 
 _jpeg.load()
 
+from . import _jpeg_dec  # noqa: E402  (the decoder's companion header, same library)
+
+_jpeg_dec.load()
+
 from . import ops  # noqa: E402,F401  (registers torch.ops.codetr.*)
 
 try:  # model assembly (pure-Python host code on top of the ops)

@@ -13,12 +13,13 @@ formulation of the model lives in oracle/ and is test infrastructure).
 
 import collections
 import math
+import os
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _assign, _cabi, _jpeg
+from . import _assign, _cabi, _jpeg, _jpeg_dec
 
 # ops served by hand-written HIP kernels in this build (kept in sync with include/codetr_hip.h)
 NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_window_attention(f16, head_dim 32)",
@@ -1005,6 +1006,146 @@ def encode_jpeg(src, rows, quality=90, subsampling="420", out_stride=None):
             if group(index, (bound + 15) // 16 * 16):
                 raise RuntimeError("encode_jpeg: a scan exceeded its proven bound")
     return [_jpeg.header(H, W, st["quality"], sub) + scans[i] + b"\xff\xd9" for i, (_, H, W) in enumerate(rows)]
+
+
+JPEG_DECODE_STATS = {"host_fallbacks": 0}   # files the GPU decoder does not support, decoded with Pillow on the host
+
+
+def jpeg_file_bytes(item):
+    """one JPEG file as a contiguous 1-D uint8 numpy array: bytes / bytearray / memoryview, a 1-D uint8 numpy array or
+    host tensor, or a str / os.PathLike path"""
+    if isinstance(item, (str, os.PathLike)):
+        with open(item, "rb") as f:
+            item = f.read()
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return np.frombuffer(item, np.uint8)
+    if torch.is_tensor(item) and not item.is_cuda:
+        item = item.detach().numpy()
+    if isinstance(item, np.ndarray) and item.dtype == np.uint8 and item.ndim == 1:
+        return np.ascontiguousarray(item)
+    raise ValueError(f"jpeg: a file is bytes, a 1-D uint8 array or host tensor, or a path; got {type(item).__name__}")
+
+
+def jpeg_parse(data):
+    """the header of one file (a contiguous 1-D uint8 numpy array) -> (return code, info, tables) of
+    codetr_jpegdec_parse; host only"""
+    return _jpeg_dec.parse(data)
+
+
+def jpeg_host_decode(data):
+    """the file decoded on the host with Pillow -> RGB uint8 [H, W, 3], counted in JPEG_DECODE_STATS; None when Pillow
+    does not import"""
+    try:
+        import io
+
+        from PIL import Image
+    except ImportError:
+        return None
+    rgb = np.asarray(Image.open(io.BytesIO(data.tobytes())).convert("RGB"))
+    JPEG_DECODE_STATS["host_fallbacks"] += 1
+    return rgb
+
+
+def jpeg_reason(rc, info):
+    if rc == 0:
+        return None
+    if rc == _cabi._D["CODETR_E_UNSUPPORTED"]:
+        return _jpeg_dec.REASONS.get(int(info[6]), "unsupported")
+    return "too_large" if rc == _cabi._D["CODETR_E_TOO_LARGE"] else "bad_header"
+
+
+def jpeg_info(data):
+    """What the header of a JPEG file says (host only; include/codetr_jpeg_dec.h's parser)
+    -> dict(supported, reason, height, width, components, sampling [(h, v)], restart_interval, scan_offset, scan_bytes);
+    reason: None, a name of the header's CODETR_JPEGDEC_R_* in lower case, 'too_large' or 'bad_header'; size and sampling
+    are those of the frame header when it was read, else 0 / []."""
+    rc, info, _ = _jpeg_dec.parse(jpeg_file_bytes(data))
+    nc = int(info[2])
+    return dict(supported=rc == 0, reason=jpeg_reason(rc, info), height=int(info[0]), width=int(info[1]), components=nc,
+                sampling=[(int(info[9 + 5 * c]), int(info[10 + 5 * c])) for c in _range(min(nc, 3))] if nc in (1, 3) else [],
+                restart_interval=int(info[3]), scan_offset=int(info[4]), scan_bytes=int(info[5]))
+
+
+def jpeg_stage(parsed, pos=0):
+    """Where the scans and tables of parsed files (file bytes, info, tables) go in a staging buffer, from byte `pos`:
+    -> (copies [(offset, uint8 array)], per launch group of PREPROCESS_BATCH_MAX (index list, tables offset), end).  The
+    scans lie back to back as they are in the files; a group's tables are contiguous and 16-byte aligned."""
+    copies, groups, scan_at = [], [], []
+    for data, info, _ in parsed:
+        scan_at.append(pos)
+        copies.append((pos, data[int(info[4]):int(info[4]) + int(info[5])]))
+        pos += int(info[5])
+    for i in _range(0, len(parsed), PREPROCESS_BATCH_MAX):
+        index = list(_range(i, min(len(parsed), i + PREPROCESS_BATCH_MAX)))
+        pos = -(-pos // 16) * 16
+        groups.append((index, pos))
+        for k in index:
+            copies.append((pos, parsed[k][2]))
+            pos += _jpeg_dec.TABLE_BYTES
+    return copies, groups, scan_at, pos
+
+
+def jpeg_decode_staged(up, parsed, groups, scan_at, dst_offsets, dst):
+    """the decoder's launches behind the upload of a buffer laid out by jpeg_stage: image k of `parsed` goes to
+    dst[dst_offsets[k]:] -> the int32 status words on the device, one per file (not fetched: no synchronisation)"""
+    status = torch.empty((len(parsed),), dtype=torch.int32, device=up.device)
+    with torch.cuda.device(up.device):
+        for index, tables_at in groups:
+            rows = [(scan_at[k], int(parsed[k][1][5]), int(parsed[k][1][0]), int(parsed[k][1][1]), dst_offsets[k]) for k in index]
+            infos = np.stack([parsed[k][1] for k in index])
+            ws = torch.empty((_jpeg_dec.workspace_bytes(rows, infos),), dtype=torch.uint8, device=up.device)
+            _jpeg_dec.decode(up, rows, infos, up[tables_at:tables_at + len(index) * _jpeg_dec.TABLE_BYTES], dst,
+                             status[index[0]:index[0] + len(index)], ws)
+    return status
+
+
+def jpeg_status_error(status, names):
+    """ValueError naming the first file with a non-zero status word, or None; status: the words on the host"""
+    for s, name in zip(status, names):
+        if int(s) != 0:
+            return ValueError(f"jpeg: {name}: the scan does not decode ({_jpeg_dec.STATUS.get(int(s), int(s))})")
+    return None
+
+
+def decode_jpeg(files, out=None, device="cuda:0"):
+    """Baseline JPEG files -> packed RGB HWC images on the device, decoded on the GPU (csrc/jpeg_dec.hip; the rule and the
+    supported files are stated in include/codetr_jpeg_dec.h): only the headers are read on the host, the scans are
+    uploaded as they are in the files, in one copy with their tables, and decoded by five launches per
+    PREPROCESS_BATCH_MAX files.
+      files   each bytes / bytearray / memoryview, a 1-D uint8 array or host tensor, or a path
+      out     a flat uint8 device buffer to decode into (at least the returned layout's bytes) instead of a new one
+    -> (the flat uint8 buffer, [(offset, H, W)] per image); images start at multiples of 16 bytes, as stage_chunk lays
+    them out.  ValueError naming the image and the reason for a bad header, a file outside the supported set, or a scan
+    that does not decode."""
+    if not len(files):
+        raise ValueError("decode_jpeg: no files")
+    parsed = []
+    for i, item in enumerate(files):
+        data = jpeg_file_bytes(item)
+        rc, info, tables = _jpeg_dec.parse(data)
+        if rc != 0:
+            raise ValueError(f"decode_jpeg: image {i}: {jpeg_reason(rc, info)}")
+        parsed.append((data, info, tables))
+    staged, total = [], 0
+    for _, info, _ in parsed:
+        staged.append((total, int(info[0]), int(info[1])))
+        total += _jpeg_dec.output_bytes(info[0], info[1])
+    if out is None:
+        out = torch.empty((total,), dtype=torch.uint8, device=device)
+    elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
+          or out.numel() < total):
+        raise ValueError(f"decode_jpeg: out must be a contiguous flat uint8 buffer of at least {total} bytes on a GPU")
+    copies, groups, scan_at, end = jpeg_stage(parsed)
+    staging = torch.empty((end,), dtype=torch.uint8, pin_memory=True)
+    host = staging.numpy()
+    for at, part in copies:
+        host[at:at + part.size] = part
+    up = staging.to(out.device, non_blocking=True)
+    status = jpeg_decode_staged(up, parsed, groups, scan_at, [o for o, _, _ in staged], out)
+    err = jpeg_status_error(status.cpu().numpy(), [f"image {i}" for i in _range(len(parsed))])
+    if err is not None:
+        raise err
+    return out, staged
 
 
 FRAME_FORMATS = _cabi.FRAME_FORMATS

@@ -274,9 +274,10 @@ def frame_settings(input_format="rgb", color=None):
     """How `__call__(..., input_format=..., color=...)` reads its arguments: `input_format` a name of
     hip_ops.FRAME_FORMATS ('rgb', 'bgr', 'rgba', 'bgra', 'gray', 'nv12', 'nv21', 'i420'); `color` None or a dict with any
     of `matrix` ('bt601' | 'bt709') and `range` ('limited' | 'full'), completed from hip_ops.FRAME_COLOR (BT.601,
-    limited range: what OpenCV's cvtColor computes) -- only the YUV formats read it.
+    limited range: what OpenCV's cvtColor computes) -- only the YUV formats read it.  `input_format` may also be 'jpeg':
+    the items are baseline JPEG files (bytes, 1-D uint8 arrays or paths), decoded on the GPU (`hip_ops.decode_jpeg`).
     -> dict(format, matrix, range)"""
-    if not isinstance(input_format, str) or input_format not in hip_ops.FRAME_FORMATS:
+    if input_format != "jpeg" and (not isinstance(input_format, str) or input_format not in hip_ops.FRAME_FORMATS):
         raise ValueError(f"input_format must be one of {sorted(hip_ops.FRAME_FORMATS)}, got {input_format!r}")
     if color is not None and (not isinstance(color, dict) or set(color) - set(FRAME_COLOR_KEYS)):
         raise ValueError(f"color must be None or a dict with keys of {FRAME_COLOR_KEYS}, got {color!r}")
@@ -717,12 +718,18 @@ class Inferencer:
           * any other host frame: its raw planes, rows packed, each plane 16-byte aligned, in the one pinned staging
             buffer (1.5 bytes per pixel of NV12 / I420 instead of 3) and one `hip_ops.frames_to_rgb` launch behind the
             copy;
+          * JPEG files (`frames["format"] == "jpeg"`): only the headers are read on the host; the scans, as they are in
+            the files, and their tables ride in the one pinned staging buffer and `hip_ops.jpeg_decode_staged` launches
+            the decoder behind the copy.  The status words stay on the device until `check_jpeg_status`.  A file the
+            GPU decoder does not support is decoded with Pillow and staged as an RGB frame of the same chunk;
           * GPU-resident frames: no upload; one launch per group of frames that share a storage, which read the planes
             where they lie (offsets relative to the storage, pitches from the strides).  With no host frame in the chunk
             the tail is a small copy of its own.
         Host and GPU frames may be mixed.  The images of a converted chunk start at multiples of 16 bytes."""
         if not len(images):
             raise ValueError("stage_chunk: no images")
+        if frames is not None and frames["format"] == "jpeg":
+            return self._stage_jpeg_chunk(images, device, frames, tail)
         if self.host_rgb(images, frames):
             shapes = []
             for image in images:
@@ -784,6 +791,76 @@ class Inferencer:
         for flat, rows in groups.values():
             hip_ops.frames_to_rgb(flat, rows, dst_bytes, frames["matrix"], frames["range"], out=src)
         return src, staged, (up[tail_at:].view(tail.dtype).view(tail.shape) if tail is not None else None)
+
+    def _stage_jpeg_chunk(self, images, device, frames, tail):
+        """stage_chunk for JPEG files"""
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        first = getattr(self, "_chunk_start", 0)
+        parsed, items, names = [], [], []
+        for i, item in enumerate(images):
+            data = hip_ops.jpeg_file_bytes(item)
+            rc, info, tables = hip_ops.jpeg_parse(data)
+            if rc == 0:
+                items.append(len(parsed))
+                parsed.append((data, info, tables))
+                names.append(f"image {first + i}")
+                continue
+            reason = hip_ops.jpeg_reason(rc, info)
+            if reason in ("bad_header", "too_large"):
+                raise ValueError(f"input_format='jpeg': image {first + i}: {reason}")
+            rgb = hip_ops.jpeg_host_decode(data)
+            if rgb is None:
+                raise ValueError(f"input_format='jpeg': image {first + i}: {reason} files are not decoded on the GPU and "
+                                 "Pillow is not installed for the host fallback")
+            items.append(parse_frame(rgb, "rgb"))
+        staged, dst_bytes = [], 0
+        for it in items:
+            H, W = (int(parsed[it][1][0]), int(parsed[it][1][1])) if isinstance(it, int) else (it.H, it.W)
+            staged.append((dst_bytes, H, W))
+            dst_bytes = -(-(dst_bytes + H * W * 3) // 16) * 16
+        if callable(tail):
+            tail = tail(staged)
+        host_rows, copies, pos = [], [], 0
+        for it, (dst, H, W) in zip(items, staged):
+            if not isinstance(it, int):
+                pos = -(-pos // 16) * 16
+                copies.append((pos, it.planes[0]))
+                host_rows.append((it.code, H, W, pos, it.planes[0].shape[1], 0, 0, 0, 0, dst))
+                pos += it.planes[0].size
+        planes_end = pos
+        scan_copies, groups, scan_at, pos = hip_ops.jpeg_stage(parsed, pos)
+        tail_at = -(-pos // 16) * 16
+        tail_bytes = tail.contiguous().view(-1).view(torch.uint8) if tail is not None else None
+        total = pos if tail is None else tail_at + tail_bytes.numel()
+        staging = torch.empty((total,), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        for at, plane in copies:
+            host[at:at + plane.size].reshape(plane.shape)[...] = plane
+        for at, part in scan_copies:
+            host[at:at + part.size] = part
+        if tail is not None:
+            staging[tail_at:] = tail_bytes
+        up = staging.to(dev, non_blocking=True)
+        src = torch.empty((dst_bytes,), dtype=torch.uint8, device=dev)
+        if host_rows:
+            hip_ops.frames_to_rgb(up[:planes_end], host_rows, dst_bytes, frames["matrix"], frames["range"], out=src)
+        if parsed:
+            dst_offsets = [staged[i][0] for i, it in enumerate(items) if isinstance(it, int)]
+            status = hip_ops.jpeg_decode_staged(up, parsed, groups, scan_at, dst_offsets, src)
+            self._jpeg_pending = getattr(self, "_jpeg_pending", []) + [(status, names)]
+        return src, staged, (up[tail_at:].view(tail.dtype).view(tail.shape) if tail is not None else None)
+
+    def check_jpeg_status(self):
+        """Fetches the status words of the JPEG chunks staged since the last call and raises ValueError for the first
+        file whose scan did not decode.  `__call__` does this behind each chunk's download of its detections, so the
+        decoder adds no synchronisation in front of the forward."""
+        pending, self._jpeg_pending = getattr(self, "_jpeg_pending", []), []
+        for status, names in pending:
+            err = hip_ops.jpeg_status_error(status.cpu().numpy(), names)
+            if err is not None:
+                raise err
 
     def view_rows(self, offsets, shapes, scale, flips):
         """One TTA scale of a chunk: images of `shapes` (H, W) at byte `offsets`, resized keep-ratio into `scale`, once
@@ -1050,6 +1127,7 @@ class Inferencer:
             return results_dict
         for start in range(0, len(images), batch_size):
             chunk = images[start:start + batch_size]
+            self._chunk_start = start
             with torch.no_grad():
                 if self.tta is not None:
                     preds, src, rows, dets = self._tta_chunk(chunk, device, dtype, frames)
@@ -1058,6 +1136,8 @@ class Inferencer:
                 else:
                     x, m, metas, src, rows = self._preprocess_chunk(chunk, device, dtype, frames)
                     preds, dets = self._postprocess_chunk(self.model(x, m), metas)
+                if frames["format"] == "jpeg":   # (the detections are on the host: the status words cost no wait)
+                    self.check_jpeg_status()
                 if self.tracker is not None:   # the ids of the rows the predictions kept (a host-side cut included)
                     ids = self.track_chunk(dets, streams[start:start + batch_size])
                     for pred, row in zip(preds, ids):

@@ -57,6 +57,12 @@ and images/s of the Inferencer at batch_size 8 over --images images taken as the
 `tracker={}`, without a tracker, and with the host composition the tracker replaces (the untracked call's predictions
 through tests/track_ref.py frame by frame, the state on the host), the three in turn, three times.
 
+`--decode jpeg` prints only a `decode` record (JPEG files as input, fp16): --images frames of 1920x1080 (the gradient
+with noise of `--vis`) written as 4:2:0 files by Pillow where it imports (no restart markers), else by encode_jpeg; the
+decoder's five launches alone on eight of them (HIP event pairs, median), the bytes uploaded beside the bytes written,
+the host parser per file, Pillow's decode per frame; and images/s of the Inferencer at batch_size 8 fed the files
+(`input_format="jpeg"`), the same files decoded by Pillow inside the timed pass, and arrays decoded beforehand, in turn.
+
     python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis] [--slice]   -> one JSON line
     python tools/bench_inferencer.py --frames nv12 --resident
     python tools/bench_inferencer.py --track
@@ -565,6 +571,93 @@ def frames_record(inf, fmt, n_images, repeats, resident, bs=8):
     return rec
 
 
+def decode_files(frames, quality=90):
+    """the frames as JPEG files: written by Pillow where it imports (4:2:0, no restart markers: what a camera or a file
+    on disk looks like), else by the project's own GPU encoder (one restart interval per MCU row) -> (files, writer)"""
+    from codetr import hip_ops
+
+    try:
+        import io
+
+        from PIL import Image
+    except ImportError:
+        flat = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).to(DEV)
+        offs = np.cumsum([0] + [f.size for f in frames]).tolist()
+        return hip_ops.encode_jpeg(flat, [(o, f.shape[0], f.shape[1]) for o, f in zip(offs, frames)], quality, "420"), "encode_jpeg"
+    files = []
+    for f in frames:
+        b = io.BytesIO()
+        Image.fromarray(f).save(b, "JPEG", quality=quality, subsampling=2)
+        files.append(b.getvalue())
+    return files, "pillow"
+
+
+def decode_record(inf, n_images, repeats, bs=8):
+    """`--decode jpeg`: the Inferencer fed JPEG files (decoded on the GPU) against the same frames decoded on the host by
+    Pillow in front of the call and against frames that are already arrays; the decoder's launches alone; the bytes of
+    the upload either way"""
+    from codetr import hip_ops
+
+    frames = vis_frames(n_images)
+    files, writer = decode_files(frames)
+    rec = {"batch_size": bs, "images": n_images, "frame_wh": list(FRAME_WH), "repeats": repeats, "dtype": "fp16",
+           "files_written_by": writer, "file_bytes_mean": int(np.mean([len(f) for f in files])),
+           "raw_bytes": int(frames[0].size), "info": hip_ops.jpeg_info(files[0])}
+    # the launches alone: eight files, staged once
+    parsed = []
+    for f in files[:8]:
+        data = hip_ops.jpeg_file_bytes(f)
+        rc, info, tables = hip_ops.jpeg_parse(data)
+        assert rc == 0, hip_ops.jpeg_reason(rc, info)
+        parsed.append((data, info, tables))
+    copies, groups, scan_at, end = hip_ops.jpeg_stage(parsed)
+    host = np.zeros(end, np.uint8)
+    for at, part in copies:
+        host[at:at + part.size] = part
+    up = torch.from_numpy(host).to(DEV)
+    offs = [k * (-(-frames[0].size // 16) * 16) for k in range(len(parsed))]
+    dst = torch.empty((offs[-1] + frames[0].size,), dtype=torch.uint8, device=DEV)
+    us = _event_us_each(lambda: hip_ops.jpeg_decode_staged(up, parsed, groups, scan_at, offs, dst), launches=50, warmup=5)
+    rec["kernels"] = {"files": len(parsed), "us_per_call_median": us, "us_per_frame": round(us / len(parsed), 1),
+                      "bytes_uploaded": int(end), "bytes_written": int(len(parsed) * frames[0].size)}
+    t0 = time.perf_counter()
+    for f in files[:8]:
+        hip_ops.jpeg_parse(hip_ops.jpeg_file_bytes(f))
+    rec["host_parse_us_per_file"] = round((time.perf_counter() - t0) / 8 * 1e6, 1)
+    arms = {"jpeg_decoded_on_gpu": lambda: inf(files, device=DEV, dtype=torch.float16, batch_size=bs, input_format="jpeg"),
+            "arrays_already_decoded": lambda: inf(frames, device=DEV, dtype=torch.float16, batch_size=bs)}
+    if writer == "pillow":
+        import io
+
+        from PIL import Image
+
+        def host_decoded():
+            return inf([np.asarray(Image.open(io.BytesIO(f)).convert("RGB")) for f in files], device=DEV, dtype=torch.float16,
+                       batch_size=bs)
+
+        arms["jpeg_decoded_by_pillow_on_host"] = host_decoded
+        t0 = time.perf_counter()
+        for f in files[:8]:
+            np.asarray(Image.open(io.BytesIO(f)).convert("RGB"))
+        rec["pillow_decode_ms_per_frame"] = round((time.perf_counter() - t0) / 8 * 1e3, 2)
+    for name in arms:
+        rec[name] = {"pass_s": []}
+    with torch.no_grad():
+        for call in arms.values():
+            call()                                             # warm-up
+        for _ in range(3):                                     # the arms in turn
+            for name, call in arms.items():
+                for _ in range(repeats):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    call()
+                    rec[name]["pass_s"].append(round(time.perf_counter() - t0, 4))
+    for name in arms:
+        rec[name]["images_per_s"] = round(n_images / min(rec[name]["pass_s"]), 2)
+        rec[name]["images_per_s_median"] = round(n_images / float(np.median(rec[name]["pass_s"])), 2)
+    return rec
+
+
 def track_detections(frames, Q=300, objects=100, seed=5):
     """`frames` frames of Q fp16 detection rows: `objects` boxes on slow straight paths with jitter (score 0.75..0.95, five
     labels), the other rows clutter of score 0.15..0.55 -> hip_ops.Detections on the device"""
@@ -860,6 +953,7 @@ def main():
     ap.add_argument("--frames", choices=("nv12", "i420", "bgr"), help="only the frames record, for frames of this format")
     ap.add_argument("--resident", action="store_true", help="with --frames: also feed the frames as GPU-resident tensors")
     ap.add_argument("--track", action="store_true", help="only the tracking record: the images as one stream")
+    ap.add_argument("--decode", choices=("jpeg",), help="only the record of JPEG files as input, decoded on the GPU")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -875,6 +969,11 @@ def main():
         print(json.dumps({"metric": "Inferencer on decoder frames (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the kernel",
                           "frames": frames_record(infs["fp16"], a.frames, a.images, a.repeats, a.resident)}))
+        return
+    if a.decode:
+        print(json.dumps({"metric": "Inferencer on JPEG files (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the decoder",
+                          "decode": decode_record(infs["fp16"], a.images, a.repeats)}))
         return
     if a.track:
         print(json.dumps({"metric": "Inferencer tracking (Swin-L config, random weights)",
