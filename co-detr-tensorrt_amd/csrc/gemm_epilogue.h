@@ -1,5 +1,5 @@
-// The output rule of every 16-bit GEMM of this directory, said once (gemm_f16.hip: the 128-tile, 256-tile, X-stationary
-// and split-K kernels; gemm_persist.h: the two persistent kernels; gemm_fp8.hip: the activation of its 16-bit output).
+// The output rule of every 16-bit GEMM of this directory, said once (gemm_tile128.hip, gemm_tile256.hip, gemm_xs.hip: the
+// 128-tile, 256-tile, X-stationary and split-K kernels; gemm_persist.h: the two persistent kernels; gemm_fp8.hip: the activation of its 16-bit output).
 // tests/epilogue_exact.py restates it in torch and tests/test_epilogue_exact_gpu.py holds every kernel to it bit for bit:
 //
 //     y = E(E(act(acc + bias)) + r)            E = ONE round-to-nearest-even to the storage type

@@ -388,7 +388,7 @@ int codetr_encoder_projections_posgen_bf16(void *stream, const void *x_dev, cons
 
 /* Which of the three kernels behind codetr_linear_* serves a (16-byte aligned) problem: "tile128" (128x128 tiles, the
  * general kernel), "tile256" (256x256 tiles, one workgroup per CU), "xs" (X-stationary short-K kernel) or
- * "unsupported" (K % 64 != 0).  Pure function of the arguments and of the CODETR_GEMM_* environment switches; it is the
+ * "unsupported" (K % 64 != 0).  Pure function of the arguments (the library reads no environment variable); it is the
  * same routine the launcher consults, so tests can assert which kernel a model shape exercises. */
 const char *codetr_linear_variant(int64_t M, int64_t N, int64_t K, int act, int has_residual, int hm_head_dim);
 

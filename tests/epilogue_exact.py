@@ -1,7 +1,7 @@
 """Exact inputs and the bit-for-bit contract of the GEMM epilogues (pure torch: the same code runs on the CPU and on the
 device; tests/test_epilogue_exact_cpu.py checks the construction, tests/test_epilogue_exact_gpu.py runs the kernels).
 
-The contract lives in csrc/gemm_epilogue.h, the header the GEMM kernels of csrc/gemm_f16.hip, csrc/gemm_persist.h and
+The contract lives in csrc/gemm_epilogue.h, the header the GEMM kernels of csrc/gemm_tile128.hip, csrc/gemm_tile256.hip, csrc/gemm_xs.hip, csrc/gemm_persist.h and
 csrc/gemm_fp8.hip take their output values from (csrc/ffn_fused.hip states its own, for its second product):
 
     y = E(E(act(acc + bias)) + r)            E = ONE round-to-nearest-even to the storage type

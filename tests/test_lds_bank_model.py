@@ -59,7 +59,7 @@ def test_ffn_fp8_w1_fragments(kb, e):
 
 @pytest.mark.parametrize("bkt", [64, 32])
 def test_f16_gemm_tile_fragments(bkt):
-    # gemm_f16.hip read_frag(): lds_tile + row * (BKT * 2) + ((chunk ^ sw<BKT>(row)) * 16), chunk = ks * 4 + (lane >> 4)
+    # gemm_tile.h read_frag(): lds_tile + row * (BKT * 2) + ((chunk ^ sw<BKT>(row)) * 16), chunk = ks * 4 + (lane >> 4)
     sw = (lambda r: (r >> 1) & 7) if bkt == 64 else (lambda r: ((r >> 2) & 3) ^ (((r >> 2) & 1) << 1))
     for ks in range(bkt // 32):
         for rowbase in (0, 16, 112):
@@ -69,7 +69,7 @@ def test_f16_gemm_tile_fragments(bkt):
 
 @pytest.mark.parametrize("K", [192, 256])
 def test_f16_xs_kernel_weight_fragments(K):
-    # gemm_f16.hip linear_xs_kernel: sW + row * (K * 2) + (((ks * 4 + grp) ^ (row & SWZ)) * 16), SWZ = 15 if K/8 % 16 == 0 else 7
+    # gemm_xs.hip linear_xs_kernel: sW + row * (K * 2) + (((ks * 4 + grp) ^ (row & SWZ)) * 16), SWZ = 15 if K/8 % 16 == 0 else 7
     swz = 15 if (K // 8) % 16 == 0 else 7
     for ks in range(K // 32):
         for nt in range(2):

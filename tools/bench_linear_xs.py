@@ -1,4 +1,4 @@
-"""The X-stationary GEMM (csrc/gemm_f16.hip linear_xs_kernel) at its launch shapes of one 4-image 1920x1280 forward: the
+"""The X-stationary GEMM (csrc/gemm_xs.hip linear_xs_kernel) at its launch shapes of one 4-image 1920x1280 forward: the
 encoder's value projection (head-major output) and (offsets | logits) projection (query + query_pos folded into the operand
 load), Swin stage 0's norm1 -> qkv and norm2 -> fc1 + GELU.  us per launch, algorithmic TB/s (X (+X2) read once, Y written
 once) and TF/s -- these launches sit between the two roofs.

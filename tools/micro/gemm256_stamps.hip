@@ -6,7 +6,7 @@
 #ifndef NOSTAMPS   // -DNOSTAMPS -DCODETR_GEMM_ABL=mask: ablation builds timed by events only (the stamps themselves cost ~15 %)
 #define CODETR_GEMM_STAMPS
 #endif
-#include "../../co-detr-tensorrt_amd/csrc/gemm_f16.hip"
+#include "../../co-detr-tensorrt_amd/csrc/gemm_tile256.hip"   // (its launch function is called directly: the front door is another file)
 
 #include <algorithm>
 #include <cstdio>
@@ -15,6 +15,10 @@
 int main(int argc, char** argv) {
   const int64_t M = argc > 1 ? atoll(argv[1]) : 80640, N = argc > 2 ? atoll(argv[2]) : 2304, K = argc > 3 ? atoll(argv[3]) : 768;
   const int act = argc > 4 ? atoi(argv[4]) : 0, res = argc > 5 ? atoi(argv[5]) : 0;
+  if (!gemm_route::big_applicable(M, N, K, 0) || act < 0 || act > 3 || (act == 3 && !res)) {
+    printf("M %lld N %lld K %lld act %d res %d is not a problem codetr_linear_* gives the 256-tile kernel\n", (long long)M, (long long)N, (long long)K, act, res);
+    return 1;
+  }
   unsigned short *X, *W, *B, *R, *Y;
   hipMalloc(&X, M * K * 2); hipMalloc(&W, N * K * 2); hipMalloc(&B, N * 2); hipMalloc(&R, M * N * 2); hipMalloc(&Y, M * N * 2);
   std::vector<unsigned short> h(std::max(M * K, N * K));
@@ -28,11 +32,11 @@ int main(int argc, char** argv) {
 #ifdef CODETR_GEMM_STAMPS
   hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &stamps, sizeof(stamps));
 #endif
-  for (int it = 0; it < 5; ++it) codetr_linear_f16(nullptr, X, W, B, res ? R : nullptr, nullptr, Y, M, N, K, act, 0, 0);
+  for (int it = 0; it < 5; ++it) gemm_route::launch_tile256(nullptr, false, X, W, B, res ? R : nullptr, Y, nullptr, (int)M, (int)N, (int)K, act);
   hipDeviceSynchronize();
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   hipEventRecord(e0);
-  codetr_linear_f16(nullptr, X, W, B, res ? R : nullptr, nullptr, Y, M, N, K, act, 0, 0);
+  gemm_route::launch_tile256(nullptr, false, X, W, B, res ? R : nullptr, Y, nullptr, (int)M, (int)N, (int)K, act);
   hipEventRecord(e1); hipDeviceSynchronize();
   float ms; hipEventElapsedTime(&ms, e0, e1);
 #ifndef CODETR_GEMM_STAMPS

@@ -7,7 +7,7 @@
 #ifndef NOSTAMPS
 #define CODETR_XS_STAMPS
 #endif
-#include "../../co-detr-tensorrt_amd/csrc/gemm_f16.hip"
+#include "../../co-detr-tensorrt_amd/csrc/gemm_xs.hip"
 
 #include <algorithm>
 #include <cstdio>
