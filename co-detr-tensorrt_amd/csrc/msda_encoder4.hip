@@ -37,10 +37,13 @@
 #include "codetr_hip.h"
 #include "device_prims.h"
 #include "large_lds.h"
+#include "msda_window.h"
 
 namespace {
 
-constexpr int kL = 5, kP = 4;
+using namespace msda_win;
+
+constexpr int kL = kLevels, kP = 4;
 constexpr int kMaxM = 16;     // heads with a staged window of their own
 constexpr int kMaxIt = 3;     // iterations (16 queries each) per wave
 #ifndef MSDA4_KQ
@@ -70,59 +73,12 @@ __device__ unsigned long long* g_msda4_stamps;
 struct Geom4 {
   int M, S, RX, RY;
   int H[kL], W[kL], start[kL];
-  int first[kL];                       // first level of level l's pass
   signed char win[kMaxM][kL][4];       // per (head, level): offsets (pixels of that level) in [x lo, x hi] x [y lo, y hi] are staged
   const float* vcounts;                // [B][L][2] valid pixels (w, h) of every level, fp32
   unsigned queue_off;                  // LDS byte offset of the fix-up queues (behind the largest pass)
   int head_major;                      // value map [B][M][S][32] (a head's rows contiguous) instead of [B][S][M][32]
 };
 
-// ---- region geometry along one axis (n pixels, R regions): pixel x belongs to region r iff (x + 0.5) / n in [r / R, (r + 1) / R)
-__host__ __device__ inline int q_bound(int r, int n, int R) { return (2 * r * n + R - 1) / (2 * R); }
-// staged columns for offsets in [lo, hi], in EXTENDED coordinates (-1 and n are the zero border):
-//   first = floor(r n / R - 1/2 + lo) clamped to [-1, n - 1]; last = ceil((r + 1) n / R - 1/2 + hi) clamped to [first + 1, n]
-__host__ __device__ inline int ext_lo(int r, int n, int R, int lo) {
-  const int num = 2 * r * n - R + 2 * lo * R;
-  const int v = num < 0 ? -1 : num / (2 * R);
-  return v > n - 1 ? n - 1 : v;
-}
-__host__ __device__ inline int ext_hi(int r, int n, int R, int hi, int first) {
-  const int num = 2 * (r + 1) * n - R + 2 * hi * R;
-  int v = num <= 0 ? 0 : (num + 2 * R - 1) / (2 * R);
-  v = v > n ? n : v;
-  return v < first + 1 ? first + 1 : v;
-}
-
-// floor(a / b) for 0 <= a < 2^22, 0 < b (one reciprocal + a fix-up; see msda_encoder.hip)
-__device__ __forceinline__ int fdiv(int a, int b) {
-  int q = (int)((float)a * __builtin_amdgcn_rcpf((float)b));
-  const int r = a - q * b;
-  q += r >= b ? 1 : 0;
-  q -= r < 0 ? 1 : 0;
-  return q;
-}
-__device__ __forceinline__ int q_bound_d(int r, int n, int R) { return fdiv(2 * r * n + R - 1, 2 * R); }
-__device__ __forceinline__ int ext_lo_d(int r, int n, int R, int lo) {
-  const int num = 2 * r * n - R + 2 * lo * R;
-  const int v = num < 0 ? -1 : fdiv(num, 2 * R);
-  return v > n - 1 ? n - 1 : v;
-}
-__device__ __forceinline__ int ext_hi_d(int r, int n, int R, int hi, int first) {
-  const int num = 2 * (r + 1) * n - R + 2 * hi * R;
-  int v = num <= 0 ? 0 : fdiv(num + 2 * R - 1, 2 * R);
-  v = v > n ? n : v;
-  return v < first + 1 ? first + 1 : v;
-}
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-__device__ __forceinline__ float unif(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-
-__device__ __forceinline__ f16x2 as_h2(unsigned u) { return __builtin_bit_cast(f16x2, u); }
-__device__ __forceinline__ unsigned pack_h2(float a, float b) {   // v_cvt_pk_f16_f32 on gfx950 (round to nearest even)
-  const f16x2 v = {(_Float16)a, (_Float16)b};
-  return __builtin_bit_cast(unsigned, v);
-}
-__device__ __forceinline__ float h_lo(unsigned u) { return (float)as_h2(u)[0]; }
-__device__ __forceinline__ float h_hi(unsigned u) { return (float)as_h2(u)[1]; }
 // acc += (float)h.lo / (float)h.hi in one instruction each
 __device__ __forceinline__ void acc_h2(float& lo, float& hi, f16x2 h) {
   const unsigned u = __builtin_bit_cast(unsigned, h);
@@ -130,82 +86,20 @@ __device__ __forceinline__ void acc_h2(float& lo, float& hi, f16x2 h) {
   asm("v_fma_mix_f32 %0, %1, 1.0, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(hi) : "v"(u));
 }
 
-// Storage type of the packed projection and of the output (the staged VALUE map is fp16 in either case: the blend runs on
-// packed halves, and gfx950 has no packed bf16 FMA -- a bf16 model's value projection writes fp16, three mantissa bits
-// more than bf16, through codetr_linear_bf16_f16out)
-struct EF16 {
-  __device__ static float lo(unsigned u) { return (float)as_h2(u)[0]; }
-  __device__ static float hi(unsigned u) { return (float)as_h2(u)[1]; }
-  __device__ static u32x4 pack8(const float (&a)[8]) {
-    return u32x4{pack_h2(a[0], a[1]), pack_h2(a[2], a[3]), pack_h2(a[4], a[5]), pack_h2(a[6], a[7])};
-  }
-};
-struct EBF16 {
-  __device__ static float lo(unsigned u) { return bf16_to_f32((unsigned short)u); }
-  __device__ static float hi(unsigned u) { return __uint_as_float(u & 0xffff0000u); }
-  __device__ static unsigned pk(float a, float b) {   // v_cvt_pk_bf16_f32 (round to nearest even)
-    const bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-  }
-  __device__ static u32x4 pack8(const float (&a)[8]) {
-    return u32x4{pk(a[0], a[1]), pk(a[2], a[3]), pk(a[4], a[5]), pk(a[6], a[7])};
-  }
-};
+// ET, WinF16 or WinBF16: storage type of the packed projection and of the output (the staged VALUE map is fp16 in either
+// case: the blend runs on packed halves, and gfx950 has no packed bf16 FMA -- a bf16 model's value projection writes fp16,
+// three mantissa bits more than bf16, through codetr_linear_bf16_f16out)
 
 // What a wave keeps about one level (all wave-uniform: SGPRs)
-struct Lv {
-  int W, H, start;           // level size, first pixel inside S
-  int px0, py0;              // window origin, extended coordinates
-  int xspan, yspan;          // largest (x0 - px0), (y0 - py0) whose four corners are staged
-  int pw, ph;                // staged columns / rows
-  unsigned base;             // LDS byte address of staged pixel (px0, py0)
-  unsigned pitch;            // pw * 64
+struct Lv : WinLv {
   float vcx, vcy;            // valid pixels along x / y
-  int qx0, qy0, qw, slot0;   // the region's queries on this level: rectangle origin, width, first slot
 };
 
-struct TileId {
-  int b, rx, ry, m;
-};
-// tile -> (image, region column / row, head): heads innermost (the M slices of a 512-byte pixel row meet in one XCD's L2),
-// regions in horizontal bands of kBand rows walked column by column (vertically adjacent regions share most of their
-// windows: an L2 hit instead of a second trip over the fabric)
-__device__ __forceinline__ TileId decode_tile(unsigned tile, const Geom4& g) {
-  TileId t;
-  const int unit = fdiv((int)tile, g.M);
-  t.m = (int)tile - unit * g.M;
-  const int regions = g.RX * g.RY;
-  t.b = fdiv(unit, regions);
-  const int reg = unit - t.b * regions;
-  const int per_band = kBand * g.RX;
-  const int band = fdiv(reg, per_band);
-  const int r = reg - band * per_band;
-  const int y0 = band * kBand;
-  const int bh = min(kBand, g.RY - y0);
-  t.rx = fdiv(r, bh);
-  t.ry = y0 + (r - t.rx * bh);
-  return t;
-}
-
-// one sample of the lane (level k, the lane's point): image coordinates -> (floor, fraction)
-struct Smp {
-  float lw, lh;
-  int x0, y0;
-};
 template <class ET>
 __device__ __forceinline__ Smp sample_at(const Lv& v, float bx, float by, unsigned o2) {
-  Smp s;
   // reference: loc = ref_k + off / (W, H); im = loc * (W, H) - 0.5 with ref_k = centre / (vr_q size_q) * vr_k and
   // vr * size = valid pixel count  ->  im = (centre / vc_q) * vc_k - 0.5 + off          (transformer.py:280-305, cu:241-247)
-  // (fmaxf: a NaN coordinate becomes a huge negative one -> outside every window and outside the gate: the sample is
-  // dropped, as by the reference's comparisons)
-  const float w_im = fmaxf(fmaf(bx, v.vcx, -0.5f) + ET::lo(o2), -3.0e38f);
-  const float h_im = fmaxf(fmaf(by, v.vcy, -0.5f) + ET::hi(o2), -3.0e38f);
-  s.lw = __builtin_amdgcn_fractf(w_im);
-  s.lh = __builtin_amdgcn_fractf(h_im);
-  s.x0 = floor_i(w_im);
-  s.y0 = floor_i(h_im);
-  return s;
+  return sample_of(nan_low(fmaf(bx, v.vcx, -0.5f) + ET::lo(o2)), nan_low(fmaf(by, v.vcy, -0.5f) + ET::hi(o2)));
 }
 
 template <int T>
@@ -229,16 +123,15 @@ __device__ __forceinline__ bool prepare(Prep (&pp)[NLV], const Lv (&lv)[kL], con
   for (int i = 0; i < NLV; ++i) {
     const Lv& v = lv[LV0 + i];
     const Smp s = sample_at<ET>(v, bx, by, o2[LV0 + i]);
-    const unsigned dx = (unsigned)(s.x0 - v.px0), dy = (unsigned)(s.y0 - v.py0);
-    const bool ok = dx <= (unsigned)v.xspan && dy <= (unsigned)v.yspan;   // all four corners are staged (or zero border)
+    const WinHit h = in_window(s, v);
     const float a = aw[LV0 + i];
     const float wy1 = s.lh * a, wy0 = a - wy1, wx0 = 1.f - s.lw;
-    const unsigned w01 = pack_h2(wy0 * wx0, wy0 * s.lw), w23 = pack_h2(wy1 * wx0, wy1 * s.lw);
-    const unsigned a_in = __umul24(dy, v.pitch) + v.base + (dx << 6);
-    pp[i].ad = ok ? a_in : v.base;   // a finite staged row for the (zero-weight) reads of a sample served elsewhere
-    pp[i].w01 = ok ? w01 : 0u;
-    pp[i].w23 = ok ? w23 : 0u;
-    allok = allok && ok;
+    const unsigned w01 = WinF16::pack2(wy0 * wx0, wy0 * s.lw), w23 = WinF16::pack2(wy1 * wx0, wy1 * s.lw);
+    const unsigned a_in = window_addr(v, h);
+    pp[i].ad = h.ok ? a_in : v.base;   // a finite staged row for the (zero-weight) reads of a sample served elsewhere
+    pp[i].w01 = h.ok ? w01 : 0u;
+    pp[i].w23 = h.ok ? w23 : 0u;
+    allok = allok && h.ok;
   }
   return allok;
 }
@@ -250,15 +143,11 @@ __device__ __forceinline__ void gather(float (&acc)[8], const Prep (&pp)[NLV], c
   constexpr int NS = 4 * NLV, DEPTH = 1, NB = DEPTH + 1;   // (rows two / three steps ahead measured slower: registers)
   f16x8 rows[NB][4];
   unsigned wA[NB], wB[NB];
-  // DPP hazard: a VGPR written by a vector instruction may be read by a DPP instruction only two wait states later.  The
-  // compiler inserts them for its own DPP forms but cannot see inside quad_bcast_add's inline assembly, and the addresses
-  // may have been written by the instruction right before (preparation directly in front of the gather: measured wrong
-  // results without this).  One s_nop per gather, tied to the address registers so that nothing moves across it.
   unsigned adr[NLV];
 #pragma unroll
   for (int i = 0; i < NLV; ++i) adr[i] = pp[i].ad;
-  if (NLV == 1) asm volatile("s_nop 1" : "+v"(adr[0]));
-  else asm volatile("s_nop 1" : "+v"(adr[0]), "+v"(adr[NLV - 1]));
+  if (NLV == 1) dpp_guard(adr[0]);   // (quad_bcast_add below reads them)
+  else dpp_guard(adr[0], adr[NLV - 1]);
   auto fetch = [&](int s_, int buf) {
     const int o = s_ & 3, i = s_ >> 2;
     const unsigned a0 = quad_bcast_add(adr[i], o, lds_lane);
@@ -360,17 +249,10 @@ struct Fix {
     for (int i = 0; i < NLV; ++i) {
       const Lv& v = lv[LV0 + i];
       const Smp s = sample_at<ET>(v, bx, by, o2[LV0 + i]);
-      const unsigned dx = (unsigned)(s.x0 - v.px0), dy = (unsigned)(s.y0 - v.py0);
-      const bool ok = dx <= (unsigned)v.xspan && dy <= (unsigned)v.yspan;
-      // cu:249: h_im > -1 && w_im > -1 && h_im < H && w_im < W  <=>  floor in [-1, size - 1]
-      const bool gate = (unsigned)(s.x0 + 1) <= (unsigned)v.W && (unsigned)(s.y0 + 1) <= (unsigned)v.H;
-      const float a = aw[LV0 + i];
-      const float wy0 = s.y0 >= 0 ? (1.f - s.lh) * a : 0.f, wy1 = s.y0 + 1 <= v.H - 1 ? s.lh * a : 0.f;   // cu:52-71
-      const float wx0 = s.x0 >= 0 ? 1.f - s.lw : 0.f, wx1 = s.x0 + 1 <= v.W - 1 ? s.lw : 0.f;
-      const int x0c = max(s.x0, 0), x1c = min(s.x0 + 1, v.W - 1), y0c = max(s.y0, 0), y1c = min(s.y0 + 1, v.H - 1);
-      rec[i] = u32x4{(unsigned)(v.start + y0c * v.W + x0c), (unsigned)((y1c - y0c) * v.W) | ((unsigned)(x1c - x0c) << 16),
-                     pack_h2(wy0 * wx0, wy0 * wx1), pack_h2(wy1 * wx0, wy1 * wx1)};
-      bad |= (!ok && gate) ? 1u << (sub + 4 * i) : 0u;
+      const bool ok = in_window(s, v).ok;
+      const FixCorners f = fix_corners(v, s, aw[LV0 + i]);
+      rec[i] = u32x4{f.first, f.strides, WinF16::pack2(f.w00, f.w01), WinF16::pack2(f.w10, f.w11)};
+      bad |= (!ok && f.gate) ? 1u << (sub + 4 * i) : 0u;
     }
     bad |= dpp_u<kXor2>(bad);
     bad |= dpp_u<kXor1>(bad);
@@ -397,7 +279,6 @@ template <class ET, int T>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void msda_encoder_v4_kernel(
     const _Float16* __restrict__ value, const unsigned short* __restrict__ packed, unsigned short* __restrict__ out,
     const Geom4 g, const int packed_stride) {
-  constexpr unsigned kRow = 64;
   constexpr int kWaves = Cfg<T>::kWaves, kPairs = Cfg<T>::kPairs;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned lds0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)smem;
@@ -416,16 +297,12 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
   const unsigned pix_bytes = g.head_major ? kRow : (unsigned)M * kRow;
 
   // ---- wave-uniform geometry -> scalar registers ----
-  const TileId t0 = decode_tile(xcd_tile(blockIdx.x, gridDim.x), g);
+  const TileId t0 = decode_tile<kBand>((int)xcd_tile(blockIdx.x, gridDim.x), g.M, g.RX, g.RY);
   const TileId t = {uni(t0.b), uni(t0.rx), uni(t0.ry), uni(t0.m)};
   Lv lv[kL];
   int total;
   {
-    // 40 divisions (per level: two window bounds and two query bounds per axis), one per LANE: lane 8 l + j computes item
-    // j of level l -- 0: first staged column, 1: last staged column (before the "at least two columns" clamp), 2 / 3: rows,
-    // 4 / 5: first query column of this region / of the next, 6 / 7: rows -- and the results return to scalar registers
-    // with v_readlane.  (Computed level by level in wave-uniform code this was 600 vector instructions per wave, a fifth of
-    // the kernel.)
+    // lane 8 l + j: item j of level l (fill_levels), its window offset byte j & 3 of the (head, level)'s win word
     const int gl = lane >> 3 > kL - 1 ? kL - 1 : lane >> 3, gj = lane & 7;
     int nW = g.W[0], nH = g.H[0], wword = 0;
     const int mw = t.m < kMaxM ? t.m : kMaxM - 1;
@@ -437,46 +314,15 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
       nH = gl == l ? g.H[l] : nH;
       wword = gl == l ? ww : wword;
     }
-    const bool ay = (gj & 2) != 0, isq = gj >= 4, plus = (gj & 1) != 0;
-    const int n = ay ? nH : nW, R = ay ? g.RY : g.RX, rr = (ay ? t.ry : t.rx) + (plus ? 1 : 0);
-    const int wv = (int)(signed char)((unsigned)wword >> (8 * (gj & 3)));
-    const int num = 2 * rr * n + (isq ? R - 1 : 2 * wv * R - R);
-    const int numd = (!isq && plus) ? num + 2 * R - 1 : num;
-    const int q = fdiv(numd > 0 ? numd : 0, 2 * R);
-    const int res = isq ? q : plus ? (num <= 0 ? 0 : (q > n ? n : q)) : (num < 0 ? -1 : (q > n - 1 ? n - 1 : q));
-    int slot = 0;
-    unsigned base = lds0;
+    const int res = region_item(gj, t.rx, t.ry, nW, nH, g.RX, g.RY,
+                                [&](bool) { return (int)(signed char)((unsigned)wword >> (8 * (gj & 3))); });
+    total = fill_levels(lv, g.W, g.H, g.start, res, lds0);
 #pragma unroll
     for (int l = 0; l < kL; ++l) {
-      Lv& v = lv[l];
-      v.W = g.W[l];
-      v.H = g.H[l];
-      v.start = g.start[l];
-      v.px0 = __builtin_amdgcn_readlane(res, 8 * l + 0);
-      int px1 = __builtin_amdgcn_readlane(res, 8 * l + 1);
-      v.py0 = __builtin_amdgcn_readlane(res, 8 * l + 2);
-      int py1 = __builtin_amdgcn_readlane(res, 8 * l + 3);
-      px1 = px1 < v.px0 + 1 ? v.px0 + 1 : px1;
-      py1 = py1 < v.py0 + 1 ? v.py0 + 1 : py1;
-      v.pw = px1 - v.px0 + 1;
-      v.ph = py1 - v.py0 + 1;
-      v.xspan = v.pw - 2;
-      v.yspan = v.ph - 2;
-      v.pitch = (unsigned)v.pw * kRow;
-      if (g.first[l] == l) base = lds0;       // a new pass starts at the front of the buffer
-      v.base = base;
-      base += (unsigned)(v.pw * v.ph) * kRow;
       const float* vc = g.vcounts + ((size_t)t.b * kL + l) * 2;
-      v.vcx = unif(vc[0]);
-      v.vcy = unif(vc[1]);
-      v.qx0 = __builtin_amdgcn_readlane(res, 8 * l + 4);
-      v.qy0 = __builtin_amdgcn_readlane(res, 8 * l + 6);
-      v.qw = __builtin_amdgcn_readlane(res, 8 * l + 5) - v.qx0;
-      const int qh = __builtin_amdgcn_readlane(res, 8 * l + 7) - v.qy0;
-      v.slot0 = slot;
-      slot += v.qw * qh;
+      lv[l].vcx = unif(vc[0]);
+      lv[l].vcy = unif(vc[1]);
     }
-    total = slot;
   }
   const int n_it = total > wave * 16 ? (total - wave * 16 + kPairs - 1) / kPairs : 0;   // <= kMaxIt (host-checked)
 
@@ -487,19 +333,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
                               (t.m * 64 + sub * 16) * 2;
 
   // ---- the wave's queries: slot -> (level, pixel) -> flattened index, centre / valid count; raw operands requested ----
-  // per-level tables, level l in LANE l (a select between two scalars costs two vector instructions -- one constant-bus
-  // operand per instruction -- so a per-lane level lookup is a ds_bpermute from these instead of a select chain)
-  int tS0 = 0, tA = 0, tB = 0, tSt = 0;
+  // (level_tables / slot_query; the reciprocals of the level's valid pixel counts sit in two tables of the same kind)
+  const LvTables tab = level_tables(lv, lane);
   float tRx = 0.f, tRy = 0.f;
 #pragma unroll
   for (int l = 0; l < kL; ++l) {
-    const bool me = lane == l;
-    tS0 = me ? lv[l].slot0 : tS0;
-    tA = me ? (lv[l].qx0 | (lv[l].qy0 << 16)) : tA;
-    tB = me ? (lv[l].W | (lv[l].qw << 16)) : tB;
-    tSt = me ? lv[l].start : tSt;
-    tRx = me ? lv[l].vcx : tRx;
-    tRy = me ? lv[l].vcy : tRy;
+    tRx = lane == l ? lv[l].vcx : tRx;
+    tRy = lane == l ? lv[l].vcy : tRy;
   }
   tRx = __builtin_amdgcn_rcpf(tRx);
   tRy = __builtin_amdgcn_rcpf(tRy);
@@ -514,20 +354,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
     if (it < n_it) {
       int sl = (it * kWaves + wave) * 16 + pl;
       sl = sl < total ? sl : total - 1;
-      int lvq = 0;
-#pragma unroll
-      for (int l = 1; l < kL; ++l) lvq += sl >= lv[l].slot0 ? 4 : 0;     // byte address of the level's lane
-      const int s0 = __builtin_amdgcn_ds_bpermute(lvq, tS0), cA = __builtin_amdgcn_ds_bpermute(lvq, tA);
-      const int cB = __builtin_amdgcn_ds_bpermute(lvq, tB), st = __builtin_amdgcn_ds_bpermute(lvq, tSt);
-      const float rx_ = __int_as_float(__builtin_amdgcn_ds_bpermute(lvq, __float_as_int(tRx)));
-      const float ry_ = __int_as_float(__builtin_amdgcn_ds_bpermute(lvq, __float_as_int(tRy)));
-      const int tq = sl - s0, qw = cB >> 16, W = cB & 0xffff;
-      const int yy = (int)(((float)tq + 0.5f) * __builtin_amdgcn_rcpf((float)qw));
-      const int y = (cA >> 16) + yy, x = (cA & 0xffff) + (tq - yy * qw);
-      qs[it] = st + y * W + x;
+      const SlotQuery sq = slot_query(lv, tab, sl);
+      const float rx_ = __int_as_float(__builtin_amdgcn_ds_bpermute(sq.lvq, __float_as_int(tRx)));
+      const float ry_ = __int_as_float(__builtin_amdgcn_ds_bpermute(sq.lvq, __float_as_int(tRy)));
+      qs[it] = sq.q;
       // get_reference_points (transformer.py:280-305): centre / (valid ratio * size) = centre / valid pixel count
-      bx[it] = ((float)x + 0.5f) * rx_;
-      by[it] = ((float)y + 0.5f) * ry_;
+      bx[it] = ((float)sq.x + 0.5f) * rx_;
+      by[it] = ((float)sq.y + 0.5f) * ry_;
       const unsigned char* pr = prow + (size_t)((unsigned)qs[it] * (unsigned)packed_stride) * 2;
       rawA[it] = *reinterpret_cast<const u32x4*>(pr);
       rawB[it] = *reinterpret_cast<const u32x4*>(pr + 16);
@@ -575,36 +408,9 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
     M4_T(a);
     if (LV0 > 0 && !(kAbl & 16)) __syncthreads();   // every wave is done reading the previous pass's rows
     M4_T(b);
-    // -- the pass's windows -> LDS, ROW-WISE: a wave takes window rows y = wave, wave + kWaves, ...; one LDS-DMA instruction
-    // moves 16 pixels of the row (4 lanes x 16 B per pixel = its 64-byte head slice) from a wave-uniform 64-bit base in
-    // SGPRs + a per-lane constant offset to the uniform LDS address of the row's chunk (+ 16 B per lane): no per-lane row /
-    // column arithmetic (the piece-linear walk of rounds 2-4 spent ~14 vector instructions per DMA on a division).  Cells
-    // outside the image -- the zero border -- are written by ds_write instead.
+    // -- the pass's windows -> LDS
 #pragma unroll
-    for (int i = 0; i < NLV; ++i) {
-      const Lv& v = lv[LV0 + i];
-      const int px_l = lane >> 2;                                      // pixel of the chunk this lane serves
-      const unsigned voff = (unsigned)px_l * pix_bytes + (unsigned)sub * 16;
-      const int chunks = (v.pw + 15) >> 4;
-      for (int y = wave; y < ((kAbl & 2) ? 0 : v.ph); y += kWaves) {
-        const int gy = v.py0 + y;
-        const bool row_in = (unsigned)gy < (unsigned)v.H;              // (uniform)
-        for (int c = 0; c < chunks; ++c) {
-          const int x0 = 16 * c;                                       // window column of lane 0's pixel
-          const unsigned dst = (v.base - lds0) + (unsigned)(y * v.pw + x0) * kRow;
-          const int gx = v.px0 + x0 + px_l;
-          const bool mine = x0 + px_l < v.pw;
-          const bool col_in = (unsigned)gx < (unsigned)v.W;
-          if (row_in) {
-            if (mine && col_in)
-              lds_dma16(vhead0 + (ptrdiff_t)(v.start + gy * v.W + v.px0 + x0) * (ptrdiff_t)pix_bytes, voff, lds0 + dst);
-            if (mine && !col_in) *reinterpret_cast<u32x4*>(smem + dst + lane * 16) = u32x4{0u, 0u, 0u, 0u};
-          } else if (mine) {
-            *reinterpret_cast<u32x4*>(smem + dst + lane * 16) = u32x4{0u, 0u, 0u, 0u};
-          }
-        }
-      }
-    }
+    for (int i = 0; i < NLV; ++i) stage_window<kWaves, kAbl>(lv[LV0 + i], vhead0, pix_bytes, smem, lds0, wave, lane, sub);
     M4_T(c);
     if (!(kAbl & 1)) wait_vmcnt<0>();
     M4_T(d);
@@ -633,17 +439,13 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
     M4_PUT(PI * 5 + 3, m4_te - m4_td); M4_PUT(PI * 5 + 4, m4_tf - m4_te);
   };
   M4_T(k1);
-  run_pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-  run_pass(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
-  run_pass(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
+  for_each_pass(run_pass);
 
   unsigned char* orow = reinterpret_cast<unsigned char*>(out) + ((size_t)t.b * g.S * M + t.m) * kRow + sub * 16;
 #pragma unroll
   for (int it = 0; it < kMaxIt; ++it)
-    if (it < n_it && (it * kWaves + wave) * 16 + pl < total) {
-      const u32x4 o = ET::pack8(acc[it]);
-      if (!(kAbl & 32) || o[0] == 0x12345678u) *reinterpret_cast<u32x4*>(orow + (size_t)((unsigned)qs[it] * ((unsigned)M * kRow))) = o;   // out is [B, S, M, 32] in either case
-    }
+    if (it < n_it && (it * kWaves + wave) * 16 + pl < total)
+      store_out<ET, kAbl>(orow, qs[it], M, acc[it]);   // out is [B, S, M, 32] in either case
 #ifdef MSDA4_STAMPS
   M4_T(k2);
   m4_s[15] = m4_tk1 - m4_tk0;   // prologue (geometry, operand loads, softmax)
@@ -654,8 +456,6 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(4, 4))) void 
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------
-constexpr int kPassFirst[kL] = {0, 1, 1, 3, 3};
-
 struct Plan4 {
   Geom4 g;
   int rc;
@@ -680,7 +480,6 @@ inline Plan4 plan4(const int64_t* shapes, int64_t S, int M, int L, int P, const 
     g.H[l] = (int)h;
     g.W[l] = (int)w;
     g.start[l] = (int)sum;
-    g.first[l] = kPassFirst[l];
     sum += h * w;
   }
   if (sum != S) return pl.rc = CODETR_E_BADARG, pl;
@@ -701,9 +500,7 @@ inline Plan4 plan4(const int64_t* shapes, int64_t S, int M, int L, int P, const 
   g.RX = (g.W[fine] + region_w - 1) / region_w;
   g.RY = (g.H[fine] + region_h - 1) / region_h;
   for (int l = 0; l < L; ++l) {   // the kernel's reciprocal-based floor division is exact below 2^22
-    const int64_t nx = 2 * (int64_t)(g.RX + 1) * g.W[l] + (2 * (int64_t)wmax + 3) * g.RX;
-    const int64_t ny = 2 * (int64_t)(g.RY + 1) * g.H[l] + (2 * (int64_t)wmax + 3) * g.RY;
-    if (nx >= (1 << 22) || ny >= (1 << 22)) return pl;
+    if (region_dividend_bound(g.W[l], g.RX, wmax) >= (1 << 22) || region_dividend_bound(g.H[l], g.RY, wmax) >= (1 << 22)) return pl;
   }
   int rows_cap = 0, slots = 0;
   for (int m = 0; m < (M < kMaxM ? M : kMaxM); ++m) {
@@ -725,7 +522,7 @@ inline Plan4 plan4(const int64_t* shapes, int64_t S, int M, int L, int P, const 
         qh = q > qh ? q : qh;
       }
       slots += qw * qh;
-      rows_pass = (kPassFirst[l] == l ? 0 : rows_pass) + pw * ph;
+      rows_pass = (pass_first(l) == l ? 0 : rows_pass) + pw * ph;
       rows_cap = rows_pass > rows_cap ? rows_pass : rows_cap;
     }
   }
@@ -774,7 +571,7 @@ int codetr_msda_encoder_forward_packed_f16(void* stream, const void* value_dev, 
                                            const void* packed_dev, int64_t packed_row_stride, const float* valid_counts_dev,
                                            int64_t B, int64_t S, int M, int D, int L, int P, const int8_t* windows_host,
                                            int region_w, int region_h, int threads, int value_head_major, void* out_dev) {
-  return launch4<EF16>(static_cast<hipStream_t>(stream), value_dev, level_shapes_host, packed_dev, packed_row_stride,
+  return launch4<WinF16>(static_cast<hipStream_t>(stream), value_dev, level_shapes_host, packed_dev, packed_row_stride,
                        valid_counts_dev, B, S, M, D, L, P, reinterpret_cast<const signed char*>(windows_host), region_w,
                        region_h, threads, value_head_major, out_dev);
 }
@@ -783,7 +580,7 @@ int codetr_msda_encoder_forward_packed_bf16(void* stream, const void* value_f16_
                                             const void* packed_dev, int64_t packed_row_stride, const float* valid_counts_dev,
                                             int64_t B, int64_t S, int M, int D, int L, int P, const int8_t* windows_host,
                                             int region_w, int region_h, int threads, int value_head_major, void* out_dev) {
-  return launch4<EBF16>(static_cast<hipStream_t>(stream), value_f16_dev, level_shapes_host, packed_dev, packed_row_stride,
+  return launch4<WinBF16>(static_cast<hipStream_t>(stream), value_f16_dev, level_shapes_host, packed_dev, packed_row_stride,
                         valid_counts_dev, B, S, M, D, L, P, reinterpret_cast<const signed char*>(windows_host), region_w,
                         region_h, threads, value_head_major, out_dev);
 }

@@ -41,6 +41,7 @@
 #include "device_prims.h"
 #include "large_lds.h"
 #include "msda_op4_plan.h"
+#include "msda_window.h"
 
 namespace {
 
@@ -59,99 +60,34 @@ static_assert(kWaves * 16 * kRecBytes <= (int)kWinBytes, "the operand records al
 constexpr int kAbl = MSDA_OP4_ABL;
 
 
-// floor(a / b) for 0 <= a < 2^22, 0 < b (one reciprocal + a fix-up)
-__device__ __forceinline__ int fdiv(int a, int b) {
-  int q = (int)((float)a * __builtin_amdgcn_rcpf((float)b));
-  const int r = a - q * b;
-  q += r >= b ? 1 : 0;
-  q -= r < 0 ? 1 : 0;
-  return q;
-}
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-__device__ __forceinline__ f16x2 as_h2(unsigned u) { return __builtin_bit_cast(f16x2, u); }
-
-// The op's two 16-bit element types, as (low, high) element pairs of a dword.  Both are 2 bytes wide: staging, operand
-// records, plan and fix-up queue do not depend on which; only widening, the blend and the final rounding do.
-struct OpF16 {
-  __device__ __forceinline__ static float elem(unsigned u, int i) { return (float)as_h2(u)[i]; }
+// The op's two element types: the blend on top of the shared widening / rounding
+struct OpF16 : WinF16 {
   // acc += (float)(half of `u`) * w in ONE instruction each: the fp16 value is read in place
   __device__ __forceinline__ static void fma2(float& lo, float& hi, unsigned u, float w) {
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "+v"(lo) : "v"(u), "v"(w));
     asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(hi) : "v"(u), "v"(w));
   }
-  __device__ __forceinline__ static unsigned pack2(float a, float b) {   // v_cvt_pk_f16_f32 (round to nearest even)
-    const f16x2 v = {(_Float16)a, (_Float16)b};
-    return __builtin_bit_cast(unsigned, v);
-  }
 };
-struct OpBF16 {
-  // exact widening: a bf16 value is the top half of the fp32 one (one shift / one mask)
-  __device__ __forceinline__ static float elem(unsigned u, int i) { return i ? __uint_as_float(u & 0xffff0000u) : bf16_to_f32((unsigned short)u); }
+struct OpBF16 : WinBF16 {
   // gfx950 has no mixed-precision FMA that reads bf16: both halves widened, then two fp32 FMAs -- twice the fp16 blend's
   // vector instructions.  (One v_pk_fma_f32 per pair instead measured 2-5 % slower: profiles/r07_msda_op_bf16.txt)
   __device__ __forceinline__ static void fma2(float& lo, float& hi, unsigned u, float w) {
     lo = fmaf(elem(u, 0), w, lo);
     hi = fmaf(elem(u, 1), w, hi);
   }
-  __device__ __forceinline__ static unsigned pack2(float a, float b) {   // v_cvt_pk_bf16_f32 (round to nearest even; a NaN stays a NaN)
-    const bf16x2 v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned, v);
-  }
 };
 
 // What a wave keeps about one level (all wave-uniform: SGPRs)
-struct Lv {
-  int W, H, start;           // level size, first pixel inside S
+struct Lv : WinLv {
   float fW, fH;
-  int px0, py0;              // window origin, extended coordinates (-1 / size = the zero border)
-  int xspan, yspan;          // largest (x0 - px0), (y0 - py0) whose four corners are staged
-  int pw, ph;                // staged columns / rows
-  unsigned base;             // LDS byte address of staged pixel (px0, py0)
-  unsigned pitch;            // pw * 64
-  int qx0, qy0, qw, slot0;   // the region's queries on this level: rectangle origin, width, first slot
 };
 
-struct TileId {
-  int b, rx, ry, m;
-};
-constexpr int kBand = 4;
-// tile -> (image, region column / row, head): heads innermost (the M slices of a 512-byte pixel row meet in one XCD's L2),
-// regions in horizontal bands of kBand rows walked column by column (vertically adjacent regions share most of their windows)
-__device__ __forceinline__ TileId decode_tile(int tile, int M, int RX, int RY) {
-  TileId t;
-  const int unit = fdiv(tile, M);
-  t.m = tile - unit * M;
-  const int regions = RX * RY;
-  t.b = fdiv(unit, regions);
-  const int reg = unit - t.b * regions;
-  const int per_band = kBand * RX;
-  const int band = fdiv(reg, per_band);
-  const int r = reg - band * per_band;
-  const int y0 = band * kBand;
-  const int bh = min(kBand, RY - y0);
-  t.rx = fdiv(r, bh);
-  t.ry = y0 + (r - t.rx * bh);
-  return t;
-}
+constexpr int kBand = 4;   // region rows per band of the tile walk (decode_tile)
 
-// one sample of the lane (level k, the lane's point): image coordinates -> (floor, fraction)
-struct Smp {
-  float lw, lh;
-  int x0, y0;
-};
 template <typename T>
 __device__ __forceinline__ Smp sample_at(const Lv& v, unsigned o2) {
-  Smp s;
-  // cu:241-247: h_im = loc_h * H - 0.5, w_im = loc_w * W - 0.5 (x first in memory).  fmaxf: a NaN coordinate becomes a huge
-  // negative one -> outside every window and outside the gate: the sample is dropped, as by the reference's comparisons
-  const float w_im = fmaxf(fmaf(T::elem(o2, 0), v.fW, -0.5f), -3.0e38f);
-  const float h_im = fmaxf(fmaf(T::elem(o2, 1), v.fH, -0.5f), -3.0e38f);
-  s.lw = __builtin_amdgcn_fractf(w_im);
-  s.lh = __builtin_amdgcn_fractf(h_im);
-  s.x0 = floor_i(w_im);
-  s.y0 = floor_i(h_im);
-  return s;
+  // cu:241-247: h_im = loc_h * H - 0.5, w_im = loc_w * W - 0.5 (x first in memory)
+  return sample_of(nan_low(fmaf(T::elem(o2, 0), v.fW, -0.5f)), nan_low(fmaf(T::elem(o2, 1), v.fH, -0.5f)));
 }
 
 // weight of level k out of the lane's five packed 16-bit values
@@ -169,16 +105,15 @@ struct Prep {
 template <typename T>
 __device__ __forceinline__ bool prepare(Prep& pp, const Lv& v, const float a, const unsigned o2) {
   const Smp s = sample_at<T>(v, o2);
-  const unsigned dx = (unsigned)(s.x0 - v.px0), dy = (unsigned)(s.y0 - v.py0);
-  const bool ok = dx <= (unsigned)v.xspan && dy <= (unsigned)v.yspan;   // all four corners are staged (or zero border)
+  const WinHit h = in_window(s, v);
   const float wy1 = s.lh * a, wy0 = a - wy1, wx0 = 1.f - s.lw;
-  const unsigned a_in = __umul24(dy, v.pitch) + v.base + (dx << 6);
-  pp.ad = ok ? a_in : v.base;
-  pp.w00 = ok ? wy0 * wx0 : 0.f;
-  pp.w01 = ok ? wy0 * s.lw : 0.f;
-  pp.w10 = ok ? wy1 * wx0 : 0.f;
-  pp.w11 = ok ? wy1 * s.lw : 0.f;
-  return ok;
+  const unsigned a_in = window_addr(v, h);
+  pp.ad = h.ok ? a_in : v.base;
+  pp.w00 = h.ok ? wy0 * wx0 : 0.f;
+  pp.w01 = h.ok ? wy0 * s.lw : 0.f;
+  pp.w10 = h.ok ? wy1 * wx0 : 0.f;
+  pp.w11 = h.ok ? wy1 * s.lw : 0.f;
+  return h.ok;
 }
 
 // gather of one iteration and one level: the quad's four points, one per step; the rows of step s + 1 are requested before
@@ -191,10 +126,8 @@ __device__ __forceinline__ void gather_level(float (&acc)[8], const Prep& pp, co
   // double buffer of whole steps needs 8 sets: the kernel runs at four waves per SIMD, 128 registers, and spilled)
   constexpr int RING = 5;
   u32x4 rows[RING];
-  // DPP hazard (see msda_encoder4.hip): the inline-assembly DPP add reads an address register the instruction right before
-  // may have written; one s_nop tied to it
   unsigned adr = pp.ad;
-  asm volatile("s_nop 1" : "+v"(adr));
+  dpp_guard(adr);   // (quad_bcast_add below reads it)
   unsigned a0[4];
 #pragma unroll
   for (int o = 0; o < 4; ++o) a0[o] = quad_bcast_add(adr, o, lds_lane);
@@ -227,15 +160,11 @@ template <typename T>
 __device__ __forceinline__ FixRec fix_record(const Lv& v, const float a, const unsigned o2) {
   FixRec f;
   const Smp s = sample_at<T>(v, o2);
-  const unsigned dx = (unsigned)(s.x0 - v.px0), dy = (unsigned)(s.y0 - v.py0);
-  f.ok = dx <= (unsigned)v.xspan && dy <= (unsigned)v.yspan;
-  // cu:249: h_im > -1 && w_im > -1 && h_im < H && w_im < W  <=>  floor in [-1, size - 1]
-  f.gate = (unsigned)(s.x0 + 1) <= (unsigned)v.W && (unsigned)(s.y0 + 1) <= (unsigned)v.H;
-  const float wy0 = s.y0 >= 0 ? (1.f - s.lh) * a : 0.f, wy1 = s.y0 + 1 <= v.H - 1 ? s.lh * a : 0.f;   // cu:52-71
-  const float wx0 = s.x0 >= 0 ? 1.f - s.lw : 0.f, wx1 = s.x0 + 1 <= v.W - 1 ? s.lw : 0.f;
-  const int x0c = max(s.x0, 0), x1c = min(s.x0 + 1, v.W - 1), y0c = max(s.y0, 0), y1c = min(s.y0 + 1, v.H - 1);
-  f.ra = u32x4{(unsigned)(v.start + y0c * v.W + x0c), (unsigned)((y1c - y0c) * v.W) | ((unsigned)(x1c - x0c) << 16), 0u, 0u};
-  f.rb = u32x4{__float_as_uint(wy0 * wx0), __float_as_uint(wy0 * wx1), __float_as_uint(wy1 * wx0), __float_as_uint(wy1 * wx1)};
+  f.ok = in_window(s, v).ok;
+  const FixCorners c = fix_corners(v, s, a);
+  f.gate = c.gate;
+  f.ra = u32x4{c.first, c.strides, 0u, 0u};
+  f.rb = u32x4{__float_as_uint(c.w00), __float_as_uint(c.w01), __float_as_uint(c.w10), __float_as_uint(c.w11)};
   return f;
 }
 
@@ -290,7 +219,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const unsigned short* __restrict__ value, const int64_t* __restrict__ spatial_shapes, const int64_t* __restrict__ level_start,
     const unsigned short* __restrict__ loc, const unsigned short* __restrict__ weight, unsigned short* __restrict__ out,
     const int B, const int S, const int M) {
-  constexpr unsigned kRow = 64;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const unsigned lds0 = (unsigned)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)smem;
 
@@ -331,15 +259,12 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const unsigned lds_lane = (unsigned)sub * 16;
     unsigned char* const rec = smem + (wave * 16 + pl) * kRecBytes;
     // ---- wave-uniform geometry -> scalar registers ----
-    const TileId t0 = decode_tile(tile, M, RX, RY);
+    const TileId t0 = decode_tile<kBand>(tile, M, RX, RY);
     const TileId t = {uni(t0.b), uni(t0.rx), uni(t0.ry), uni(t0.m)};
     Lv lv[kL];
     int total;
     {
-      // 40 divisions (per level: two window bounds and two query bounds per axis), one per LANE: lane 8 l + j computes item
-      // j of level l -- 0: first staged column, 1: last staged column (before the "at least two columns" clamp), 2 / 3: rows,
-      // 4 / 5: first query column of this region / of the next, 6 / 7: rows -- and the results return to scalar registers
-      // with v_readlane
+      // lane 8 l + j: item j of level l (fill_levels), its window offset the level's margin, -mg on the low side, +mg on the high
       const int gl = lane >> 3 > kL - 1 ? kL - 1 : lane >> 3, gj = lane & 7;
       int nW = plan.W[0], nH = plan.H[0], mgl = plan.mg[0];
 #pragma unroll
@@ -348,45 +273,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
         nH = gl == l ? plan.H[l] : nH;
         mgl = gl == l ? plan.mg[l] : mgl;
       }
-      const bool ay = (gj & 2) != 0, isq = gj >= 4, plus = (gj & 1) != 0;
-      const int n = ay ? nH : nW, R = ay ? RY : RX, rr = (ay ? t.ry : t.rx) + (plus ? 1 : 0);
-      const int wv = plus ? mgl : -mgl;
-      const int num = 2 * rr * n + (isq ? R - 1 : 2 * wv * R - R);
-      const int numd = (!isq && plus) ? num + 2 * R - 1 : num;
-      const int q = fdiv(numd > 0 ? numd : 0, 2 * R);
-      const int res = isq ? q : plus ? (num <= 0 ? 0 : (q > n ? n : q)) : (num < 0 ? -1 : (q > n - 1 ? n - 1 : q));
-      int slot = 0;
-      unsigned base = lds0;
+      const int res = region_item(gj, t.rx, t.ry, nW, nH, RX, RY, [&](bool plus) { return plus ? mgl : -mgl; });
+      total = fill_levels(lv, plan.W, plan.H, plan.start, res, lds0);
 #pragma unroll
       for (int l = 0; l < kL; ++l) {
-        Lv& v = lv[l];
-        v.W = plan.W[l];
-        v.H = plan.H[l];
-        v.fW = (float)v.W;
-        v.fH = (float)v.H;
-        v.start = plan.start[l];
-        v.px0 = __builtin_amdgcn_readlane(res, 8 * l + 0);
-        int px1 = __builtin_amdgcn_readlane(res, 8 * l + 1);
-        v.py0 = __builtin_amdgcn_readlane(res, 8 * l + 2);
-        int py1 = __builtin_amdgcn_readlane(res, 8 * l + 3);
-        px1 = px1 < v.px0 + 1 ? v.px0 + 1 : px1;
-        py1 = py1 < v.py0 + 1 ? v.py0 + 1 : py1;
-        v.pw = px1 - v.px0 + 1;
-        v.ph = py1 - v.py0 + 1;
-        v.xspan = v.pw - 2;
-        v.yspan = v.ph - 2;
-        v.pitch = (unsigned)v.pw * kRow;
-        if (pass_first(l) == l) base = lds0;       // a new pass starts at the front of the buffer
-        v.base = base;
-        base += (unsigned)(v.pw * v.ph) * kRow;
-        v.qx0 = __builtin_amdgcn_readlane(res, 8 * l + 4);
-        v.qy0 = __builtin_amdgcn_readlane(res, 8 * l + 6);
-        v.qw = __builtin_amdgcn_readlane(res, 8 * l + 5) - v.qx0;
-        const int qh = __builtin_amdgcn_readlane(res, 8 * l + 7) - v.qy0;
-        v.slot0 = slot;
-        slot += v.qw * qh;
+        lv[l].fW = (float)plan.W[l];
+        lv[l].fH = (float)plan.H[l];
       }
-      total = slot;
     }
     const int n_it = total > wave * 16 ? (total - wave * 16 + kPairs - 1) / kPairs : 0;   // <= kMaxIt (the plan's slot bound)
 
@@ -397,15 +290,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     const unsigned char* w_b = reinterpret_cast<const unsigned char*>(weight) + ((size_t)t.b * S * M + t.m) * 40;
 
     // ---- the wave's queries: slot -> (level, pixel) -> flattened index; raw operands requested ----
-    int tS0 = 0, tA = 0, tB = 0, tSt = 0;   // per-level tables, level l in LANE l (looked up with ds_bpermute)
-#pragma unroll
-    for (int l = 0; l < kL; ++l) {
-      const bool me = lane == l;
-      tS0 = me ? lv[l].slot0 : tS0;
-      tA = me ? (lv[l].qx0 | (lv[l].qy0 << 16)) : tA;
-      tB = me ? (lv[l].W | (lv[l].qw << 16)) : tB;
-      tSt = me ? lv[l].start : tSt;
-    }
+    const LvTables tab = level_tables(lv, lane);
     int qs[kMaxIt];
     u32x4 rawA[kMaxIt];
     u32x2 rawB[kMaxIt], rawC[kMaxIt];
@@ -417,15 +302,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
       if (it < n_it) {
         int sl = (it * kWaves + wave) * 16 + pl;
         sl = sl < total ? sl : total - 1;
-        int lvq = 0;
-#pragma unroll
-        for (int l = 1; l < kL; ++l) lvq += sl >= lv[l].slot0 ? 4 : 0;     // byte address of the level's lane
-        const int s0 = __builtin_amdgcn_ds_bpermute(lvq, tS0), cA = __builtin_amdgcn_ds_bpermute(lvq, tA);
-        const int cB = __builtin_amdgcn_ds_bpermute(lvq, tB), st = __builtin_amdgcn_ds_bpermute(lvq, tSt);
-        const int tq = sl - s0, qw = cB >> 16, W = cB & 0xffff;
-        const int yy = (int)(((float)tq + 0.5f) * __builtin_amdgcn_rcpf((float)qw));
-        const int y = (cA >> 16) + yy, x = (cA & 0xffff) + (tq - yy * qw);
-        qs[it] = st + y * W + x;
+        qs[it] = slot_query(lv, tab, sl).q;
         // a quad fetches whole 16-byte pieces of the pair's rows: lane p the four (x, y) of level p; then lane 0 level 4, lanes
         // 1 and 2 weights 0-7 / 8-15, lane 3 weights 16-19 (its second 8-byte load repeats the first: nothing past the row)
         const unsigned pair = (unsigned)qs[it] * (unsigned)M;
@@ -471,34 +348,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
     auto run_pass = [&](auto lv0_c, auto nlv_c) {
       constexpr int LV0 = decltype(lv0_c)::value, NLV = decltype(nlv_c)::value;
       if (LV0 > 0) __syncthreads();   // every wave is done reading the previous pass's rows
-      // -- the pass's windows -> LDS, ROW-WISE: a wave takes window rows y = wave, wave + 8, ...; one LDS-DMA instruction moves
-      // 16 pixels of the row (4 lanes x 16 B per pixel = its 64-byte head slice) from a wave-uniform base + a per-lane constant
-      // offset; cells outside the image -- the zero border -- are written by ds_write instead
+      // -- the pass's windows -> LDS
 #pragma unroll
-      for (int i = 0; i < NLV; ++i) {
-        const Lv& v = lv[LV0 + i];
-        const int px_l = lane >> 2;                                      // pixel of the chunk this lane serves
-        const unsigned voff = (unsigned)px_l * pix_bytes + (unsigned)sub * 16;
-        const int chunks = (v.pw + 15) >> 4;
-        for (int y = wave; y < ((kAbl & 2) ? 0 : v.ph); y += kWaves) {
-          const int gy = v.py0 + y;
-          const bool row_in = (unsigned)gy < (unsigned)v.H;              // (uniform)
-          for (int c = 0; c < chunks; ++c) {
-            const int x0 = 16 * c;                                       // window column of lane 0's pixel
-            const unsigned dst = (v.base - lds0) + (unsigned)(y * v.pw + x0) * kRow;
-            const int gx = v.px0 + x0 + px_l;
-            const bool mine = x0 + px_l < v.pw;
-            const bool col_in = (unsigned)gx < (unsigned)v.W;
-            if (row_in) {
-              if (mine && col_in)
-                lds_dma16(vhead0 + (ptrdiff_t)(v.start + gy * v.W + v.px0 + x0) * (ptrdiff_t)pix_bytes, voff, lds0 + dst);
-              if (mine && !col_in) *reinterpret_cast<u32x4*>(smem + dst + lane * 16) = u32x4{0u, 0u, 0u, 0u};
-            } else if (mine) {
-              *reinterpret_cast<u32x4*>(smem + dst + lane * 16) = u32x4{0u, 0u, 0u, 0u};
-            }
-          }
-        }
-      }
+      for (int i = 0; i < NLV; ++i) stage_window<kWaves, kAbl>(lv[LV0 + i], vhead0, pix_bytes, smem, lds0, wave, lane, sub);
       wait_vmcnt<0>();
       __syncthreads();
 #pragma unroll
@@ -516,19 +368,13 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(4, 4))
           if (!clean) fixup<T, LV0, NLV>(acc[it], lv, awp[it], o2[it], queue, vhead, pix_bytes, sub);
         }
     };
-    run_pass(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
-    run_pass(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{});
-    run_pass(std::integral_constant<int, 3>{}, std::integral_constant<int, 2>{});
+    for_each_pass(run_pass);
 
     unsigned char* orow = reinterpret_cast<unsigned char*>(out) + ((size_t)t.b * S * M + t.m) * kRow + sub * 16;
 #pragma unroll
     for (int it = 0; it < kMaxIt; ++it)
-      if (it < n_it && (it * kWaves + wave) * 16 + pl < total) {
-        const float (&a)[8] = acc[it];
-        const u32x4 o = {T::pack2(a[0], a[1]), T::pack2(a[2], a[3]), T::pack2(a[4], a[5]), T::pack2(a[6], a[7])};
-        if (!(kAbl & 32) || o[0] == 0x12345678u)
-          *reinterpret_cast<u32x4*>(orow + (size_t)((unsigned)qs[it] * ((unsigned)M * kRow))) = o;
-      }
+      if (it < n_it && (it * kWaves + wave) * 16 + pl < total)
+        store_out<T, kAbl>(orow, qs[it], M, acc[it]);
   }
 }
 

@@ -10,9 +10,13 @@
 #pragma once
 #include <stdint.h>
 
+#include "msda_window_geom.h"
+
 namespace codetr_op4 {
 
-constexpr int kL = 5, kP = 4;
+using namespace msda_win;   // idiv / cdiv, pass_first
+
+constexpr int kL = kLevels, kP = 4;
 constexpr int kRegion = 16;          // a workgroup's region: 16 x 16 pixels of the finest level
 constexpr int kThreads = 512;
 constexpr int kPairs = kThreads / 4; // (query, head) pairs per workgroup iteration
@@ -25,24 +29,6 @@ struct Plan {
   int RX, RY;                        // regions along x / y
   int mg[kL];                        // window margin of each level, pixels of that level
 };
-
-// floor(a / b) for 0 <= a < 2^22, 0 < b.  Device: one float reciprocal + an exact fix-up (a 32-bit integer division is ~40
-// instructions, and the general kernel evaluates the verdict below in every workgroup of its skipped launch).
-__host__ __device__ inline int idiv(int a, int b) {
-#ifdef __HIP_DEVICE_COMPILE__
-  int q = (int)((float)a * __builtin_amdgcn_rcpf((float)b));
-  const int r = a - q * b;
-  q += r >= b ? 1 : 0;
-  q -= r < 0 ? 1 : 0;
-  return q;
-#else
-  return a / b;
-#endif
-}
-__host__ __device__ inline int cdiv(int a, int b) { return idiv(a + b - 1, b); }
-
-// first level of the pass a level belongs to: passes {0}, {1, 2}, {3, 4}
-__host__ __device__ inline int pass_first(int l) { return l == 0 ? 0 : l <= 2 ? 1 : 3; }
 
 // Pixels a pass (levels first .. last) stages at margin mg, an upper bound over the regions.  Staged columns of a region on
 // level l: floor(r n / R - 1/2 - mg) .. ceil((r + 1) n / R - 1/2 + mg), clamped to the level plus its zero border
