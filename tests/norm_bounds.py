@@ -145,10 +145,13 @@ def _assemble(ex, rel, e_mean):
     return Bound(u * (ex.out.abs() + fp32) + TINY[ex.dtype] + fp32, fp32)
 
 
-def bound_layernorm(ex):
-    """Bound(total, fp32): the derived elementwise bound on |kernel - ex.out| and the part of it that fp32 arithmetic owns"""
-    G, NCH = ln_config(ex.out.shape[-1])
-    n_s = 8 * NCH + int(math.log2(G))
+def bound_layernorm(ex, n_s=None):
+    """Bound(total, fp32): the derived elementwise bound on |kernel - ex.out| and the part of it that fp32 arithmetic owns.
+    n_s: the additions between an element and the row sum, for a kernel that sums in another shape than layernorm.hip's
+    (the fused FFN / Swin MLP epilogues: C / 4 in-lane values and two shuffles, tests/ffn_bounds.py)"""
+    if n_s is None:
+        G, NCH = ln_config(ex.out.shape[-1])
+        n_s = 8 * NCH + int(math.log2(G))
     e_mean = E32 * (n_s + 2) * ex.x.abs().mean(-1, keepdim=True)
     e_var = E32 * (n_s + 5) * (ex.var + e_mean ** 2 + ex.eps) + e_mean ** 2
     rel = _rsqrt_rel(e_var / (ex.var + ex.eps)) + 2 * E32
