@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _assign, _cabi, _jpeg, _jpeg_dec
+from . import _assign, _cabi, _jpeg, _jpeg_dec, _wbf
 
 # ops served by hand-written HIP kernels in this build (kept in sync with include/codetr_hip.h)
 NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_window_attention(f16, head_dim 32)",
@@ -617,6 +617,8 @@ def detections_to_host(dets):
     """postprocess_detections' (or postprocess_detections_soft's, `index` included) result on the host: one
     device-to-host copy of the packed buffer"""
     N, Q = dets.scores.shape
+    if isinstance(dets, WbfDetections):
+        return _wbf_views(dets.packed.cpu(), N, Q, dets.scores.dtype)
     return _detection_views(dets.packed.cpu(), N, Q, dets.scores.dtype, isinstance(dets, SoftDetections))
 
 
@@ -688,6 +690,37 @@ def _tta_mode(nms):
     return _cabi.TTA_NMS_MODES[method], float(nms.get("iou_threshold", 0.3)), float(nms.get("min_score", 1e-3))
 
 
+def _merge_operands(name, view_dets, flips, widths):
+    """the operand checks of tta_merge and wbf_merge (`name`) -> (dtype, device, N, V, Q, boxes, scores, labels, count,
+    flips, widths): the entries concatenated in order, `widths` a tensor"""
+    if not view_dets:
+        raise ValueError(f"{name}: no views")
+    scores0 = view_dets[0].scores
+    _gpu(scores0, name)
+    dtype, dev, Q = scores0.dtype, scores0.device, scores0.shape[-1]
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"{name}: detections in f16, bf16 or f32")
+    if not torch.is_tensor(widths):
+        widths = torch.tensor([float(w) for w in widths], dtype=torch.float32)
+    N = widths.numel()
+    if N == 0 or any(d.scores.dim() != 2 or d.scores.shape[0] % N or d.scores.shape[1] != Q or d.scores.dtype != dtype
+                     for d in view_dets):
+        raise ValueError(f"{name}: every entry [views * N, Q] detections of one dtype, N = len(widths) > 0")
+    V = sum(d.scores.shape[0] for d in view_dets) // N
+    flips = [bool(f) for f in flips]
+    if len(flips) != V:
+        raise ValueError(f"{name}: {V} views but {len(flips)} flip flags")
+    if V > TTA_MAX_VIEWS or V * Q > TTA_MAX_CANDIDATES:
+        raise ValueError(f"{name}: at most {TTA_MAX_VIEWS} views and {TTA_MAX_CANDIDATES} candidates per image, "
+                         f"got {V} views of {Q}")
+    one = len(view_dets) == 1
+    boxes = (view_dets[0].boxes if one else torch.cat([d.boxes for d in view_dets])).contiguous()
+    scores = (view_dets[0].scores if one else torch.cat([d.scores for d in view_dets])).contiguous()
+    labels = (view_dets[0].labels if one else torch.cat([d.labels for d in view_dets])).contiguous()
+    count = (view_dets[0].count if one else torch.cat([d.count for d in view_dets])).contiguous()
+    return dtype, dev, N, V, Q, boxes, scores, labels, count, flips, widths
+
+
 def tta_merge(view_dets, flips, widths, nms=None, max_per_img=None):
     """mmdet DetTTAModel._merge_single_sample for a batch of N images in one launch (csrc/prepost.hip; semantics:
     include/codetr_hip.h): the views' detections un-flipped, concatenated, batched_nms(nms), the best max_per_img kept.
@@ -701,31 +734,7 @@ def tta_merge(view_dets, flips, widths, nms=None, max_per_img=None):
     -> SoftDetections over [N, K] rows (K = max_per_img, or V * Q): `index` is c = v * Q + j of every row, scores are
     the decayed ones in the soft modes; `detections_to_host` fetches all of it in one copy."""
     mode, iou, min_score = _tta_mode(dict(nms) if nms is not None else {})
-    if not view_dets:
-        raise ValueError("tta_merge: no views")
-    scores0 = view_dets[0].scores
-    _gpu(scores0, "tta_merge")
-    dtype, dev, Q = scores0.dtype, scores0.device, scores0.shape[-1]
-    if dtype not in (torch.float16, torch.bfloat16, torch.float32):
-        raise ValueError("tta_merge: detections in f16, bf16 or f32")
-    if not torch.is_tensor(widths):
-        widths = torch.tensor([float(w) for w in widths], dtype=torch.float32)
-    N = widths.numel()
-    if N == 0 or any(d.scores.dim() != 2 or d.scores.shape[0] % N or d.scores.shape[1] != Q or d.scores.dtype != dtype
-                     for d in view_dets):
-        raise ValueError("tta_merge: every entry [views * N, Q] detections of one dtype, N = len(widths) > 0")
-    V = sum(d.scores.shape[0] for d in view_dets) // N
-    flips = [bool(f) for f in flips]
-    if len(flips) != V:
-        raise ValueError(f"tta_merge: {V} views but {len(flips)} flip flags")
-    if V > TTA_MAX_VIEWS or V * Q > TTA_MAX_CANDIDATES:
-        raise ValueError(f"tta_merge: at most {TTA_MAX_VIEWS} views and {TTA_MAX_CANDIDATES} candidates per image, "
-                         f"got {V} views of {Q}")
-    one = len(view_dets) == 1
-    boxes = (view_dets[0].boxes if one else torch.cat([d.boxes for d in view_dets])).contiguous()
-    scores = (view_dets[0].scores if one else torch.cat([d.scores for d in view_dets])).contiguous()
-    labels = (view_dets[0].labels if one else torch.cat([d.labels for d in view_dets])).contiguous()
-    count = (view_dets[0].count if one else torch.cat([d.count for d in view_dets])).contiguous()
+    dtype, dev, N, V, Q, boxes, scores, labels, count, flips, widths = _merge_operands("tta_merge", view_dets, flips, widths)
     keep = 0 if max_per_img is None else int(max_per_img)
     K = keep if keep > 0 else V * Q
     out = _new_detections(N, K, dtype, dev, True, Q == 0)
@@ -736,6 +745,114 @@ def tta_merge(view_dets, flips, widths, nms=None, max_per_img=None):
                         sum(1 << v for v, f in enumerate(flips) if f), widths.to(dev, torch.float32).contiguous(), mode,
                         iou, min_score, keep, out.boxes, out.scores, out.labels, out.index, out.count)
     return out
+
+
+# wbf_merge's result: the fields of SoftDetections + votes [N,K] int32, the number of candidates fused into every row --
+# six views of the one byte buffer `packed` (labels, count, index, votes, boxes, scores in this order)
+WbfDetections = collections.namedtuple("WbfDetections", "boxes scores labels count index votes packed")
+WBF_MAX_CANDIDATES = _wbf.MAX_CANDIDATES
+WBF = dict(iou_threshold=0.55, skip_box_thr=0.0, conf_type="avg", weights=None)   # ensemble_boxes' defaults
+
+
+def _wbf_views(packed, N, K, dtype):
+    es = torch.empty((), dtype=dtype).element_size()
+    o1 = N * K * 8
+    o2 = o1 + N * 4
+    o3 = o2 + N * K * 4
+    o4 = o3 + N * K * 4
+    o5 = o4 + N * K * 4 * es
+    o6 = o5 + N * K * es
+    return WbfDetections(packed[o4:o5].view(dtype).view(N, K, 4), packed[o5:o6].view(dtype).view(N, K),
+                         packed[:o1].view(torch.int64).view(N, K), packed[o1:o2].view(torch.int32),
+                         packed[o2:o3].view(torch.int32).view(N, K), packed[o3:o4].view(torch.int32).view(N, K), packed)
+
+
+def wbf_settings(d=None):
+    """the `wbf` dict of a weighted boxes fusion, validated and completed from WBF -> dict(iou_threshold, skip_box_thr,
+    conf_type 'avg' | 'max', weights None or a list of positive floats)"""
+    if d is not None and not isinstance(d, dict):
+        raise ValueError(f"wbf must be None or a dict with keys of {sorted(WBF)}")
+    out = dict(WBF)
+    unknown = set(d or {}) - set(out)
+    if unknown:
+        raise ValueError(f"wbf: unknown key(s) {sorted(unknown)}; known: {sorted(out)}")
+    out.update(d or {})
+    if out["conf_type"] in ("box_and_model_avg", "absent_model_aware_avg"):
+        raise NotImplementedError(f"wbf conf_type {out['conf_type']!r} is not built: 'avg' or 'max'")
+    if out["conf_type"] not in _wbf.CONF_TYPES:
+        raise ValueError(f"wbf conf_type must be 'avg' or 'max', got {out['conf_type']!r}")
+    for key in ("iou_threshold", "skip_box_thr"):
+        out[key] = float(out[key])
+        if not math.isfinite(out[key]):
+            raise ValueError(f"wbf {key} must be finite")
+    if out["weights"] is not None:
+        out["weights"] = [float(w) for w in out["weights"]]
+        if not out["weights"] or any(not math.isfinite(w) or w <= 0 for w in out["weights"]):
+            raise ValueError("wbf weights: None or a non-empty list of finite positive numbers")
+    return out
+
+
+def wbf_merge(view_dets, flips, widths, wbf=None, max_per_img=None):
+    """Weighted boxes fusion of the views' detections for a batch of N images in one launch (csrc/prepost.hip; the rule:
+    include/codetr_wbf.h): un-flipped, clustered per label in descending confidence, every cluster emitted as its
+    confidence-weighted mean box with a score that says how many views agreed; the best max_per_img kept.
+      view_dets, flips, widths, max_per_img   as tta_merge
+      wbf          dict(iou_threshold, skip_box_thr, conf_type 'avg' | 'max', weights: one per view); None: WBF
+    -> WbfDetections over [N, K] rows (K = max_per_img, or V * Q): `index` is the c = v * Q + j of every row's founder,
+    `votes` its number of members; `detections_to_host` fetches all of it in one copy."""
+    w = wbf_settings(wbf)
+    dtype, dev, N, V, Q, boxes, scores, labels, count, flips, widths = _merge_operands("wbf_merge", view_dets, flips, widths)
+    if V * Q > WBF_MAX_CANDIDATES:
+        raise ValueError(f"wbf_merge: at most {WBF_MAX_CANDIDATES} candidates per image, got {V} views of {Q}")
+    if w["weights"] is not None and len(w["weights"]) != V:
+        raise ValueError(f"wbf_merge: {V} views but {len(w['weights'])} weights")
+    keep = 0 if max_per_img is None else int(max_per_img)
+    K = keep if keep > 0 else V * Q
+    es = torch.empty((), dtype=dtype).element_size()
+    nbytes = N * K * 16 + N * 4 + N * K * 5 * es
+    out = _wbf_views((torch.zeros if Q == 0 else torch.empty)((nbytes,), dtype=torch.uint8, device=dev), N, K, dtype)
+    if Q == 0:
+        return out
+    with torch.cuda.device(dev):
+        _wbf.wbf_merge(boxes.view(V, N, Q, 4), scores.view(V, N, Q), labels.view(V, N, Q), count.view(V, N),
+                       sum(1 << v for v, f in enumerate(flips) if f), widths.to(dev, torch.float32).contiguous(),
+                       w["weights"], _wbf.CONF_TYPES[w["conf_type"]], w["iou_threshold"], w["skip_box_thr"], keep,
+                       out.boxes, out.scores, out.labels, out.index, out.count, out.votes)
+    return out
+
+
+def weighted_boxes_fusion(boxes_list, scores_list, labels_list, weights=None, iou_thr=0.55, skip_box_thr=0.0,
+                          conf_type="avg"):
+    """`ensemble_boxes.weighted_boxes_fusion`'s call shape for one image, the counterpart of `soft_nms`: one entry per
+    model (or view) in each list -- boxes [n_i, 4], scores [n_i], labels [n_i], tensors on the GPU or array-likes; pixel
+    or normalised coordinates -- `weights` one per entry.  -> (boxes [E, 4], scores [E], labels [E] int64) in descending
+    score order, fp32 on the GPU.  The ragged lists are padded into the [V, 1, Q] operands of one wbf_merge launch; the
+    rule and its deviations from the package are include/codetr_wbf.h's (parity is unpinned)."""
+    V = len(scores_list)
+    if V == 0 or len(boxes_list) != V or len(labels_list) != V:
+        raise ValueError("weighted_boxes_fusion: boxes_list, scores_list and labels_list of one length > 0")
+    dev = next((t.device for t in scores_list if torch.is_tensor(t) and t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    sc = [torch.as_tensor(s, dtype=torch.float32).reshape(-1).to(dev) for s in scores_list]
+    bx = [torch.as_tensor(b, dtype=torch.float32).reshape(-1, 4).to(dev) for b in boxes_list]
+    lb = [torch.as_tensor(l).reshape(-1).to(dev, torch.int64) for l in labels_list]
+    if any(b.shape[0] != s.shape[0] or l.shape[0] != s.shape[0] for b, s, l in zip(bx, sc, lb)):
+        raise ValueError("weighted_boxes_fusion: every entry n boxes [n, 4], n scores and n labels")
+    Q = max(s.shape[0] for s in sc)
+    if Q == 0:
+        return (torch.zeros((0, 4), dtype=torch.float32, device=dev), torch.zeros((0,), dtype=torch.float32, device=dev),
+                torch.zeros((0,), dtype=torch.int64, device=dev))
+    boxes = torch.zeros((V, Q, 4), dtype=torch.float32, device=dev)
+    scores = torch.zeros((V, Q), dtype=torch.float32, device=dev)
+    labels = torch.zeros((V, Q), dtype=torch.int64, device=dev)
+    for v in range(V):
+        n = sc[v].shape[0]
+        boxes[v, :n], scores[v, :n], labels[v, :n] = bx[v], sc[v], lb[v]
+    count = torch.tensor([s.shape[0] for s in sc], dtype=torch.int32, device=dev)
+    dets = wbf_merge([Detections(boxes, scores, labels, count, None)], [False] * V, [0.0],
+                     dict(iou_threshold=iou_thr, skip_box_thr=skip_box_thr, conf_type=conf_type,
+                          weights=None if weights is None else list(weights)))
+    c = int(dets.count[0])
+    return dets.boxes[0, :c], dets.scores[0, :c], dets.labels[0, :c]
 
 
 SLICE_MAX_VIEWS = _cabi.SLICE_MAX_VIEWS

@@ -43,6 +43,21 @@ view's own scale factors as divisors; then one ``hip_ops.tta_merge`` launch and 
 ``views * num_queries <= 4096``.  Parity with mmdet / mmcv is unpinned (neither is installed here); as in the soft-NMS
 kernel classes are told apart by comparing labels, ties go to the lowest index and the IoU arithmetic is the project's.
 
+``tta["wbf"]`` (beyond the reference; weighted boxes fusion, Solovyev et al., as the ``ensemble_boxes`` package runs it):
+``tta=dict(scales=..., flip=..., wbf=dict(iou_threshold=0.55, skip_box_thr=0.0, conf_type='avg' | 'max', weights=None),
+max_per_img=...)`` merges the views with one ``hip_ops.wbf_merge`` launch in place of ``tta_merge``: the views' boxes are
+clustered per class and every cluster comes back as its confidence-weighted mean box, with a score that says how many
+views agreed; every prediction gains ``"votes"``, the number of boxes fused into each detection.  ``wbf`` and ``nms`` are
+alternatives (both: ``ValueError``).  ``weights``: one per view, or one per model.  The rule, its two deviations from the
+package (the tie rule; live = positive confidence) and its limits are stated in ``include/codetr_wbf.h``; parity with
+``ensemble_boxes`` is unpinned (it is not installed here).
+
+``ensemble`` (with ``tta`` only; beyond the reference): ``ensemble=[model_b, ...]`` names further models that run on the
+same pre-processed views; their detections are further views of the merge, ``v = (k * S + s) * F + f`` with ``k = 0`` for
+the main model, S scales and F flips.  All models must return the same number of detections per image; the 16-view and
+4096-candidate limits apply to the total.  ``tta=dict(scales=[the config's scale], ...)`` is a plain ensemble.  It works
+with the ``nms`` merges too.
+
 ``slicing`` (beyond the reference; sliced inference as in SAHI): ``None``, the default, changes nothing.  A dict
 ``dict(tile=(w, h), overlap=0.2 | (ox, oy), full_image=True, merge=dict(type='nmm' | 'nms', metric='ios' | 'iou',
 threshold=0.5, class_agnostic=False), max_per_img=300, tile_batch=8)`` (the defaults shown; only ``tile`` is required)
@@ -169,8 +184,9 @@ def _pairs(scale):
 
 
 def tta_settings(cfg, tta):
-    """How `Inferencer(..., tta=...)` reads its argument: None -> None; a dict(scales, flip, nms, max_per_img) is
-    validated; "config" takes `cfg.tta_model['tta_cfg']` (nms, max_per_img) and, from the TestTimeAug step of
+    """How `Inferencer(..., tta=...)` reads its argument: None -> None; a dict(scales, flip, nms | wbf, max_per_img) is
+    validated (`wbf`: the dict of hip_ops.wbf_settings -- weighted boxes fusion in place of the NMS merge; the result
+    then holds it completed under "wbf" and None under "nms", otherwise None under "wbf"); "config" takes `cfg.tta_model['tta_cfg']` (nms, max_per_img) and, from the TestTimeAug step of
     `cfg.tta_pipeline`, every Resize scale and whether the RandomFlip branch holds both prob 0 and prob 1 (ValueError
     when the config has neither entry).  -> dict(scales [(long, short)], flip, nms dict(type, iou_threshold, method,
     min_score), max_per_img or None, views [(scale, flipped)] in launch order: v = s * (2 if flip else 1) + f,
@@ -200,8 +216,10 @@ def tta_settings(cfg, tta):
             raise NotImplementedError(f"RandomFlip probabilities {probs}: a TTA flip branch is prob=0. [and prob=1.]")
         tta = dict(scales=scales, flip=1.0 in probs, nms=tta_cfg.get("nms", dict(type="nms", iou_threshold=0.5)),
                    max_per_img=tta_cfg.get("max_per_img"))
-    if not isinstance(tta, dict) or set(tta) - {"scales", "flip", "nms", "max_per_img"} or "scales" not in tta:
-        raise ValueError("tta must be None, 'config' or dict(scales, flip, nms, max_per_img)")
+    if not isinstance(tta, dict) or set(tta) - {"scales", "flip", "nms", "wbf", "max_per_img"} or "scales" not in tta:
+        raise ValueError("tta must be None, 'config' or dict(scales, flip, nms | wbf, max_per_img)")
+    if tta.get("wbf") is not None and tta.get("nms") is not None:
+        raise ValueError("tta: nms and wbf are two ways to merge the views: give one of them")
     scales = _pairs(tta["scales"]) if tta["scales"] else []
     if not scales or any(len(p) != 2 or min(p) <= 0 for p in scales):
         raise ValueError("tta scales: a non-empty list of positive (long, short) pairs")
@@ -209,7 +227,8 @@ def tta_settings(cfg, tta):
     nms = dict(tta.get("nms") or dict(type="nms", iou_threshold=0.5))
     kind = nms.get("type", "nms")
     if kind not in ("nms", "soft_nms"):
-        raise NotImplementedError(f"tta nms type {kind!r}: 'nms' and 'soft_nms' are built")
+        raise NotImplementedError(f"tta nms type {kind!r}: 'nms' and 'soft_nms' are built"
+                                  + (" (weighted boxes fusion is the tta key wbf=dict(...))" if kind == "wbf" else ""))
     out_nms = dict(type=kind, iou_threshold=float(nms.get("iou_threshold", 0.5 if kind == "nms" else 0.3)),
                    method=nms.get("method", "linear"), min_score=float(nms.get("min_score", 1e-3)))
     if kind == "soft_nms":
@@ -218,8 +237,33 @@ def tta_settings(cfg, tta):
     views = [(s, f) for s in scales for f in ((False, True) if flip else (False,))]
     if len(views) > hip_ops.TTA_MAX_VIEWS:
         raise ValueError(f"tta: {len(views)} views, at most {hip_ops.TTA_MAX_VIEWS} (scales x flips) are merged")
-    return dict(scales=scales, flip=flip, nms=out_nms, max_per_img=int(mpi) if mpi is not None and mpi > 0 else None,
-                views=views)
+    wbf = hip_ops.wbf_settings(tta["wbf"]) if tta.get("wbf") is not None else None
+    return dict(scales=scales, flip=flip, nms=out_nms if wbf is None else None, wbf=wbf,
+                max_per_img=int(mpi) if mpi is not None and mpi > 0 else None, views=views)
+
+
+def ensemble_settings(ensemble, tta):
+    """How `Inferencer(..., ensemble=...)` reads its argument: None (or an empty list) -> []; a list of further models,
+    which run on the views of `tta` (the result of tta_settings) next to the main model, their detections further views
+    of the merge: v = (k * S + s) * F + f with k = 0 for the main model.  ValueError without tta, for more views in all
+    than the merge takes, and for wbf weights that are neither one per view nor one per model; per-model weights are
+    expanded to per-view weights in tta["wbf"]."""
+    models = list(ensemble) if ensemble is not None else []
+    if models and tta is None:
+        raise ValueError("ensemble needs tta: tta=dict(scales=[the config's scale], ...) is a plain ensemble")
+    if tta is None:
+        return models
+    per_model, total = len(tta["views"]), len(tta["views"]) * (1 + len(models))
+    if total > hip_ops.TTA_MAX_VIEWS:
+        raise ValueError(f"ensemble: {1 + len(models)} models x {per_model} views, at most {hip_ops.TTA_MAX_VIEWS} views "
+                         "are merged")
+    w = tta["wbf"]["weights"] if tta["wbf"] is not None else None
+    if w is not None:
+        if len(w) == 1 + len(models):
+            tta["wbf"]["weights"] = [wk for wk in w for _ in range(per_model)]
+        elif len(w) != total:
+            raise ValueError(f"wbf weights: {len(w)} given, one per view ({total}) or one per model ({1 + len(models)})")
+    return models
 
 
 SLICING_KEYS = ("tile", "overlap", "full_image", "merge", "max_per_img", "tile_batch")
@@ -496,7 +540,7 @@ class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
                  slicing=None, tracker=None, vis_format=None,
-                 track_association=None):
+                 track_association=None, ensemble=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -540,6 +584,7 @@ class Inferencer:
         if self.scale is None:
             raise ValueError("Resize is not found in the test pipeline")
         self.tta = tta_settings(self.cfg, tta)
+        self.ensemble = ensemble_settings(ensemble, self.tta)
         self.slicing = slicing_settings(slicing)
         if self.slicing is not None and self.tta is not None:
             raise NotImplementedError("slicing together with tta is not built: one or the other")
@@ -902,22 +947,36 @@ class Inferencer:
         src, staged, tail = self.stage_chunk(images, device, frames, tail_of)
         widths = tail[:4 * N].view(torch.float32)
         div = tail[4 * N:].view(dtype).view(len(plans), len(flips) * N, 4)
-        view_dets = []
+        view_dets = [[] for _ in range(1 + len(self.ensemble))]   # per model, its scales in order
+        total = len(t["views"]) * (1 + len(self.ensemble))
         for s, (rows, metas, batch_hw) in enumerate(plans):
             x, m = hip_ops.preprocess_views(src, rows, batch_hw, self.mean, self.std, self.pad_val, self.pad_value, dtype)
             preds = self.model(x, m)
             Q = preds[1].shape[1]
-            if s == 0 and len(t["views"]) * Q > hip_ops.TTA_MAX_CANDIDATES:   # (Q is the model's: known after a forward)
-                raise ValueError(f"tta: {len(t['views'])} views of {Q} detections exceed the merge kernel's "
+            if s == 0 and total * Q > hip_ops.TTA_MAX_CANDIDATES:   # (Q is the model's: known after a forward)
+                raise ValueError(f"tta: {total} views of {Q} detections exceed the merge kernel's "
                                  f"{hip_ops.TTA_MAX_CANDIDATES} candidates per image")
-            view_dets.append(self.postprocess_device(preds, metas, div[s]))
-        dets = hip_ops.tta_merge(view_dets, [f for _, f in t["views"]], widths, t["nms"], t["max_per_img"])
+            view_dets[0].append(self.postprocess_device(preds, metas, div[s]))
+            for k, model in enumerate(self.ensemble, 1):   # the further models on the same pre-processed views
+                preds_k = model(x, m)
+                if preds_k[1].shape[1] != Q:
+                    raise ValueError(f"ensemble: model {k} returns {preds_k[1].shape[1]} detections per image, the main "
+                                     f"model {Q}: the merged views need one Q")
+                view_dets[k].append(self.postprocess_device(preds_k, metas, div[s]))
+        view_dets = [d for per_model in view_dets for d in per_model]   # v = (k * S + s) * F + f
+        view_flips = [f for _, f in t["views"]] * (1 + len(self.ensemble))
+        if t["wbf"] is not None:
+            dets = hip_ops.wbf_merge(view_dets, view_flips, widths, t["wbf"], t["max_per_img"])
+        else:
+            dets = hip_ops.tta_merge(view_dets, view_flips, widths, t["nms"], t["max_per_img"])
         host = hip_ops.detections_to_host(dets)
         out = []
         for i in range(N):
             c = int(host.count[i])
             out.append({"labels": host.labels[i, :c].tolist(), "scores": host.scores[i, :c].float().tolist(),
                         "bboxes": host.boxes[i, :c].float().tolist()})
+            if t["wbf"] is not None:
+                out[-1]["votes"] = host.votes[i, :c].tolist()
         return out, src, staged, dets
 
     # ---- sliced inference -------------------------------------------------------------------------------------

@@ -32,6 +32,9 @@
 // slice_merge_kernel  the fusion of the tiles' detections, up to 4096 candidates per image: shifted by the tile's origin,
 //                     clipped to the image, then greedy per-label (or class-agnostic) NMS or non-maximum merging under
 //                     IoU or IoS (intersection over the smaller area), sorted by score, cut to max_per_img.
+// wbf_merge_kernel    weighted boxes fusion (include/codetr_wbf.h) over the operands and the front end of tta_merge_kernel:
+//                     per label the candidates join, in descending confidence, the cluster whose fused box they overlap
+//                     most, or found one; every cluster emits its confidence-weighted mean box and its votes.
 // The merge and soft-NMS kernels are their own front ends over ONE set of device functions: pack_key (the tie rule), bitonic_desc
 // (either key layout), block_scan / block_sum / block_max_u64, segment_starts, run_segments (the greedy chain with both
 // threshold rules) and write_row / zero_row.  postprocess_kernel and the kernels above it are on the Inferencer's default
@@ -40,6 +43,7 @@
 #include <stdint.h>
 
 #include "codetr_hip.h"
+#include "codetr_wbf.h"
 #include "device_prims.h"
 #include "large_lds.h"
 
@@ -954,6 +958,216 @@ __global__ __launch_bounds__(kNmsThreads) void slice_merge_kernel(
   if (tid == 0) count_out[n] = M;
 }
 
+// ---- weighted boxes fusion (include/codetr_wbf.h states the rule): tta_merge_kernel's operands, LDS layout and sorts with a
+// chain of its own ---------------------------------------------------------------------------------------------------------
+static_assert(CODETR_WBF_MAX_CANDIDATES == kTtaMaxC, "the WBF kernel uses the TTA merge's LDS layout and 16-bit tables");
+
+struct WbfWeights {  // the weight of every view, in the kernargs
+  float w[CODETR_TTA_MAX_VIEWS];
+};
+
+// a cluster's output key: (score, founder c) as pack_key orders them, with the votes (<= 4096: 13 bits) below the index
+constexpr int kWbfVoteBits = 13;
+__device__ __forceinline__ unsigned long long wbf_out_key(float score, unsigned c, unsigned votes) {
+  return ((unsigned long long)score_key(score) << 32) | ((unsigned long long)(kTtaMaxC - 1 - c) << kWbfVoteBits) | votes;
+}
+__device__ __forceinline__ int lowest_bit(unsigned m) { return __builtin_ctz(m); }
+__device__ __forceinline__ int lowest_bit(unsigned long long m) { return __builtin_ctzll(m); }
+
+// the fusion chains: a wave takes whole segments; lane l holds positions a + l + 64 e and two masks over them, `todo` (not
+// yet processed) and `found` (founders of a cluster).  A cluster lives in its founder's slots, which only the founder's
+// lane reads or writes once it is founded: s_box = the sums SX1, SY1, SX2, SY2, s_score = SC, s_out = (bits of top) << 32 | n.
+// A step: the pick k is a wave reduction of pack_key(conf, position) over `todo`; every lane measures k against its
+// clusters; a wave reduction of pack_key(ovr, founder position) over those with ovr > iou_thr names the winner (highest
+// ovr, ties to the lowest position = the lowest founder c), whose lane adds k to the sums -- or k's lane founds a cluster.
+// At the end of a segment every founder's slots become what the epilogue reads: s_box the fused box, s_score the score,
+// s_out the output key.  The step loop is counted (a segment of b - a positions takes b - a steps).  No workgroup barrier.
+template <class Mask>
+__device__ __forceinline__ void wbf_segments(const unsigned short* s_seg, int S, float4* s_box, float* s_score,
+                                             const unsigned* s_idx, unsigned long long* s_out, bool conf_max, float iou_thr,
+                                             float wsum, float wmax, int lane, int wave) {
+#pragma clang fp contract(off)
+  constexpr Mask kOne = 1;
+  for (int seg = wave; seg < S; seg += kNmsWaves) {
+    const int a = s_seg[seg], b = s_seg[seg + 1];
+    const int ne = (b - a + 63) >> 6;  // <= the bits of Mask
+    Mask todo = 0, found = 0;
+    for (int e = 0; e < ne; ++e) todo |= (a + lane + 64 * e < b) ? kOne << e : Mask(0);
+    for (int step = a; step < b; ++step) {
+      unsigned long long best = 0;
+      for (Mask m = todo; m != 0; m &= m - 1) {
+        const int p = a + lane + 64 * lowest_bit(m);
+        const unsigned long long k = pack_key(s_score[p], (unsigned)p);
+        best = k > best ? k : best;
+      }
+      best = wave_max_u64(best);
+      if (best == 0ull) break;  // (wave-uniform) the segment is exhausted
+      const int k = (int)inv_index((unsigned)best);
+      const float4 bk = s_box[k];
+      const float ak = box_area(bk), ck = s_score[k];
+      unsigned long long win = 0;
+      for (Mask m = found; m != 0; m &= m - 1) {
+        const int p = a + lane + 64 * lowest_bit(m);
+        const float4 sum = s_box[p];
+        const float sc = s_score[p];
+        const float4 f = make_float4(sum.x / sc, sum.y / sc, sum.z / sc, sum.w / sc);
+        const float ovr = soft_overlap(f, box_area(f), bk, ak);
+        if (ovr > iou_thr) {  // (a NaN overlap compares false)
+          const unsigned long long key = pack_key(ovr, (unsigned)p);
+          win = key > win ? key : win;
+        }
+      }
+      win = wave_max_u64(win);
+      const bool mine = ((k - a) & 63) == lane;
+      if (mine) todo &= ~(kOne << ((k - a) >> 6));
+      if (win == 0ull) {  // (wave-uniform) k founds a cluster, in its own slots: s_score[k] is SC already
+        if (mine) {
+          found |= kOne << ((k - a) >> 6);
+          s_box[k] = make_float4(ck * bk.x, ck * bk.y, ck * bk.z, ck * bk.w);
+          s_out[k] = ((unsigned long long)__float_as_uint(ck) << 32) | 1ull;
+        }
+      } else {
+        const int q = (int)inv_index((unsigned)win);
+        if (((q - a) & 63) == lane) {
+          float4 sum = s_box[q];
+          const float px = ck * bk.x, py = ck * bk.y, pz = ck * bk.z, pw = ck * bk.w;
+          sum.x = sum.x + px;
+          sum.y = sum.y + py;
+          sum.z = sum.z + pz;
+          sum.w = sum.w + pw;
+          s_box[q] = sum;
+          s_score[q] = s_score[q] + ck;
+          s_out[q] += 1ull;
+        }
+      }
+    }
+    for (Mask m = found; m != 0; m &= m - 1) {
+      const int p = a + lane + 64 * lowest_bit(m);
+      const float4 sum = s_box[p];
+      const float sc = s_score[p];
+      const unsigned long long st = s_out[p];
+      const unsigned votes = (unsigned)st;
+      const float nf = (float)votes, top = __uint_as_float((unsigned)(st >> 32));
+      const float score = conf_max ? top / wmax : ((sc / nf) * fminf(nf, wsum)) / wsum;
+      s_box[p] = make_float4(sum.x / sc, sum.y / sc, sum.z / sc, sum.w / sc);
+      s_score[p] = score;
+      s_out[p] = wbf_out_key(score, inv_index(s_idx[p]), votes);
+    }
+  }
+}
+
+// grid N, 1024 threads: image n's V views of Q detections (rows j < count[v, n] are candidates, c = v Q + j) -> the fused
+// clusters in output order, cut to max_keep, count_out[n] of them; rows [count_out, K) of the outputs are zero.
+// P = the power of two >= V Q; wsum, wmax: the sum (in view order) and the maximum of the V weights.
+template <class T>
+__global__ __launch_bounds__(kNmsThreads) void wbf_merge_kernel(
+    const T* __restrict__ boxes, const T* __restrict__ scores, const int64_t* __restrict__ labels,
+    const int* __restrict__ count, int V, int N, int Q, int P, unsigned flip_mask, const float* __restrict__ width,
+    WbfWeights weights, float wsum, float wmax, int conf_max, float iou_thr, float skip_thr, int max_keep, int K,
+    T* __restrict__ boxes_out, T* __restrict__ scores_out, int64_t* __restrict__ labels_out, int* __restrict__ index_out,
+    int* __restrict__ count_out, int* __restrict__ votes_out) {
+  extern __shared__ __align__(16) unsigned char wbf_lds[];
+  float4* s_box = reinterpret_cast<float4*>(wbf_lds);  // by position after sort 1; a founder's: the sums, then the fused box
+  unsigned long long* s_lab = reinterpret_cast<unsigned long long*>(wbf_lds + (size_t)16 * P);  // sort 1, major key
+  unsigned long long* s_out = s_lab;  // (after the segments are found) a founder's (top, n), then its output key; else 0
+  float* s_score = reinterpret_cast<float*>(wbf_lds + (size_t)24 * P);  // conf; a founder's: SC, then the score
+  unsigned* s_idx = reinterpret_cast<unsigned*>(wbf_lds + (size_t)28 * P);  // sort 1, minor key: inv_index(c); 0 = none
+  unsigned short* s_pos = reinterpret_cast<unsigned short*>(wbf_lds + (size_t)32 * P);  // c -> position
+  unsigned short* s_seg = reinterpret_cast<unsigned short*>(wbf_lds + (size_t)34 * P);  // segment starts, then Vn
+  __shared__ float s_w[CODETR_TTA_MAX_VIEWS];
+  __shared__ int s_wave[kNmsWaves];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = blockIdx.x;
+  const int C = V * Q;
+  // element (v, n, j) of the stacked inputs
+  auto at = [&](int c, int& v) -> size_t {
+    v = c / Q;
+    return ((size_t)v * N + n) * Q + (size_t)(c - v * Q);
+  };
+  if (tid < CODETR_TTA_MAX_VIEWS) {
+    float w = 0.f;
+#pragma unroll
+    for (int v = 0; v < CODETR_TTA_MAX_VIEWS; ++v) w = tid == v ? weights.w[v] : w;  // (constant indices: no scratch copy)
+    s_w[tid] = w;
+  }
+  __syncthreads();
+
+  // front end: the sort keys of the live candidates, (label, c), everything else 0
+  int nlive = 0;
+  for (int c = tid; c < P; c += kNmsThreads) {
+    bool live = false;
+    unsigned long long lab = 0;
+    if (c < C) {
+      int v;
+      const size_t e = at(c, v);
+      if (c - v * Q < count[v * N + n]) {
+        const float s = to_f32(scores[e]);
+        const float conf = s * s_w[v];
+        live = s >= skip_thr && conf > 0.f;  // (a NaN fails both)
+        lab = (unsigned long long)labels[e];
+      }
+    }
+    s_lab[c] = live ? lab : 0ull;
+    s_idx[c] = live ? inv_index((unsigned)c) : 0u;
+    nlive += live ? 1 : 0;
+  }
+  const int Vn = block_sum(nlive, s_wave, lane, wave);  // (its barriers: the sort keys are complete)
+
+  // 1. by (label, c), descending: every label a contiguous segment in ascending c, empty slots last; boxes un-flipped
+  bitonic_desc<kTtaMaxC>(LabelIndexKeys{s_lab, s_idx}, P, tid);
+  const float Wimg = width[n];
+  for (int p = tid; p < Vn; p += kNmsThreads) {
+    const unsigned c = inv_index(s_idx[p]);
+    int v;
+    const size_t e = at((int)c, v);
+    float4 b = make_float4(to_f32(boxes[4 * e]), to_f32(boxes[4 * e + 1]), to_f32(boxes[4 * e + 2]), to_f32(boxes[4 * e + 3]));
+    if (flip_mask >> v & 1u) {  // un-flip: (W - x2, y1, W - x1, y2)
+      const float x1 = Wimg - b.z, x2 = Wimg - b.x;
+      b.x = x1;
+      b.z = x2;
+    }
+    s_box[p] = b;
+    s_score[p] = to_f32(scores[e]) * s_w[v];
+    s_pos[c] = (unsigned short)p;
+  }
+  // 2. - 4. segments (the labels were then read for the last time: their array becomes s_out), the fusion chains (up to
+  //    1024 slots a lane holds at most 16 positions of a segment: the 32-bit masks), the clusters by (score, founder c)
+  const int S = segment_starts<kTtaMaxC>(s_lab, Vn, s_seg, s_wave, tid);
+  for (int p = tid; p < P; p += kNmsThreads) s_out[p] = 0ull;
+  __syncthreads();
+  if (P <= kNmsThreads)
+    wbf_segments<unsigned>(s_seg, S, s_box, s_score, s_idx, s_out, conf_max != 0, iou_thr, wsum, wmax, lane, wave);
+  else
+    wbf_segments<unsigned long long>(s_seg, S, s_box, s_score, s_idx, s_out, conf_max != 0, iou_thr, wsum, wmax, lane, wave);
+  __syncthreads();
+  bitonic_desc<kTtaMaxC>(ScoreKeys{s_out}, P, tid);
+  int nout = 0;
+  for (int p = tid; p < P; p += kNmsThreads) nout += s_out[p] != 0ull ? 1 : 0;
+  const int E = block_sum(nout, s_wave, lane, wave);
+  const int M = (max_keep > 0 && max_keep < E) ? max_keep : E;
+
+  // 5. cut, round once to T
+  T* bo = boxes_out + (size_t)n * K * 4;
+  T* so = scores_out + (size_t)n * K;
+  int64_t* lo = labels_out + (size_t)n * K;
+  int* io = index_out + (size_t)n * K;
+  int* vo = votes_out + (size_t)n * K;
+  for (int r = tid; r < K; r += kNmsThreads) {
+    if (r < M) {
+      const unsigned low = (unsigned)s_out[r];
+      const unsigned c = (unsigned)(kTtaMaxC - 1) - (low >> kWbfVoteBits);
+      const int p = s_pos[c];
+      int v;
+      write_row(bo, so, lo, io, r, s_box[p], from_f32<T>(s_score[p]), labels[at((int)c, v)], (int)c);
+      vo[r] = (int)(low & ((1u << kWbfVoteBits) - 1u));
+    } else {
+      zero_row(bo, so, lo, io, r);
+      vo[r] = 0;
+    }
+  }
+  if (tid == 0) count_out[n] = M;
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 
 // what a launch returns: 0, or the HIP error it left
@@ -1154,6 +1368,43 @@ int launch_slice_merge(void* stream, const void* boxes, const void* scores, cons
   return launched();
 }
 
+template <class T>
+int launch_wbf_merge(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count,
+                     int64_t V, int64_t N, int64_t Q, uint32_t flip_mask, const float* width, const float* weights,
+                     int conf_type, float iou_threshold, float skip_box_thr, int64_t max_keep, void* boxes_out,
+                     void* scores_out, int64_t* labels_out, int* index_out, int* count_out, int* votes_out) {
+  if (!boxes || !scores || !labels || !count || !width || !boxes_out || !scores_out || !labels_out || !index_out ||
+      !count_out || !votes_out || V <= 0 || N <= 0 || Q <= 0)
+    return CODETR_E_BADARG;
+  if (conf_type != CODETR_WBF_CONF_AVG && conf_type != CODETR_WBF_CONF_MAX) return CODETR_E_BADARG;
+  if (!__builtin_isfinite(iou_threshold) || !__builtin_isfinite(skip_box_thr)) return CODETR_E_BADARG;
+  if (V < 32 && (flip_mask >> V) != 0u) return CODETR_E_BADARG;  // a flip bit of a view that does not exist
+  if (V > CODETR_TTA_MAX_VIEWS || Q > kTtaMaxC || V * Q > kTtaMaxC || N > 0x7fffffffLL / kTtaMaxC ||
+      max_keep > 0x7fffffffLL)
+    return CODETR_E_TOO_LARGE;
+  WbfWeights wt = {};
+  float wsum = 0.f, wmax = 0.f;
+  for (int v = 0; v < (int)V; ++v) {
+    const float w = weights ? weights[v] : 1.f;
+    if (!__builtin_isfinite(w) || !(w > 0.f)) return CODETR_E_BADARG;
+    wt.w[v] = w;
+    wsum = wsum + w;  // in view order, one rounding per addition
+    wmax = w > wmax ? w : wmax;
+  }
+  const int C = (int)(V * Q);
+  int P = 1;
+  while (P < C) P <<= 1;
+  if (const hipError_t e = allow_large_lds<wbf_merge_kernel<T>>((int)tta_lds_bytes(kTtaMaxC)); e != hipSuccess)
+    return (int)e;
+  hipLaunchKernelGGL((wbf_merge_kernel<T>), dim3((unsigned)N), dim3(kNmsThreads), tta_lds_bytes(P),
+                     static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                     labels, count, (int)V, (int)N, (int)Q, P, flip_mask, width, wt, wsum, wmax,
+                     conf_type == CODETR_WBF_CONF_MAX ? 1 : 0, iou_threshold, skip_box_thr,
+                     max_keep > 0 ? (int)max_keep : 0, max_keep > 0 ? (int)max_keep : C, static_cast<T*>(boxes_out),
+                     static_cast<T*>(scores_out), labels_out, index_out, count_out, votes_out);
+  return launched();
+}
+
 }  // namespace
 
 extern "C" {
@@ -1244,6 +1495,17 @@ CODETR_ENTRIES(codetr_slice_merge, launch_slice_merge,
                (stream, boxes_dev, scores_dev, labels_dev, count_dev, rows_dev, origin_dev, size_dev, R, N, V, Q, metric,
                 mode, threshold, class_agnostic, max_keep, boxes_out_dev, scores_out_dev, labels_out_dev, index_out_dev,
                 count_out_dev))
+int codetr_wbf_abi_version(void) { return CODETR_WBF_ABI_VERSION; }
+
+CODETR_ENTRIES(codetr_wbf_merge, launch_wbf_merge,
+               (void* stream, const void* boxes_dev, const void* scores_dev, const int64_t* labels_dev,
+                const int* count_dev, int64_t V, int64_t N, int64_t Q, uint32_t flip_mask, const float* width_dev,
+                const float* weights_host, int conf_type, float iou_threshold, float skip_box_thr, int64_t max_keep,
+                void* boxes_out_dev, void* scores_out_dev, int64_t* labels_out_dev, int* index_out_dev,
+                int* count_out_dev, int* votes_out_dev),
+               (stream, boxes_dev, scores_dev, labels_dev, count_dev, V, N, Q, flip_mask, width_dev, weights_host,
+                conf_type, iou_threshold, skip_box_thr, max_keep, boxes_out_dev, scores_out_dev, labels_out_dev,
+                index_out_dev, count_out_dev, votes_out_dev))
 #undef CODETR_ENTRIES
 
 }  // extern "C"

@@ -20,8 +20,9 @@ post-processing kernels are read from its kernel statistics.
 `--tta` adds a `tta` sub-record (test-time augmentation, fp16): images/s of `Inferencer(tta=dict(scales=TTA_SCALES,
 flip=...))` at batch_size 4 over --tta-images images, with and without the flip, beside the sum of three plain runs of
 the same Inferencer with its Resize set to each scale (and no fixed Pad) -- the way to the same unflipped views without
-the feature --; and the two TTA kernels alone, HIP events as above: tta_merge at N = 8, Q = 300 with 2 and 6 views for
-both label layouts, preprocess_views beside preprocess_batch on the same 8 images resized into (1152, 768) (twice the rows: each
+the feature --, and with the flip merged by weighted boxes fusion (`wbf=dict()`) instead of NMS; and the TTA kernels
+alone, HIP events as above: tta_merge and wbf_merge at N = 8, Q = 300 with 2 and 6 views for both label layouts,
+preprocess_views beside preprocess_batch on the same 8 images resized into (1152, 768) (twice the rows: each
 image plain and mirrored).
 
 `--vis` adds a `vis` sub-record (the visualisation, fp16): images/s of `Inferencer(visualizer={})` at batch_size 8 with
@@ -168,8 +169,9 @@ def _event_us(call, launches=200, warmup=20):
 
 
 def tta_kernel_times():
-    """us per launch of tta_merge_kernel (N = 8, Q = 300, fp16; V = 2 and 6; hard NMS at 0.5 and linear soft-NMS) and of
-    preprocess_views_kernel beside preprocess_batch_kernel"""
+    """us per launch of tta_merge_kernel (N = 8, Q = 300, fp16; V = 2 and 6; hard NMS at 0.5 and linear soft-NMS), of
+    wbf_merge_kernel on the same inputs (conf_type avg, IoU 0.55) and of preprocess_views_kernel beside
+    preprocess_batch_kernel"""
     from codetr import hip_ops
     from codetr.inferencer import rescale_size
 
@@ -179,7 +181,7 @@ def tta_kernel_times():
     wh = torch.rand(N, Q, 2, generator=g) * 150 + 2
     base = torch.cat((c, c + wh), -1)
     widths = torch.full((N,), 1000.0, device=DEV)
-    out = {"tta_merge_kernel": {}}
+    out = {"tta_merge_kernel": {}, "wbf_merge_kernel": {}}
     for V in (2, 6):
         boxes = (base[None] + (torch.rand(V, N, Q, 4, generator=g) - 0.5) * 6).half().to(DEV)   # near duplicates across views
         scores = torch.rand(V, N, Q, generator=g).half().to(DEV)
@@ -192,6 +194,8 @@ def tta_kernel_times():
                 call = lambda: hip_ops.tta_merge(dets, [v % 2 == 1 for v in range(V)], widths, nms, 300)  # noqa: E731
                 out["tta_merge_kernel"][f"V{V}_{name}_{mode}"] = {"us_per_launch": _event_us(call),
                                                                   "detections": int(call().count.sum())}
+            call = lambda: hip_ops.wbf_merge(dets, [v % 2 == 1 for v in range(V)], widths, None, 300)  # noqa: E731
+            out["wbf_merge_kernel"][f"V{V}_{name}"] = {"us_per_launch": _event_us(call), "detections": int(call().count.sum())}
     images = synthetic_images(N, seed=2)
     src = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images])).to(DEV)
     rows, off = [], 0
@@ -229,9 +233,10 @@ def tta_record(inf, n_images, repeats, bs=4):
 
     images = synthetic_images(n_images, seed=3)
     rec = {"scales": TTA_SCALES, "batch_size": bs, "images": n_images, "repeats": repeats, "dtype": "fp16"}
-    for name, flip in (("tta_3_scales_flip", True), ("tta_3_scales", False)):
-        t = Inferencer(inf.model, bench.CFG, dataset_meta=None, tta=dict(scales=TTA_SCALES, flip=flip,
-                                                                         nms=dict(type="nms", iou_threshold=0.6), max_per_img=100))
+    for name, flip, merge in (("tta_3_scales_flip", True, dict(nms=dict(type="nms", iou_threshold=0.6))),
+                              ("tta_3_scales", False, dict(nms=dict(type="nms", iou_threshold=0.6))),
+                              ("tta_3_scales_flip_wbf", True, dict(wbf=dict()))):
+        t = Inferencer(inf.model, bench.CFG, dataset_meta=None, tta=dict(scales=TTA_SCALES, flip=flip, max_per_img=100, **merge))
         times = _passes(t, images, bs, repeats)
         rec[name] = {"images_per_s": round(n_images / min(times), 3), "pass_s": [round(v, 4) for v in times]}
     # the Inferencer reads `scale` and `pad_size` on every call (preprocess_batch), so one instance serves all scales

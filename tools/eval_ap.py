@@ -195,9 +195,10 @@ def run_proxy(args):
             json.dump(report, f, indent=1)
 
 
-def parse_tta(text):
+def parse_tta(text, merge="nms"):
     """--tta SCALES[,flip]: 'LONGxSHORT+LONGxSHORT...[,flip]', e.g. '1333x800+2000x1200,flip' -> the Inferencer's tta
-    dict; the views are merged with hard NMS at IoU 0.6 and cut to 100 detections per image"""
+    dict; the views are merged with hard NMS at IoU 0.6 (--tta-merge nms, the default) or by weighted boxes fusion with
+    the Inferencer's defaults (--tta-merge wbf) and cut to 100 detections per image"""
     parts = text.split(",")
     if len(parts) > 2 or (len(parts) == 2 and parts[1] != "flip"):
         raise SystemExit(f"--tta {text!r}: expected SCALES[,flip] with SCALES = LONGxSHORT[+LONGxSHORT...]")
@@ -207,6 +208,8 @@ def parse_tta(text):
         scales = []
     if not scales or any(len(s) != 2 for s in scales):
         raise SystemExit(f"--tta {text!r}: expected SCALES[,flip] with SCALES = LONGxSHORT[+LONGxSHORT...]")
+    if merge == "wbf":
+        return dict(scales=scales, flip=len(parts) == 2, wbf=dict(), max_per_img=100)
     return dict(scales=scales, flip=len(parts) == 2, nms=dict(type="nms", iou_threshold=0.6), max_per_img=100)
 
 
@@ -248,7 +251,7 @@ def run_coco(args):
     # --nms config: the post-processing the config specifies (soft-NMS + max_per_img, what the published AP was
     # produced with); hard: the reference Inferencer's hard NMS at the config's IoU threshold, no cut
     inf = Inferencer(model, args.config, meta, score_threshold=0.0, nms_type="config" if args.nms == "config" else None,
-                     tta=parse_tta(args.tta) if args.tta else None, slicing=parse_slice(args.slice) if args.slice else None)
+                     tta=parse_tta(args.tta, args.tta_merge) if args.tta else None, slicing=parse_slice(args.slice) if args.slice else None)
     dets, gts = [], []
     images = ann["images"][:args.limit] if args.limit else ann["images"]
     for im in images:
@@ -283,6 +286,8 @@ def main():
     c.add_argument("--tta", default=None, metavar="SCALES[,flip]",
                    help="test-time augmentation: scales as LONGxSHORT joined by '+', e.g. 1333x800+2000x1200,flip; the "
                         "views are merged with hard NMS at IoU 0.6, 100 detections per image")
+    c.add_argument("--tta-merge", choices=("nms", "wbf"), default="nms",
+                   help="how --tta's views are merged: nms (hard NMS at IoU 0.6) or wbf (weighted boxes fusion, IoU 0.55)")
     c.add_argument("--slice", default=None, metavar="WxH,overlap[,full]",
                    help="sliced inference: tile size and overlap ratio, e.g. 640x640,0.2,full (full: the whole image is a "
                         "view too); fused by greedy non-maximum merging at IoS 0.5, 100 detections per image")
