@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _assign, _cabi, _jpeg, _jpeg_dec, _wbf
+from . import _assign, _cabi, _jpeg, _jpeg_dec, _motion, _wbf
 
 # ops served by hand-written HIP kernels in this build (kept in sync with include/codetr_hip.h)
 NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_window_attention(f16, head_dim 32)",
@@ -1395,7 +1395,7 @@ def track_state_to_host(state):
 TRACK_ASSOCIATIONS = tuple(_assign.ASSOCIATIONS)   # "greedy" (the default, codetr_hip.h's rule) and "optimal"
 
 
-def track_update(dets, state, streams=None, settings=None, association="greedy"):
+def track_update(dets, state, streams=None, settings=None, association="greedy", motion=None):
     """Tracking-by-detection for the frames of a chunk in one launch per PREPROCESS_BATCH_MAX rows (csrc/track.hip; the
     rule, modelled on mmdet's ByteTracker, is stated in include/codetr_hip.h): the three greedy associations, the Kalman
     filters, retirement and track starts of every stream on the device.
@@ -1407,6 +1407,9 @@ def track_update(dets, state, streams=None, settings=None, association="greedy")
       association  "greedy": the three greedy associations of codetr_hip.h; "optimal": each association is an assignment
                 problem over integer gains, solved in the same launch (csrc/track_assign.hip; the rule is stated in
                 include/codetr_assign.h).  The state is the same: a stream may switch between calls
+      motion    None, or estimate_motion's [N, 4] float32 (dx, dy, valid, 0 per row) on the detections' device: a valid,
+                finite motion is added to the predicted centres of the row's live tracks before association
+                (codetr_track_update3_*, include/codetr_motion.h).  None calls exactly the entry points it always did
     -> [N, Q] int32 on the device: the id of the track each row updated or started, negated while the track is
     tentative, 0 for no track and beyond count."""
     cfg = track_settings(settings)
@@ -1424,6 +1427,11 @@ def track_update(dets, state, streams=None, settings=None, association="greedy")
     if scores.dim() != 2 or tuple(dets.boxes.shape) != tuple(scores.shape) + (4,):
         raise ValueError("track_update: boxes [N,Q,4], scores [N,Q], labels [N,Q], count [N]")
     N, Q = scores.shape
+    if motion is not None:
+        if not torch.is_tensor(motion) or motion.dtype != torch.float32 or tuple(motion.shape) != (N, 4) or \
+                motion.device != scores.device:
+            raise ValueError("track_update: motion must be a [N, 4] float32 tensor on the detections' device")
+        motion = motion.contiguous()
     streams = track_streams(streams, N)
     if any(v >= state.shape[0] for v in streams):
         raise ValueError(f"track_update: a stream index outside the state's {state.shape[0]} streams")
@@ -1442,11 +1450,92 @@ def track_update(dets, state, streams=None, settings=None, association="greedy")
             j = min(N, i + PREPROCESS_BATCH_MAX)
             args = (boxes[i:j], scores[i:j], labels[i:j], count[i:j], streams[i:j], state, T, thr,
                     cfg["num_frames_retain"], cfg["num_tentatives"], cfg["weight_iou_with_det_scores"], ids[i:j])
-            if association == "greedy":
+            if motion is not None:
+                _motion.track_update3(*args, _assign.ASSOCIATIONS[association], motion[i:j])
+            elif association == "greedy":
                 _cabi.track_update(*args)
             else:
                 _assign.track_update2(*args, _assign.ASSOCIATIONS[association])
     return ids
+
+
+# camera-motion compensation (include/codetr_motion.h states the rule and these settings' ranges)
+MOTION = dict(grid=_motion.GRID_MAX, search=8, texture=2, min_blocks=4)
+MotionState = collections.namedtuple("MotionState", "have H W k thumb")
+
+
+def motion_settings(d=None):
+    """the settings of estimate_motion, validated and completed from MOTION -> a new dict.  ValueError for an unknown key or
+    a value that is not an integer of its range: grid 32..160, search 1..16, texture 0..65535, min_blocks 1..100."""
+    out = dict(MOTION)
+    d = dict(d or {})
+    unknown = set(d) - set(out)
+    if unknown:
+        raise ValueError(f"motion: unknown key(s) {sorted(unknown)}; known: {sorted(out)}")
+    ranges = dict(grid=(_motion.GRID_MIN, _motion.GRID_MAX), search=(1, _motion.SEARCH_MAX),
+                  texture=(0, _motion.TEXTURE_MAX), min_blocks=(1, _motion.MAX_BLOCKS))
+    for key, (lo, hi) in ranges.items():
+        v = d.get(key, out[key])
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+            raise ValueError(f"motion {key} must be an integer in {lo}..{hi}, got {v!r}")
+        out[key] = int(v)
+    return out
+
+
+def new_motion_state(S, device):
+    """the motion states of S fresh streams: zeros [S, 16 + 160 * 160] uint8 on `device` (int32 have, H, W, k, then the
+    stream's last thumbnail; motion_state_to_host decodes it)"""
+    if int(S) < 1:
+        raise ValueError(f"new_motion_state: at least one stream, got {S}")
+    return torch.zeros((int(S), _motion.state_bytes()), dtype=torch.uint8, device=device)
+
+
+def motion_state_to_host(state):
+    """the states of new_motion_state / estimate_motion on the host (one device-to-host copy) -> MotionState of numpy
+    arrays: have, H, W, k [S] int32 and thumb [S, 160 * 160] uint8 (rows at pitch W // k, zero behind them)"""
+    raw = state.cpu().numpy()
+    hdr = raw[:, :16].copy().view(np.int32)
+    return MotionState(hdr[:, 0].copy(), hdr[:, 1].copy(), hdr[:, 2].copy(), hdr[:, 3].copy(), raw[:, 16:].copy())
+
+
+def estimate_motion(src_u8, rows, state, streams=None, settings=None):
+    """The global image motion between the consecutive frames of every stream, in three launches per
+    PREPROCESS_BATCH_MAX images and without a synchronisation (csrc/motion.hip; include/codetr_motion.h states the rule:
+    block matching of gray thumbnails, a median vote, translation only).
+      src_u8    one flat uint8 device buffer holding RGB HWC images (Inferencer.upload's)
+      rows      (offset, H, W) per image
+      state     new_motion_state's tensor, updated in place: it keeps every stream's last thumbnail between calls
+      streams   the state index in [0, S) of every row, as track_update's
+      settings  the keys of MOTION (motion_settings)
+    -> (motion [N, 4] float32: dx, dy, valid (1.0 / 0.0), 0 -- scene content at p in the previous frame of the stream is
+    at p + (dx, dy) in this one, in source pixels; diag [N, 4] int32: k, blocks, textured, agreeing), on the device."""
+    cfg = motion_settings(settings)
+    _gpu(src_u8, "estimate_motion")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
+        raise ValueError("estimate_motion: expected one contiguous flat uint8 buffer")
+    if not torch.is_tensor(state) or state.dtype != torch.uint8 or state.dim() != 2 or not state.is_contiguous() or \
+            state.shape[0] < 1 or state.shape[1] != _motion.state_bytes():
+        raise ValueError("estimate_motion: the state is a contiguous [S, 16 + 160 * 160] uint8 tensor (new_motion_state)")
+    if state.device != src_u8.device:
+        raise ValueError("estimate_motion: the state lives on another device than the images")
+    rows = [tuple(int(v) for v in r) for r in rows]
+    N = len(rows)
+    for off, H, W in rows:
+        if not (1 <= H <= _cabi.FRAME_MAX_SIDE and 1 <= W <= _cabi.FRAME_MAX_SIDE) or off < 0 or off + H * W * 3 > src_u8.numel():
+            raise ValueError(f"estimate_motion: image (offset {off}, {H}x{W}) outside the buffer or larger than "
+                             f"{_cabi.FRAME_MAX_SIDE} a side")
+    streams = track_streams(streams, N)
+    if any(v >= state.shape[0] for v in streams):
+        raise ValueError(f"estimate_motion: a stream index outside the state's {state.shape[0]} streams")
+    motion = torch.empty((N, 4), dtype=torch.float32, device=src_u8.device)
+    diag = torch.empty((N, 4), dtype=torch.int32, device=src_u8.device)
+    four = (cfg["grid"], cfg["search"], cfg["texture"], cfg["min_blocks"])
+    with torch.cuda.device(src_u8.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            work = torch.empty((_motion.work_bytes(j - i),), dtype=torch.uint8, device=src_u8.device)
+            _motion.estimate(src_u8, rows[i:j], streams[i:j], state, four, work, motion[i:j], diag[i:j])
+    return motion, diag
 
 
 ASSIGN_MAX_ROWS, ASSIGN_MAX_COLS, ASSIGN_MAX_GAIN = _assign.MAX_ROWS, _assign.MAX_COLS, _assign.MAX_GAIN

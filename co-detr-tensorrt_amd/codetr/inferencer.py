@@ -127,6 +127,16 @@ are compared and ties go to the lowest slot and row.
 does, solved inside the same one launch per chunk (``include/codetr_assign.h`` states the gains, the procedure and its
 tie rule; ``csrc/track_assign.hip``).  Greedy loses an identity where two objects cross and the best single pair leaves
 the other track nothing above the threshold; the assignment keeps both.  The states are the same for both rules.
+
+``track_motion`` (with a tracker only): ``None``, the default, changes nothing.  ``"translation"`` or
+``dict(type="translation", grid=160, search=8, texture=2, min_blocks=4)`` turns camera-motion compensation on: per chunk
+``hip_ops.estimate_motion`` (three launches behind the staging, in front of the forward and of the drawing;
+``csrc/motion.hip``) estimates the translation between the consecutive frames of every stream from the chunk's own
+images, the motion stays on the device and ``codetr_track_update3_*`` adds it to the predicted track centres before
+association, so a pan, a shake or a preset change keeps the ids.  Every result dict gains ``"camera_motion"``:
+``[dx, dy]`` in source pixels, or ``None`` where there is none (a stream's first frame, a size change, too little texture
+or agreement).  ``include/codetr_motion.h`` states the rule and its limits: translation only, a reach of ``search * k``
+pixels per frame (96 px at 1920 x 1080 by default).
 """
 import collections
 import colorsys
@@ -498,6 +508,22 @@ def track_association_setting(track_association, tracker):
     return track_association
 
 
+def track_motion_settings(track_motion, tracker):
+    """How `Inferencer(..., track_motion=...)` reads its argument: None -> None; "translation" -> hip_ops.MOTION;
+    dict(type="translation", grid=..., search=..., texture=..., min_blocks=...) is validated and completed from it
+    (hip_ops.motion_settings); ValueError for anything else, and for a setting given without a tracker"""
+    if track_motion is None:
+        return None
+    if isinstance(track_motion, str):
+        track_motion = dict(type=track_motion)
+    if not isinstance(track_motion, dict) or track_motion.get("type") != "translation":
+        raise ValueError('track_motion must be None, "translation" or a dict with type="translation" and keys of '
+                         f"{sorted(hip_ops.MOTION)}, got {track_motion!r}")
+    if tracker is None:
+        raise ValueError("track_motion without a tracker: Inferencer(..., tracker=dict(...)) turns tracking on")
+    return hip_ops.motion_settings({k: v for k, v in track_motion.items() if k != "type"})
+
+
 def vis_format_settings(vis_format):
     """How `Inferencer(..., vis_format=...)` reads its argument: None and "png" -> None (vis/%08d.png through zlib, as
     before); "jpeg" or a dict with keys of VIS_FORMAT_KEYS, type "jpeg" -> dict(quality, subsampling), the validated
@@ -540,7 +566,7 @@ class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
                  slicing=None, tracker=None, vis_format=None,
-                 track_association=None, ensemble=None):
+                 track_association=None, ensemble=None, track_motion=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -594,7 +620,11 @@ class Inferencer:
         self.tracker = tracker_settings(tracker, self.cfg)
         self.track_association = track_association_setting(track_association, self.tracker)
         self._track_state = None   # [rows, state bytes] uint8 on the device of the first tracked call
-        self._track_rows = {}      # stream -> its row of _track_state
+        self._track_rows = {}      # stream -> its row of _track_state (and of _motion_state)
+        self.track_motion = track_motion_settings(track_motion, self.tracker)
+        self._motion_state = None  # [rows, 16 + 160 * 160] uint8: every stream's last thumbnail, on the device
+        self._chunk_streams = None   # the streams of the chunk __call__ is staging (a tracked call with track_motion)
+        self._chunk_motion = None    # its [N, 4] motion on the device: _stage_call_chunk -> track_chunk
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -636,7 +666,7 @@ class Inferencer:
         """preprocess_batch + the RGB buffer on the device and every image's (offset, H, W) in it, for the visualisation"""
         if not len(images):
             raise ValueError("preprocess_batch: no images")
-        src, staged, _ = self.stage_chunk(images, device, frames)
+        src, staged, _ = self._stage_call_chunk(images, device, frames)
         rows, metas = [], []
         d = self.pad_size_divisor
         for offset, H, W in staged:
@@ -944,7 +974,7 @@ class Inferencer:
             div = torch.cat([self.divisors(metas, dtype) for _, metas, _ in plans])      # [S * F * N, 4]
             return torch.cat((widths.view(torch.uint8), div.view(-1).view(torch.uint8)))
 
-        src, staged, tail = self.stage_chunk(images, device, frames, tail_of)
+        src, staged, tail = self._stage_call_chunk(images, device, frames, tail_of)
         widths = tail[:4 * N].view(torch.float32)
         div = tail[4 * N:].view(dtype).view(len(plans), len(flips) * N, 4)
         view_dets = [[] for _ in range(1 + len(self.ensemble))]   # per model, its scales in order
@@ -1054,7 +1084,7 @@ class Inferencer:
             div = self.divisors(metas, dtype)                                                     # [R, 4]
             return torch.cat([t.view(-1).view(torch.uint8) for t in (origins, sizes, view_rows, div)])
 
-        src, staged, tail = self.stage_chunk(images, device, frames, tail_of)
+        src, staged, tail = self._stage_call_chunk(images, device, frames, tail_of)
         rows, metas, table, batch_hw = plan
         R, V = len(rows), len(table[0])
         origins = tail[:8 * R].view(torch.float32).view(R, 2)
@@ -1080,30 +1110,57 @@ class Inferencer:
 
     # ---- tracking ---------------------------------------------------------------------------------------------
     def reset_tracks(self, stream=None):
-        """forget the tracks of one stream, or of all (None): its state is zeroed, ids start at 1 again"""
+        """forget the tracks of one stream, or of all (None): its state is zeroed, ids start at 1 again; with
+        track_motion its last thumbnail goes too (the stream's next frame has no motion)"""
         if stream is None:
-            self._track_state, self._track_rows = None, {}
+            self._track_state, self._track_rows, self._motion_state = None, {}, None
         elif hip_ops.track_streams(stream, 1)[0] in self._track_rows:
-            self._track_state[self._track_rows[int(stream)]].zero_()
+            for state in (self._track_state, self._motion_state):
+                if state is not None and self._track_rows[int(stream)] < state.shape[0]:
+                    state[self._track_rows[int(stream)]].zero_()
+
+    def _stream_state(self, state, new, streams, dev):
+        """the state tensor of `streams` (`new(rows)` makes a fresh one), grown to hold the row of every stream seen"""
+        if state is not None and state.device != dev:
+            raise ValueError(f"the track states live on {state.device}: reset_tracks() before a call on {dev}")
+        for s in streams:
+            self._track_rows.setdefault(s, len(self._track_rows))
+        have = 0 if state is None else state.shape[0]
+        if len(self._track_rows) > have:   # (grows by doubling: a new camera is rare)
+            grown = new(max(len(self._track_rows), 2 * have))
+            if have:
+                grown[:have].copy_(state)
+            state = grown
+        return state
+
+    def _stage_call_chunk(self, images, device, frames, tail=None):
+        """stage_chunk for a chunk of __call__: with track_motion the camera-motion estimate of the chunk's own images
+        (whole frames, not views or tiles) is launched behind the staging -- in front of the forward, and of draw_chunk,
+        which draws into that buffer.  The motion stays on the device for track_chunk."""
+        src, staged, tail = self.stage_chunk(images, device, frames, tail)
+        self._chunk_motion = None
+        if self.track_motion is not None and self._chunk_streams is not None:
+            self._motion_state = self._stream_state(self._motion_state, lambda n: hip_ops.new_motion_state(n, src.device),
+                                                    self._chunk_streams, src.device)
+            self._chunk_motion, _ = hip_ops.estimate_motion(src, staged, self._motion_state,
+                                                            [self._track_rows[s] for s in self._chunk_streams],
+                                                            self.track_motion)
+        return src, staged, tail
 
     def track_chunk(self, dets, streams):
         """the track ids of a chunk's final detections: one hip_ops.track_update launch on the states kept on the device
-        and one device-to-host copy -> [N, Q] int32 numpy.  A stream's state is created on its first frame."""
+        and one device-to-host copy -> [N, Q] int32 numpy.  A stream's state is created on its first frame.  With
+        track_motion the chunk's motion (_stage_call_chunk) feeds the launch and its copy follows the ids':
+        -> (ids, [N, 4] float32 numpy)."""
         dev = dets.scores.device
         T = self.tracker["max_tracks"]
-        if self._track_state is not None and self._track_state.device != dev:
-            raise ValueError(f"the track states live on {self._track_state.device}: reset_tracks() before a call on {dev}")
-        for s in streams:
-            self._track_rows.setdefault(s, len(self._track_rows))
-        have = 0 if self._track_state is None else self._track_state.shape[0]
-        if len(self._track_rows) > have:   # (grows by doubling: a new camera is rare)
-            grown = hip_ops.new_track_state(max(len(self._track_rows), 2 * have), T, dev)
-            if have:
-                grown[:have].copy_(self._track_state)
-            self._track_state = grown
-        ids = hip_ops.track_update(dets, self._track_state, [self._track_rows[s] for s in streams], self.tracker,
-                                   self.track_association)
-        return ids.cpu().numpy()
+        self._track_state = self._stream_state(self._track_state, lambda n: hip_ops.new_track_state(n, T, dev), streams, dev)
+        rows = [self._track_rows[s] for s in streams]
+        if self.track_motion is None:
+            return hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association).cpu().numpy()
+        ids = hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association,
+                                   motion=self._chunk_motion)
+        return ids.cpu().numpy(), self._chunk_motion.cpu().numpy()
 
     # ---- visualisation and files --------------------------------------------------------------------------
     def download_chunk(self, src, rows):
@@ -1187,6 +1244,7 @@ class Inferencer:
         for start in range(0, len(images), batch_size):
             chunk = images[start:start + batch_size]
             self._chunk_start = start
+            self._chunk_streams = streams[start:start + batch_size] if self.track_motion is not None else None
             with torch.no_grad():
                 if self.tta is not None:
                     preds, src, rows, dets = self._tta_chunk(chunk, device, dtype, frames)
@@ -1199,8 +1257,13 @@ class Inferencer:
                     self.check_jpeg_status()
                 if self.tracker is not None:   # the ids of the rows the predictions kept (a host-side cut included)
                     ids = self.track_chunk(dets, streams[start:start + batch_size])
+                    if self.track_motion is not None:
+                        ids, motion = ids
+                        for pred, m in zip(preds, motion):
+                            pred["camera_motion"] = [float(m[0]), float(m[1])] if m[2] == 1.0 else None
                     for pred, row in zip(preds, ids):
                         pred["track_ids"] = row[:len(pred["labels"])].tolist()
+                    self._chunk_streams = None
                 drawn = [None] * len(chunk)
                 if visualise and draw_pred:
                     drawn = self.draw_chunk(src, rows, dets, pred_score_thr, download=want_arrays)

@@ -1,4 +1,5 @@
-// The tracker with a choice of association: codetr_track_update2_* of include/codetr_assign.h.  The walk over a stream's
+// The tracker with a choice of association: codetr_track_update2_* of include/codetr_assign.h, and the same with the
+// camera motion of every row added to the predicted centres: codetr_track_update3_* of include/codetr_motion.h.  The walk over a stream's
 // frames, the filters, retirement and starts are track_common.h's (shared with track.hip and its pinned kernel); the
 // greedy association is match_phase as it is there, the optimal one is assign_phase below, which hands the procedure of
 // assign_core.h the integer gains of the header, computed on the fly from the boxes in LDS (no T x Q matrix).
@@ -13,6 +14,7 @@
 #include "track_common.h"
 
 #include "assign_core.h"
+#include "codetr_motion.h"
 
 namespace {
 
@@ -100,24 +102,61 @@ __global__ __launch_bounds__(kThreads) void track_update2_kernel(const T* __rest
                });
 }
 
+// track_update2_kernel with the camera motion of every row (codetr_motion.h; `motion` [N, 4] or null) added to the predicted
+// centres.  A kernel of its own, its text repeated, because the code of track_update2_kernel is pinned.
 template <class T>
+__global__ __launch_bounds__(kThreads) void track_update3_kernel(const T* __restrict__ boxes, const T* __restrict__ scores,
+                                                                 const int64_t* __restrict__ labels,
+                                                                 const int* __restrict__ count, int N, int Q, RowTable tab,
+                                                                 unsigned char* __restrict__ states, int maxT,
+                                                                 Settings cfg, int* __restrict__ ids_out, int association,
+                                                                 const float* __restrict__ motion) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const int tid = threadIdx.x;
+  const AssignLds a = assign_carve(lds_raw + lds2_offset(maxT, Q), maxT, max(maxT, Q));
+  track_stream<true>(
+      lds_raw, boxes, scores, labels, count, N, Q, tab, states, maxT, cfg, ids_out,
+      [&](const Lds& s, int cnt, int f) {  // 3. to 5. the three associations
+        const bool w = cfg.weight_iou != 0;
+        if (association == CODETR_ASSOCIATION_OPTIMAL) {  // (uniform)
+          assign_phase(s, a, maxT, cnt, f, 0, 1, w, cfg.match_high, tid);
+          assign_phase(s, a, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid);
+          assign_phase(s, a, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
+        } else {
+          match_phase(s, maxT, cnt, f, 0, 1, w, cfg.match_high, tid);
+          match_phase(s, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid);
+          match_phase(s, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
+        }
+      },
+      motion);
+}
+
+template <class T, bool kMotion = false>
 int launch_track2(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count, int64_t N,
                   int64_t Q, const int* stream_of_row, int64_t S, void* state, int64_t max_tracks, const float* settings,
-                  int64_t retain, int64_t tentatives, int weight_iou, int* ids_out, int association) {
+                  int64_t retain, int64_t tentatives, int weight_iou, int* ids_out, int association,
+                  const float* motion = nullptr) {
   if (association != CODETR_ASSOCIATION_GREEDY && association != CODETR_ASSOCIATION_OPTIMAL) return CODETR_E_BADARG;
   return checked_track_launch(
       boxes, scores, labels, count, N, Q, stream_of_row, S, state, max_tracks, settings, retain, tentatives, weight_iou,
       ids_out, [&](const RowTable& tab, const Settings& cfg) -> hipError_t {
         const int64_t lds = lds2_bytes_of(max_tracks, Q);
-        if (lds + kStaticLds > 64 * 1024)  // (the opt-in is needed once dynamic + static LDS pass 64 KB)
-          if (const hipError_t e = allow_large_lds<track_update2_kernel<T>>(
-                  (int)lds2_bytes_of(CODETR_TRACK_MAX_TRACKS, CODETR_POSTPROCESS_MAX_Q));
-              e != hipSuccess)
-            return e;
-        hipLaunchKernelGGL((track_update2_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
-                           static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
-                           labels, count, (int)N, (int)Q, tab, static_cast<unsigned char*>(state), (int)max_tracks, cfg,
-                           ids_out, association);
+        const int lds_max = (int)lds2_bytes_of(CODETR_TRACK_MAX_TRACKS, CODETR_POSTPROCESS_MAX_Q);
+        if constexpr (kMotion) {
+          if (lds + kStaticLds > 64 * 1024)  // (the opt-in is needed once dynamic + static LDS pass 64 KB)
+            if (const hipError_t e = allow_large_lds<track_update3_kernel<T>>(lds_max); e != hipSuccess) return e;
+          hipLaunchKernelGGL((track_update3_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
+                             static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                             labels, count, (int)N, (int)Q, tab, static_cast<unsigned char*>(state), (int)max_tracks, cfg,
+                             ids_out, association, motion);
+        } else {
+          if (lds + kStaticLds > 64 * 1024)
+            if (const hipError_t e = allow_large_lds<track_update2_kernel<T>>(lds_max); e != hipSuccess) return e;
+          hipLaunchKernelGGL((track_update2_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
+                             static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                             labels, count, (int)N, (int)Q, tab, static_cast<unsigned char*>(state), (int)max_tracks, cfg,
+                             ids_out, association);
+        }
         return hipSuccess;
       });
 }
@@ -140,5 +179,20 @@ CODETR_TRACK2_ENTRY(f16, _Float16)
 CODETR_TRACK2_ENTRY(bf16, Bf16)
 CODETR_TRACK2_ENTRY(f32, float)
 #undef CODETR_TRACK2_ENTRY
+
+#define CODETR_TRACK3_ENTRY(SUFFIX, TYPE)                                                                                  \
+  int codetr_track_update3_##SUFFIX(void* stream, const void* boxes_dev, const void* scores_dev,                           \
+                                    const int64_t* labels_dev, const int* count_dev, int64_t N, int64_t Q,                 \
+                                    const int* stream_of_row_host, int64_t S, void* state_dev, int64_t max_tracks,         \
+                                    const float* settings_host, int64_t retain, int64_t tentatives, int weight_iou,        \
+                                    int* track_id_out_dev, int association, const float* motion_dev) {                     \
+    return launch_track2<TYPE, true>(stream, boxes_dev, scores_dev, labels_dev, count_dev, N, Q, stream_of_row_host, S,    \
+                                     state_dev, max_tracks, settings_host, retain, tentatives, weight_iou,                 \
+                                     track_id_out_dev, association, motion_dev);                                           \
+  }
+CODETR_TRACK3_ENTRY(f16, _Float16)
+CODETR_TRACK3_ENTRY(bf16, Bf16)
+CODETR_TRACK3_ENTRY(f32, float)
+#undef CODETR_TRACK3_ENTRY
 
 }  // extern "C"

@@ -234,13 +234,15 @@ __device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f,
 }
 
 // One stream's rows of a launch, walked in row order (the kernel body of both translation units).  `associate(s, cnt, f)`
-// runs steps 3 to 5 on the frame's candidates and predicted tracks and ends with a barrier.
-template <class T, class Assoc>
+// runs steps 3 to 5 on the frame's candidates and predicted tracks and ends with a barrier.  kMotion (codetr_motion.h):
+// `motion` [N, 4] = dx, dy, valid, 0 per row, or null; a valid, finite motion is added to the predicted centres.
+template <bool kMotion = false, class T, class Assoc>
 __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __restrict__ boxes,
                                              const T* __restrict__ scores, const int64_t* __restrict__ labels,
                                              const int* __restrict__ count, int N, int Q, const RowTable& tab,
                                              unsigned char* __restrict__ states, int maxT, const Settings& cfg,
-                                             int* __restrict__ ids_out, Assoc associate) {
+                                             int* __restrict__ ids_out, Assoc associate,
+                                             const float* __restrict__ motion = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
   bool have = false;
@@ -279,6 +281,14 @@ __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __
       s.out[j] = 0;
     }
     // 2. predict
+    float mdx = 0.f, mdy = 0.f;
+    bool moved = false;  // (uniform)
+    if constexpr (kMotion) {
+      if (motion) {
+        mdx = motion[4 * (int64_t)n], mdy = motion[4 * (int64_t)n + 1];
+        moved = motion[4 * (int64_t)n + 2] == 1.0f && __builtin_isfinite(mdx) && __builtin_isfinite(mdy);
+      }
+    }
     for (int t = tid; t < maxT; t += kThreads) {
       s.match[t] = -1;
       if (s.id[t] == 0) continue;
@@ -294,6 +304,9 @@ __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __
         q[0] = ((A + 2.f * B) + C) + sp * sp;
         q[maxT] = B + C;
         q[2 * maxT] = C + sv * sv;
+      }
+      if constexpr (kMotion) {
+        if (moved) s.mean[t] = s.mean[t] + mdx, s.mean[2 * maxT + t] = s.mean[2 * maxT + t] + mdy;
       }
       const float cx = s.mean[t], cy = s.mean[2 * maxT + t], a = s.mean[4 * maxT + t], hh = s.mean[6 * maxT + t];
       const float w = a * hh;

@@ -58,6 +58,11 @@ and images/s of the Inferencer at batch_size 8 over --images images taken as the
 `tracker={}`, without a tracker, and with the host composition the tracker replaces (the untracked call's predictions
 through tests/track_ref.py frame by frame, the state on the host), the three in turn, three times.
 
+`--track --motion` prints only a `track_motion` record (camera-motion compensation, fp16): estimate_motion's three
+launches alone on 8 frames of 1920x1080 beside a device-to-device copy of the same bytes (HIP event pairs, median of 200);
+track_update on the two `--track` workloads with and without a motion operand, alternating; and images/s of the tracked
+Inferencer at batch_size 8 over 16 panned 1920x1080 frames as one stream, with and without `track_motion`, in turn.
+
 `--decode jpeg` prints only a `decode` record (JPEG files as input, fp16): --images frames of 1920x1080 (the gradient
 with noise of `--vis`) written as 4:2:0 files by Pillow where it imports (no restart markers), else by encode_jpeg; the
 decoder's five launches alone on eight of them (HIP event pairs, median), the bytes uploaded beside the bytes written,
@@ -67,6 +72,7 @@ the host parser per file, Pillow's decode per frame; and images/s of the Inferen
     python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis] [--slice]   -> one JSON line
     python tools/bench_inferencer.py --frames nv12 --resident
     python tools/bench_inferencer.py --track
+    python tools/bench_inferencer.py --track --motion
 """
 import argparse
 import csv
@@ -872,6 +878,79 @@ def track_record(inf, images, repeats, bs=8):
     return rec
 
 
+def motion_record(inf, repeats, bs=8, frames=16):
+    """camera-motion compensation (`--track --motion`): estimate_motion alone on 8 frames of 1920 x 1080 beside a
+    device-to-device copy of the same bytes (HIP events, 200 launches); track_update on the --track workloads with and
+    without a motion operand, alternating; the tracked Inferencer on panned 1920 x 1080 frames as one stream with and
+    without track_motion, the two in turn, three times"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import motion_cases
+    from codetr import hip_ops
+    from codetr.inferencer import Inferencer
+
+    H, W, margin = 1080, 1920, 128
+    canvas = motion_cases.texture(5, H + 2 * margin, W + 2 * margin, 48)
+    rng = np.random.default_rng(9)
+    pans = [(0, 0)] + [(int(rng.integers(-60, 61)), int(rng.integers(-40, 41))) for _ in range(frames - 1)]
+    shifts, x, y = [], 0, 0
+    for dx, dy in pans:   # (a walk that stays inside the canvas margin)
+        dx = -dx if abs(x + dx) > margin else dx
+        dy = -dy if abs(y + dy) > margin else dy
+        x, y = x + dx, y + dy
+        shifts.append((x, y))
+    images = [motion_cases.view(canvas, (H, W), s, margin) for s in shifts]
+    rec = {"frames": frames, "frame_hw": [H, W], "batch_size": bs, "dtype": "fp16"}
+
+    buf = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images[:8]])).to(DEV)
+    rows = [(i * H * W * 3, H, W) for i in range(8)]
+    state = hip_ops.new_motion_state(1, DEV)
+    motion, diag = hip_ops.estimate_motion(buf, rows, state)
+    dst = torch.empty_like(buf)
+    rec["estimate"] = {"bytes": buf.numel(), "motion": motion.cpu().tolist(), "diag": diag.cpu().tolist(),
+                       "true_pans": [[shifts[i][0] - shifts[i - 1][0], shifts[i][1] - shifts[i - 1][1]] for i in range(1, 8)],
+                       "us_per_call_median": [], "copy_us_median": []}
+    for _ in range(3):                                                        # the two in turn
+        rec["estimate"]["us_per_call_median"].append(_event_us_each(lambda: hip_ops.estimate_motion(buf, rows, state)))
+        rec["estimate"]["copy_us_median"].append(_event_us_each(lambda: dst.copy_(buf)))
+
+    dets = track_detections(8, 300, 100)
+    moved = torch.tensor([[3.5, -2.25, 1.0, 0.0]] * 8, dtype=torch.float32, device=DEV)
+    rec["track_update"] = {}
+    for name, streams in (("8_frames_of_1_stream", [0] * 8), ("1_frame_of_8_streams", list(range(8)))):
+        rec["track_update"][name] = {"without_motion_us": [], "with_motion_us": []}
+        states = {}
+        for key in ("without_motion_us", "with_motion_us"):
+            states[key] = hip_ops.new_track_state(8, hip_ops.TRACKER["max_tracks"], DEV)
+            for _ in range(1 if name[0] == "8" else 8):
+                hip_ops.track_update(dets, states[key], streams)
+        for _ in range(3):
+            for key, m in (("without_motion_us", None), ("with_motion_us", moved)):
+                rec["track_update"][name][key].append(
+                    _event_us_each(lambda: hip_ops.track_update(dets, states[key], streams, motion=m), launches=100, warmup=5))
+
+    arms = {"tracker": Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={}),
+            "tracker_and_motion": Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={}, track_motion="translation")}
+    for name in arms:
+        rec[name] = {"pass_s": []}
+    with torch.no_grad():
+        for name, arm in arms.items():                                        # warm-up
+            got = arm(images, device=DEV, dtype=torch.float16, batch_size=bs)["predictions"]
+            if name == "tracker_and_motion":
+                rec["camera_motion_first_8"] = [p["camera_motion"] for p in got[:8]]
+        for _ in range(3):
+            for name, arm in arms.items():
+                for _ in range(repeats):
+                    arm.reset_tracks()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    arm(images, device=DEV, dtype=torch.float16, batch_size=bs)
+                    rec[name]["pass_s"].append(round(time.perf_counter() - t0, 4))
+    for name in arms:
+        rec[name]["images_per_s"] = round(len(images) / min(rec[name]["pass_s"]), 2)
+        rec[name]["images_per_s_median"] = round(len(images) / float(np.median(rec[name]["pass_s"])), 2)
+    return rec
+
+
 def bench_cfg():
     import bench
 
@@ -958,6 +1037,7 @@ def main():
     ap.add_argument("--frames", choices=("nv12", "i420", "bgr"), help="only the frames record, for frames of this format")
     ap.add_argument("--resident", action="store_true", help="with --frames: also feed the frames as GPU-resident tensors")
     ap.add_argument("--track", action="store_true", help="only the tracking record: the images as one stream")
+    ap.add_argument("--motion", action="store_true", help="with --track: only the camera-motion record (track_motion)")
     ap.add_argument("--decode", choices=("jpeg",), help="only the record of JPEG files as input, decoded on the GPU")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -979,6 +1059,11 @@ def main():
         print(json.dumps({"metric": "Inferencer on JPEG files (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the decoder",
                           "decode": decode_record(infs["fp16"], a.images, a.repeats)}))
+        return
+    if a.track and a.motion:
+        print(json.dumps({"metric": "Inferencer tracking with camera-motion compensation (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the kernels",
+                          "track_motion": motion_record(infs["fp16"], a.repeats)}))
         return
     if a.track:
         print(json.dumps({"metric": "Inferencer tracking (Swin-L config, random weights)",
