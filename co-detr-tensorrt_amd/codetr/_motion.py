@@ -26,6 +26,8 @@ SIGNATURES = {name: (_cabi._CTYPE[_cheader.kind(ret, returned=True)], [_cabi._CT
 
 _cabi.CALLS.setdefault("motion_estimate", 0)
 _cabi.CALLS.setdefault("track_update3", 0)
+_cabi.CALLS.setdefault("motion_estimate2", 0)
+_cabi.CALLS.setdefault("track_update4", 0)
 _lib = None
 
 
@@ -59,30 +61,42 @@ def work_bytes(N):
     return int(load().codetr_motion_work_bytes(int(N)))
 
 
-def estimate(src, rows, streams, state, settings, work, motion_out, diag_out):
+def work2_bytes(N):
+    return int(load().codetr_motion_work2_bytes(int(N)))
+
+
+def estimate(src, rows, streams, state, settings, work, motion_out, diag_out, similarity=False):
     """src flat uint8, rows [(offset, H, W)] of N images, streams N ints, state [S, state_bytes()] uint8, settings
     (grid, search, texture, min_blocks), work uint8 of work_bytes(N), motion_out [N, 4] float32, diag_out [N, 4] int32,
-    all contiguous on one device (include/codetr_motion.h)"""
-    _cabi.CALLS["motion_estimate"] += 1
+    all contiguous on one device (include/codetr_motion.h); similarity: codetr_motion_estimate2_u8 with work2_bytes(N) of
+    work and [N, 8] outputs"""
+    name = "codetr_motion_estimate2_u8" if similarity else "codetr_motion_estimate_u8"
+    _cabi.CALLS["motion_estimate2" if similarity else "motion_estimate"] += 1
     N = len(rows)
     flat = [int(v) for r in rows for v in r]
-    rc = load().codetr_motion_estimate_u8(
+    rc = getattr(load(), name)(
         _cabi.current_stream_ptr(src.device), src.data_ptr(), src.numel(), N, (ctypes.c_int64 * (3 * N))(*flat),
         (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(),
         (ctypes.c_int * 4)(*[int(v) for v in settings]), work.data_ptr(), work.numel(), motion_out.data_ptr(),
         diag_out.data_ptr())
-    _cabi.check(rc, "codetr_motion_estimate_u8")
+    _cabi.check(rc, name)
 
 
 def track_update3(boxes, scores, labels, count, streams, state, max_tracks, thresholds, retain, tentatives, weight_iou,
-                  ids_out, association, motion):
-    """_assign.track_update2's arguments + motion ([N, 4] float32 on the device, or None) -> codetr_track_update3_*"""
-    _cabi.CALLS["track_update3"] += 1
+                  ids_out, association, motion, form=3):
+    """_assign.track_update2's arguments + motion ([N, 4] float32 on the device, or None) -> codetr_track_update3_*;
+    form=4: motion [N, 8] -> codetr_track_update4_*"""
+    _cabi.CALLS[f"track_update{form}"] += 1
     N, Q = scores.shape
-    name = "codetr_track_update3_" + _cabi._SUFFIX[scores.dtype]
+    name = f"codetr_track_update{form}_" + _cabi._SUFFIX[scores.dtype]
     rc = getattr(load(), name)(
         _cabi.current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
         (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
         (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
         ids_out.data_ptr(), int(association), None if motion is None else motion.data_ptr())
     _cabi.check(rc, name)
+
+
+def track_update4(*args):
+    """track_update3's arguments with motion [N, 8] float32 (estimate's similarity rows) -> codetr_track_update4_*"""
+    track_update3(*args, form=4)

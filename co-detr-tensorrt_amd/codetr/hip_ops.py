@@ -1409,7 +1409,9 @@ def track_update(dets, state, streams=None, settings=None, association="greedy",
                 include/codetr_assign.h).  The state is the same: a stream may switch between calls
       motion    None, or estimate_motion's [N, 4] float32 (dx, dy, valid, 0 per row) on the detections' device: a valid,
                 finite motion is added to the predicted centres of the row's live tracks before association
-                (codetr_track_update3_*, include/codetr_motion.h).  None calls exactly the entry points it always did
+                (codetr_track_update3_*, include/codetr_motion.h).  None calls exactly the entry points it always did.
+                Or estimate_motion(model="similarity")'s [N, 8] float32: by the row's model the similarity moves the
+                predicted centres, their velocities and the height, or the translation is added (codetr_track_update4_*)
     -> [N, Q] int32 on the device: the id of the track each row updated or started, negated while the track is
     tentative, 0 for no track and beyond count."""
     cfg = track_settings(settings)
@@ -1428,9 +1430,9 @@ def track_update(dets, state, streams=None, settings=None, association="greedy",
         raise ValueError("track_update: boxes [N,Q,4], scores [N,Q], labels [N,Q], count [N]")
     N, Q = scores.shape
     if motion is not None:
-        if not torch.is_tensor(motion) or motion.dtype != torch.float32 or tuple(motion.shape) != (N, 4) or \
-                motion.device != scores.device:
-            raise ValueError("track_update: motion must be a [N, 4] float32 tensor on the detections' device")
+        if not torch.is_tensor(motion) or motion.dtype != torch.float32 or \
+                tuple(motion.shape) not in ((N, 4), (N, 8)) or motion.device != scores.device:
+            raise ValueError("track_update: motion must be a [N, 4] or [N, 8] float32 tensor on the detections' device")
         motion = motion.contiguous()
     streams = track_streams(streams, N)
     if any(v >= state.shape[0] for v in streams):
@@ -1450,7 +1452,9 @@ def track_update(dets, state, streams=None, settings=None, association="greedy",
             j = min(N, i + PREPROCESS_BATCH_MAX)
             args = (boxes[i:j], scores[i:j], labels[i:j], count[i:j], streams[i:j], state, T, thr,
                     cfg["num_frames_retain"], cfg["num_tentatives"], cfg["weight_iou_with_det_scores"], ids[i:j])
-            if motion is not None:
+            if motion is not None and motion.shape[1] == 8:
+                _motion.track_update4(*args, _assign.ASSOCIATIONS[association], motion[i:j])
+            elif motion is not None:
                 _motion.track_update3(*args, _assign.ASSOCIATIONS[association], motion[i:j])
             elif association == "greedy":
                 _cabi.track_update(*args)
@@ -1461,6 +1465,7 @@ def track_update(dets, state, streams=None, settings=None, association="greedy",
 
 # camera-motion compensation (include/codetr_motion.h states the rule and these settings' ranges)
 MOTION = dict(grid=_motion.GRID_MAX, search=8, texture=2, min_blocks=4)
+MOTION_MODELS = ("translation", "similarity")
 MotionState = collections.namedtuple("MotionState", "have H W k thumb")
 
 
@@ -1498,17 +1503,25 @@ def motion_state_to_host(state):
     return MotionState(hdr[:, 0].copy(), hdr[:, 1].copy(), hdr[:, 2].copy(), hdr[:, 3].copy(), raw[:, 16:].copy())
 
 
-def estimate_motion(src_u8, rows, state, streams=None, settings=None):
+def estimate_motion(src_u8, rows, state, streams=None, settings=None, model="translation"):
     """The global image motion between the consecutive frames of every stream, in three launches per
     PREPROCESS_BATCH_MAX images and without a synchronisation (csrc/motion.hip; include/codetr_motion.h states the rule:
-    block matching of gray thumbnails, a median vote, translation only).
+    block matching of gray thumbnails, a median vote, translation only).  model="similarity": five launches, the same
+    votes fitted with a zoom and a roll as well (the header's version 2); the state is the same, so a stream may switch
+    between the models from call to call.
       src_u8    one flat uint8 device buffer holding RGB HWC images (Inferencer.upload's)
       rows      (offset, H, W) per image
       state     new_motion_state's tensor, updated in place: it keeps every stream's last thumbnail between calls
       streams   the state index in [0, S) of every row, as track_update's
       settings  the keys of MOTION (motion_settings)
     -> (motion [N, 4] float32: dx, dy, valid (1.0 / 0.0), 0 -- scene content at p in the previous frame of the stream is
-    at p + (dx, dy) in this one, in source pixels; diag [N, 4] int32: k, blocks, textured, agreeing), on the device."""
+    at p + (dx, dy) in this one, in source pixels; diag [N, 4] int32: k, blocks, textured, agreeing), on the device.
+    model="similarity" -> (motion [N, 8] float32: dx, dy, valid, model (2.0 similarity, 1.0 translation, 0.0 none), a, b,
+    px, py -- content at p is at (px + dx, py + dy) + [[a, -b], [b, a]] (p - (px, py)); diag [N, 8] int32: the four above,
+    eligible pairs, the best pair's inliers, its i, its j)."""
+    if model not in MOTION_MODELS:
+        raise ValueError(f"estimate_motion: model must be one of {list(MOTION_MODELS)}, got {model!r}")
+    sim = model == "similarity"
     cfg = motion_settings(settings)
     _gpu(src_u8, "estimate_motion")
     if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
@@ -1527,14 +1540,18 @@ def estimate_motion(src_u8, rows, state, streams=None, settings=None):
     streams = track_streams(streams, N)
     if any(v >= state.shape[0] for v in streams):
         raise ValueError(f"estimate_motion: a stream index outside the state's {state.shape[0]} streams")
-    motion = torch.empty((N, 4), dtype=torch.float32, device=src_u8.device)
-    diag = torch.empty((N, 4), dtype=torch.int32, device=src_u8.device)
+    motion = torch.empty((N, 8 if sim else 4), dtype=torch.float32, device=src_u8.device)
+    diag = torch.empty((N, 8 if sim else 4), dtype=torch.int32, device=src_u8.device)
     four = (cfg["grid"], cfg["search"], cfg["texture"], cfg["min_blocks"])
     with torch.cuda.device(src_u8.device):
         for i in range(0, N, PREPROCESS_BATCH_MAX):
             j = min(N, i + PREPROCESS_BATCH_MAX)
-            work = torch.empty((_motion.work_bytes(j - i),), dtype=torch.uint8, device=src_u8.device)
-            _motion.estimate(src_u8, rows[i:j], streams[i:j], state, four, work, motion[i:j], diag[i:j])
+            nbytes = _motion.work2_bytes(j - i) if sim else _motion.work_bytes(j - i)
+            work = torch.empty((nbytes,), dtype=torch.uint8, device=src_u8.device)
+            if sim:
+                _motion.estimate(src_u8, rows[i:j], streams[i:j], state, four, work, motion[i:j], diag[i:j], similarity=True)
+            else:
+                _motion.estimate(src_u8, rows[i:j], streams[i:j], state, four, work, motion[i:j], diag[i:j])
     return motion, diag
 
 

@@ -137,6 +137,14 @@ association, so a pan, a shake or a preset change keeps the ids.  Every result d
 ``[dx, dy]`` in source pixels, or ``None`` where there is none (a stream's first frame, a size change, too little texture
 or agreement).  ``include/codetr_motion.h`` states the rule and its limits: translation only, a reach of ``search * k``
 pixels per frame (96 px at 1920 x 1080 by default).
+
+``"similarity"`` (same keys) fits a zoom and a roll as well as the pan to the same block votes (two more launches, the
+header's version 2) and ``codetr_track_update4_*`` moves the predicted centres, their velocities and the heights with it: a
+PTZ camera that zooms, a drone that climbs or yaws, a handheld camera that rolls.  A frame whose similarity is not valid
+falls back to its translation, so the mode is never worse than ``"translation"``.  ``"camera_motion"`` stays ``[dx, dy]`` (of
+a similarity: the inliers' mean displacement), and every result dict also gains ``"camera_transform"``: the 2 x 3 matrix
+``[[a, -b, tx], [b, a, ty]]`` that maps a point of the stream's previous frame to this one (``[[1, 0, dx], [0, 1, dy]]``
+for a translation), or ``None``.  Shear and perspective are not modelled and the boxes stay axis-aligned.
 """
 import collections
 import colorsys
@@ -508,16 +516,37 @@ def track_association_setting(track_association, tracker):
     return track_association
 
 
+def track_motion_model(track_motion):
+    """the model of a `track_motion` argument that track_motion_settings accepted: None, "translation" or
+    "similarity" (a string, or a dict's type)"""
+    if track_motion is None:
+        return None
+    return track_motion if isinstance(track_motion, str) else track_motion["type"]
+
+
+def camera_transform(row):
+    """a row of hip_ops.estimate_motion(model="similarity") (dx, dy, valid, model, a, b, px, py) -> the 2 x 3 matrix
+    [[a, -b, tx], [b, a, ty]] as nested lists, t = (px + dx, py + dy) - M (px, py), in float64 from the eight floats;
+    [[1, 0, dx], [0, 1, dy]] for a translation row; None for an invalid one"""
+    dx, dy, valid, model, a, b, px, py = (float(v) for v in row)
+    if valid != 1.0:
+        return None
+    if model != 2.0:
+        return [[1.0, 0.0, dx], [0.0, 1.0, dy]]
+    return [[a, -b, (px + dx) - (a * px - b * py)], [b, a, (py + dy) - (b * px + a * py)]]
+
+
 def track_motion_settings(track_motion, tracker):
-    """How `Inferencer(..., track_motion=...)` reads its argument: None -> None; "translation" -> hip_ops.MOTION;
+    """How `Inferencer(..., track_motion=...)` reads its argument: None -> None; "translation" or "similarity" (the model:
+    track_motion_model) -> hip_ops.MOTION;
     dict(type="translation", grid=..., search=..., texture=..., min_blocks=...) is validated and completed from it
     (hip_ops.motion_settings); ValueError for anything else, and for a setting given without a tracker"""
     if track_motion is None:
         return None
     if isinstance(track_motion, str):
         track_motion = dict(type=track_motion)
-    if not isinstance(track_motion, dict) or track_motion.get("type") != "translation":
-        raise ValueError('track_motion must be None, "translation" or a dict with type="translation" and keys of '
+    if not isinstance(track_motion, dict) or track_motion.get("type") not in hip_ops.MOTION_MODELS:
+        raise ValueError('track_motion must be None, "translation", "similarity" or a dict with one of them as type and keys of '
                          f"{sorted(hip_ops.MOTION)}, got {track_motion!r}")
     if tracker is None:
         raise ValueError("track_motion without a tracker: Inferencer(..., tracker=dict(...)) turns tracking on")
@@ -622,6 +651,7 @@ class Inferencer:
         self._track_state = None   # [rows, state bytes] uint8 on the device of the first tracked call
         self._track_rows = {}      # stream -> its row of _track_state (and of _motion_state)
         self.track_motion = track_motion_settings(track_motion, self.tracker)
+        self.track_motion_model = track_motion_model(track_motion)   # None, "translation" or "similarity"
         self._motion_state = None  # [rows, 16 + 160 * 160] uint8: every stream's last thumbnail, on the device
         self._chunk_streams = None   # the streams of the chunk __call__ is staging (a tracked call with track_motion)
         self._chunk_motion = None    # its [N, 4] motion on the device: _stage_call_chunk -> track_chunk
@@ -1144,14 +1174,14 @@ class Inferencer:
                                                     self._chunk_streams, src.device)
             self._chunk_motion, _ = hip_ops.estimate_motion(src, staged, self._motion_state,
                                                             [self._track_rows[s] for s in self._chunk_streams],
-                                                            self.track_motion)
+                                                            self.track_motion, model=self.track_motion_model)
         return src, staged, tail
 
     def track_chunk(self, dets, streams):
         """the track ids of a chunk's final detections: one hip_ops.track_update launch on the states kept on the device
         and one device-to-host copy -> [N, Q] int32 numpy.  A stream's state is created on its first frame.  With
         track_motion the chunk's motion (_stage_call_chunk) feeds the launch and its copy follows the ids':
-        -> (ids, [N, 4] float32 numpy)."""
+        -> (ids, [N, 4] float32 numpy, or [N, 8] under "similarity")."""
         dev = dets.scores.device
         T = self.tracker["max_tracks"]
         self._track_state = self._stream_state(self._track_state, lambda n: hip_ops.new_track_state(n, T, dev), streams, dev)
@@ -1261,6 +1291,8 @@ class Inferencer:
                         ids, motion = ids
                         for pred, m in zip(preds, motion):
                             pred["camera_motion"] = [float(m[0]), float(m[1])] if m[2] == 1.0 else None
+                            if self.track_motion_model == "similarity":
+                                pred["camera_transform"] = camera_transform(m)
                     for pred, row in zip(preds, ids):
                         pred["track_ids"] = row[:len(pred["labels"])].tolist()
                     self._chunk_streams = None

@@ -1,6 +1,8 @@
 // Camera-motion estimate for the tracker: codetr_motion_estimate_u8 of include/codetr_motion.h, which states the rule
 // operation by operation (integers, one fp32 division per axis at the end); this file follows that text.  Three launches
 // on the caller's stream, nothing host-visible in between; the thumbnails and the votes live in the caller's scratch.
+// codetr_motion_estimate2_u8 (the header's version 2, the similarity model) adds two launches behind them: see the section
+// at the end of the kernels.
 //
 // motion_thumb_kernel     grid (bands, th, N), 256 threads: one workgroup per band of <= 1024 source pixels (a whole number
 //                        of cells) of one thumbnail row.  A byte mover over 3-byte pixels: the k source rows of the band come
@@ -276,20 +278,178 @@ __global__ __launch_bounds__(kFinishThreads) void motion_finish_kernel(RowTab ta
   }
 }
 
-}  // namespace
+// ---- the similarity model (version 2 of the header) ---------------------------------------------------------------------
+// Two launches behind the three above, which run as they are (the third writes its translation row into the scratch):
+// motion_sim_pairs_kernel grid (kSimGroups, N), 256 threads: the row's textured blocks, numbered in ascending block order,
+//                        sit in LDS as one int4 each (block indices and 256 g + v: a ds_read_b128 that every lane of a
+//                        wave reads at one address); lanes over the n * n ordered index pairs, a row's share strided over its
+//                        kSimGroups workgroups; a lane with an eligible pair counts the pair's inliers over all blocks with
+//                        the reduced int32 test of the header.  Best pair of the workgroup: one 64-bit maximum (count, ~i,
+//                        ~j) by wave shuffles, then over the waves in LDS; one slot per workgroup in the scratch.
+// motion_sim_fit_kernel   grid N, 128 threads (a thread per textured block): the maximum of the row's slots, the inliers of
+//                        that pair, the refit's int64 sums by LDS atomics (integers: the order does not matter), the four
+//                        divisions; or the translation row, or zeros.
+constexpr int kSimGroups = 8;
+constexpr int kSimThreads = 256;
+constexpr int kSimSlotInts = 4;  // per (row, workgroup): key high, key low, eligible pairs, 0
+constexpr int kSimRowInts = 8 + kSimGroups * kSimSlotInts;  // per row; the scratch holds the translation rule's motion
+                                                           // [N, 4], then its diag [N, 4], then the slots [N, kSimGroups]
+static_assert(CODETR_MOTION_MAX_BLOCKS <= 128, "the compaction below ranks over the first two waves' lanes");
 
-extern "C" {
-
-int codetr_motion_abi_version(void) { return CODETR_MOTION_ABI_VERSION; }
-int64_t codetr_motion_state_bytes(void) { return kStateBytes; }
-int64_t codetr_motion_work_bytes(int64_t N) {
-  if (N <= 0 || N > CODETR_PREPROCESS_BATCH_MAX) return CODETR_E_BADARG;
-  return N * (int64_t)(kThumbBytes + 4 * kVoteInts);
+// The textured blocks of a row in ascending block order -> pts[t] = {bx, by, 256 bx + vx, 256 by + vy}; returns n.  Every
+// thread of the workgroup calls it (blockDim.x a multiple of 64, >= 128); two barriers.
+__device__ __forceinline__ int sim_gather(const Row& r, const int* __restrict__ vote, int4* pts, int* wcount) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nb = vote[0] != 0 ? r.nbx * r.nby : 0;  // (uniform)
+  const bool mine = tid < nb && vote[4 + 3 * tid] != 0;
+  const unsigned long long b = __ballot(mine);
+  if (lane == 0 && wave < 2) wcount[wave] = __popcll(b);
+  __syncthreads();
+  if (mine) {
+    const int t = (wave ? wcount[0] : 0) + __popcll(b & ((1ull << lane) - 1ull));
+    const int by = tid / r.nbx, bx = tid - by * r.nbx;
+    pts[t] = make_int4(bx, by, 256 * bx + vote[4 + 3 * tid + 1], 256 * by + vote[4 + 3 * tid + 2]);
+  }
+  __syncthreads();
+  return wcount[0] + wcount[1];
 }
 
-int codetr_motion_estimate_u8(void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* rows_host,
-                              const int* stream_of_row_host, int64_t S, void* state_dev, const int* settings_host,
-                              void* work_dev, int64_t work_bytes, float* motion_out_dev, int* diag_out_dev) {
+// the pair (i, j) of the header in reduced form: r' = F(m) - F(i), F(m) = A' G_m + B' G_m_perp - dd' W_m, against 16 dd'.
+// Every factor is below 2^17 in magnitude and every product below 2^21 (the header's bound), so the products are exact as
+// 24-bit multiplies (v_mul_i32_i24, full rate; v_mul_lo_u32 is quarter rate); the test is branch-free so that the loop over
+// the blocks keeps several LDS reads in flight.
+struct SimPair {
+  int A, B, dd, fx, fy, tol;
+};
+__device__ __forceinline__ SimPair sim_pair(int4 pi, int4 pj) {
+  const int Dx = pj.x - pi.x, Dy = pj.y - pi.y, ex = pj.z - pi.z, ey = pj.w - pi.w;
+  SimPair p;
+  p.A = Dx * ex + Dy * ey, p.B = Dx * ey - Dy * ex, p.dd = Dx * Dx + Dy * Dy;
+  p.fx = p.A * pi.x - p.B * pi.y - p.dd * pi.z;
+  p.fy = p.A * pi.y + p.B * pi.x - p.dd * pi.w;
+  p.tol = 16 * p.dd;
+  return p;
+}
+__device__ __forceinline__ bool sim_inlier(const SimPair& p, int4 pm) {
+  const int rx = __mul24(p.A, pm.x) - __mul24(p.B, pm.y) - __mul24(p.dd, pm.z) - p.fx;
+  const int ry = __mul24(p.A, pm.y) + __mul24(p.B, pm.x) - __mul24(p.dd, pm.w) - p.fy;
+  return ((int)(abs(rx) <= p.tol) & (int)(abs(ry) <= p.tol)) != 0;
+}
+
+__global__ __launch_bounds__(kSimThreads) void motion_sim_pairs_kernel(RowTab tab, const int* __restrict__ votes,
+                                                                      int* __restrict__ sim) {
+  __shared__ int4 pts[128];
+  __shared__ int wcount[2];
+  __shared__ unsigned long long red_key[kSimThreads / 64];
+  __shared__ int red_pairs[kSimThreads / 64];
+  const int row = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = sim_gather(tab.r[row], votes + (int64_t)row * kVoteInts, pts, wcount);  // (uniform, <= 100)
+  unsigned long long best = 0;
+  int pairs = 0;
+  for (int p = blockIdx.x * kSimThreads + tid; p < n * n; p += kSimGroups * kSimThreads) {
+    const int i = p / n, j = p - i * n;
+    if (i >= j) continue;
+    const int4 pi = pts[i], pj = pts[j];
+    const SimPair q = sim_pair(pi, pj);
+    if (q.dd < 4) continue;
+    pairs += 1;
+    int c = 0;
+#pragma unroll 4
+    for (int m = 0; m < n; ++m) c += sim_inlier(q, pts[m]);
+    const unsigned long long key = ((unsigned long long)c << 32) | ((unsigned)(0xffff - i) << 16) | (unsigned)(0xffff - j);
+    best = key > best ? key : best;
+  }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    const unsigned lo = __shfl_xor((unsigned)best, m, 64), hi = __shfl_xor((unsigned)(best >> 32), m, 64);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    best = o > best ? o : best;
+    pairs += __shfl_xor(pairs, m, 64);
+  }
+  if (lane == 0) red_key[wave] = best, red_pairs[wave] = pairs;
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int i = 1; i < kSimThreads / 64; ++i) best = red_key[i] > best ? red_key[i] : best, pairs += red_pairs[i];
+    int* slot = sim + 8 * (int64_t)gridDim.y + ((int64_t)row * kSimGroups + blockIdx.x) * kSimSlotInts;
+    slot[0] = (int)(unsigned)(best >> 32), slot[1] = (int)(unsigned)best, slot[2] = pairs, slot[3] = 0;
+  }
+}
+
+__global__ __launch_bounds__(kFinishThreads) void motion_sim_fit_kernel(RowTab tab, int R, int min_blocks,
+                                                                       const int* __restrict__ votes,
+                                                                       const int* __restrict__ sim,
+                                                                       float* __restrict__ motion, int* __restrict__ diag) {
+  __shared__ int4 pts[128];
+  __shared__ int wcount[2];
+  __shared__ unsigned long long sums[8];  // c2, sp_x, sp_y, sq_x, sq_y, sum |P|^2, sum P.Q, sum P x Q (two's complement)
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const Row& r = tab.r[row];  // (uniform)
+  const int n = sim_gather(r, votes + (int64_t)row * kVoteInts, pts, wcount);
+  const int N = gridDim.x;
+  const int* slots = sim + 8 * (int64_t)N + (int64_t)row * kSimGroups * kSimSlotInts;
+  unsigned long long best = 0;
+  int pairs = 0;
+#pragma unroll
+  for (int g = 0; g < kSimGroups; ++g) {  // (every thread reads the same words)
+    const int* slot = slots + g * kSimSlotInts;
+    const unsigned long long key = ((unsigned long long)(unsigned)slot[0] << 32) | (unsigned)slot[1];
+    best = key > best ? key : best;
+    pairs += slot[2];
+  }
+  const int bi = pairs ? 0xffff - (int)((best >> 16) & 0xffff) : -1, bj = pairs ? 0xffff - (int)(best & 0xffff) : -1;
+  if (tid < 8) sums[tid] = 0;
+  __syncthreads();
+  if (pairs && tid < n) {
+    const int4 pm = pts[tid];
+    if (sim_inlier(sim_pair(pts[bi], pts[bj]), pm)) {
+      const long long off = 16 * R + 128;  // P = 256 g + 16 R + 128, Q = P + v
+      const long long Px = 256 * pm.x + off, Py = 256 * pm.y + off, Qx = pm.z + off, Qy = pm.w + off;
+      atomicAdd(&sums[0], 1ull);
+      atomicAdd(&sums[1], (unsigned long long)Px);
+      atomicAdd(&sums[2], (unsigned long long)Py);
+      atomicAdd(&sums[3], (unsigned long long)Qx);
+      atomicAdd(&sums[4], (unsigned long long)Qy);
+      atomicAdd(&sums[5], (unsigned long long)(Px * Px + Py * Py));
+      atomicAdd(&sums[6], (unsigned long long)(Px * Qx + Py * Qy));
+      atomicAdd(&sums[7], (unsigned long long)(Px * Qy - Py * Qx));
+    }
+  }
+  __syncthreads();
+  if (tid != 0) return;
+  const long long c = (long long)sums[0], spx = (long long)sums[1], spy = (long long)sums[2], sqx = (long long)sums[3],
+                  sqy = (long long)sums[4];
+  const long long Sxx = c * (long long)sums[5] - (spx * spx + spy * spy);
+  const long long An = c * (long long)sums[6] - (spx * sqx + spy * sqy);
+  const long long Bn = c * (long long)sums[7] - (spx * sqy - spy * sqx);
+  const bool valid = n >= min_blocks && pairs >= 1 && c >= min_blocks && 2 * c >= n && Sxx > 0 && 2 * An >= Sxx &&
+                     An <= 2 * Sxx && 2 * (Bn < 0 ? -Bn : Bn) <= Sxx;
+  const float* tm = reinterpret_cast<const float*>(sim) + 4 * (int64_t)row;  // the translation rule's row: dx, dy, valid, 0
+  const int* td = sim + 4 * (int64_t)N + 4 * (int64_t)row;
+  float* m = motion + 8 * (int64_t)row;
+  if (valid) {
+    const float den = (float)(16 * c);
+    m[0] = (float)((sqx - spx) * r.k) / den, m[1] = (float)((sqy - spy) * r.k) / den, m[2] = 1.f, m[3] = 2.f;
+    m[4] = (float)An / (float)Sxx, m[5] = (float)Bn / (float)Sxx;
+    m[6] = (float)(spx * r.k) / den, m[7] = (float)(spy * r.k) / den;
+  } else {
+    const bool t = tm[2] == 1.f;
+    m[0] = t ? tm[0] : 0.f, m[1] = t ? tm[1] : 0.f, m[2] = t ? 1.f : 0.f, m[3] = t ? 1.f : 0.f, m[4] = t ? 1.f : 0.f;
+    m[5] = 0.f, m[6] = 0.f, m[7] = 0.f;
+  }
+  int* d = diag + 8 * (int64_t)row;
+  d[0] = td[0], d[1] = td[1], d[2] = td[2], d[3] = td[3];
+  d[4] = pairs, d[5] = pairs ? (int)(best >> 32) : 0, d[6] = bi, d[7] = bj;
+}
+
+// what the two entry points share: every argument check, then the row table and the launch extents
+struct Plan {
+  RowTab tab;
+  int R, texture, min_blocks, bands, th_max, nb_max;
+};
+int plan_of(const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* rows_host, const int* stream_of_row_host,
+            int64_t S, void* state_dev, const int* settings_host, void* work_dev, int64_t work_bytes, int64_t work_need,
+            const void* motion_out_dev, const void* diag_out_dev, Plan& plan) {
   if (!src_dev || !rows_host || !stream_of_row_host || !state_dev || !settings_host || !work_dev || !motion_out_dev ||
       !diag_out_dev || src_bytes <= 0 || N <= 0 || S <= 0)
     return CODETR_E_BADARG;
@@ -298,9 +458,9 @@ int codetr_motion_estimate_u8(void* stream, const void* src_dev, int64_t src_byt
   if (G < CODETR_MOTION_GRID_MIN || G > CODETR_MOTION_GRID_MAX || R < 1 || R > CODETR_MOTION_SEARCH_MAX || texture < 0 ||
       texture > CODETR_MOTION_TEXTURE_MAX || min_blocks < 1 || min_blocks > CODETR_MOTION_MAX_BLOCKS)
     return CODETR_E_BADARG;
-  if (work_bytes < N * (int64_t)(kThumbBytes + 4 * kVoteInts) || ((uintptr_t)work_dev & 3u) || ((uintptr_t)state_dev & 3u))
-    return CODETR_E_BADARG;
-  RowTab tab = {};
+  if (work_bytes < N * work_need || ((uintptr_t)work_dev & 3u) || ((uintptr_t)state_dev & 3u)) return CODETR_E_BADARG;
+  RowTab& tab = plan.tab;
+  tab = {};
   int bands = 1, th_max = 1, nb_max = 1;
   for (int64_t n = 0; n < N; ++n) {
     const int64_t off = rows_host[3 * n], H = rows_host[3 * n + 1], W = rows_host[3 * n + 2];
@@ -328,16 +488,66 @@ int codetr_motion_estimate_u8(void* stream, const void* src_dev, int64_t src_byt
     th_max = r.th > th_max ? r.th : th_max;
     nb_max = r.nbx * r.nby > nb_max ? r.nbx * r.nby : nb_max;
   }
+  plan.R = R, plan.texture = texture, plan.min_blocks = min_blocks;
+  plan.bands = bands, plan.th_max = th_max, plan.nb_max = nb_max;
+  return 0;
+}
+
+// the three launches of the translation rule
+void launch_translation(hipStream_t s, const Plan& plan, const void* src_dev, int64_t N, void* state_dev, void* work_dev,
+                        float* motion, int* diag) {
   unsigned char* thumbs = static_cast<unsigned char*>(work_dev);
   int* votes = reinterpret_cast<int*>(thumbs + N * (int64_t)kThumbBytes);
   unsigned char* states = static_cast<unsigned char*>(state_dev);
+  hipLaunchKernelGGL(motion_thumb_kernel, dim3((unsigned)plan.bands, (unsigned)plan.th_max, (unsigned)N), dim3(kThreads), 0,
+                     s, static_cast<const unsigned char*>(src_dev), plan.tab, thumbs);
+  hipLaunchKernelGGL(motion_match_kernel, dim3((unsigned)plan.nb_max, (unsigned)N), dim3(kThreads), 0, s, plan.tab, plan.R,
+                     plan.texture, states, thumbs, votes);
+  hipLaunchKernelGGL(motion_finish_kernel, dim3((unsigned)N), dim3(kFinishThreads), 0, s, plan.tab, plan.min_blocks, thumbs,
+                     votes, states, motion, diag);
+}
+
+}  // namespace
+
+extern "C" {
+
+int codetr_motion_abi_version(void) { return CODETR_MOTION_ABI_VERSION; }
+int64_t codetr_motion_state_bytes(void) { return kStateBytes; }
+int64_t codetr_motion_work_bytes(int64_t N) {
+  if (N <= 0 || N > CODETR_PREPROCESS_BATCH_MAX) return CODETR_E_BADARG;
+  return N * (int64_t)(kThumbBytes + 4 * kVoteInts);
+}
+int64_t codetr_motion_work2_bytes(int64_t N) {
+  if (N <= 0 || N > CODETR_PREPROCESS_BATCH_MAX) return CODETR_E_BADARG;
+  return N * (int64_t)(kThumbBytes + 4 * kVoteInts + 4 * kSimRowInts);
+}
+
+int codetr_motion_estimate_u8(void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* rows_host,
+                              const int* stream_of_row_host, int64_t S, void* state_dev, const int* settings_host,
+                              void* work_dev, int64_t work_bytes, float* motion_out_dev, int* diag_out_dev) {
+  Plan plan;
+  if (const int rc = plan_of(src_dev, src_bytes, N, rows_host, stream_of_row_host, S, state_dev, settings_host, work_dev,
+                             work_bytes, kThumbBytes + 4 * kVoteInts, motion_out_dev, diag_out_dev, plan))
+    return rc;
+  launch_translation(static_cast<hipStream_t>(stream), plan, src_dev, N, state_dev, work_dev, motion_out_dev, diag_out_dev);
+  const hipError_t err = hipGetLastError();
+  return err == hipSuccess ? 0 : (int)err;
+}
+
+int codetr_motion_estimate2_u8(void* stream, const void* src_dev, int64_t src_bytes, int64_t N, const int64_t* rows_host,
+                               const int* stream_of_row_host, int64_t S, void* state_dev, const int* settings_host,
+                               void* work_dev, int64_t work_bytes, float* motion_out_dev, int* diag_out_dev) {
+  Plan plan;
+  if (const int rc = plan_of(src_dev, src_bytes, N, rows_host, stream_of_row_host, S, state_dev, settings_host, work_dev,
+                             work_bytes, kThumbBytes + 4 * kVoteInts + 4 * kSimRowInts, motion_out_dev, diag_out_dev, plan))
+    return rc;
   const hipStream_t s = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(motion_thumb_kernel, dim3((unsigned)bands, (unsigned)th_max, (unsigned)N), dim3(kThreads), 0, s,
-                     static_cast<const unsigned char*>(src_dev), tab, thumbs);
-  hipLaunchKernelGGL(motion_match_kernel, dim3((unsigned)nb_max, (unsigned)N), dim3(kThreads), 0, s, tab, R, texture,
-                     states, thumbs, votes);
-  hipLaunchKernelGGL(motion_finish_kernel, dim3((unsigned)N), dim3(kFinishThreads), 0, s, tab, min_blocks, thumbs, votes,
-                     states, motion_out_dev, diag_out_dev);
+  const int* votes = reinterpret_cast<const int*>(static_cast<unsigned char*>(work_dev) + N * (int64_t)kThumbBytes);
+  int* sim = reinterpret_cast<int*>(static_cast<unsigned char*>(work_dev) + N * (int64_t)(kThumbBytes + 4 * kVoteInts));
+  launch_translation(s, plan, src_dev, N, state_dev, work_dev, reinterpret_cast<float*>(sim), sim + 4 * N);
+  hipLaunchKernelGGL(motion_sim_pairs_kernel, dim3(kSimGroups, (unsigned)N), dim3(kSimThreads), 0, s, plan.tab, votes, sim);
+  hipLaunchKernelGGL(motion_sim_fit_kernel, dim3((unsigned)N), dim3(kFinishThreads), 0, s, plan.tab, plan.R, plan.min_blocks,
+                     votes, sim, motion_out_dev, diag_out_dev);
   const hipError_t err = hipGetLastError();
   return err == hipSuccess ? 0 : (int)err;
 }

@@ -1,5 +1,6 @@
 // The tracker with a choice of association: codetr_track_update2_* of include/codetr_assign.h, and the same with the
-// camera motion of every row added to the predicted centres: codetr_track_update3_* of include/codetr_motion.h.  The walk over a stream's
+// camera motion of every row added to the predicted centres: codetr_track_update3_* of include/codetr_motion.h, or applied as a
+// similarity: codetr_track_update4_*.  The walk over a stream's
 // frames, the filters, retirement and starts are track_common.h's (shared with track.hip and its pinned kernel); the
 // greedy association is match_phase as it is there, the optimal one is assign_phase below, which hands the procedure of
 // assign_core.h the integer gains of the header, computed on the fly from the boxes in LDS (no T x Q matrix).
@@ -131,7 +132,36 @@ __global__ __launch_bounds__(kThreads) void track_update3_kernel(const T* __rest
       motion);
 }
 
-template <class T, bool kMotion = false>
+// track_update4_kernel with the similarity of every row (codetr_motion.h, version 2; `motion` [N, 8] or null): by the row's
+// model the predicted centres, their velocities and the height are moved about (px, py), or the translation is added.
+template <class T>
+__global__ __launch_bounds__(kThreads) void track_update4_kernel(const T* __restrict__ boxes, const T* __restrict__ scores,
+                                                                 const int64_t* __restrict__ labels,
+                                                                 const int* __restrict__ count, int N, int Q, RowTable tab,
+                                                                 unsigned char* __restrict__ states, int maxT,
+                                                                 Settings cfg, int* __restrict__ ids_out, int association,
+                                                                 const float* __restrict__ motion) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const int tid = threadIdx.x;
+  const AssignLds a = assign_carve(lds_raw + lds2_offset(maxT, Q), maxT, max(maxT, Q));
+  track_stream<2>(
+      lds_raw, boxes, scores, labels, count, N, Q, tab, states, maxT, cfg, ids_out,
+      [&](const Lds& s, int cnt, int f) {  // 3. to 5. the three associations
+        const bool w = cfg.weight_iou != 0;
+        if (association == CODETR_ASSOCIATION_OPTIMAL) {  // (uniform)
+          assign_phase(s, a, maxT, cnt, f, 0, 1, w, cfg.match_high, tid);
+          assign_phase(s, a, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid);
+          assign_phase(s, a, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
+        } else {
+          match_phase(s, maxT, cnt, f, 0, 1, w, cfg.match_high, tid);
+          match_phase(s, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid);
+          match_phase(s, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
+        }
+      },
+      motion);
+}
+
+template <class T, int kMotion = 0>
 int launch_track2(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count, int64_t N,
                   int64_t Q, const int* stream_of_row, int64_t S, void* state, int64_t max_tracks, const float* settings,
                   int64_t retain, int64_t tentatives, int weight_iou, int* ids_out, int association,
@@ -142,7 +172,14 @@ int launch_track2(void* stream, const void* boxes, const void* scores, const int
       ids_out, [&](const RowTable& tab, const Settings& cfg) -> hipError_t {
         const int64_t lds = lds2_bytes_of(max_tracks, Q);
         const int lds_max = (int)lds2_bytes_of(CODETR_TRACK_MAX_TRACKS, CODETR_POSTPROCESS_MAX_Q);
-        if constexpr (kMotion) {
+        if constexpr (kMotion == 2) {
+          if (lds + kStaticLds > 64 * 1024)
+            if (const hipError_t e = allow_large_lds<track_update4_kernel<T>>(lds_max); e != hipSuccess) return e;
+          hipLaunchKernelGGL((track_update4_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
+                             static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                             labels, count, (int)N, (int)Q, tab, static_cast<unsigned char*>(state), (int)max_tracks, cfg,
+                             ids_out, association, motion);
+        } else if constexpr (kMotion == 1) {
           if (lds + kStaticLds > 64 * 1024)  // (the opt-in is needed once dynamic + static LDS pass 64 KB)
             if (const hipError_t e = allow_large_lds<track_update3_kernel<T>>(lds_max); e != hipSuccess) return e;
           hipLaunchKernelGGL((track_update3_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
@@ -186,7 +223,7 @@ CODETR_TRACK2_ENTRY(f32, float)
                                     const int* stream_of_row_host, int64_t S, void* state_dev, int64_t max_tracks,         \
                                     const float* settings_host, int64_t retain, int64_t tentatives, int weight_iou,        \
                                     int* track_id_out_dev, int association, const float* motion_dev) {                     \
-    return launch_track2<TYPE, true>(stream, boxes_dev, scores_dev, labels_dev, count_dev, N, Q, stream_of_row_host, S,    \
+    return launch_track2<TYPE, 1>(stream, boxes_dev, scores_dev, labels_dev, count_dev, N, Q, stream_of_row_host, S,    \
                                      state_dev, max_tracks, settings_host, retain, tentatives, weight_iou,                 \
                                      track_id_out_dev, association, motion_dev);                                           \
   }
@@ -194,5 +231,20 @@ CODETR_TRACK3_ENTRY(f16, _Float16)
 CODETR_TRACK3_ENTRY(bf16, Bf16)
 CODETR_TRACK3_ENTRY(f32, float)
 #undef CODETR_TRACK3_ENTRY
+
+#define CODETR_TRACK4_ENTRY(SUFFIX, TYPE)                                                                                  \
+  int codetr_track_update4_##SUFFIX(void* stream, const void* boxes_dev, const void* scores_dev,                           \
+                                    const int64_t* labels_dev, const int* count_dev, int64_t N, int64_t Q,                 \
+                                    const int* stream_of_row_host, int64_t S, void* state_dev, int64_t max_tracks,         \
+                                    const float* settings_host, int64_t retain, int64_t tentatives, int weight_iou,        \
+                                    int* track_id_out_dev, int association, const float* motion_dev) {                     \
+    return launch_track2<TYPE, 2>(stream, boxes_dev, scores_dev, labels_dev, count_dev, N, Q, stream_of_row_host, S,       \
+                                  state_dev, max_tracks, settings_host, retain, tentatives, weight_iou, track_id_out_dev,  \
+                                  association, motion_dev);                                                                \
+  }
+CODETR_TRACK4_ENTRY(f16, _Float16)
+CODETR_TRACK4_ENTRY(bf16, Bf16)
+CODETR_TRACK4_ENTRY(f32, float)
+#undef CODETR_TRACK4_ENTRY
 
 }  // extern "C"

@@ -235,8 +235,10 @@ __device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f,
 
 // One stream's rows of a launch, walked in row order (the kernel body of both translation units).  `associate(s, cnt, f)`
 // runs steps 3 to 5 on the frame's candidates and predicted tracks and ends with a barrier.  kMotion (codetr_motion.h):
-// `motion` [N, 4] = dx, dy, valid, 0 per row, or null; a valid, finite motion is added to the predicted centres.
-template <bool kMotion = false, class T, class Assoc>
+// 1: `motion` [N, 4] = dx, dy, valid, 0 per row, or null; a valid, finite motion is added to the predicted centres.
+// 2: `motion` [N, 8] = dx, dy, valid, model, a, b, px, py per row, or null; by the model a similarity about (px, py) moves
+// the predicted centres, their velocities and the height (codetr_track_update4_*), or the translation is added as under 1.
+template <int kMotion = 0, class T, class Assoc>
 __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __restrict__ boxes,
                                              const T* __restrict__ scores, const int64_t* __restrict__ labels,
                                              const int* __restrict__ count, int N, int Q, const RowTable& tab,
@@ -283,10 +285,24 @@ __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __
     // 2. predict
     float mdx = 0.f, mdy = 0.f;
     bool moved = false;  // (uniform)
-    if constexpr (kMotion) {
+    if constexpr (kMotion == 1) {
       if (motion) {
         mdx = motion[4 * (int64_t)n], mdy = motion[4 * (int64_t)n + 1];
         moved = motion[4 * (int64_t)n + 2] == 1.0f && __builtin_isfinite(mdx) && __builtin_isfinite(mdy);
+      }
+    }
+    float ma = 1.f, mb = 0.f, mpx = 0.f, mpy = 0.f, mqx = 0.f, mqy = 0.f, ms = 1.f;
+    bool turned = false;  // (uniform)
+    if constexpr (kMotion == 2) {
+      if (motion) {
+        const float* m = motion + 8 * (int64_t)n;
+        mdx = m[0], mdy = m[1], ma = m[4], mb = m[5], mpx = m[6], mpy = m[7];
+        const bool shift = __builtin_isfinite(mdx) && __builtin_isfinite(mdy);
+        turned = m[3] == 2.0f && shift && __builtin_isfinite(ma) && __builtin_isfinite(mb) && __builtin_isfinite(mpx) &&
+                 __builtin_isfinite(mpy);
+        moved = m[3] == 1.0f && shift;
+        mqx = mpx + mdx, mqy = mpy + mdy;
+        ms = __builtin_sqrtf(ma * ma + mb * mb);  // (the correctly rounded sequence, not the bare v_sqrt_f32 of __fsqrt_rn)
       }
     }
     for (int t = tid; t < maxT; t += kThreads) {
@@ -305,8 +321,20 @@ __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __
         q[maxT] = B + C;
         q[2 * maxT] = C + sv * sv;
       }
-      if constexpr (kMotion) {
+      if constexpr (kMotion != 0) {
         if (moved) s.mean[t] = s.mean[t] + mdx, s.mean[2 * maxT + t] = s.mean[2 * maxT + t] + mdy;
+      }
+      if constexpr (kMotion == 2) {
+        if (turned) {
+          const float ux = s.mean[t] - mpx, uy = s.mean[2 * maxT + t] - mpy;
+          s.mean[t] = mqx + (ma * ux - mb * uy);
+          s.mean[2 * maxT + t] = mqy + (mb * ux + ma * uy);
+          const float vx = s.mean[maxT + t], vy = s.mean[3 * maxT + t];
+          s.mean[maxT + t] = ma * vx - mb * vy;
+          s.mean[3 * maxT + t] = mb * vx + ma * vy;
+          s.mean[6 * maxT + t] = s.mean[6 * maxT + t] * ms;
+          s.mean[7 * maxT + t] = s.mean[7 * maxT + t] * ms;
+        }
       }
       const float cx = s.mean[t], cy = s.mean[2 * maxT + t], a = s.mean[4 * maxT + t], hh = s.mean[6 * maxT + t];
       const float w = a * hh;

@@ -70,6 +70,72 @@
  *   and dx and dy are both finite.  Velocities, covariances, steps 1 and 3 to 9 and the state layout are unchanged.
  *   NULL gives codetr_track_update2_*'s ids and state bytes.
  */
+/* Version 2: the SIMILARITY model (zoom and roll as well as the pan), fitted to the same block votes; everything above is
+ * as it was, and what it says of the translation model holds for codetr_motion_estimate_u8 and codetr_track_update3_*.
+ *
+ * Limits of the similarity model: shear and perspective are not modelled; the reach is the translation rule's per block
+ * (`search` cells), which at the corners of a 160-cell thumbnail with search = 8 is roughly 5 % of zoom or 0.05 rad of roll
+ * per frame (8 cells over the 80 x 80 half-diagonal's 113 cells leave 7 %, less the pan; derived from the geometry, not
+ * measured); the tracker's boxes stay axis-aligned (a roll turns the centres, not the boxes); parity with OpenCV's
+ * estimateAffinePartial2D is unpinned.
+ *
+ * The rule.  Thumbnails, blocks, the texture test and the votes are the rule above.  All of the following is exact integer
+ * arithmetic up to the conversions and divisions of "Output".
+ * Points: block b = (bx, by) has the centre P_b = (16 (R + 16 bx + 8), 16 (R + 16 by + 8)) in sixteenths of a cell (cell i
+ *   covers [i, i + 1)), and the image Q_b = P_b + (vx_b, vy_b).  The textured blocks, in ascending b, are numbered
+ *   0 .. n - 1; i, j and m below are such numbers, g_i = (bx, by) of block i.
+ * Hypotheses: every pair i < j with |D|^2 >= 4, D = g_j - g_i ("eligible").  For it d = P_j - P_i (= 256 D),
+ *   e = Q_j - Q_i, dd = d.d, A = d.e, B = d_x e_y - d_y e_x.  Block m is an inlier of the pair iff both components of
+ *       r = A u + B u_perp - dd w,    u = P_m - P_i,  u_perp = (-u_y, u_x),  w = Q_m - Q_i
+ *   are at most 16 dd in absolute value (one cell, the translation rule's tolerance; i and j are inliers of their own pair:
+ *   dd e = A d + B d_perp, so r = 0; r / dd is the pair's similarity applied to u, less w.  The sign of the B term is
+ *   the one under which this holds: with - B u_perp, as the rule was first proposed, a pair's own j is no inlier of it
+ *   under any roll).  d and u are multiples of 256: with D, U = u / 256, A' = D.e, B' = D_x e_y - D_y e_x, dd' = D.D the
+ *   test is |A' U + B' U_perp - dd' w| <= 16 dd' per component.  Bound: block indices are 0 .. 9, |v| <= 264 per
+ *   component, so |D|, |U| <= 9, |e|, |w| <= 2304 + 528, |A'|, |B'| <= 2 * 9 * 2832 < 2^16, dd' <= 162, and every term and
+ *   sum of the reduced test is below 2 * 9 * 2^16 + 162 * 2832 < 2^21: int32 holds it (also when the test is taken as
+ *   the difference of its value at block m and at block i from a common origin, as csrc/motion.hip takes it).
+ *   The best pair has the most inliers c2; ties go to the lowest i, then the lowest j.
+ * Validity: n >= min_blocks, at least one eligible pair, c2 >= min_blocks, 2 c2 >= n, and the refit's four conditions.
+ * Refit over the best pair's inliers, int64 sums: sp = sum P, sq = sum Q, Sxx = c2 sum |P|^2 - |sp|^2,
+ *   An = c2 sum P.Q - sp.sq, Bn = c2 sum (P_x Q_y - P_y Q_x) - (sp_x sq_y - sp_y sq_x).  Required: Sxx > 0, 2 An >= Sxx,
+ *   An <= 2 Sxx, 2 |Bn| <= Sxx (the scale stays inside [0.5, 2]).
+ * Output of a similarity row: [dx, dy, 1, 2, a, b, px, py].  Every integer operand is converted to fp32 once (round to
+ *   nearest even), each output is one IEEE fp32 division:
+ *     a = (float)An / (float)Sxx, b = (float)Bn / (float)Sxx,
+ *     px = (float)(sp_x k) / (float)(16 c2), py likewise: the inliers' centroid in source pixels,
+ *     dx = (float)((sq_x - sp_x) k) / (float)(16 c2), dy likewise: their mean displacement.
+ *   Meaning: scene content at p in the previous frame appears at (px + dx, py + dy) + M (p - (px, py)) in this frame,
+ *   M = [[a, -b], [b, a]].
+ * Fallback: a row whose similarity is not valid holds the translation rule's result over all textured blocks:
+ *   [dx, dy, 1, 1, 1, 0, 0, 0] with codetr_motion_estimate_u8's dx and dy (bit-equal) where that is valid, eight zeros
+ *   otherwise.  The fourth float is the row's model: 2, 1 or 0.
+ *
+ * codetr_motion_estimate2_u8: codetr_motion_estimate_u8's arguments, checks and state (a stream may switch between the
+ *   two from call to call), except
+ *     work_dev, work_bytes  codetr_motion_work2_bytes(N) bytes, 4-byte aligned
+ *     motion_out_dev        [N, 8] float32 as above
+ *     diag_out_dev          [N, 8] int32: k, nbx * nby, textured n, the translation rule's agreeing c (as above), eligible
+ *                           pairs, the best pair's inliers c2 (0 without an eligible pair), its i, its j (-1 without one).
+ *                           The last four are of the search alone: min_blocks and the refit have no say in them.
+ *   Five launches on `stream`, no host synchronisation: the three above (the third writes its row into the scratch, and
+ *   the states), motion_sim_pairs_kernel (a row's pairs over the lanes of several workgroups, the votes in LDS; the best pair of
+ *   each workgroup is one packed 64-bit maximum: count, ~i, ~j) and motion_sim_fit_kernel (one workgroup per row: the best of
+ *   the workgroups' pairs, its inliers, the refit and the row).
+ *
+ * codetr_track_update4_{f16,bf16,f32}: codetr_track_update3_* with motion_dev [N, 8] float32 as motion_out_dev of
+ *   codetr_motion_estimate2_u8, or NULL.  In step 2 of "Tracking", after m[0] = m[0] + m[maxT] of a live track and before
+ *   its predicted box, by the row's model float:
+ *     2.0f and a, b, px, py, dx, dy all finite -- fp32, one rounding per operation in the order written, no contraction:
+ *       ux = cx - px; uy = cy - py;
+ *       cx = (px + dx) + (a * ux - b * uy); cy = (py + dy) + (b * ux + a * uy);
+ *       the velocities of cx and cy: (vx, vy) = (a * vx - b * vy, b * vx + a * vy);
+ *       s = sqrt(a * a + b * b), correctly rounded; h = h * s; the velocity of h is multiplied by s too.
+ *       The aspect ratio and all covariances stay.  (BoT-SORT transforms the covariance as well: this library's deviation.)
+ *     1.0f and dx, dy finite -- codetr_track_update3_*'s two additions.
+ *     anything else -- nothing is applied.
+ *   NULL gives codetr_track_update2_*'s ids and state bytes.
+ */
 #ifndef CODETR_MOTION_H_
 #define CODETR_MOTION_H_
 
@@ -81,7 +147,7 @@
 extern "C" {
 #endif
 
-#define CODETR_MOTION_ABI_VERSION 1
+#define CODETR_MOTION_ABI_VERSION 2
 #define CODETR_MOTION_GRID_MIN 32
 #define CODETR_MOTION_GRID_MAX 160
 #define CODETR_MOTION_BLOCK 16
@@ -106,6 +172,27 @@ int codetr_track_update3_bf16(void *stream, const void *boxes_dev, const void *s
                               int64_t tentatives, int weight_iou, int *track_id_out_dev, int association,
                               const float *motion_dev);
 int codetr_track_update3_f32(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                             const int *count_dev, int64_t N, int64_t Q, const int *stream_of_row_host, int64_t S,
+                             void *state_dev, int64_t max_tracks, const float *settings_host, int64_t retain,
+                             int64_t tentatives, int weight_iou, int *track_id_out_dev, int association,
+                             const float *motion_dev);
+
+/* version 2 */
+int64_t codetr_motion_work2_bytes(int64_t N);
+int codetr_motion_estimate2_u8(void *stream, const void *src_dev, int64_t src_bytes, int64_t N, const int64_t *rows_host,
+                               const int *stream_of_row_host, int64_t S, void *state_dev, const int *settings_host,
+                               void *work_dev, int64_t work_bytes, float *motion_out_dev, int *diag_out_dev);
+int codetr_track_update4_f16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                             const int *count_dev, int64_t N, int64_t Q, const int *stream_of_row_host, int64_t S,
+                             void *state_dev, int64_t max_tracks, const float *settings_host, int64_t retain,
+                             int64_t tentatives, int weight_iou, int *track_id_out_dev, int association,
+                             const float *motion_dev);
+int codetr_track_update4_bf16(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
+                              const int *count_dev, int64_t N, int64_t Q, const int *stream_of_row_host, int64_t S,
+                              void *state_dev, int64_t max_tracks, const float *settings_host, int64_t retain,
+                              int64_t tentatives, int weight_iou, int *track_id_out_dev, int association,
+                              const float *motion_dev);
+int codetr_track_update4_f32(void *stream, const void *boxes_dev, const void *scores_dev, const int64_t *labels_dev,
                              const int *count_dev, int64_t N, int64_t Q, const int *stream_of_row_host, int64_t S,
                              void *state_dev, int64_t max_tracks, const float *settings_host, int64_t retain,
                              int64_t tentatives, int weight_iou, int *track_id_out_dev, int association,

@@ -62,6 +62,9 @@ through tests/track_ref.py frame by frame, the state on the host), the three in 
 launches alone on 8 frames of 1920x1080 beside a device-to-device copy of the same bytes (HIP event pairs, median of 200);
 track_update on the two `--track` workloads with and without a motion operand, alternating; and images/s of the tracked
 Inferencer at batch_size 8 over 16 panned 1920x1080 frames as one stream, with and without `track_motion`, in turn.
+`--track --motion similarity` adds the similarity model beside each of them: the estimate's five launches (their excess
+over the three is the fit), the same on 8 frames of 320x320 with all 81 blocks textured, track_update with [N, 8] rows,
+and the Inferencer with `track_motion="similarity"`.
 
 `--decode jpeg` prints only a `decode` record (JPEG files as input, fp16): --images frames of 1920x1080 (the gradient
 with noise of `--vis`) written as 4:2:0 files by Pillow where it imports (no restart markers), else by encode_jpeg; the
@@ -73,6 +76,7 @@ the host parser per file, Pillow's decode per frame; and images/s of the Inferen
     python tools/bench_inferencer.py --frames nv12 --resident
     python tools/bench_inferencer.py --track
     python tools/bench_inferencer.py --track --motion
+    python tools/bench_inferencer.py --track --motion similarity
 """
 import argparse
 import csv
@@ -878,11 +882,14 @@ def track_record(inf, images, repeats, bs=8):
     return rec
 
 
-def motion_record(inf, repeats, bs=8, frames=16):
+def motion_record(inf, repeats, bs=8, frames=16, model="translation"):
     """camera-motion compensation (`--track --motion`): estimate_motion alone on 8 frames of 1920 x 1080 beside a
     device-to-device copy of the same bytes (HIP events, 200 launches); track_update on the --track workloads with and
     without a motion operand, alternating; the tracked Inferencer on panned 1920 x 1080 frames as one stream with and
-    without track_motion, the two in turn, three times"""
+    without track_motion, the two in turn, three times.  model="similarity" (`--motion similarity`): the estimate's
+    five-launch form beside the three-launch one (the difference is the two launches of the fit), the five-launch form on
+    8 frames of 320 x 320 with all 81 blocks textured (the largest search there is), track_update with [N, 8] against
+    [N, 4] rows, and a third Inferencer arm"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))
     import motion_cases
     from codetr import hip_ops
@@ -909,27 +916,51 @@ def motion_record(inf, repeats, bs=8, frames=16):
     rec["estimate"] = {"bytes": buf.numel(), "motion": motion.cpu().tolist(), "diag": diag.cpu().tolist(),
                        "true_pans": [[shifts[i][0] - shifts[i - 1][0], shifts[i][1] - shifts[i - 1][1]] for i in range(1, 8)],
                        "us_per_call_median": [], "copy_us_median": []}
-    for _ in range(3):                                                        # the two in turn
+    sim = model == "similarity"
+    if sim:
+        motion8, diag8 = hip_ops.estimate_motion(buf, rows, state, model="similarity")
+        rec["estimate"].update({"similarity_motion": motion8.cpu().tolist(), "similarity_diag": diag8.cpu().tolist(),
+                                "similarity_us_per_call_median": [], "similarity_81_blocks_us_median": [],
+                                "translation_81_blocks_us_median": []})
+        fine = motion_cases.texture(5, 320 + 2 * margin, 320 + 2 * margin, 12)   # (fine enough that every block is textured)
+        small = [motion_cases.view(fine, (320, 320), (s[0] // 8, s[1] // 8), margin) for s in shifts[:8]]
+        buf81 = torch.from_numpy(np.concatenate([im.reshape(-1) for im in small])).to(DEV)
+        rows81 = [(i * 320 * 320 * 3, 320, 320) for i in range(8)]
+        state81 = hip_ops.new_motion_state(1, DEV)
+        rec["estimate"]["diag_81_blocks"] = hip_ops.estimate_motion(buf81, rows81, state81, model="similarity")[1].cpu().tolist()
+    for _ in range(3):                                                        # in turn
         rec["estimate"]["us_per_call_median"].append(_event_us_each(lambda: hip_ops.estimate_motion(buf, rows, state)))
+        if sim:
+            rec["estimate"]["similarity_us_per_call_median"].append(
+                _event_us_each(lambda: hip_ops.estimate_motion(buf, rows, state, model="similarity")))
+            rec["estimate"]["similarity_81_blocks_us_median"].append(
+                _event_us_each(lambda: hip_ops.estimate_motion(buf81, rows81, state81, model="similarity")))
+            rec["estimate"]["translation_81_blocks_us_median"].append(
+                _event_us_each(lambda: hip_ops.estimate_motion(buf81, rows81, state81)))
         rec["estimate"]["copy_us_median"].append(_event_us_each(lambda: dst.copy_(buf)))
 
     dets = track_detections(8, 300, 100)
     moved = torch.tensor([[3.5, -2.25, 1.0, 0.0]] * 8, dtype=torch.float32, device=DEV)
+    turned = torch.tensor([[3.5, -2.25, 1.0, 2.0, 1.0, 0.0, 960.0, 540.0]] * 8, dtype=torch.float32, device=DEV)
+    operands = [("without_motion_us", None), ("with_motion_us", moved)] + ([("with_similarity_us", turned)] if sim else [])
     rec["track_update"] = {}
     for name, streams in (("8_frames_of_1_stream", [0] * 8), ("1_frame_of_8_streams", list(range(8)))):
-        rec["track_update"][name] = {"without_motion_us": [], "with_motion_us": []}
+        rec["track_update"][name] = {key: [] for key, _ in operands}
         states = {}
-        for key in ("without_motion_us", "with_motion_us"):
+        for key, _ in operands:
             states[key] = hip_ops.new_track_state(8, hip_ops.TRACKER["max_tracks"], DEV)
             for _ in range(1 if name[0] == "8" else 8):
                 hip_ops.track_update(dets, states[key], streams)
         for _ in range(3):
-            for key, m in (("without_motion_us", None), ("with_motion_us", moved)):
+            for key, m in operands:
                 rec["track_update"][name][key].append(
                     _event_us_each(lambda: hip_ops.track_update(dets, states[key], streams, motion=m), launches=100, warmup=5))
 
     arms = {"tracker": Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={}),
             "tracker_and_motion": Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={}, track_motion="translation")}
+    if sim:
+        arms["tracker_and_similarity"] = Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={},
+                                                    track_motion="similarity")
     for name in arms:
         rec[name] = {"pass_s": []}
     with torch.no_grad():
@@ -1037,7 +1068,9 @@ def main():
     ap.add_argument("--frames", choices=("nv12", "i420", "bgr"), help="only the frames record, for frames of this format")
     ap.add_argument("--resident", action="store_true", help="with --frames: also feed the frames as GPU-resident tensors")
     ap.add_argument("--track", action="store_true", help="only the tracking record: the images as one stream")
-    ap.add_argument("--motion", action="store_true", help="with --track: only the camera-motion record (track_motion)")
+    ap.add_argument("--motion", nargs="?", const="translation", choices=("translation", "similarity"),
+                    help="with --track: only the camera-motion record (track_motion); similarity: with the similarity "
+                         "model's arms beside the translation's")
     ap.add_argument("--decode", choices=("jpeg",), help="only the record of JPEG files as input, decoded on the GPU")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -1063,7 +1096,7 @@ def main():
     if a.track and a.motion:
         print(json.dumps({"metric": "Inferencer tracking with camera-motion compensation (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the kernels",
-                          "track_motion": motion_record(infs["fp16"], a.repeats)}))
+                          "track_motion": motion_record(infs["fp16"], a.repeats, model=a.motion)}))
         return
     if a.track:
         print(json.dumps({"metric": "Inferencer tracking (Swin-L config, random weights)",
