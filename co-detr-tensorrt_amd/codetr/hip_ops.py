@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _assign, _cabi, _jpeg, _jpeg_dec, _motion, _wbf
+from . import _appearance, _assign, _cabi, _jpeg, _jpeg_dec, _motion, _wbf
 
 # ops served by hand-written HIP kernels in this build (kept in sync with include/codetr_hip.h)
 NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_window_attention(f16, head_dim 32)",
@@ -1394,8 +1394,88 @@ def track_state_to_host(state):
 
 TRACK_ASSOCIATIONS = tuple(_assign.ASSOCIATIONS)   # "greedy" (the default, codetr_hip.h's rule) and "optimal"
 
+# the appearance cue (include/codetr_appearance.h states the rule, these settings' ranges and the cue's limits).  The two
+# thresholds are BoT-SORT's appearance_thresh (0.25, as a distance) and proximity_thresh as recalled (unpinned: BoT-SORT
+# is not installed here); reid_gate is this library's own
+APPEARANCE = dict(appearance_thr=0.75, proximity_thr=0.5, reid_gate=1.5)
+APPEARANCE_BINS = _appearance.BINS
 
-def track_update(dets, state, streams=None, settings=None, association="greedy", motion=None):
+
+def appearance_settings(d=None):
+    """the settings of the appearance cue, validated and completed from APPEARANCE -> a new dict.  ValueError for an
+    unknown key or a value that is not a finite number of its range: the thresholds in [0, 1], reid_gate >= 0."""
+    out = dict(APPEARANCE)
+    d = dict(d or {})
+    unknown = set(d) - set(out)
+    if unknown:
+        raise ValueError(f"appearance: unknown key(s) {sorted(unknown)}; known: {sorted(out)}")
+    for key, hi in (("appearance_thr", 1.0), ("proximity_thr", 1.0), ("reid_gate", math.inf)):
+        v = d.get(key, out[key])
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not math.isfinite(v) or \
+                not 0 <= v <= hi:
+            raise ValueError(f"appearance {key} must be a finite number in [0, {hi}], got {v!r}")
+        out[key] = float(v)
+    return out
+
+
+_appearance_settings = appearance_settings   # (track_update has an argument of that name)
+
+
+def appearance_descriptors(src_u8, rows, dets):
+    """The colour descriptor of every detection in one launch per PREPROCESS_BATCH_MAX rows and without a synchronisation
+    (csrc/appearance.hip; include/codetr_appearance.h states the rule: 16 x 32 samples over the inner three quarters of
+    the box, two stripes of 64 two-bit RGB bins).
+      src_u8  one flat uint8 device buffer holding RGB HWC images (Inferencer.upload's)
+      rows    (offset, H, W) per image, one per row of the detections
+      dets    Detections / SoftDetections over [N, Q] rows in source pixels (boxes and count are read)
+    -> [N, Q, 128] int16 on the device (the header's uint16 bits: a value is at most 256); zeros for a row beyond count,
+    with a non-finite coordinate or without area."""
+    _gpu(src_u8, "appearance_descriptors")
+    if src_u8.dtype != torch.uint8 or src_u8.dim() != 1 or not src_u8.is_contiguous():
+        raise ValueError("appearance_descriptors: expected one contiguous flat uint8 buffer")
+    boxes = dets.boxes
+    if not torch.is_tensor(boxes) or boxes.dtype not in (torch.float16, torch.bfloat16, torch.float32) or \
+            boxes.dim() != 3 or boxes.shape[2] != 4 or boxes.device != src_u8.device:
+        raise ValueError("appearance_descriptors: boxes [N, Q, 4] in f16, bf16 or f32 on the images' device")
+    N, Q = boxes.shape[:2]
+    rows = [tuple(int(v) for v in r) for r in rows]
+    if len(rows) != N or tuple(dets.count.shape) != (N,):
+        raise ValueError(f"appearance_descriptors: one image row and one count per detection row ({N})")
+    for off, H, W in rows:
+        if not (1 <= H <= _cabi.FRAME_MAX_SIDE and 1 <= W <= _cabi.FRAME_MAX_SIDE) or off < 0 or off + H * W * 3 > src_u8.numel():
+            raise ValueError(f"appearance_descriptors: image (offset {off}, {H}x{W}) outside the buffer or larger than "
+                             f"{_cabi.FRAME_MAX_SIDE} a side")
+    if Q > _cabi.POSTPROCESS_MAX_Q:
+        raise ValueError(f"appearance_descriptors: at most {_cabi.POSTPROCESS_MAX_Q} detection rows per frame, got {Q}")
+    desc = torch.empty((N, Q, _appearance.BINS), dtype=torch.int16, device=src_u8.device)
+    if N == 0 or Q == 0:
+        return desc
+    boxes, count = boxes.contiguous(), dets.count.contiguous()
+    with torch.cuda.device(src_u8.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            _appearance.describe(src_u8, rows[i:j], boxes[i:j], count[i:j], desc[i:j])
+    return desc
+
+
+def new_appearance_state(S, max_tracks, device):
+    """the appearance states of S fresh streams of max_tracks slots each: zeros [S, max_tracks, 128] int16 on `device`
+    (the header's uint16 in sixteenths; appearance_state_to_host decodes it)"""
+    if int(S) < 1:
+        raise ValueError(f"new_appearance_state: at least one stream, got {S}")
+    if not 1 <= int(max_tracks) <= TRACK_MAX_TRACKS:
+        raise ValueError(f"new_appearance_state: max_tracks in 1..{TRACK_MAX_TRACKS}, got {max_tracks}")
+    return torch.zeros((int(S), int(max_tracks), _appearance.BINS), dtype=torch.int16, device=device)
+
+
+def appearance_state_to_host(state):
+    """the states of new_appearance_state / track_update on the host (one device-to-host copy) -> [S, T, 128] numpy
+    uint16"""
+    return state.cpu().numpy().view(np.uint16).copy()
+
+
+def track_update(dets, state, streams=None, settings=None, association="greedy", motion=None, appearance=None,
+                 appearance_state=None, appearance_settings=None):
     """Tracking-by-detection for the frames of a chunk in one launch per PREPROCESS_BATCH_MAX rows (csrc/track.hip; the
     rule, modelled on mmdet's ByteTracker, is stated in include/codetr_hip.h): the three greedy associations, the Kalman
     filters, retirement and track starts of every stream on the device.
@@ -1412,6 +1492,13 @@ def track_update(dets, state, streams=None, settings=None, association="greedy",
                 (codetr_track_update3_*, include/codetr_motion.h).  None calls exactly the entry points it always did.
                 Or estimate_motion(model="similarity")'s [N, 8] float32: by the row's model the similarity moves the
                 predicted centres, their velocities and the height, or the translation is added (codetr_track_update4_*)
+      appearance  None, or appearance_descriptors' [N, Q, 128] int16 of these detections: the first two associations add
+                the colour similarity of track and candidate to the pair value, and a lost track inside the gate can match
+                on it alone (codetr_track_update5_*, include/codetr_appearance.h).  A [N, 4] motion is widened on the
+                device to [N, 8] with model = valid.  None calls exactly the entry points it always did.
+      appearance_state     new_appearance_state's tensor for the same streams and max_tracks, updated in place; given
+                exactly when `appearance` is
+      appearance_settings  the keys of APPEARANCE (appearance_settings)
     -> [N, Q] int32 on the device: the id of the track each row updated or started, negated while the track is
     tentative, 0 for no track and beyond count."""
     cfg = track_settings(settings)
@@ -1434,6 +1521,25 @@ def track_update(dets, state, streams=None, settings=None, association="greedy",
                 tuple(motion.shape) not in ((N, 4), (N, 8)) or motion.device != scores.device:
             raise ValueError("track_update: motion must be a [N, 4] or [N, 8] float32 tensor on the detections' device")
         motion = motion.contiguous()
+    if (appearance is None) != (appearance_state is None):
+        raise ValueError("track_update: appearance and appearance_state go together (appearance_descriptors, "
+                         "new_appearance_state)")
+    app_cfg = None
+    if appearance is not None:
+        app_cfg = _appearance_settings(appearance_settings)
+        if not torch.is_tensor(appearance) or appearance.dtype != torch.int16 or \
+                tuple(appearance.shape) != (N, Q, _appearance.BINS) or appearance.device != scores.device:
+            raise ValueError(f"track_update: appearance must be a [N, Q, {_appearance.BINS}] int16 tensor on the "
+                             "detections' device (appearance_descriptors)")
+        if not torch.is_tensor(appearance_state) or appearance_state.dtype != torch.int16 or \
+                appearance_state.dim() != 3 or not appearance_state.is_contiguous() or \
+                appearance_state.device != scores.device or \
+                tuple(appearance_state.shape) != (state.shape[0], T, _appearance.BINS):
+            raise ValueError(f"track_update: appearance_state must be a contiguous [{state.shape[0]}, {T}, "
+                             f"{_appearance.BINS}] int16 tensor on the detections' device (new_appearance_state)")
+        appearance = appearance.contiguous()
+        if motion is not None and motion.shape[1] == 4:   # model = valid: 1.0 adds the translation, 0.0 nothing
+            motion = torch.cat([motion[:, :3], motion[:, 2:3], torch.zeros_like(motion)], dim=1).contiguous()
     streams = track_streams(streams, N)
     if any(v >= state.shape[0] for v in streams):
         raise ValueError(f"track_update: a stream index outside the state's {state.shape[0]} streams")
@@ -1448,11 +1554,18 @@ def track_update(dets, state, streams=None, settings=None, association="greedy",
     thr = (cfg["obj_score_thrs"]["high"], cfg["obj_score_thrs"]["low"], cfg["init_track_thr"],
            cfg["match_iou_thrs"]["high"], cfg["match_iou_thrs"]["low"], cfg["match_iou_thrs"]["tentative"])
     with torch.cuda.device(scores.device):
+        work = None
+        if appearance is not None:
+            work = torch.empty((_appearance.work_bytes(state.shape[0], T, Q),), dtype=torch.uint8, device=scores.device)
         for i in range(0, N, PREPROCESS_BATCH_MAX):
             j = min(N, i + PREPROCESS_BATCH_MAX)
             args = (boxes[i:j], scores[i:j], labels[i:j], count[i:j], streams[i:j], state, T, thr,
                     cfg["num_frames_retain"], cfg["num_tentatives"], cfg["weight_iou_with_det_scores"], ids[i:j])
-            if motion is not None and motion.shape[1] == 8:
+            if appearance is not None:
+                _appearance.track_update5(*args, _assign.ASSOCIATIONS[association], None if motion is None else motion[i:j],
+                                          appearance[i:j], appearance_state,
+                                          (app_cfg["appearance_thr"], app_cfg["proximity_thr"], app_cfg["reid_gate"]), work)
+            elif motion is not None and motion.shape[1] == 8:
                 _motion.track_update4(*args, _assign.ASSOCIATIONS[association], motion[i:j])
             elif motion is not None:
                 _motion.track_update3(*args, _assign.ASSOCIATIONS[association], motion[i:j])

@@ -145,6 +145,15 @@ falls back to its translation, so the mode is never worse than ``"translation"``
 a similarity: the inliers' mean displacement), and every result dict also gains ``"camera_transform"``: the 2 x 3 matrix
 ``[[a, -b, tx], [b, a, ty]]`` that maps a point of the stream's previous frame to this one (``[[1, 0, dx], [0, 1, dy]]``
 for a translation), or ``None``.  Shear and perspective are not modelled and the boxes stay axis-aligned.
+
+``track_appearance`` (with a tracker only): ``None``, the default, means no launch and no change.  ``"color"`` or
+``dict(type="color", appearance_thr=0.75, proximity_thr=0.5, reid_gate=1.5)`` adds an appearance cue to the first two
+associations: per chunk, after the chunk's final detections and before the drawing launch writes into the RGB buffer, one
+``hip_ops.appearance_descriptors`` launch (``csrc/appearance.hip``) gathers a colour histogram of every detection from the
+chunk's own images, and ``codetr_track_update5_*`` adds its similarity with the track's kept appearance to the pair value:
+an object that re-enters away from its prediction keeps its id, and two objects that change lanes behind an occluder do
+not swap theirs.  It works with every ``input_format``, ``track_association`` and ``track_motion``; predictions gain no
+key.  ``include/codetr_appearance.h`` states the rule and its limits: hard 2-bit colour bins, two stripes, nothing learned.
 """
 import collections
 import colorsys
@@ -553,6 +562,22 @@ def track_motion_settings(track_motion, tracker):
     return hip_ops.motion_settings({k: v for k, v in track_motion.items() if k != "type"})
 
 
+def track_appearance_settings(track_appearance, tracker):
+    """How `Inferencer(..., track_appearance=...)` reads its argument: None -> None; "color" -> hip_ops.APPEARANCE; a dict
+    with type="color" and keys of hip_ops.APPEARANCE is validated and completed from it (hip_ops.appearance_settings);
+    ValueError for anything else, and for a setting given without a tracker"""
+    if track_appearance is None:
+        return None
+    if isinstance(track_appearance, str):
+        track_appearance = dict(type=track_appearance)
+    if not isinstance(track_appearance, dict) or track_appearance.get("type") != "color":
+        raise ValueError('track_appearance must be None, "color" or a dict with type="color" and keys of '
+                         f"{sorted(hip_ops.APPEARANCE)}, got {track_appearance!r}")
+    if tracker is None:
+        raise ValueError("track_appearance without a tracker: Inferencer(..., tracker=dict(...)) turns tracking on")
+    return hip_ops.appearance_settings({k: v for k, v in track_appearance.items() if k != "type"})
+
+
 def vis_format_settings(vis_format):
     """How `Inferencer(..., vis_format=...)` reads its argument: None and "png" -> None (vis/%08d.png through zlib, as
     before); "jpeg" or a dict with keys of VIS_FORMAT_KEYS, type "jpeg" -> dict(quality, subsampling), the validated
@@ -595,7 +620,7 @@ class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
                  slicing=None, tracker=None, vis_format=None,
-                 track_association=None, ensemble=None, track_motion=None):
+                 track_association=None, ensemble=None, track_motion=None, track_appearance=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -655,6 +680,8 @@ class Inferencer:
         self._motion_state = None  # [rows, 16 + 160 * 160] uint8: every stream's last thumbnail, on the device
         self._chunk_streams = None   # the streams of the chunk __call__ is staging (a tracked call with track_motion)
         self._chunk_motion = None    # its [N, 4] motion on the device: _stage_call_chunk -> track_chunk
+        self.track_appearance = track_appearance_settings(track_appearance, self.tracker)
+        self._appearance_state = None   # [rows, max_tracks, 128] int16: every track's appearance, on the device
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -1141,11 +1168,12 @@ class Inferencer:
     # ---- tracking ---------------------------------------------------------------------------------------------
     def reset_tracks(self, stream=None):
         """forget the tracks of one stream, or of all (None): its state is zeroed, ids start at 1 again; with
-        track_motion its last thumbnail goes too (the stream's next frame has no motion)"""
+        track_motion its last thumbnail goes too (the stream's next frame has no motion), with track_appearance the
+        appearances of its tracks"""
         if stream is None:
-            self._track_state, self._track_rows, self._motion_state = None, {}, None
+            self._track_state, self._track_rows, self._motion_state, self._appearance_state = None, {}, None, None
         elif hip_ops.track_streams(stream, 1)[0] in self._track_rows:
-            for state in (self._track_state, self._motion_state):
+            for state in (self._track_state, self._motion_state, self._appearance_state):
                 if state is not None and self._track_rows[int(stream)] < state.shape[0]:
                     state[self._track_rows[int(stream)]].zero_()
 
@@ -1177,19 +1205,30 @@ class Inferencer:
                                                             self.track_motion, model=self.track_motion_model)
         return src, staged, tail
 
-    def track_chunk(self, dets, streams):
+    def track_chunk(self, dets, streams, src=None, src_rows=None):
         """the track ids of a chunk's final detections: one hip_ops.track_update launch on the states kept on the device
         and one device-to-host copy -> [N, Q] int32 numpy.  A stream's state is created on its first frame.  With
         track_motion the chunk's motion (_stage_call_chunk) feeds the launch and its copy follows the ids':
-        -> (ids, [N, 4] float32 numpy, or [N, 8] under "similarity")."""
+        -> (ids, [N, 4] float32 numpy, or [N, 8] under "similarity").  With track_appearance one
+        hip_ops.appearance_descriptors launch on the chunk's RGB buffer `src` (images `src_rows`: still undrawn) goes in
+        front, and the tracking launch takes the descriptors and the streams' appearance states."""
         dev = dets.scores.device
         T = self.tracker["max_tracks"]
         self._track_state = self._stream_state(self._track_state, lambda n: hip_ops.new_track_state(n, T, dev), streams, dev)
         rows = [self._track_rows[s] for s in streams]
+        app = {}
+        if self.track_appearance is not None:
+            self._appearance_state = self._stream_state(self._appearance_state,
+                                                        lambda n: hip_ops.new_appearance_state(n, T, dev), streams, dev)
+            if self._appearance_state.shape[0] != self._track_state.shape[0]:   # (the two grow together)
+                raise RuntimeError("the appearance states and the track states hold different numbers of streams")
+            app = dict(appearance=hip_ops.appearance_descriptors(src, src_rows, dets),
+                       appearance_state=self._appearance_state, appearance_settings=self.track_appearance)
         if self.track_motion is None:
-            return hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association).cpu().numpy()
+            return hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association,
+                                        **app).cpu().numpy()
         ids = hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association,
-                                   motion=self._chunk_motion)
+                                   motion=self._chunk_motion, **app)
         return ids.cpu().numpy(), self._chunk_motion.cpu().numpy()
 
     # ---- visualisation and files --------------------------------------------------------------------------
@@ -1286,7 +1325,7 @@ class Inferencer:
                 if frames["format"] == "jpeg":   # (the detections are on the host: the status words cost no wait)
                     self.check_jpeg_status()
                 if self.tracker is not None:   # the ids of the rows the predictions kept (a host-side cut included)
-                    ids = self.track_chunk(dets, streams[start:start + batch_size])
+                    ids = self.track_chunk(dets, streams[start:start + batch_size], src, rows)
                     if self.track_motion is not None:
                         ids, motion = ids
                         for pred, m in zip(preds, motion):

@@ -1,6 +1,7 @@
 // The tracker with a choice of association: codetr_track_update2_* of include/codetr_assign.h, and the same with the
 // camera motion of every row added to the predicted centres: codetr_track_update3_* of include/codetr_motion.h, or applied as a
-// similarity: codetr_track_update4_*.  The walk over a stream's
+// similarity: codetr_track_update4_*, or with the appearance cue of include/codetr_appearance.h on top of that:
+// codetr_track_update5_*.  The walk over a stream's
 // frames, the filters, retirement and starts are track_common.h's (shared with track.hip and its pinned kernel); the
 // greedy association is match_phase as it is there, the optimal one is assign_phase below, which hands the procedure of
 // assign_core.h the integer gains of the header, computed on the fly from the boxes in LDS (no T x Q matrix).
@@ -15,6 +16,7 @@
 #include "track_common.h"
 
 #include "assign_core.h"
+#include "codetr_appearance.h"
 #include "codetr_motion.h"
 
 namespace {
@@ -28,9 +30,11 @@ __host__ __device__ inline int64_t lds2_bytes_of(int64_t T, int64_t Q) {
 }
 
 // one optimal association (steps 3 to 5 of the rule under CODETR_ASSOCIATION_OPTIMAL); kind and cls as match_phase.
-// Ends with a barrier.
+// Ends with a barrier.  kApp (codetr_appearance.h): `add` [T][pitch], the stream's appearance addends.
+template <bool kApp = false>
 __device__ __forceinline__ void assign_phase(const Lds& s, const AssignLds& a, int T, int cnt, int f, int kind, int cls,
-                                             bool weighted, float thr, int tid) {
+                                             bool weighted, float thr, int tid, const float* add = nullptr,
+                                             int pitch = 0) {
   const int lane = tid & 63, wave = tid >> 6;
   int R = 0;  // rows: the phase's tracks with at least one eligible pair, in ascending slot order
 #pragma unroll
@@ -48,7 +52,8 @@ __device__ __forceinline__ void assign_phase(const Lds& s, const AssignLds& a, i
       need &= need - 1;
       float v;
       int j;
-      wave_best(s, wave * 64 + l + k * kThreads, cnt, cls, weighted, thr, -1, lane, v, j);
+      const int wt = wave * 64 + l + k * kThreads;
+      wave_best<kApp>(s, wt, cnt, cls, weighted, thr, -1, lane, v, j, kApp ? add + (int64_t)wt * pitch : nullptr);
       if (lane == l) has = j != kNone;
     }
     int tot;
@@ -65,7 +70,8 @@ __device__ __forceinline__ void assign_phase(const Lds& s, const AssignLds& a, i
     if (s.clabel[j] != s.label[t]) return 0;
     const float4 tb = s.tbox[t], cb = s.cbox[j];
     const float iou = overlap(tb, box_area(tb), cb, box_area(cb));
-    const float val = weighted ? iou * s.cscore[j] : iou;
+    float val = weighted ? iou * s.cscore[j] : iou;
+    if constexpr (kApp) val = val + add[(int64_t)t * pitch + j];
     return val >= thr ? 1 + (int)(fminf(val - thr, 2.0f) * 1048576.0f) : 0;  // (a NaN compares false)
   };
   assign_solve(a, R, M, gain_of, tid);
@@ -161,6 +167,90 @@ __global__ __launch_bounds__(kThreads) void track_update4_kernel(const T* __rest
       motion);
 }
 
+// track_update4_kernel with the appearance cue of codetr_appearance.h: `app.desc` [N, Q, 128] or null.  The first two
+// associations take the pair values with the addends track_stream's pre-pass left in `app.add`; the third is as it was.
+// With a null `app.desc` every branch below is update4's.  LDS as update2: the cue lives in global memory.
+template <class T>
+__global__ __launch_bounds__(kThreads) void track_update5_kernel(const T* __restrict__ boxes, const T* __restrict__ scores,
+                                                                 const int64_t* __restrict__ labels,
+                                                                 const int* __restrict__ count, int N, int Q, RowTable tab,
+                                                                 unsigned char* __restrict__ states, int maxT,
+                                                                 Settings cfg, int* __restrict__ ids_out, int association,
+                                                                 const float* __restrict__ motion, App app) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  const int tid = threadIdx.x;
+  const AssignLds a = assign_carve(lds_raw + lds2_offset(maxT, Q), maxT, max(maxT, Q));
+  const float* add = app.desc ? app.add + (int64_t)blockIdx.x * maxT * Q : nullptr;
+  track_stream<2, true>(
+      lds_raw, boxes, scores, labels, count, N, Q, tab, states, maxT, cfg, ids_out,
+      [&](const Lds& s, int cnt, int f) {  // 3. to 5. the three associations
+        const bool w = cfg.weight_iou != 0;
+        if (association == CODETR_ASSOCIATION_OPTIMAL) {  // (uniform)
+          if (app.desc) {
+            assign_phase<true>(s, a, maxT, cnt, f, 0, 1, w, cfg.match_high, tid, add, Q);
+            assign_phase<true>(s, a, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid, add, Q);
+          } else {
+            assign_phase(s, a, maxT, cnt, f, 0, 1, w, cfg.match_high, tid);
+            assign_phase(s, a, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid);
+          }
+          assign_phase(s, a, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
+        } else {
+          if (app.desc) {
+            match_phase<true>(s, maxT, cnt, f, 0, 1, w, cfg.match_high, tid, add, Q);
+            match_phase<true>(s, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid, add, Q);
+          } else {
+            match_phase(s, maxT, cnt, f, 0, 1, w, cfg.match_high, tid);
+            match_phase(s, maxT, cnt, f, 1, 1, w, cfg.match_tentative, tid);
+          }
+          match_phase(s, maxT, cnt, f, 2, 2, false, cfg.match_low, tid);
+        }
+      },
+      motion, app);
+}
+
+// the checks of codetr_track_update5_*'s own arguments (before any HIP call) -> 0 and `app`, or an error code
+int app_of(const uint16_t* desc, void* app_state, const float* app_settings, void* work, int64_t work_bytes, int64_t S,
+           int64_t max_tracks, int64_t Q, App& app) {
+  app = App{};
+  if (!desc) return 0;
+  if (!app_state || !app_settings || !work || ((uintptr_t)desc & 15u) || ((uintptr_t)app_state & 3u) ||
+      ((uintptr_t)work & 3u))
+    return CODETR_E_BADARG;
+  if (S <= 0 || max_tracks <= 0 || Q <= 0) return CODETR_E_BADARG;
+  if (S > 0x7fffffffLL || max_tracks > CODETR_TRACK_MAX_TRACKS || Q > CODETR_POSTPROCESS_MAX_Q) return CODETR_E_TOO_LARGE;
+  const float thr = app_settings[0], prox = app_settings[1], gate = app_settings[2];
+  if (!__builtin_isfinite(thr) || !__builtin_isfinite(prox) || !__builtin_isfinite(gate) || thr < 0.f || thr > 1.f ||
+      prox < 0.f || prox > 1.f || gate < 0.f)
+    return CODETR_E_BADARG;
+  if (work_bytes < 4 * S * max_tracks * Q) return CODETR_E_BADARG;
+  app.desc = desc, app.g = static_cast<unsigned*>(app_state), app.add = static_cast<float*>(work);
+  app.thr = thr, app.prox = prox, app.gate = gate;
+  return 0;
+}
+
+template <class T>
+int launch_track5(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count, int64_t N,
+                  int64_t Q, const int* stream_of_row, int64_t S, void* state, int64_t max_tracks, const float* settings,
+                  int64_t retain, int64_t tentatives, int weight_iou, int* ids_out, int association, const float* motion,
+                  const uint16_t* desc, void* app_state, const float* app_settings, void* work, int64_t work_bytes) {
+  if (association != CODETR_ASSOCIATION_GREEDY && association != CODETR_ASSOCIATION_OPTIMAL) return CODETR_E_BADARG;
+  App app;
+  if (const int rc = app_of(desc, app_state, app_settings, work, work_bytes, S, max_tracks, Q, app)) return rc;
+  return checked_track_launch(
+      boxes, scores, labels, count, N, Q, stream_of_row, S, state, max_tracks, settings, retain, tentatives, weight_iou,
+      ids_out, [&](const RowTable& tab, const Settings& cfg) -> hipError_t {
+        const int64_t lds = lds2_bytes_of(max_tracks, Q);
+        const int lds_max = (int)lds2_bytes_of(CODETR_TRACK_MAX_TRACKS, CODETR_POSTPROCESS_MAX_Q);
+        if (lds + kStaticLds > 64 * 1024)
+          if (const hipError_t e = allow_large_lds<track_update5_kernel<T>>(lds_max); e != hipSuccess) return e;
+        hipLaunchKernelGGL((track_update5_kernel<T>), dim3((unsigned)S), dim3(kThreads), (size_t)lds,
+                           static_cast<hipStream_t>(stream), static_cast<const T*>(boxes), static_cast<const T*>(scores),
+                           labels, count, (int)N, (int)Q, tab, static_cast<unsigned char*>(state), (int)max_tracks, cfg,
+                           ids_out, association, motion, app);
+        return hipSuccess;
+      });
+}
+
 template <class T, int kMotion = 0>
 int launch_track2(void* stream, const void* boxes, const void* scores, const int64_t* labels, const int* count, int64_t N,
                   int64_t Q, const int* stream_of_row, int64_t S, void* state, int64_t max_tracks, const float* settings,
@@ -246,5 +336,22 @@ CODETR_TRACK4_ENTRY(f16, _Float16)
 CODETR_TRACK4_ENTRY(bf16, Bf16)
 CODETR_TRACK4_ENTRY(f32, float)
 #undef CODETR_TRACK4_ENTRY
+
+#define CODETR_TRACK5_ENTRY(SUFFIX, TYPE)                                                                                  \
+  int codetr_track_update5_##SUFFIX(void* stream, const void* boxes_dev, const void* scores_dev,                           \
+                                    const int64_t* labels_dev, const int* count_dev, int64_t N, int64_t Q,                 \
+                                    const int* stream_of_row_host, int64_t S, void* state_dev, int64_t max_tracks,         \
+                                    const float* settings_host, int64_t retain, int64_t tentatives, int weight_iou,        \
+                                    int* track_id_out_dev, int association, const float* motion_dev,                       \
+                                    const uint16_t* desc_dev, void* app_state_dev, const float* app_settings_host,         \
+                                    void* work_dev, int64_t work_bytes) {                                                  \
+    return launch_track5<TYPE>(stream, boxes_dev, scores_dev, labels_dev, count_dev, N, Q, stream_of_row_host, S,          \
+                               state_dev, max_tracks, settings_host, retain, tentatives, weight_iou, track_id_out_dev,     \
+                               association, motion_dev, desc_dev, app_state_dev, app_settings_host, work_dev, work_bytes); \
+  }
+CODETR_TRACK5_ENTRY(f16, _Float16)
+CODETR_TRACK5_ENTRY(bf16, Bf16)
+CODETR_TRACK5_ENTRY(f32, float)
+#undef CODETR_TRACK5_ENTRY
 
 }  // extern "C"

@@ -118,8 +118,10 @@ __device__ __forceinline__ void take_better(float& v, int& j, float ov, int oj) 
 
 // the best free candidate of class `cls` for track t, by the whole wave (t is wave-uniform): lanes stride over the
 // candidates, then one wave arg-max.  `skip`: a candidate taken so recently that its cls byte may not be visible yet.
+// kApp (codetr_appearance.h): `add` is the track's row of appearance addends, one per candidate, added to the value.
+template <bool kApp = false>
 __device__ __forceinline__ void wave_best(const Lds& s, int t, int cnt, int cls, bool weighted, float thr, int skip,
-                                          int lane, float& best_v, int& best_j) {
+                                          int lane, float& best_v, int& best_j, const float* add = nullptr) {
   const float4 tb = s.tbox[t];
   const float ta = box_area(tb);
   const long long tl = s.label[t];
@@ -129,7 +131,8 @@ __device__ __forceinline__ void wave_best(const Lds& s, int t, int cnt, int cls,
     if (s.cls[j] != cls || j == skip || s.clabel[j] != tl) continue;
     const float4 cb = s.cbox[j];
     const float iou = overlap(tb, ta, cb, box_area(cb));
-    const float val = weighted ? iou * s.cscore[j] : iou;
+    float val = weighted ? iou * s.cscore[j] : iou;
+    if constexpr (kApp) val = val + add[j];
     if (val >= thr && (bj == kNone || val > bv)) bv = val, bj = j;  // (a NaN compares false; ascending j: ties keep the lower)
   }
 #pragma unroll
@@ -160,9 +163,10 @@ __device__ __forceinline__ int block_rank(bool flag, int* wsum, int lane, int wa
 }
 
 // one greedy association (steps 3 to 5 of the rule).  kind 0: confirmed tracks, 1: tentative tracks, 2: confirmed tracks
-// matched in the previous frame.  Ends with a barrier.
+// matched in the previous frame.  Ends with a barrier.  kApp: `add` [T][pitch], the stream's appearance addends.
+template <bool kApp = false>
 __device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f, int kind, int cls, bool weighted, float thr,
-                                            int tid) {
+                                            int tid, const float* add = nullptr, int pitch = 0) {
   const int lane = tid & 63, wave = tid >> 6;
   float bv[kOwn];
   int bj[kOwn];
@@ -182,7 +186,8 @@ __device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f,
       need &= need - 1;
       float v;
       int j;
-      wave_best(s, wave * 64 + l + k * kThreads, cnt, cls, weighted, thr, -1, lane, v, j);
+      const int wt = wave * 64 + l + k * kThreads;
+      wave_best<kApp>(s, wt, cnt, cls, weighted, thr, -1, lane, v, j, kApp ? add + (int64_t)wt * pitch : nullptr);
       if (lane == l) bv[k] = v, bj[k] = j;
     }
     any |= elig;
@@ -225,9 +230,103 @@ __device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f,
         need &= need - 1;
         float nv;
         int nj;
-        wave_best(s, wave * 64 + l + k * kThreads, cnt, cls, weighted, thr, j, lane, nv, nj);
+        const int wt = wave * 64 + l + k * kThreads;
+        wave_best<kApp>(s, wt, cnt, cls, weighted, thr, j, lane, nv, nj, kApp ? add + (int64_t)wt * pitch : nullptr);
         if (lane == l) bv[k] = nv, bj[k] = nj;
       }
+    }
+  }
+  __syncthreads();
+}
+
+// ---- the appearance cue of codetr_appearance.h (codetr_track_update5_*) ----
+struct App {
+  const unsigned short* desc = nullptr;  // [N, Q, 128] descriptors, 16-byte aligned; null: no cue
+  unsigned* g = nullptr;                 // [S][T][64] the appearance states, two uint16 per word
+  float* add = nullptr;                  // [S][T][Q] scratch: the addend of every pair
+  float thr = 0.f, prox = 0.f, gate = 0.f;
+};
+constexpr int kAppFreed = -2, kAppStarted = -3;  // s.match of a slot freed (step 7) / started by candidate j: kAppStarted - j
+
+// The addends of a frame, a wave per live track: lanes stride over the candidates and compute the gate; a gated lane then
+// walks its candidate's 128 bins against the track's, which the wave holds two per lane (read lane by lane).  Every
+// j < cnt of a live track is written: s where it is added, 0 elsewhere.  Only `high` candidates of the track's label are
+// gated: the associations look at no other pair.  Ends with a barrier.
+__device__ __forceinline__ void app_addends(const Lds& s, const App& app, int b, int n, int T, int Q, int cnt, int f,
+                                            int lane, int wave) {
+  const float gate2 = app.gate * app.gate;
+  for (int t = wave; t < T; t += kWaves) {  // (wave-uniform)
+    if (s.id[t] == 0) continue;
+    const float4 tb = s.tbox[t];
+    const float ta = box_area(tb);
+    const long long tl = s.label[t];
+    const float cx = s.mean[t], cy = s.mean[2 * T + t], a = s.mean[4 * T + t], hh = s.mean[6 * T + t];
+    const bool lost = s.tent[t] == 0 && s.last[t] != f - 1 && app.gate > 0.f;
+    const float wt = a * hh;
+    const float r2 = gate2 * (wt * wt + hh * hh);
+    const int g32 = (int)app.g[((int64_t)b * T + t) * 64 + lane];
+    float* row = app.add + ((int64_t)b * T + t) * Q;
+    for (int j0 = 0; j0 < cnt; j0 += 64) {
+      const int j = j0 + lane;
+      bool need = false;
+      if (j < cnt && s.cls[j] == 1 && s.clabel[j] == tl) {
+        const float4 cb = s.cbox[j];
+        const float iou = overlap(tb, ta, cb, box_area(cb));
+        need = iou >= app.prox;  // (a NaN compares false)
+        if (lost) {
+          const float dx = (cb.x + cb.z) * 0.5f - cx, dy = (cb.y + cb.w) * 0.5f - cy;
+          const float d2 = dx * dx + dy * dy;
+          need = need || d2 <= r2;
+        }
+      }
+      float addend = 0.f;
+      if (need) {
+        const uint4* dp = reinterpret_cast<const uint4*>(app.desc + ((int64_t)n * Q + j) * 128);
+        int I = 0;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+          const uint4 d4 = dp[q];
+          const unsigned d[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const unsigned gk = (unsigned)__builtin_amdgcn_readlane(g32, 4 * q + e);
+            I += (int)min(gk & 0xffffu, (d[e] & 0xffffu) << 4) + (int)min(gk >> 16, (d[e] >> 16) << 4);
+          }
+        }
+        const float sim = (float)I / 8192.0f;
+        addend = sim >= app.thr ? sim : 0.f;
+      }
+      if (j < cnt) row[j] = addend;
+    }
+  }
+  __syncthreads();
+}
+
+// Steps 6 to 8 of the cue, a wave per slot, two bins per lane: a track matched to a `high` candidate blends (or, all zero,
+// takes) its descriptor, a freed slot is zeroed, a started track takes its candidate's.  Ends with a barrier, which also
+// orders these stores before the next frame's reads.
+__device__ __forceinline__ void app_update(const Lds& s, const App& app, int b, int n, int T, int Q, float obj_high,
+                                           int lane, int wave) {
+  const unsigned* desc32 = reinterpret_cast<const unsigned*>(app.desc);
+  for (int t = wave; t < T; t += kWaves) {  // (wave-uniform)
+    const int m = s.match[t];
+    unsigned* gp = app.g + ((int64_t)b * T + t) * 64 + lane;
+    if (m == kAppFreed) {
+      *gp = 0u;
+    } else if (m <= kAppStarted || (m >= 0 && s.cscore[m] > obj_high)) {
+      const int j = m >= 0 ? m : kAppStarted - m;
+      const unsigned d = desc32[((int64_t)n * Q + j) * 64 + lane];
+      const unsigned dlo = ((d & 0xffffu) << 4) & 0xffffu, dhi = ((d >> 16) << 4) & 0xffffu;
+      unsigned out = dlo | (dhi << 16);
+      if (m >= 0) {
+        const unsigned g = *gp;
+        if (__ballot(g != 0u) != 0ull) {
+          const unsigned lo = (7u * (g & 0xffffu) + ((d & 0xffffu) << 4) + 4u) >> 3;
+          const unsigned hi = (7u * (g >> 16) + ((d >> 16) << 4) + 4u) >> 3;
+          out = (lo & 0xffffu) | (hi << 16);
+        }
+      }
+      *gp = out;
     }
   }
   __syncthreads();
@@ -238,13 +337,16 @@ __device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f,
 // 1: `motion` [N, 4] = dx, dy, valid, 0 per row, or null; a valid, finite motion is added to the predicted centres.
 // 2: `motion` [N, 8] = dx, dy, valid, model, a, b, px, py per row, or null; by the model a similarity about (px, py) moves
 // the predicted centres, their velocities and the height (codetr_track_update4_*), or the translation is added as under 1.
-template <int kMotion = 0, class T, class Assoc>
+// kApp (codetr_appearance.h; `app.desc` non-null): after step 2 a pre-pass writes the appearance addend of every pair the
+// first two associations can evaluate into `app.add`, and after step 8 the appearances of the stream's slots are blended,
+// zeroed or started in global memory; s.match carries what happened to a slot (kAppFreed, kAppStarted - j) to that pass.
+template <int kMotion = 0, bool kApp = false, class T, class Assoc>
 __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __restrict__ boxes,
                                              const T* __restrict__ scores, const int64_t* __restrict__ labels,
                                              const int* __restrict__ count, int N, int Q, const RowTable& tab,
                                              unsigned char* __restrict__ states, int maxT, const Settings& cfg,
                                              int* __restrict__ ids_out, Assoc associate,
-                                             const float* __restrict__ motion = nullptr) {
+                                             const float* __restrict__ motion = nullptr, const App& app = App{}) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x;
   bool have = false;
@@ -342,6 +444,9 @@ __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __
       s.tbox[t] = make_float4(cx - hw, cy - hv, cx + hw, cy + hv);
     }
     __syncthreads();
+    if constexpr (kApp) {
+      if (app.desc) app_addends(s, app, b, n, maxT, Q, cnt, f, lane, wave);  // (uniform; ends with a barrier)
+    }
 
     // 3. to 5. the three associations
     associate(s, cnt, f);
@@ -384,6 +489,7 @@ __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __
         for (int i = 0; i < 8; ++i) s.mean[i * maxT + t] = 0.f;
 #pragma unroll
         for (int i = 0; i < 12; ++i) s.cov[i * maxT + t] = 0.f;
+        if constexpr (kApp) s.match[t] = kAppFreed;
       }
     }
     __syncthreads();
@@ -422,12 +528,16 @@ __device__ __forceinline__ void track_stream(unsigned char* lds_raw, const T* __
         const int id = issued + r + 1, tent = f != 0;
         s.id[t] = id, s.hits[t] = 1, s.tent[t] = tent, s.last[t] = f, s.label[t] = s.clabel[j];
         s.out[j] = tent ? -id : id;
+        if constexpr (kApp) s.match[t] = kAppStarted - j;
       }
       nstart += tot;
     }
     issued += min(nstart, nfree);
     refused += max(nstart - nfree, 0);
     __syncthreads();
+    if constexpr (kApp) {
+      if (app.desc) app_update(s, app, b, n, maxT, Q, cfg.obj_high, lane, wave);  // (uniform; ends with a barrier)
+    }
 
     // 9. one id per candidate row, 0 beyond the count
     for (int j = tid; j < Q; j += kThreads) ids_out[(int64_t)n * Q + j] = j < cnt ? s.out[j] : 0;

@@ -66,6 +66,11 @@ Inferencer at batch_size 8 over 16 panned 1920x1080 frames as one stream, with a
 over the three is the fit), the same on 8 frames of 320x320 with all 81 blocks textured, track_update with [N, 8] rows,
 and the Inferencer with `track_motion="similarity"`.
 
+`--track --appearance` prints only a `track_appearance` record (the appearance cue, fp16): appearance_descriptors alone at
+N = 8, Q = 300 on 1920x1080 frames beside a device-to-device copy of the bytes it samples (HIP event pairs, median of 200);
+track_update on the two `--track` workloads with and without the descriptors, greedy and optimal, alternating; and images/s
+of the tracked Inferencer at batch_size 8 over 16 frames of 1920x1080 as one stream, with and without `track_appearance`.
+
 `--decode jpeg` prints only a `decode` record (JPEG files as input, fp16): --images frames of 1920x1080 (the gradient
 with noise of `--vis`) written as 4:2:0 files by Pillow where it imports (no restart markers), else by encode_jpeg; the
 decoder's five launches alone on eight of them (HIP event pairs, median), the bytes uploaded beside the bytes written,
@@ -77,6 +82,7 @@ the host parser per file, Pillow's decode per frame; and images/s of the Inferen
     python tools/bench_inferencer.py --track
     python tools/bench_inferencer.py --track --motion
     python tools/bench_inferencer.py --track --motion similarity
+    python tools/bench_inferencer.py --track --appearance
 """
 import argparse
 import csv
@@ -982,6 +988,78 @@ def motion_record(inf, repeats, bs=8, frames=16, model="translation"):
     return rec
 
 
+def appearance_record(inf, repeats, bs=8, frames=16):
+    """the appearance cue (`--track --appearance`): appearance_descriptors alone at N = 8, Q = 300 on 1920 x 1080 frames
+    beside a device-to-device copy of the bytes it reads (the sampled pixels: 512 x 3 bytes per participating row; HIP
+    events, 200 launches); track_update on the --track workload (300 rows, 100 live tracks) with and without the operand,
+    greedy and optimal, alternating; the tracked Inferencer at batch_size 8 over 16 frames of 1920 x 1080 as one stream
+    with and without track_appearance, the two in turn, three times"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import motion_cases
+    from codetr import hip_ops
+    from codetr.inferencer import Inferencer
+
+    H, W, margin = 1080, 1920, 16
+    canvas = motion_cases.texture(5, H + 2 * margin, W + 2 * margin, 48)
+    images = [motion_cases.view(canvas, (H, W), (f % 8, f % 5), margin) for f in range(frames)]
+    rec = {"frames": frames, "frame_hw": [H, W], "batch_size": bs, "dtype": "fp16"}
+
+    buf = torch.from_numpy(np.concatenate([im.reshape(-1) for im in images[:8]])).to(DEV)
+    rows = [(i * H * W * 3, H, W) for i in range(8)]
+    dets = track_detections(8, 300, 100)
+    desc = hip_ops.appearance_descriptors(buf, rows, dets)
+    participating = int((desc.view(8, 300, -1).sum(dim=2) != 0).sum())
+    read = torch.empty(participating * 512 * 3, dtype=torch.uint8, device=DEV)
+    dst = torch.empty_like(read)
+    rec["describe"] = {"rows": [8, 300], "participating_rows": participating, "bytes_read": read.numel(),
+                       "bytes_written": desc.numel() * 2, "us_per_call_median": [], "copy_us_median": []}
+    for _ in range(3):                                                        # in turn
+        rec["describe"]["us_per_call_median"].append(_event_us_each(lambda: hip_ops.appearance_descriptors(buf, rows, dets)))
+        rec["describe"]["copy_us_median"].append(_event_us_each(lambda: dst.copy_(read)))
+
+    T = hip_ops.TRACKER["max_tracks"]
+    rec["track_update"] = {}
+    for name, streams in (("8_frames_of_1_stream", [0] * 8), ("1_frame_of_8_streams", list(range(8)))):
+        rec["track_update"][name] = {}
+        for association in hip_ops.TRACK_ASSOCIATIONS:
+            arm = rec["track_update"][name][association] = {"without_appearance_us": [], "with_appearance_us": []}
+            states = {key: hip_ops.new_track_state(8, T, DEV) for key in arm}
+            astate = hip_ops.new_appearance_state(8, T, DEV)
+            kws = {"without_appearance_us": {}, "with_appearance_us": dict(appearance=desc, appearance_state=astate)}
+            for key in arm:
+                for _ in range(1 if name[0] == "8" else 8):
+                    hip_ops.track_update(dets, states[key], streams, association=association, **kws[key])
+            for _ in range(3):
+                for key in arm:
+                    arm[key].append(_event_us_each(
+                        lambda: hip_ops.track_update(dets, states[key], streams, association=association, **kws[key]),
+                        launches=100, warmup=5))
+            host = hip_ops.track_state_to_host(states["with_appearance_us"])
+            arm["live_tracks_per_stream"] = int((host.id[0] != 0).sum())
+
+    arms = {"tracker": Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={}),
+            "tracker_and_appearance": Inferencer(inf.model, bench_cfg(), dataset_meta=None, tracker={},
+                                                 track_appearance="color")}
+    for name in arms:
+        rec[name] = {"pass_s": []}
+    with torch.no_grad():
+        for name, arm in arms.items():                                        # warm-up
+            got = arm(images, device=DEV, dtype=torch.float16, batch_size=bs)["predictions"]
+            rec[name]["detections_per_image"] = round(float(np.mean([len(p["labels"]) for p in got])), 1)
+        for _ in range(3):
+            for name, arm in arms.items():
+                for _ in range(repeats):
+                    arm.reset_tracks()
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    arm(images, device=DEV, dtype=torch.float16, batch_size=bs)
+                    rec[name]["pass_s"].append(round(time.perf_counter() - t0, 4))
+    for name in arms:
+        rec[name]["images_per_s"] = round(len(images) / min(rec[name]["pass_s"]), 2)
+        rec[name]["images_per_s_median"] = round(len(images) / float(np.median(rec[name]["pass_s"])), 2)
+    return rec
+
+
 def bench_cfg():
     import bench
 
@@ -1071,6 +1149,9 @@ def main():
     ap.add_argument("--motion", nargs="?", const="translation", choices=("translation", "similarity"),
                     help="with --track: only the camera-motion record (track_motion); similarity: with the similarity "
                          "model's arms beside the translation's")
+    ap.add_argument("--appearance", action="store_true",
+                    help="with --track: only the appearance record (track_appearance): the descriptors, the tracking "
+                         "launch with and without them, the tracked Inferencer with and without the cue")
     ap.add_argument("--decode", choices=("jpeg",), help="only the record of JPEG files as input, decoded on the GPU")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -1092,6 +1173,11 @@ def main():
         print(json.dumps({"metric": "Inferencer on JPEG files (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the decoder",
                           "decode": decode_record(infs["fp16"], a.images, a.repeats)}))
+        return
+    if a.track and a.appearance:
+        print(json.dumps({"metric": "Inferencer tracking with the appearance cue (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the kernels",
+                          "track_appearance": appearance_record(infs["fp16"], a.repeats)}))
         return
     if a.track and a.motion:
         print(json.dumps({"metric": "Inferencer tracking with camera-motion compensation (Swin-L config, random weights)",
