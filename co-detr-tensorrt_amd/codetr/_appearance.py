@@ -75,14 +75,9 @@ def track_update5(boxes, scores, labels, count, streams, state, max_tracks, thre
     [S, T, 128] int16, app_settings (appearance_thr, proximity_thr, reid_gate), work uint8 of work_bytes(S, T, Q)
     -> codetr_track_update5_*"""
     _cabi.CALLS["track_update5"] += 1
-    N, Q = scores.shape
     name = "codetr_track_update5_" + _cabi._SUFFIX[scores.dtype]
-    rc = getattr(load(), name)(
-        _cabi.current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
-        (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
-        (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
-        ids_out.data_ptr(), int(association), None if motion is None else motion.data_ptr(),
-        None if desc is None else desc.data_ptr(), None if app_state is None else app_state.data_ptr(),
-        None if app_settings is None else (ctypes.c_float * 3)(*[float(v) for v in app_settings]),
-        None if work is None else work.data_ptr(), 0 if work is None else work.numel())
-    _cabi.check(rc, name)
+    _cabi._track_call(getattr(load(), name), name, boxes, scores, labels, count, streams, state, max_tracks, thresholds,
+                      retain, tentatives, weight_iou, ids_out, int(association), _cabi._ptr(motion), _cabi._ptr(desc),
+                      _cabi._ptr(app_state),
+                      None if app_settings is None else (ctypes.c_float * 3)(*[float(v) for v in app_settings]),
+                      _cabi._ptr(work), 0 if work is None else work.numel())

@@ -3,7 +3,6 @@ header of codetr_hip.h with a version of its own).  As in _jpeg.py the header is
 and the CODETR_ASSIGN_* / CODETR_ASSOCIATION_* constants are read from it with _cheader.parse, and a library that lacks
 an entry point is an ImportError.
 """
-import ctypes
 import os
 
 from . import _cabi, _cheader
@@ -62,11 +61,6 @@ def track_update2(boxes, scores, labels, count, streams, state, max_tracks, thre
                   ids_out, association):
     """_cabi.track_update's arguments + association (a value of ASSOCIATIONS) -> codetr_track_update2_*"""
     _cabi.CALLS["track_update2"] += 1
-    N, Q = scores.shape
     name = "codetr_track_update2_" + _cabi._SUFFIX[scores.dtype]
-    rc = getattr(load(), name)(
-        _cabi.current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
-        (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
-        (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
-        ids_out.data_ptr(), int(association))
-    _cabi.check(rc, name)
+    _cabi._track_call(getattr(load(), name), name, boxes, scores, labels, count, streams, state, max_tracks, thresholds,
+                      retain, tentatives, weight_iou, ids_out, int(association))

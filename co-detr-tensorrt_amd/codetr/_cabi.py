@@ -555,6 +555,23 @@ def track_state_bytes(max_tracks) -> int:
     return n
 
 
+def _ptr(tensor):
+    """the device pointer of an optional tensor operand"""
+    return None if tensor is None else tensor.data_ptr()
+
+
+def _track_call(fn, what, boxes, scores, labels, count, streams, state, max_tracks, thresholds, retain, tentatives,
+                weight_iou, ids_out, *extras):
+    """one codetr_track_update*_ entry `fn`: the arguments every form takes, marshalled here and nowhere else, then the
+    form's own (already ctypes-level values)"""
+    N, Q = scores.shape
+    rc = fn(current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
+            (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
+            (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
+            ids_out.data_ptr(), *extras)
+    check(rc, what)
+
+
 def track_update(boxes, scores, labels, count, streams, state, max_tracks, thresholds, retain, tentatives, weight_iou,
                  ids_out):
     """boxes [N,Q,4] / scores [N,Q] in one dtype, labels [N,Q] int64, count [N] int32, N <= PREPROCESS_BATCH_MAX;
@@ -562,13 +579,8 @@ def track_update(boxes, scores, labels, count, streams, state, max_tracks, thres
     (obj high, obj low, init, match high, match low, match tentative); ids_out [N,Q] int32 (include/codetr_hip.h states
     the rule)"""
     CALLS["track_update"] += 1
-    N, Q = scores.shape
-    rc = getattr(load(), _entry("codetr_track_update", scores.dtype))(
-        current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
-        (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
-        (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
-        ids_out.data_ptr())
-    check(rc, "codetr_track_update")
+    _track_call(getattr(load(), _entry("codetr_track_update", scores.dtype)), "codetr_track_update", boxes, scores, labels,
+                count, streams, state, max_tracks, thresholds, retain, tentatives, weight_iou, ids_out)
 
 
 def mask_pyramid(img_masks, shapes):

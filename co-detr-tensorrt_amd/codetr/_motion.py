@@ -87,14 +87,9 @@ def track_update3(boxes, scores, labels, count, streams, state, max_tracks, thre
     """_assign.track_update2's arguments + motion ([N, 4] float32 on the device, or None) -> codetr_track_update3_*;
     form=4: motion [N, 8] -> codetr_track_update4_*"""
     _cabi.CALLS[f"track_update{form}"] += 1
-    N, Q = scores.shape
     name = f"codetr_track_update{form}_" + _cabi._SUFFIX[scores.dtype]
-    rc = getattr(load(), name)(
-        _cabi.current_stream_ptr(scores.device), boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), count.data_ptr(), N, Q,
-        (ctypes.c_int * N)(*[int(v) for v in streams]), state.shape[0], state.data_ptr(), int(max_tracks),
-        (ctypes.c_float * 6)(*[float(v) for v in thresholds]), int(retain), int(tentatives), 1 if weight_iou else 0,
-        ids_out.data_ptr(), int(association), None if motion is None else motion.data_ptr())
-    _cabi.check(rc, name)
+    _cabi._track_call(getattr(load(), name), name, boxes, scores, labels, count, streams, state, max_tracks, thresholds,
+                      retain, tentatives, weight_iou, ids_out, int(association), _cabi._ptr(motion))
 
 
 def track_update4(*args):

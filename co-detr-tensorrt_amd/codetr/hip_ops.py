@@ -1476,16 +1476,17 @@ def appearance_state_to_host(state):
 
 def track_update(dets, state, streams=None, settings=None, association="greedy", motion=None, appearance=None,
                  appearance_state=None, appearance_settings=None):
-    """Tracking-by-detection for the frames of a chunk in one launch per PREPROCESS_BATCH_MAX rows (csrc/track.hip; the
-    rule, modelled on mmdet's ByteTracker, is stated in include/codetr_hip.h): the three greedy associations, the Kalman
-    filters, retirement and track starts of every stream on the device.
+    """Tracking-by-detection for the frames of a chunk in one launch per PREPROCESS_BATCH_MAX rows (track_kernel in
+    csrc/track.hip, one kernel text instantiated per form of the update; the rule, modelled on mmdet's ByteTracker, is
+    stated in include/codetr_hip.h): the three greedy associations, the Kalman filters, retirement and track starts of
+    every stream on the device.
       dets      Detections / SoftDetections over [N, Q] rows, Q <= 1024: whatever the chunk's last launch produced
       state     new_track_state's tensor, updated in place; it stays on the device between calls
       streams   the state index in [0, S) of every row: one int for all rows, or one per row; None: 0.  The rows of a
                 stream are its consecutive frames in row order (and from call to call)
       settings  the keys of TRACKER (track_settings); max_tracks must be the state's
       association  "greedy": the three greedy associations of codetr_hip.h; "optimal": each association is an assignment
-                problem over integer gains, solved in the same launch (csrc/track_assign.hip; the rule is stated in
+                problem over integer gains, solved in the same launch (codetr_track_update2_*; the rule is stated in
                 include/codetr_assign.h).  The state is the same: a stream may switch between calls
       motion    None, or estimate_motion's [N, 4] float32 (dx, dy, valid, 0 per row) on the detections' device: a valid,
                 finite motion is added to the predicted centres of the row's live tracks before association

@@ -125,7 +125,7 @@ are compared and ties go to the lowest slot and row.
 ``track_association`` (with a tracker only): ``None``, the default, or ``"greedy"`` keeps that rule and its launch;
 ``"optimal"`` makes each of the three associations an assignment problem over integer gains, as mmdet's ``lapjv`` call
 does, solved inside the same one launch per chunk (``include/codetr_assign.h`` states the gains, the procedure and its
-tie rule; ``csrc/track_assign.hip``).  Greedy loses an identity where two objects cross and the best single pair leaves
+tie rule; ``csrc/track_common.h``).  Greedy loses an identity where two objects cross and the best single pair leaves
 the other track nothing above the threshold; the assignment keeps both.  The states are the same for both rules.
 
 ``track_motion`` (with a tracker only): ``None``, the default, changes nothing.  ``"translation"`` or

@@ -11,7 +11,7 @@
 #include <stdint.h>
 
 #include "codetr_appearance.h"
-#include "device_prims.h"
+#include "box_prims.h"
 
 namespace {
 
@@ -20,13 +20,6 @@ constexpr int kWaves = kThreads / 64;
 constexpr int kBins = CODETR_APPEARANCE_BINS;
 static_assert(CODETR_APPEARANCE_COLS * CODETR_APPEARANCE_ROWS == 8 * 64, "eight samples per lane");
 static_assert(kBins == 2 * 64, "two counters per lane");
-
-struct Bf16 {
-  unsigned short bits;
-};
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
-__device__ __forceinline__ float to_f32(Bf16 v) { return bf16_to_f32(v.bits); }
 
 struct ImageTable {  // a kernel argument: byte offset, H, W of every image
   int64_t off[CODETR_PREPROCESS_BATCH_MAX];

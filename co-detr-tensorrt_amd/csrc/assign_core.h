@@ -1,6 +1,6 @@
 // The assignment procedure of include/codetr_assign.h as device code for one workgroup of 256 threads, written once:
-// assign.hip (codetr_assign_i32) gives it gains read from memory, track_assign.hip gains computed on the fly from the
-// boxes in LDS.  Integer arithmetic only; every loop is counted.
+// assign.hip (codetr_assign_i32) gives it gains read from memory, the tracker (track_common.h) gains computed on the fly
+// from the boxes in LDS.  Integer arithmetic only; every loop is counted.
 //
 // A thread owns the columns tid, tid + 256, .. (at most kAsgOwn): their dist and visited flags live in its registers.
 // u, v, pred and owner are in LDS (assign_lds_bytes).  A round = one relax of the thread's columns against the current

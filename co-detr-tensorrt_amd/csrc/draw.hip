@@ -22,7 +22,7 @@
 #include <string.h>
 
 #include "codetr_hip.h"
-#include "device_prims.h"
+#include "box_prims.h"
 
 // The 5x7 font, authored for this library: ASCII 32..126, 7 bytes per glyph, top row first, bit 4 = the leftmost pixel.
 // One initialiser for the kernel's __constant__ copy and for the host copy that codetr_draw_font hands out.
@@ -61,13 +61,6 @@ static_assert(kDrawMaxQ <= 65536, "the LDS lists hold uint16 indices");
 
 __constant__ unsigned char d_font[CODETR_DRAW_FONT_BYTES] = {CODETR_DRAW_FONT_ROWS};
 const unsigned char h_font[CODETR_DRAW_FONT_BYTES] = {CODETR_DRAW_FONT_ROWS};
-
-struct Bf16 {
-  unsigned short bits;
-};
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
-__device__ __forceinline__ float to_f32(Bf16 v) { return bf16_to_f32(v.bits); }
 
 struct DrawImage {
   int64_t offset;

@@ -44,20 +44,12 @@
 
 #include "codetr_hip.h"
 #include "codetr_wbf.h"
-#include "device_prims.h"
+#include "box_prims.h"
 #include "large_lds.h"
 
 namespace {
 
-// bfloat16 storage (the bf16 model's instantiations); conversions round to nearest even as ATen does, NaN stays NaN
-struct Bf16 {
-  unsigned short bits;
-};
-
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
-__device__ __forceinline__ float to_f32(Bf16 v) { return bf16_to_f32(v.bits); }
-
+// fp32 -> the element type (to_f32 and Bf16: box_prims.h); round to nearest even as ATen does, NaN stays NaN
 template <class T>
 __device__ __forceinline__ T from_f32(float v) {
   return (T)v;
@@ -521,23 +513,8 @@ __device__ __forceinline__ void zero_row(T* bo, T* so, int64_t* lo, int* io, int
 // ---- per-class greedy NMS over label segments: soft-NMS and the merge of test-time augmentation's views
 // (include/codetr_hip.h states the semantics of both) ----------------------------------------------------------------------
 
-// IoU of the picked box k and candidate j, fp32 with one rounding per operation (no contraction into an FMA: the CPU
-// reference rounds w * h before it subtracts); NaN for two zero-area boxes.  With contraction off (w * h) of the same box
-// is the same rounded product every time it is computed, so an area may be stored or computed again: run_segments'
-// kStoredArea, the one policy difference of the two kernels.
-__device__ __forceinline__ float box_area(float4 b) {
-#pragma clang fp contract(off)
-  const float w = b.z - b.x, h = b.w - b.y;
-  return w * h;
-}
-__device__ __forceinline__ float soft_overlap(float4 bk, float ak, float4 bj, float aj) {
-#pragma clang fp contract(off)
-  const float w = fmaxf(0.f, fminf(bk.z, bj.z) - fmaxf(bk.x, bj.x));
-  const float h = fmaxf(0.f, fminf(bk.w, bj.w) - fmaxf(bk.y, bj.y));
-  const float inter = w * h;
-  const float uni = ak + aj;
-  return inter / (uni - inter);
-}
+// The IoU of the picked box k and candidate j is box_prims.h's box_iou over box_area: an area may be stored or computed
+// again (run_segments' kStoredArea, the one policy difference of the two kernels).
 // intersection over the smaller area (SAHI's IOS), the same rounded intersection; NaN when the smaller area is 0
 __device__ __forceinline__ float ios_overlap(float4 bk, float ak, float4 bj, float aj) {
 #pragma clang fp contract(off)
@@ -625,7 +602,7 @@ __device__ __forceinline__ void run_segments(const unsigned short* s_seg, int S,
           const int p = a + lane + 64 * e;
           const float4 bj = s_box[p];
           const float aj = kStoredArea ? s_area[p] : box_area(bj);
-          const float ovr = (kSlice && ios) ? ios_overlap(bk, ak, bj, aj) : soft_overlap(bk, ak, bj, aj);
+          const float ovr = (kSlice && ios) ? ios_overlap(bk, ak, bj, aj) : box_iou(bk, ak, bj, aj);
           if (kHardToo && hard) {
             if (ovr > iou_thr) {
               alive &= ~(kOne << e);
@@ -1011,7 +988,7 @@ __device__ __forceinline__ void wbf_segments(const unsigned short* s_seg, int S,
         const float4 sum = s_box[p];
         const float sc = s_score[p];
         const float4 f = make_float4(sum.x / sc, sum.y / sc, sum.z / sc, sum.w / sc);
-        const float ovr = soft_overlap(f, box_area(f), bk, ak);
+        const float ovr = box_iou(f, box_area(f), bk, ak);
         if (ovr > iou_thr) {  // (a NaN overlap compares false)
           const unsigned long long key = pack_key(ovr, (unsigned)p);
           win = key > win ? key : win;

@@ -1,14 +1,17 @@
-// What the two tracking translation units share (track.hip: codetr_track_update_*, the greedy rule of codetr_hip.h;
-// track_assign.hip: codetr_track_update2_*, which adds the optimal association of codetr_assign.h): the LDS layout, the
-// pair value, the greedy association, the walk over a stream's frames with the association left to the caller, and the
-// argument checks of the launchers.
+// The tracker's device code and argument checks (track.hip holds the one kernel, its launcher and the entry points): the
+// LDS layout, the pair value, the greedy association (the rule of codetr_hip.h) and the optimal one (codetr_assign.h), the
+// appearance cue (codetr_appearance.h), the walk over a stream's frames with the association left to the caller, and the
+// argument checks of the launcher.
 // fp32 with one rounding per operation: contraction is off for everything below, divisions are IEEE.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "assign_core.h"
+#include "box_prims.h"
+#include "codetr_appearance.h"
 #include "codetr_hip.h"
-#include "device_prims.h"
+#include "codetr_motion.h"
 #include "large_lds.h"
 
 #pragma clang fp contract(off)
@@ -21,13 +24,6 @@ constexpr int kOwn = CODETR_TRACK_MAX_TRACKS / kThreads;  // tracks a thread own
 constexpr int kNone = 0x7fffffff;
 constexpr int kStaticLds = 1024;  // an upper bound of what the compiler adds for the workgroup votes (256 bytes today)
 static_assert(CODETR_TRACK_MAX_TRACKS % kThreads == 0, "a whole number of tracks per thread");
-
-struct Bf16 {
-  unsigned short bits;
-};
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(_Float16 v) { return (float)v; }
-__device__ __forceinline__ float to_f32(Bf16 v) { return bf16_to_f32(v.bits); }
 
 struct RowTable {  // a kernel argument, like prepost.hip's BatchTable: the stream of every row
   int stream[CODETR_PREPROCESS_BATCH_MAX];
@@ -98,19 +94,6 @@ __device__ __forceinline__ Lds carve(unsigned char* base, int T, int Q) {
   return s;
 }
 
-__device__ __forceinline__ float box_area(float4 b) {
-  const float w = b.z - b.x, h = b.w - b.y;
-  return w * h;
-}
-// the library's IoU (prepost.hip's soft_overlap): NaN for two zero-area boxes
-__device__ __forceinline__ float overlap(float4 bk, float ak, float4 bj, float aj) {
-  const float w = fmaxf(0.f, fminf(bk.z, bj.z) - fmaxf(bk.x, bj.x));
-  const float h = fmaxf(0.f, fminf(bk.w, bj.w) - fmaxf(bk.y, bj.y));
-  const float inter = w * h;
-  const float uni = ak + aj;
-  return inter / (uni - inter);
-}
-
 // (v, j) of the better of two bests: the higher value, ties to the lower j; j == kNone: no candidate
 __device__ __forceinline__ void take_better(float& v, int& j, float ov, int oj) {
   if (oj != kNone && (j == kNone || ov > v || (ov == v && oj < j))) v = ov, j = oj;
@@ -130,7 +113,7 @@ __device__ __forceinline__ void wave_best(const Lds& s, int t, int cnt, int cls,
   for (int j = lane; j < cnt; j += 64) {
     if (s.cls[j] != cls || j == skip || s.clabel[j] != tl) continue;
     const float4 cb = s.cbox[j];
-    const float iou = overlap(tb, ta, cb, box_area(cb));
+    const float iou = box_iou(tb, ta, cb, box_area(cb));
     float val = weighted ? iou * s.cscore[j] : iou;
     if constexpr (kApp) val = val + add[j];
     if (val >= thr && (bj == kNone || val > bv)) bv = val, bj = j;  // (a NaN compares false; ascending j: ties keep the lower)
@@ -239,6 +222,75 @@ __device__ __forceinline__ void match_phase(const Lds& s, int T, int cnt, int f,
   __syncthreads();
 }
 
+// ---- the optimal association of codetr_assign.h: the procedure of assign_core.h over the integer gains of the header,
+// computed on the fly from the boxes in LDS (no T x Q matrix).  The solver's LDS (8 T + 12 max(T, Q) + 96 bytes) lies
+// behind the tracker's: 114 KB together at T = 512, Q = 1024. ----
+static_assert(CODETR_TRACK_MAX_TRACKS <= CODETR_ASSIGN_MAX_ROWS && CODETR_POSTPROCESS_MAX_Q <= CODETR_ASSIGN_MAX_COLS,
+              "the tracker's largest problem fits the solver");
+
+__host__ __device__ inline int64_t lds2_offset(int64_t T, int64_t Q) { return round16(lds_bytes_of(T, Q)); }
+__host__ __device__ inline int64_t lds2_bytes_of(int64_t T, int64_t Q) {
+  return lds2_offset(T, Q) + assign_lds_bytes(T, T > Q ? T : Q);
+}
+
+// one optimal association (steps 3 to 5 of the rule under CODETR_ASSOCIATION_OPTIMAL); kind and cls as match_phase.  The
+// phase's tracks with an eligible pair are found as the greedy phase finds its first bests (a wave per track, lanes over
+// the candidates) and compacted in slot order into the free-slot list (unused until step 8); the columns are all
+// candidates of the frame.  Ends with a barrier.  kApp: `add` [T][pitch], the stream's appearance addends.
+template <bool kApp = false>
+__device__ __forceinline__ void assign_phase(const Lds& s, const AssignLds& a, int T, int cnt, int f, int kind, int cls,
+                                             bool weighted, float thr, int tid, const float* add = nullptr,
+                                             int pitch = 0) {
+  const int lane = tid & 63, wave = tid >> 6;
+  int R = 0;  // rows: the phase's tracks with at least one eligible pair, in ascending slot order
+#pragma unroll
+  for (int k = 0; k < kOwn; ++k) {
+    const int t = tid + k * kThreads;
+    bool elig = false;
+    if (t < T && s.id[t] != 0 && s.match[t] < 0) {
+      const bool tent = s.tent[t] != 0;
+      elig = kind == 1 ? tent : (!tent && (kind == 0 || s.last[t] == f - 1));
+    }
+    bool has = false;
+    unsigned long long need = __ballot(elig);
+    while (need) {  // (wave-uniform, at most 64 turns)
+      const int l = __ffsll((long long)need) - 1;
+      need &= need - 1;
+      float v;
+      int j;
+      const int wt = wave * 64 + l + k * kThreads;
+      wave_best<kApp>(s, wt, cnt, cls, weighted, thr, -1, lane, v, j, kApp ? add + (int64_t)wt * pitch : nullptr);
+      if (lane == l) has = j != kNone;
+    }
+    int tot;
+    const int r = R + block_rank(has, s.wsum, lane, wave, tot);
+    if (has) s.freelist[r] = (unsigned short)t;
+    R += tot;
+  }
+  __syncthreads();
+  if (R == 0) return;  // (uniform)
+  const int M = max(R, cnt);
+  const auto gain_of = [&](int r, int j) -> int {
+    if (j >= cnt || s.cls[j] != cls) return 0;  // (virtual, of another class, taken, or taking no part)
+    const int t = s.freelist[r];
+    if (s.clabel[j] != s.label[t]) return 0;
+    const float4 tb = s.tbox[t], cb = s.cbox[j];
+    const float iou = box_iou(tb, box_area(tb), cb, box_area(cb));
+    float val = weighted ? iou * s.cscore[j] : iou;
+    if constexpr (kApp) val = val + add[(int64_t)t * pitch + j];
+    return val >= thr ? 1 + (int)(fminf(val - thr, 2.0f) * 1048576.0f) : 0;  // (a NaN compares false)
+  };
+  assign_solve(a, R, M, gain_of, tid);
+  for (int j = tid; j < cnt; j += kThreads) {
+    const int o = a.owner[j];
+    if (o >= 0 && gain_of(o, j) > 0) {
+      s.match[s.freelist[o]] = j;
+      s.cls[j] = 0;  // taken (only this thread reads cls[j] in this loop)
+    }
+  }
+  __syncthreads();
+}
+
 // ---- the appearance cue of codetr_appearance.h (codetr_track_update5_*) ----
 struct App {
   const unsigned short* desc = nullptr;  // [N, Q, 128] descriptors, 16-byte aligned; null: no cue
@@ -271,7 +323,7 @@ __device__ __forceinline__ void app_addends(const Lds& s, const App& app, int b,
       bool need = false;
       if (j < cnt && s.cls[j] == 1 && s.clabel[j] == tl) {
         const float4 cb = s.cbox[j];
-        const float iou = overlap(tb, ta, cb, box_area(cb));
+        const float iou = box_iou(tb, ta, cb, box_area(cb));
         need = iou >= app.prox;  // (a NaN compares false)
         if (lost) {
           const float dx = (cb.x + cb.z) * 0.5f - cx, dy = (cb.y + cb.w) * 0.5f - cy;
@@ -332,7 +384,7 @@ __device__ __forceinline__ void app_update(const Lds& s, const App& app, int b, 
   __syncthreads();
 }
 
-// One stream's rows of a launch, walked in row order (the kernel body of both translation units).  `associate(s, cnt, f)`
+// One stream's rows of a launch, walked in row order (the kernel's body).  `associate(s, cnt, f)`
 // runs steps 3 to 5 on the frame's candidates and predicted tracks and ends with a barrier.  kMotion (codetr_motion.h):
 // 1: `motion` [N, 4] = dx, dy, valid, 0 per row, or null; a valid, finite motion is added to the predicted centres.
 // 2: `motion` [N, 8] = dx, dy, valid, model, a, b, px, py per row, or null; by the model a similarity about (px, py) moves

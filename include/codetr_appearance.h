@@ -74,7 +74,7 @@
  *                        library allocates nothing; may be NULL with desc_dev NULL).  It holds one fp32 per (stream, slot,
  *                        candidate): the addend of the pair (s where it is added, 0 elsewhere), written by a pre-pass of
  *                        every frame (a wave per live track) and looked up by the associations.
- *   One launch (track_update5_kernel in csrc/track_assign.hip), one workgroup per stream; the appearance state stays in
+ *   One launch (track_kernel's form with the cue, csrc/track.hip), one workgroup per stream; the appearance state stays in
  *   global memory.  With desc_dev NULL the ids and state bytes are codetr_track_update4_*'s and no appearance state is
  *   touched.  CODETR_E_BADARG also for a setting outside its range, a missing or misaligned buffer, work_bytes too small.
  */

@@ -1,5 +1,5 @@
 """GPU: the appearance cue -- `codetr_appearance_describe_*` (csrc/appearance.hip), `codetr_track_update5_*`
-(csrc/track_assign.hip) and the Inferencer's `track_appearance="color"` -- against the numpy restatement
+(csrc/track.hip) and the Inferencer's `track_appearance="color"` -- against the numpy restatement
 (tests/appearance_ref.py), bit for bit: every uint16 of the descriptors, the ids of every row, the whole decoded track state
 and the appearance states, which sit between sentinel-filled guard rows."""
 import functools

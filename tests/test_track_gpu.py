@@ -1,4 +1,4 @@
-"""GPU: `track_update_kernel` and the Inferencer's tracker against `track_ref`, bit for bit -- the ids of every row and
+"""GPU: `codetr_track_update_*` and the Inferencer's tracker against `track_ref`, bit for bit -- the ids of every row and
 the whole decoded state.  Id buffers are sentinel-filled and the states sit between sentinel-filled guard rows."""
 import numpy as np
 import pytest

@@ -725,7 +725,7 @@ def crowd_detections(frames, Q=300, objects=100, seed=9, side=350.0):
 
 
 def track_kernel_times(Q=300, objects=100):
-    """us per launch of the tracking kernels, greedy (track_update_kernel) and optimal (track_update2_kernel) alternating
+    """us per launch of the tracking kernels, greedy (track_kernel<false, ..>) and optimal (track_kernel<true, 0, ..>) alternating
     in one session: 8 frames of one stream, one frame of each of 8 streams, and 8 frames of a crowd of overlapping
     objects; the states hold about `objects` live tracks (8 frames are walked before the clock starts).  For the crowd
     the restatements (tests/) give the solver's rounds per frame and the frames on which the two associations differ."""

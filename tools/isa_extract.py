@@ -2,12 +2,25 @@
 and (optionally) the longest loop bodies.  Usage: python tools/isa_extract.py file.s <substring of the mangled name> [out.s]
 
 Compare two listings (or two directories of *.s with equal file names), e.g. before and after a change to a shared header:
-    python tools/isa_extract.py diff old.s new.s [--rename OLD=NEW ...] [--only TEXT]
+    python tools/isa_extract.py diff old.s new.s [--rename OLD=NEW ...] [--pair OLD=NEW ...] [--only TEXT]
 Kernels are paired by demangled name without namespace qualifiers (--rename maps a piece of a name of the old listing that
 the change renamed, e.g. 'kernel<=kernel<HalfT, ' for a template that gained a parameter; --only keeps the kernels of
 either listing whose name, after renaming, contains TEXT -- one element type of a listing that holds two); of each pair the instruction text is compared after dropping labels, directives, comments and symbol
 names, and the .amdhsa_ resource block (registers, LDS, scratch).  One line per kernel: `identical`, `same instructions,
-different order`, or `different` with counts; the exit status is 1 if any kernel is different or unpaired."""
+different order`, or `different` with counts; the exit status is 1 if any kernel is different or unpaired.
+
+--pair OLD=NEW pairs kernels whose names no --rename can turn into one another: a kernel of the old listing whose name
+contains OLD with the kernel of the new listing whose name contains NEW.  The name is the mangled one, or the demangled one
+before its parameter list; `{}` stands for any text and must be the same text on both sides.  A side may be several
+listings joined with `+`, for kernels that moved between files.  The tracker's five kernels against the one template
+that replaced them (profiles/r28_track_unify.txt):
+    python tools/isa_extract.py diff old/track.s+old/track_assign.s new/track.s \\
+        --pair 'track_update_kernel<{}>=track_kernel<false, 0, false, {}>' \\
+        --pair 'track_update2_kernel<{}>=track_kernel<true, 0, false, {}, int>' \\
+        --pair 'track_update3_kernel<{}>=track_kernel<true, 1, false, {}, int, float const* restrict>' \\
+        --pair 'track_update4_kernel<{}>=track_kernel<true, 2, false, {}, int, float const* restrict>' \\
+        --pair 'track_update5_kernel<{}>=track_kernel<true, 2, true, {}, int, float const* restrict, App>'
+"""
 import collections
 import os
 import re
@@ -62,29 +75,47 @@ def instructions(body):
 
 
 def demangled(names):
+    """(_Float16 goes in as the encoding of `half`, a builtin type like it: a demangler that does not know DF16_ would
+    leave the whole name mangled; the result says _Float16 again)"""
     for tool in ("/opt/rocm/llvm/bin/llvm-cxxfilt", "llvm-cxxfilt", "c++filt"):
         try:
-            res = subprocess.run([tool], input="\n".join(names) + "\n", stdout=subprocess.PIPE, text=True, check=True)
-            return res.stdout.split("\n")[:len(names)]
+            res = subprocess.run([tool], input="\n".join(n.replace("DF16_", "Dh") for n in names) + "\n",
+                                 stdout=subprocess.PIPE, text=True, check=True)
+            return [re.sub(r"\bhalf\b", "_Float16", n) for n in res.stdout.split("\n")[:len(names)]]
         except (OSError, subprocess.CalledProcessError):
             continue
     sys.exit("no demangler found (llvm-cxxfilt or c++filt)")
 
 
-def by_plain_name(path, renames):
-    ks, res = kernels(path), resources(path)
+def _paired(mangled, plain, pairs, side):
+    """--pair OLD=NEW: a kernel of the old listing (side 0) whose mangled name, or demangled name before the parameter
+    list, contains OLD and one of the new listing (side 1) that contains NEW go under one name, NEW; every `{}` stands for
+    any text, which must be the same on both sides ('update3_kernel<{}>=kernel<true, 1, {}, int>': one option per form)"""
+    for pair in pairs:
+        pattern = "(.+?)".join(re.escape(piece) for piece in pair[side].split("{}"))
+        m = re.search(pattern, mangled) or re.search(pattern, plain.split("(")[0])
+        if m:
+            return pair[1].format(*m.groups())
+    return plain
+
+
+def by_plain_name(paths, renames, pairs=(), side=0):
     out = {}
-    for mangled, plain in zip(ks, demangled(list(ks))):
-        plain = re.sub(r"(\(anonymous namespace\)|\b\w+)::", "", plain)
-        for old, new in renames:
-            plain = re.sub(r"\b%s\b" % re.escape(old), new, plain)
-        assert plain not in out, plain
-        out[plain] = (instructions(ks[mangled]), res.get(mangled))
+    for path in paths.split("+"):
+        ks, res = kernels(path), resources(path)
+        for mangled, plain in zip(ks, demangled(list(ks))):
+            plain = re.sub(r"(\(anonymous namespace\)|\b\w+)::", "", plain)
+            for old, new in renames:
+                plain = re.sub(r"\b%s\b" % re.escape(old), new, plain)
+            plain = _paired(mangled, plain, pairs, side)
+            assert plain not in out, plain
+            out[plain] = (instructions(ks[mangled]), res.get(mangled))
     return out
 
 
-def diff_listings(old, new, renames, only=""):
-    a, b = ({k: v for k, v in by_plain_name(path, rn).items() if only in k} for path, rn in ((old, renames), (new, [])))
+def diff_listings(old, new, renames, only="", pairs=()):
+    a, b = ({k: v for k, v in by_plain_name(path, rn, pairs, side).items() if only in k}
+            for side, (path, rn) in enumerate(((old, renames), (new, []))))
     bad = 0
     for name in sorted(set(a) | set(b)):
         short = name if len(name) <= 150 else name[:147] + "..."
@@ -111,19 +142,20 @@ def diff_listings(old, new, renames, only=""):
 
 def diff_main(argv):
     renames = [tuple(argv[i + 1].split("=")) for i, x in enumerate(argv) if x == "--rename"]
+    pairs = [tuple(argv[i + 1].split("=")) for i, x in enumerate(argv) if x == "--pair"]
     only = "".join(argv[i + 1] for i, x in enumerate(argv) if x == "--only")
-    flags = ("--rename", "--only")
+    flags = ("--rename", "--pair", "--only")
     old, new = [x for i, x in enumerate(argv) if x not in flags and (i == 0 or argv[i - 1] not in flags)]
     if os.path.isdir(old):
-        pairs = [(os.path.join(old, f), os.path.join(new, f)) for f in sorted(os.listdir(old)) if f.endswith(".s")]
+        files = [(os.path.join(old, f), os.path.join(new, f)) for f in sorted(os.listdir(old)) if f.endswith(".s")]
     else:
-        pairs = [(old, new)]
+        files = [(old, new)]
     total = bad = 0
-    for o, n in pairs:
-        print(os.path.basename(o))
-        t, b = diff_listings(o, n, renames, only)
+    for o, n in files:
+        print(" + ".join(os.path.basename(p) for p in o.split("+")), "->", " + ".join(os.path.basename(p) for p in n.split("+")))
+        t, b = diff_listings(o, n, renames, only, pairs)
         total, bad = total + t, bad + b
-    print(f"{total} kernels and device functions in {len(pairs)} listing(s): {bad} different or unpaired")
+    print(f"{total} kernels and device functions in {len(files)} listing(s): {bad} different or unpaired")
     return 1 if bad else 0
 
 
