@@ -192,37 +192,42 @@ class DinoTransformerDecoder(nn.Module):
         if not _cabi.decoder_layer_supported(C, M, L, P, F, 4, C // 2):
             return None
 
-        def build():
-            cat = lambda ts: torch.cat([t.detach().reshape(-1) for t in ts]).contiguous()  # noqa: E731
+        return hip_ops.derived(params, "_codetr_decoder_blobs", lambda: self._pack_blobs(reg_branches, L, P, F))
 
-            frag = pack_fragment_major
+    def _pack_blobs(self, reg_branches, L, P, F):
+        """The four kinds of packed blob of codetr_decoder_layer_f16 in the order include/codetr_hip.h documents (any
+        device: the packing is index arithmetic)."""
+        from . import _cabi
+        rp = list(self.ref_point_head)
+        C = self.embed_dims
+        cat = lambda ts: torch.cat([t.detach().reshape(-1) for t in ts]).contiguous()  # noqa: E731
 
-            tails, heads = [], []
-            for lid, layer in enumerate(self.layers):
-                sa, ca, ffn = layer.attentions[0], layer.attentions[1], layer.ffns[0]
-                n1, n2, n3 = layer.norms
-                fc1, fc2 = ffn.layers[0][0], ffn.layers[1]
-                rb = list(reg_branches[lid])
-                pad = rb[4].bias.new_zeros(4)
-                wol = torch.cat((ca.sampling_offsets.weight, ca.attention_weights.weight), 0)
-                # matrices first (fragment-major), then the small vectors (the kernel copies those to LDS once)
-                tails.append(cat([frag(sa.attn.out_proj.weight), frag(wol, 512), frag(ca.output_proj.weight),
-                                  frag(fc1.weight), frag(fc2.weight), frag(rb[0].weight), frag(rb[2].weight),
-                                  frag(rb[4].weight, 16),
-                                  sa.attn.out_proj.bias, n1.weight, n1.bias, ca.sampling_offsets.bias,
-                                  ca.attention_weights.bias, ca.output_proj.bias, n2.weight, n2.bias, fc1.bias, fc2.bias,
-                                  n3.weight, n3.bias, rb[0].bias, rb[2].bias, rb[4].bias, pad]))
-                Wi, bi = sa.attn.in_proj_weight, sa.attn.in_proj_bias               # rows [q | k | v]
-                heads.append(cat([frag(Wi[: 2 * C]), frag(Wi[2 * C:]), bi]))
-            pos = cat([frag(rp[0].weight), frag(rp[2].weight), rp[0].bias, rp[2].bias])
-            fin = cat([self.norm.weight, self.norm.bias])
-            sizes = [_cabi.decoder_layer_blob_halfs(w, L, P, F) for w in range(4)]
-            if (any(t.numel() != sizes[0] for t in tails) or any(h.numel() != sizes[1] for h in heads)
-                    or pos.numel() != sizes[2] or fin.numel() != sizes[3]):
-                raise AssertionError("decoder_layer weight blobs do not match the library's layout")
-            return dict(tails=tails, heads=heads, pos=pos, fin=fin, L=L, P=P, F=F)
+        frag = pack_fragment_major
 
-        return hip_ops.derived(params, "_codetr_decoder_blobs", build)
+        tails, heads = [], []
+        for lid, layer in enumerate(self.layers):
+            sa, ca, ffn = layer.attentions[0], layer.attentions[1], layer.ffns[0]
+            n1, n2, n3 = layer.norms
+            fc1, fc2 = ffn.layers[0][0], ffn.layers[1]
+            rb = list(reg_branches[lid])
+            pad = rb[4].bias.new_zeros(4)
+            wol = torch.cat((ca.sampling_offsets.weight, ca.attention_weights.weight), 0)
+            # matrices first (fragment-major), then the small vectors (the kernel copies those to LDS once)
+            tails.append(cat([frag(sa.attn.out_proj.weight), frag(wol, 512), frag(ca.output_proj.weight),
+                              frag(fc1.weight), frag(fc2.weight), frag(rb[0].weight), frag(rb[2].weight),
+                              frag(rb[4].weight, 16),
+                              sa.attn.out_proj.bias, n1.weight, n1.bias, ca.sampling_offsets.bias,
+                              ca.attention_weights.bias, ca.output_proj.bias, n2.weight, n2.bias, fc1.bias, fc2.bias,
+                              n3.weight, n3.bias, rb[0].bias, rb[2].bias, rb[4].bias, pad]))
+            Wi, bi = sa.attn.in_proj_weight, sa.attn.in_proj_bias               # rows [q | k | v]
+            heads.append(cat([frag(Wi[: 2 * C]), frag(Wi[2 * C:]), bi]))
+        pos = cat([frag(rp[0].weight), frag(rp[2].weight), rp[0].bias, rp[2].bias])
+        fin = cat([self.norm.weight, self.norm.bias])
+        sizes = [_cabi.decoder_layer_blob_halfs(w, L, P, F) for w in range(4)]
+        if (any(t.numel() != sizes[0] for t in tails) or any(h.numel() != sizes[1] for h in heads)
+                or pos.numel() != sizes[2] or fin.numel() != sizes[3]):
+            raise AssertionError("decoder_layer weight blobs do not match the library's layout")
+        return dict(tails=tails, heads=heads, pos=pos, fin=fin, L=L, P=P, F=F)
 
     def _forward_fused(self, blobs, query, v_all, reference_points, valid_ratios, spatial_shapes, level_start_index):
         """6 x (self-attention core, one codetr_decoder_layer_f16 launch) + the head-only launch in front."""
