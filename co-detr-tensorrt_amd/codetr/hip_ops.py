@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _appearance, _assign, _cabi, _jpeg, _jpeg_dec, _motion, _wbf
+from . import _appearance, _assign, _cabi, _jpeg, _jpeg_dec, _motion, _redact, _wbf
 
 # ops served by hand-written HIP kernels in this build (kept in sync with include/codetr_hip.h)
 NATIVE = {"msda", "linear(f16/bf16, K%64==0)", "layer_norm(f16/bf16)", "swin_window_attention(f16, head_dim 32)",
@@ -1029,6 +1029,113 @@ def draw_detections(buf_u8, rows, dets, names, palette, style=None):
             _cabi.draw_detections(buf_u8, rows[i:j], boxes[i:j], scores[i:j], labels[i:j], count[i:j],
                                   palette.contiguous(), names.contiguous(), st["line_width"], st["alpha"], st["score_thr"],
                                   (tc[0] << 16) | (tc[1] << 8) | tc[2], st["font_scale"], st["draw_labels"])
+    return buf_u8
+
+
+# redaction of detected regions (include/codetr_redact.h states the rule and its limits).  "blur" is the library's own: a
+# box filter over fixed cells and a tent reconstruction; parity with OpenCV's blur is unpinned (cv2 is not installed here)
+REDACT = dict(mode="pixelate", score_thr=0.3, expand=0.1, shape="box", cell=16, fill=(0, 0, 0))
+REDACT_MODES = tuple(_redact.MODES)
+REDACT_SHAPES = tuple(_redact.SHAPES)
+REDACT_CELLS = _redact.CELLS
+_redact_work = {}   # device -> the "blur" workspace on it (uint8), grown when a call needs more
+
+
+def redact_style(settings=None):
+    """the settings of redact_detections, validated and completed from REDACT -> a new dict.  ValueError, naming the key,
+    for an unknown key, a mode outside REDACT_MODES, a shape outside REDACT_SHAPES, a cell outside REDACT_CELLS, an expand
+    outside [0, 1], a score_thr that is not a number, a fill that is not three whole values in 0..255."""
+    st = dict(REDACT)
+    settings = dict(settings or {})
+    unknown = set(settings) - set(st)
+    if unknown:
+        raise ValueError(f"redact: unknown key(s) {sorted(unknown)}; known: {sorted(st)}")
+    st.update(settings)
+
+    def number(key):
+        v = st[key]
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != v:
+            raise ValueError(f"redact: {key} must be a number, got {v!r}")
+        return float(v)
+
+    if not isinstance(st["mode"], str) or st["mode"] not in REDACT_MODES:
+        raise ValueError(f"redact: mode must be one of {list(REDACT_MODES)}, got {st['mode']!r}")
+    if not isinstance(st["shape"], str) or st["shape"] not in REDACT_SHAPES:
+        raise ValueError(f"redact: shape must be one of {list(REDACT_SHAPES)}, got {st['shape']!r}")
+    cell = st["cell"]
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or int(cell) not in REDACT_CELLS:
+        raise ValueError(f"redact: cell must be one of {list(REDACT_CELLS)}, got {cell!r}")
+    st["cell"] = int(cell)
+    st["score_thr"] = number("score_thr")
+    st["expand"] = number("expand")
+    if not 0.0 <= st["expand"] <= 1.0:
+        raise ValueError(f"redact: expand must be in [0, 1], got {st['expand']!r}")
+    fill = st["fill"]
+    if not isinstance(fill, (tuple, list)) or len(fill) != 3 or any(
+            isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or int(v) != v or
+            not 0 <= v <= 255 for v in fill):
+        raise ValueError(f"redact: fill must be three whole values in 0..255, got {fill!r}")
+    st["fill"] = tuple(int(v) for v in fill)
+    return st
+
+
+def redact_detections(buf_u8, rows, dets, settings=None, select=None):
+    """Redaction of the detected regions in one launch per PREPROCESS_BATCH_MAX images ("blur": two) and without a
+    synchronisation (csrc/redact.hip; include/codetr_redact.h states the rule): the pixels under every detection with a
+    score above settings['score_thr'] and a selected label -- its box grown by settings['expand'], or the ellipse inside
+    it -- become the mean of their cell ("pixelate"), the tent interpolation of the cell means ("blur") or
+    settings['fill'].  In place; an unmasked pixel is never written.
+      buf_u8    one flat uint8 device buffer holding RGB HWC images (Inferencer.upload's)
+      rows      (offset, H, W) per image
+      dets      Detections / SoftDetections over [N, Q] rows, N = len(rows), Q <= 4096, boxes in image coordinates
+      settings  the keys of REDACT
+      select    [C] uint8 on the device, 1 = redact this label (any other label is left); None = every label
+    -> buf_u8.  ValueError for Q > 4096, a bad setting, a wrong dtype or shape, CPU tensors.  Nothing is launched when
+    N == 0 or Q == 0.  "blur" keeps one workspace per device and grows it."""
+    st = redact_style(settings)
+    tensors = dict(buf=buf_u8, boxes=dets.boxes, scores=dets.scores, labels=dets.labels, count=dets.count)
+    if select is not None:
+        tensors["select"] = select
+    for key, t in tensors.items():
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != buf_u8.device:
+            raise ValueError(f"redact_detections: {key} must be a tensor on the image buffer's GPU")
+    if buf_u8.dtype != torch.uint8 or buf_u8.dim() != 1 or not buf_u8.is_contiguous():
+        raise ValueError("redact_detections: expected one contiguous flat uint8 buffer")
+    if select is not None and (select.dtype != torch.uint8 or select.dim() != 1 or select.numel() == 0):
+        raise ValueError("redact_detections: select must be a [C] uint8 table, C > 0")
+    dtype = dets.scores.dtype
+    if dtype not in (torch.float16, torch.bfloat16, torch.float32) or dets.boxes.dtype != dtype or \
+            dets.labels.dtype != torch.int64 or dets.count.dtype != torch.int32:
+        raise ValueError("redact_detections: boxes and scores in one dtype of f16 / bf16 / f32, labels int64, count int32")
+    rows = [tuple(int(v) for v in r) for r in rows]
+    N = len(rows)
+    if dets.scores.dim() != 2 or dets.scores.shape[0] != N or tuple(dets.boxes.shape) != tuple(dets.scores.shape) + (4,) \
+            or dets.labels.shape != dets.scores.shape or tuple(dets.count.shape) != (N,):
+        raise ValueError("redact_detections: boxes [N,Q,4], scores [N,Q], labels [N,Q], count [N], N = len(rows)")
+    Q = dets.scores.shape[1]
+    if Q > DRAW_MAX_Q:
+        raise ValueError(f"redact_detections: at most {DRAW_MAX_Q} detection rows per image, got {Q}")
+    for off, H, W in rows:
+        if not (1 <= H <= DRAW_MAX_SIDE and 1 <= W <= DRAW_MAX_SIDE) or off < 0 or off + H * W * 3 > buf_u8.numel():
+            raise ValueError(f"redact_detections: image (offset {off}, {H}x{W}) outside the buffer or larger than "
+                             f"{DRAW_MAX_SIDE} a side")
+    if N == 0 or Q == 0:
+        return buf_u8
+    boxes, scores, labels, count = (t.contiguous() for t in (dets.boxes, dets.scores, dets.labels, dets.count))
+    select = None if select is None else select.contiguous()
+    fill = st["fill"]
+    with torch.cuda.device(buf_u8.device):
+        for i in range(0, N, PREPROCESS_BATCH_MAX):
+            j = min(N, i + PREPROCESS_BATCH_MAX)
+            work = None
+            if st["mode"] == "blur":   # (launches on one stream run in order: the next group may reuse the workspace)
+                need, key = _redact.work_bytes(rows[i:j], st["cell"]), str(buf_u8.device)
+                work = _redact_work.get(key)
+                if work is None or work.numel() < need:
+                    work = _redact_work[key] = torch.empty((need,), dtype=torch.uint8, device=buf_u8.device)
+            _redact.redact_detections(buf_u8, rows[i:j], boxes[i:j], scores[i:j], labels[i:j], count[i:j], select,
+                                      _redact.MODES[st["mode"]], _redact.SHAPES[st["shape"]], st["cell"], st["score_thr"],
+                                      st["expand"], (fill[0] << 16) | (fill[1] << 8) | fill[2], work)
     return buf_u8
 
 

@@ -154,6 +154,18 @@ chunk's own images, and ``codetr_track_update5_*`` adds its similarity with the 
 an object that re-enters away from its prediction keeps its id, and two objects that change lanes behind an occluder do
 not swap theirs.  It works with every ``input_format``, ``track_association`` and ``track_motion``; predictions gain no
 key.  ``include/codetr_appearance.h`` states the rule and its limits: hard 2-bit colour bins, two stripes, nothing learned.
+
+``redact``: ``None``, the default, means no launch, no new key and no change.
+``dict(mode="pixelate", classes=None, score_thr=0.3, expand=0.1, shape="box", cell=16, fill=(0, 0, 0))`` (``redact_settings``)
+makes the detected regions unrecognisable in every image that leaves the call: per chunk, after ``track_chunk`` (the
+appearance descriptors read the original pixels) and before the drawing and the JPEG encoder, ``hip_ops.redact_detections``
+(``csrc/redact.hip``) pixelates, blurs or fills, in place in the chunk's RGB buffer, the box -- grown by ``expand``, or the
+ellipse inside it -- of every final detection of the selected classes with a score above ``score_thr``.  With ``redact``
+set, ``return_vis`` and ``out_dir`` work without a visualiser and give the redacted images undrawn; with one the outlines
+and labels are drawn over the redacted pixels; ``draw_pred=False`` gives redaction without drawing; a JPEG ``vis_format``
+encodes the redacted buffer.  Every result dict gains ``"redacted"``: the indices of its rows that were selected.
+``include/codetr_redact.h`` states the rule byte for byte; "blur" is the library's own (cell means and a tent), parity with
+OpenCV's blur is unpinned.
 """
 import collections
 import colorsys
@@ -508,6 +520,59 @@ def visualizer_settings(cfg, visualizer, dataset_meta=None):
                 colors=torch.tensor(palette, dtype=torch.uint8).view(-1, 3))
 
 
+REDACT_KEYS = ("mode", "classes", "score_thr", "expand", "shape", "cell", "fill")
+
+
+def redact_settings(cfg, redact, dataset_meta=None, visualizer=None):
+    """How `Inferencer(..., redact=...)` reads its argument: None -> None; a dict with keys of REDACT_KEYS is validated
+    and completed from hip_ops.REDACT (hip_ops.redact_style: a ValueError names the key) plus `classes`: None (every
+    label) or a list of class names or ids.  Names resolve as the visualiser's do: `visualizer['classes']` (the settings
+    visualizer_settings returned), else dataset_meta['classes'], else str(label) for the query head's num_classes labels.
+    -> dict(style, classes: the sorted ids or None, select: the [C] uint8 table of hip_ops.redact_detections or None)"""
+    if redact is None:
+        return None
+    if not isinstance(redact, dict):
+        raise ValueError(f"redact must be None or a dict with keys of {REDACT_KEYS}")
+    unknown = set(redact) - set(REDACT_KEYS)
+    if unknown:
+        raise ValueError(f"redact: unknown key(s) {sorted(unknown)}; known: {list(REDACT_KEYS)}")
+    style = hip_ops.redact_style({k: v for k, v in redact.items() if k != "classes"})
+    classes = redact.get("classes")
+    if classes is None:
+        return dict(style=style, classes=None, select=None)
+    names = visualizer["classes"] if visualizer is not None else _meta(dataset_meta, "classes")
+    if names is None:
+        head = cfg.model.get("query_head") or {}
+        names = [str(i) for i in range(int(head.get("num_classes", 80)))]
+    names = [str(c) for c in names]
+    if isinstance(classes, (str, bytes)) or not isinstance(classes, (list, tuple)) or len(classes) == 0:
+        raise ValueError(f"redact: classes must be None or a non-empty list of class names or ids, got {classes!r}")
+    ids = set()
+    for c in classes:
+        if isinstance(c, str):
+            if c not in names:
+                raise ValueError(f"redact: classes: unknown class name {c!r}")
+            ids.add(names.index(c))
+        elif isinstance(c, (int, np.integer)) and not isinstance(c, bool) and 0 <= int(c) < len(names):
+            ids.add(int(c))
+        else:
+            raise ValueError(f"redact: classes: {c!r} is neither a class name nor an id in 0..{len(names) - 1}")
+    select = torch.zeros(len(names), dtype=torch.uint8)
+    select[sorted(ids)] = 1
+    return dict(style=style, classes=sorted(ids), select=select)
+
+
+def redacted_rows(pred, redact):
+    """the indices of the rows of a prediction dict that the redaction selects (include/codetr_redact.h, "Selection"),
+    from the labels, scores and boxes the prediction carries: score > score_thr in fp32, a selected label, four finite
+    coordinates"""
+    thr = np.float32(redact["style"]["score_thr"])
+    chosen = None if redact["classes"] is None else set(redact["classes"])
+    boxes = np.asarray(pred["bboxes"], np.float32).reshape(-1, 4)
+    return [j for j, (s, l) in enumerate(zip(pred["scores"], pred["labels"]))
+            if np.float32(s) > thr and (chosen is None or l in chosen) and bool(np.isfinite(boxes[j]).all())]
+
+
 VIS_FORMAT_KEYS = ("type", "quality", "subsampling")
 VIS_DOWNLOADS = {"rgb": 0}   # device-to-host copies of a chunk's whole RGB buffer made for the visualisation, this process
 
@@ -620,7 +685,7 @@ class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
                  slicing=None, tracker=None, vis_format=None,
-                 track_association=None, ensemble=None, track_motion=None, track_appearance=None):
+                 track_association=None, ensemble=None, track_motion=None, track_appearance=None, redact=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -682,6 +747,8 @@ class Inferencer:
         self._chunk_motion = None    # its [N, 4] motion on the device: _stage_call_chunk -> track_chunk
         self.track_appearance = track_appearance_settings(track_appearance, self.tracker)
         self._appearance_state = None   # [rows, max_tracks, 128] int16: every track's appearance, on the device
+        self.redact = redact_settings(self.cfg, redact, dataset_meta, self.visualizer)
+        self._redact_tables = {}   # device -> the class table on it: uploaded on the first redacting call there
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -1247,11 +1314,28 @@ class Inferencer:
         if key not in self._vis_tables:
             self._vis_tables[key] = (v["names"].to(src.device), v["colors"].to(src.device))
         names, colors = self._vis_tables[key]
-        if self.max_per_img is not None and not self.soft and self.tta is None and self.slicing is None:
-            # the hard path cuts to max_per_img on the host (postprocess_batch): the kernel gets the clamped count
-            dets = dets._replace(count=dets.count.clamp(max=self.max_per_img))
-        hip_ops.draw_detections(src, rows, dets, names, colors, dict(v["style"], score_thr=float(pred_score_thr)))
+        hip_ops.draw_detections(src, rows, self._clamped(dets), names, colors,
+                                dict(v["style"], score_thr=float(pred_score_thr)))
         return self.download_chunk(src, rows) if download else [None] * len(rows)
+
+    def _clamped(self, dets):
+        """the chunk's final detections as the predictions keep them: the hard path cuts to max_per_img on the host
+        (postprocess_batch), so a kernel that follows the predictions gets the clamped count"""
+        if self.max_per_img is not None and not self.soft and self.tta is None and self.slicing is None:
+            return dets._replace(count=dets.count.clamp(max=self.max_per_img))
+        return dets
+
+    def redact_chunk(self, src, rows, dets):
+        """the chunk's detected regions redacted in its uploaded images: hip_ops.redact_detections on the buffer the
+        preprocessing read, in place and on the same stream -- behind track_chunk (the appearance descriptors read the
+        original pixels), in front of draw_chunk and encode_jpeg.  No copy, no synchronisation."""
+        select = self.redact["select"]
+        if select is not None:
+            key = str(src.device)
+            if key not in self._redact_tables:
+                self._redact_tables[key] = select.to(src.device)
+            select = self._redact_tables[key]
+        hip_ops.redact_detections(src, rows, self._clamped(dets), self.redact["style"], select)
 
     def save_outputs(self, pred, vis, out_dir, no_save_pred, jpeg=None):
         """the files of one image (reference pred2dict :303-341, visualize :214-219): vis/%08d.png from the array `vis`,
@@ -1275,7 +1359,7 @@ class Inferencer:
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
                  batch_size: int = 1, input_format: str = "rgb", color=None, streams=None) -> Dict:
-        if show or return_datasamples or (return_vis and self.visualizer is None):
+        if show or return_datasamples or (return_vis and self.visualizer is None and self.redact is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
@@ -1284,7 +1368,8 @@ class Inferencer:
         plain = self.host_rgb(images, frames)   # what the reference takes; everything else is staged per chunk
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
-        visualise = self.visualizer is not None and (return_vis or save_vis)
+        # (with `redact` the images come out without a visualiser too: redacted and undrawn)
+        visualise = (self.visualizer is not None or self.redact is not None) and bool(return_vis or save_vis)
         if isinstance(return_vis, str):
             if return_vis != "jpeg" or self.vis_format is None:
                 raise ValueError('return_vis="jpeg" needs Inferencer(..., vis_format="jpeg"); otherwise pass a bool')
@@ -1304,6 +1389,8 @@ class Inferencer:
                     res = self.run_inference(x, m, [meta])[0]
                 pred = {"labels": res["labels"].tolist(), "scores": res["scores"].float().tolist(),
                         "bboxes": res["bboxes"].float().tolist()}
+                if self.redact is not None:   # (no image leaves this call: the rows it would redact, nothing launched)
+                    pred["redacted"] = redacted_rows(pred, self.redact)
                 if print_result:
                     print(pred)
                 self.save_outputs(pred, None, out_dir, no_save_pred)
@@ -1336,9 +1423,15 @@ class Inferencer:
                         pred["track_ids"] = row[:len(pred["labels"])].tolist()
                     self._chunk_streams = None
                 drawn = [None] * len(chunk)
-                if visualise and draw_pred:
+                if self.redact is not None:
+                    for pred in preds:
+                        pred["redacted"] = redacted_rows(pred, self.redact)
+                    if visualise:   # behind the descriptors, in front of the drawing and the encoder
+                        self.redact_chunk(src, rows, dets)
+                if visualise and draw_pred and self.visualizer is not None:
                     drawn = self.draw_chunk(src, rows, dets, pred_score_thr, download=want_arrays)
-                elif want_arrays and plain:   # the originals, as mmdet returns the undrawn image; nothing launched
+                elif want_arrays and plain and self.redact is None:
+                    # the originals, as mmdet returns the undrawn image; nothing launched
                     drawn = [im.copy() for im in chunk]
                 elif want_arrays:             # the undrawn converted frames: one download of the chunk's RGB buffer
                     drawn = self.download_chunk(src, rows)

@@ -77,12 +77,20 @@ decoder's five launches alone on eight of them (HIP event pairs, median), the by
 the host parser per file, Pillow's decode per frame; and images/s of the Inferencer at batch_size 8 fed the files
 (`input_format="jpeg"`), the same files decoded by Pillow inside the timed pass, and arrays decoded beforehand, in turn.
 
+`--redact MODE` prints only a `redact` record (redaction of detected regions, fp16; MODE is pixelate, blur or fill):
+redact_detections alone per mode on 8 frames of 1920x1080 at N = 8, Q = 300 with 20 person-sized boxes per frame (HIP event
+pairs, median of 200), beside a device-to-device copy of the buffer's bytes, draw_detections on the same operands, the
+same frames with no selected row (the early exit) and the numpy restatement on one frame; and images/s of
+`Inferencer(visualizer={}, vis_format="jpeg")(frames, out_dir=...)` at batch_size 8 with and without `redact=dict(mode=MODE)`,
+alternating.
+
     python tools/bench_inferencer.py [--images 32] [--repeats 3] [--no-profile] [--tta] [--vis] [--slice]   -> one JSON line
     python tools/bench_inferencer.py --frames nv12 --resident
     python tools/bench_inferencer.py --track
     python tools/bench_inferencer.py --track --motion
     python tools/bench_inferencer.py --track --motion similarity
     python tools/bench_inferencer.py --track --appearance
+    python tools/bench_inferencer.py --redact blur
 """
 import argparse
 import csv
@@ -501,6 +509,92 @@ def vis_files_record(inf, fmt, n_images, repeats, bs=8):
         shutil.rmtree(root, ignore_errors=True)
     if fmt == "jpeg":
         rec["encoder"] = jpeg_kernel_times(frames[:8], v.vis_format["quality"], v.vis_format["subsampling"])
+    return rec
+
+
+def redact_kernel_times(frames, Q=300, people=20, seed=11):
+    """us per hip_ops.redact_detections call of every mode on the frames (one buffer) with `people` person-sized boxes of
+    Q rows per frame above the threshold, beside a device-to-device copy of the buffer, draw_detections on the same
+    operands, the same call with no selected row, and the numpy restatement of one frame on this machine's CPU"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import redact_ref
+
+    from codetr import hip_ops
+    from codetr.inferencer import generated_palette
+
+    N, (H, W) = len(frames), frames[0].shape[:2]
+    rng = np.random.default_rng(seed)
+    boxes = np.zeros((N, Q, 4), np.float32)
+    c = rng.uniform((0, 0), (W, H), (N, Q, 2))
+    wh = np.stack((rng.uniform(60, 160, (N, Q)), rng.uniform(160, 420, (N, Q))), -1)      # persons: 60-160 x 160-420
+    boxes[...] = np.concatenate((c - wh / 2, c + wh / 2), -1)
+    scores = np.full((N, Q), 0.1, np.float32)
+    scores[:, :people] = rng.uniform(0.4, 1.0, (N, people))
+    labels = np.zeros((N, Q), np.int64)
+    src = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).to(DEV)
+    buf, other = src.clone(), torch.empty_like(src)
+    rows = [(n * H * W * 3, H, W) for n in range(N)]
+    dets = hip_ops.Detections(torch.from_numpy(boxes).half().to(DEV), torch.from_numpy(scores).half().to(DEV),
+                              torch.from_numpy(labels).to(DEV), torch.full((N,), Q, dtype=torch.int32, device=DEV), None)
+    none = torch.zeros(1, dtype=torch.uint8, device=DEV)   # label 0 is not selected: no row is
+    names = hip_ops.draw_names_table(["person"]).to(DEV)
+    colors = torch.tensor(generated_palette(1), dtype=torch.uint8, device=DEV)
+    rec = {"frames": N, "frame_wh": [W, H], "Q": Q, "rows_above_threshold_per_frame": people, "buffer_bytes": src.numel(),
+           "launches": 200, "timing": "HIP event pair around each call, median"}
+    calls = [("torch_copy_buffer", lambda: other.copy_(buf)),
+             ("draw_detections", lambda: hip_ops.draw_detections(buf, rows, dets, names, colors))]
+    for mode in ("fill", "pixelate", "blur"):
+        for shape in ("box", "ellipse"):
+            st = dict(mode=mode, shape=shape)
+            calls.append((f"redact_{mode}_{shape}", lambda st=st: hip_ops.redact_detections(buf, rows, dets, st)))
+        calls.append((f"redact_{mode}_no_selected_row",
+                      lambda st=dict(mode=mode): hip_ops.redact_detections(buf, rows, dets, st, none)))
+    for again in ("", "_again"):
+        for name, call in calls:
+            buf.copy_(src)
+            rec[name + again] = {"us_per_call_median": _event_us_each(call, launches=200, warmup=10)}
+    buf.copy_(src)
+    hip_ops.redact_detections(buf, rows, dets, dict(mode="blur"))
+    got = buf[:H * W * 3].cpu().numpy().reshape(H, W, 3)
+    t0 = time.perf_counter()
+    ref, red = redact_ref.redact(frames[0], dets.boxes[0].float().cpu().numpy(), dets.scores[0].float().cpu().numpy(), labels[0],
+                                 dict(mode="blur"))
+    rec["numpy_restatement_blur_one_frame_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+    rec["matches_restatement"] = bool(np.array_equal(got, ref))
+    rec["masked_pixels_frame_0"] = int((ref != frames[0]).any(-1).sum())
+    rec["redacted_rows_frame_0"] = len(red)
+    return rec
+
+
+def redact_record(inf, mode, n_images, repeats, bs=8):
+    """the kernels alone (redact_kernel_times) and images/s of the Inferencer writing vis/%08d.jpg from 1920x1080 frames at
+    batch_size 8, fp16, with and without redact=dict(mode=mode), alternating.  Random weights: the record says how many rows
+    a frame had redacted."""
+    import bench
+    from codetr.inferencer import Inferencer
+
+    frames = vis_frames(n_images)
+    kw = dict(dataset_meta=None, visualizer={}, vis_format="jpeg")
+    off, on = Inferencer(inf.model, bench.CFG, **kw), Inferencer(inf.model, bench.CFG, redact=dict(mode=mode), **kw)
+    root = tempfile.mkdtemp(prefix="bench_redact_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    rec = {"mode": mode, "batch_size": bs, "images": n_images, "frame_wh": [1920, 1080], "repeats": repeats, "dtype": "fp16",
+           "vis_format": "jpeg", "out_dir": "tmpfs" if root.startswith("/dev/shm") else "temporary directory"}
+    try:
+        for name, who in (("vis_jpeg", off), ("vis_jpeg_redact", on), ("vis_jpeg_again", off), ("vis_jpeg_redact_again", on)):
+            with torch.no_grad():
+                who(frames[:bs], device=DEV, dtype=torch.float16, batch_size=bs, out_dir=os.path.join(root, name))   # warm-up
+                times = []
+                for _ in range(repeats):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = who(frames, device=DEV, dtype=torch.float16, batch_size=bs, out_dir=os.path.join(root, name))
+                    times.append(time.perf_counter() - t0)
+            rec[name] = {"images_per_s": round(n_images / min(times), 2), "pass_s": [round(t, 4) for t in times]}
+            if who is on:
+                rec["redacted_rows_per_image"] = round(sum(len(p["redacted"]) for p in out["predictions"]) / n_images, 1)
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+    rec["kernels"] = redact_kernel_times(frames[:8])
     return rec
 
 
@@ -1153,6 +1247,9 @@ def main():
                     help="with --track: only the appearance record (track_appearance): the descriptors, the tracking "
                          "launch with and without them, the tracked Inferencer with and without the cue")
     ap.add_argument("--decode", choices=("jpeg",), help="only the record of JPEG files as input, decoded on the GPU")
+    ap.add_argument("--redact", choices=("pixelate", "blur", "fill"),
+                    help="only the redaction record: redact_detections alone per mode, and the Inferencer writing JPEG "
+                         "files with and without redact=dict(mode=MODE)")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -1173,6 +1270,11 @@ def main():
         print(json.dumps({"metric": "Inferencer on JPEG files (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock; HIP events for the decoder",
                           "decode": decode_record(infs["fp16"], a.images, a.repeats)}))
+        return
+    if a.redact:
+        print(json.dumps({"metric": "Inferencer redaction of detected regions (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass; HIP events for the kernels",
+                          "redact": redact_record(infs["fp16"], a.redact, a.images, a.repeats)}))
         return
     if a.track and a.appearance:
         print(json.dumps({"metric": "Inferencer tracking with the appearance cue (Swin-L config, random weights)",
