@@ -112,6 +112,43 @@ def load():
     return lib
 
 
+def companion(header, stem, what):
+    """The binding of a companion header of codetr_hip.h, include/<header>, with a version of its own (the define
+    CODETR_<STEM>_ABI_VERSION, the entry point codetr_<stem>_abi_version) -> (HEADER_PATH, functions, defines, SIGNATURES,
+    load).  The header is the one written copy: the signatures are read from it with _cheader.parse, and a header that is
+    not there is an ImportError.  load() -> the shared library with the header's prototypes set, cached; ImportError when
+    it lacks an entry point or its `what` ABI version is not the header's."""
+    path = os.path.join(os.path.dirname(_cheader.HEADER_PATH), header)
+    if not os.path.isfile(path):
+        raise ImportError(f"C ABI header not found at {path}; the {what} binding is derived from it")
+    with open(path) as f:
+        functions, defines = _cheader.parse(f.read())
+    signatures = {name: (_CTYPE[_cheader.kind(ret, returned=True)], [_CTYPE[_cheader.kind(t)] for t, _ in params])
+                  for name, (ret, params) in functions.items()}
+    expect = defines[f"CODETR_{stem.upper()}_ABI_VERSION"]
+    bound = []
+
+    def load_companion():
+        if bound:
+            return bound[0]
+        load()
+        lib = _lib   # (the plain library: these entries are not part of a launch plan and are never recorded)
+        for name, (res, args) in signatures.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise ImportError(f"{LIB_PATH} does not export {name}; rebuild the extension") from e
+            fn.restype = res
+            fn.argtypes = args
+        ver = getattr(lib, f"codetr_{stem}_abi_version")()
+        if ver != expect:
+            raise ImportError(f"{LIB_PATH} has {what} ABI version {ver}, host expects {expect}; rebuild the extension")
+        bound.append(lib)
+        return lib
+
+    return path, functions, defines, signatures, load_companion
+
+
 def strerror(code: int) -> str:
     return load().codetr_hip_strerror(code).decode()
 

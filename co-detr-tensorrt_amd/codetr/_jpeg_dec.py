@@ -1,20 +1,15 @@
 """ctypes binding of the JPEG decoder entry points of libcodetr_hip.so (C ABI: include/codetr_jpeg_dec.h, a companion
-header of codetr_hip.h with a version of its own).  As in _jpeg.py the header is the one written copy: the signatures and
-the CODETR_JPEGDEC_* constants are read from it with _cheader.parse, and a library that lacks an entry point is an
+header of codetr_hip.h with a version of its own).  The header is the one written copy: the signatures and
+the CODETR_JPEGDEC_* constants are read from it by _cabi.companion, and a library that lacks an entry point is an
 ImportError.  Flat integer and byte arrays only.
 """
 import ctypes
-import os
 
 import numpy as np
 
-from . import _cabi, _cheader
+from . import _cabi
 
-HEADER_PATH = os.path.join(os.path.dirname(_cheader.HEADER_PATH), "codetr_jpeg_dec.h")
-if not os.path.isfile(HEADER_PATH):
-    raise ImportError(f"C ABI header not found at {HEADER_PATH}; the JPEG decoder binding is derived from it")
-with open(HEADER_PATH) as _f:
-    functions, defines = _cheader.parse(_f.read())
+HEADER_PATH, functions, defines, SIGNATURES, load = _cabi.companion("codetr_jpeg_dec.h", "jpegdec", "JPEG decoder")
 
 ABI_VERSION = defines["CODETR_JPEGDEC_ABI_VERSION"]
 INFO_INTS = defines["CODETR_JPEGDEC_INFO_INTS"]
@@ -26,33 +21,7 @@ MAX_FILE_BYTES = defines["CODETR_JPEGDEC_MAX_FILE_BYTES"]
 REASONS = {v: k[len("CODETR_JPEGDEC_R_"):].lower() for k, v in defines.items() if k.startswith("CODETR_JPEGDEC_R_")}
 STATUS = {v: k[len("CODETR_JPEGDEC_S_"):].lower() for k, v in defines.items() if k.startswith("CODETR_JPEGDEC_S_")}
 
-SIGNATURES = {name: (_cabi._CTYPE[_cheader.kind(ret, returned=True)], [_cabi._CTYPE[_cheader.kind(t)] for t, _ in params])
-              for name, (ret, params) in functions.items()}
-
 _cabi.CALLS.setdefault("jpeg_decode", 0)
-_lib = None
-
-
-def load():
-    """the shared library with the decoder's prototypes set; ImportError when it is absent or older than this header"""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _cabi.load()
-    lib = _cabi._lib   # (the plain library: these entries are not part of a launch plan and are never recorded)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise ImportError(f"{_cabi.LIB_PATH} does not export {name}; rebuild the extension") from e
-        fn.restype = res
-        fn.argtypes = args
-    ver = lib.codetr_jpegdec_abi_version()
-    if ver != ABI_VERSION:
-        raise ImportError(f"{_cabi.LIB_PATH} has JPEG decoder ABI version {ver}, host expects {ABI_VERSION}; rebuild the "
-                          "extension")
-    _lib = lib
-    return lib
 
 
 def parse(data):

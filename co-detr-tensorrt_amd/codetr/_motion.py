@@ -1,18 +1,13 @@
 """ctypes binding of the camera-motion entry points of libcodetr_hip.so (C ABI: include/codetr_motion.h, a companion
-header of codetr_hip.h with a version of its own).  As in _assign.py the header is the one written copy: the signatures
-and the CODETR_MOTION_* constants are read from it with _cheader.parse, and a library that lacks an entry point is an
+header of codetr_hip.h with a version of its own).  The header is the one written copy: the signatures
+and the CODETR_MOTION_* constants are read from it by _cabi.companion, and a library that lacks an entry point is an
 ImportError.
 """
 import ctypes
-import os
 
-from . import _cabi, _cheader
+from . import _cabi
 
-HEADER_PATH = os.path.join(os.path.dirname(_cheader.HEADER_PATH), "codetr_motion.h")
-if not os.path.isfile(HEADER_PATH):
-    raise ImportError(f"C ABI header not found at {HEADER_PATH}; the camera-motion binding is derived from it")
-with open(HEADER_PATH) as _f:
-    functions, defines = _cheader.parse(_f.read())
+HEADER_PATH, functions, defines, SIGNATURES, load = _cabi.companion("codetr_motion.h", "motion", "camera-motion")
 
 ABI_VERSION = defines["CODETR_MOTION_ABI_VERSION"]
 GRID_MIN, GRID_MAX = defines["CODETR_MOTION_GRID_MIN"], defines["CODETR_MOTION_GRID_MAX"]
@@ -21,36 +16,10 @@ SEARCH_MAX = defines["CODETR_MOTION_SEARCH_MAX"]
 TEXTURE_MAX = defines["CODETR_MOTION_TEXTURE_MAX"]
 MAX_BLOCKS = defines["CODETR_MOTION_MAX_BLOCKS"]
 
-SIGNATURES = {name: (_cabi._CTYPE[_cheader.kind(ret, returned=True)], [_cabi._CTYPE[_cheader.kind(t)] for t, _ in params])
-              for name, (ret, params) in functions.items()}
-
 _cabi.CALLS.setdefault("motion_estimate", 0)
 _cabi.CALLS.setdefault("track_update3", 0)
 _cabi.CALLS.setdefault("motion_estimate2", 0)
 _cabi.CALLS.setdefault("track_update4", 0)
-_lib = None
-
-
-def load():
-    """the shared library with the camera-motion prototypes set; ImportError when it is absent or older than this header"""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _cabi.load()
-    lib = _cabi._lib   # (the plain library: these entries are not part of a launch plan and are never recorded)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise ImportError(f"{_cabi.LIB_PATH} does not export {name}; rebuild the extension") from e
-        fn.restype = res
-        fn.argtypes = args
-    ver = lib.codetr_motion_abi_version()
-    if ver != ABI_VERSION:
-        raise ImportError(f"{_cabi.LIB_PATH} has camera-motion ABI version {ver}, host expects {ABI_VERSION}; rebuild the "
-                          "extension")
-    _lib = lib
-    return lib
 
 
 def state_bytes():

@@ -1,18 +1,13 @@
 """ctypes binding of the redaction entry points of libcodetr_hip.so (C ABI: include/codetr_redact.h, a companion header
-of codetr_hip.h with a version of its own).  As in _appearance.py the header is the one written copy: the signatures and
-the CODETR_REDACT_* constants are read from it with _cheader.parse, and a library that lacks an entry point is an
+of codetr_hip.h with a version of its own).  The header is the one written copy: the signatures and
+the CODETR_REDACT_* constants are read from it by _cabi.companion, and a library that lacks an entry point is an
 ImportError.
 """
 import ctypes
-import os
 
-from . import _cabi, _cheader
+from . import _cabi
 
-HEADER_PATH = os.path.join(os.path.dirname(_cheader.HEADER_PATH), "codetr_redact.h")
-if not os.path.isfile(HEADER_PATH):
-    raise ImportError(f"C ABI header not found at {HEADER_PATH}; the redaction binding is derived from it")
-with open(HEADER_PATH) as _f:
-    functions, defines = _cheader.parse(_f.read())
+HEADER_PATH, functions, defines, SIGNATURES, load = _cabi.companion("codetr_redact.h", "redact", "redaction")
 
 ABI_VERSION = defines["CODETR_REDACT_ABI_VERSION"]
 TILE = defines["CODETR_REDACT_TILE"]
@@ -20,33 +15,7 @@ MODES = {name: defines["CODETR_REDACT_" + name.upper()] for name in ("pixelate",
 SHAPES = {name: defines["CODETR_REDACT_" + name.upper()] for name in ("box", "ellipse")}
 CELLS = (4, 8, 16, 32, 64)
 
-SIGNATURES = {name: (_cabi._CTYPE[_cheader.kind(ret, returned=True)], [_cabi._CTYPE[_cheader.kind(t)] for t, _ in params])
-              for name, (ret, params) in functions.items()}
-
 _cabi.CALLS.setdefault("redact_detections", 0)
-_lib = None
-
-
-def load():
-    """the shared library with the redaction prototypes set; ImportError when it is absent or older than this header"""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _cabi.load()
-    lib = _cabi._lib   # (the plain library: these entries are not part of a launch plan and are never recorded)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise ImportError(f"{_cabi.LIB_PATH} does not export {name}; rebuild the extension") from e
-        fn.restype = res
-        fn.argtypes = args
-    ver = lib.codetr_redact_abi_version()
-    if ver != ABI_VERSION:
-        raise ImportError(f"{_cabi.LIB_PATH} has redaction ABI version {ver}, host expects {ABI_VERSION}; rebuild the "
-                          "extension")
-    _lib = lib
-    return lib
 
 
 def _table(rows):

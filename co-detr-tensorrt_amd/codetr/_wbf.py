@@ -1,49 +1,19 @@
 """ctypes binding of the weighted-boxes-fusion entry points of libcodetr_hip.so (C ABI: include/codetr_wbf.h, a companion
-header of codetr_hip.h with a version of its own).  As in _assign.py the header is the one written copy: the signatures
-and the CODETR_WBF_* constants are read from it with _cheader.parse, and a library that lacks an entry point is an
+header of codetr_hip.h with a version of its own).  The header is the one written copy: the signatures
+and the CODETR_WBF_* constants are read from it by _cabi.companion, and a library that lacks an entry point is an
 ImportError.
 """
 import ctypes
-import os
 
-from . import _cabi, _cheader
+from . import _cabi
 
-HEADER_PATH = os.path.join(os.path.dirname(_cheader.HEADER_PATH), "codetr_wbf.h")
-if not os.path.isfile(HEADER_PATH):
-    raise ImportError(f"C ABI header not found at {HEADER_PATH}; the WBF binding is derived from it")
-with open(HEADER_PATH) as _f:
-    functions, defines = _cheader.parse(_f.read())
+HEADER_PATH, functions, defines, SIGNATURES, load = _cabi.companion("codetr_wbf.h", "wbf", "WBF")
 
 ABI_VERSION = defines["CODETR_WBF_ABI_VERSION"]
 MAX_CANDIDATES = defines["CODETR_WBF_MAX_CANDIDATES"]
 CONF_TYPES = {"avg": defines["CODETR_WBF_CONF_AVG"], "max": defines["CODETR_WBF_CONF_MAX"]}
 
-SIGNATURES = {name: (_cabi._CTYPE[_cheader.kind(ret, returned=True)], [_cabi._CTYPE[_cheader.kind(t)] for t, _ in params])
-              for name, (ret, params) in functions.items()}
-
 _cabi.CALLS.setdefault("wbf_merge", 0)
-_lib = None
-
-
-def load():
-    """the shared library with the WBF prototypes set; ImportError when it is absent or older than this header"""
-    global _lib
-    if _lib is not None:
-        return _lib
-    _cabi.load()
-    lib = _cabi._lib   # (the plain library: these entries are not part of a launch plan and are never recorded)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise ImportError(f"{_cabi.LIB_PATH} does not export {name}; rebuild the extension") from e
-        fn.restype = res
-        fn.argtypes = args
-    ver = lib.codetr_wbf_abi_version()
-    if ver != ABI_VERSION:
-        raise ImportError(f"{_cabi.LIB_PATH} has WBF ABI version {ver}, host expects {ABI_VERSION}; rebuild the extension")
-    _lib = lib
-    return lib
 
 
 def wbf_merge(boxes, scores, labels, count, flip_mask, width, weights, conf_type, iou_threshold, skip_box_thr, max_keep,

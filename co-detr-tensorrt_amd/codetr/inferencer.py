@@ -178,7 +178,7 @@ from typing import Dict, List, Optional
 import numpy as np
 import torch
 
-from . import hip_ops
+from . import detection_ops, hip_ops
 from .config import Config
 
 
@@ -210,7 +210,7 @@ def nms_settings(test_cfg, nms_type=None):
     if test_cfg.get("max_per_img", -1) > 0:
         out["max_per_img"] = int(test_cfg["max_per_img"])
     if out["type"] == "soft_nms":
-        hip_ops._soft_method(out["method"])   # 'gaussian' raises NotImplementedError, an unknown name ValueError
+        detection_ops._soft_method(out["method"])   # 'gaussian' raises NotImplementedError, an unknown name ValueError
     return out
 
 
@@ -271,7 +271,7 @@ def tta_settings(cfg, tta):
     out_nms = dict(type=kind, iou_threshold=float(nms.get("iou_threshold", 0.5 if kind == "nms" else 0.3)),
                    method=nms.get("method", "linear"), min_score=float(nms.get("min_score", 1e-3)))
     if kind == "soft_nms":
-        hip_ops._soft_method(out_nms["method"])   # 'gaussian' raises NotImplementedError, an unknown name ValueError
+        detection_ops._soft_method(out_nms["method"])   # 'gaussian' raises NotImplementedError, an unknown name ValueError
     mpi = tta.get("max_per_img")
     views = [(s, f) for s in scales for f in ((False, True) if flip else (False,))]
     if len(views) > hip_ops.TTA_MAX_VIEWS:
