@@ -166,6 +166,20 @@ and labels are drawn over the redacted pixels; ``draw_pred=False`` gives redacti
 encodes the redacted buffer.  Every result dict gains ``"redacted"``: the indices of its rows that were selected.
 ``include/codetr_redact.h`` states the rule byte for byte; "blur" is the library's own (cell means and a tent), parity with
 OpenCV's blur is unpinned.
+
+``crops``: ``None``, the default, means no launch, no new key and no change.
+``dict(size=(w, h), classes=None, score_thr=0.3, expand=0.0, fit="stretch", pad_value=(114, 114, 114), max_per_img=32,
+tensor=None)`` (``crops_settings``; only ``size`` is required) hands over the detected objects themselves for a second-stage
+model: per chunk, after ``track_chunk`` and before the redaction, the drawing and the JPEG encoder -- the crops show the
+original pixels -- ``hip_ops.crop_detections`` (``csrc/crops.hip``) resamples, with antialiasing, the box of each of the
+first ``max_per_img`` final detections of the selected classes with a score of at least ``score_thr`` to ``size``.  Every
+result dict gains ``"crop_rows"``, the indices of its rows that were cropped (they index ``track_ids`` too);
+``results["crops"]`` holds one ``[k, h, w, 3]`` uint8 array per image, fetched by one device-to-host copy of the crop slots
+per chunk -- the frame is never downloaded.  ``tensor=dict(mean, std, dtype)`` adds ``results["crop_tensors"]``: per image a
+``[k, 3, h, w]`` view, on the device, of the chunk's normalised output; with it ``download=False`` leaves the uint8 arrays
+on the device and ``results["crops"]`` out.  Like ``tracker``, ``crops`` keeps a call on the chunk path.
+``include/codetr_crops.h`` states the rule byte for byte: the filter is Pillow's antialiased BILINEAR, the arithmetic is
+not; nothing is learned, boxes stay axis-aligned, parity with cv2 is unpinned.
 """
 import collections
 import colorsys
@@ -537,29 +551,35 @@ def redact_settings(cfg, redact, dataset_meta=None, visualizer=None):
     if unknown:
         raise ValueError(f"redact: unknown key(s) {sorted(unknown)}; known: {list(REDACT_KEYS)}")
     style = hip_ops.redact_style({k: v for k, v in redact.items() if k != "classes"})
-    classes = redact.get("classes")
+    ids, select = _selected_classes("redact", cfg, redact.get("classes"), dataset_meta, visualizer)
+    return dict(style=style, classes=ids, select=select)
+
+
+def _selected_classes(label, cfg, classes, dataset_meta, visualizer):
+    """the `classes` of a redact / crops argument: None (every label) or a list of class names or ids -> (the sorted
+    ids, the [C] uint8 table on the host), or (None, None)"""
     if classes is None:
-        return dict(style=style, classes=None, select=None)
+        return None, None
     names = visualizer["classes"] if visualizer is not None else _meta(dataset_meta, "classes")
     if names is None:
         head = cfg.model.get("query_head") or {}
         names = [str(i) for i in range(int(head.get("num_classes", 80)))]
     names = [str(c) for c in names]
     if isinstance(classes, (str, bytes)) or not isinstance(classes, (list, tuple)) or len(classes) == 0:
-        raise ValueError(f"redact: classes must be None or a non-empty list of class names or ids, got {classes!r}")
+        raise ValueError(f"{label}: classes must be None or a non-empty list of class names or ids, got {classes!r}")
     ids = set()
     for c in classes:
         if isinstance(c, str):
             if c not in names:
-                raise ValueError(f"redact: classes: unknown class name {c!r}")
+                raise ValueError(f"{label}: classes: unknown class name {c!r}")
             ids.add(names.index(c))
         elif isinstance(c, (int, np.integer)) and not isinstance(c, bool) and 0 <= int(c) < len(names):
             ids.add(int(c))
         else:
-            raise ValueError(f"redact: classes: {c!r} is neither a class name nor an id in 0..{len(names) - 1}")
+            raise ValueError(f"{label}: classes: {c!r} is neither a class name nor an id in 0..{len(names) - 1}")
     select = torch.zeros(len(names), dtype=torch.uint8)
     select[sorted(ids)] = 1
-    return dict(style=style, classes=sorted(ids), select=select)
+    return sorted(ids), select
 
 
 def redacted_rows(pred, redact):
@@ -571,6 +591,54 @@ def redacted_rows(pred, redact):
     boxes = np.asarray(pred["bboxes"], np.float32).reshape(-1, 4)
     return [j for j, (s, l) in enumerate(zip(pred["scores"], pred["labels"]))
             if np.float32(s) > thr and (chosen is None or l in chosen) and bool(np.isfinite(boxes[j]).all())]
+
+
+def crops_settings(cfg, crops, dataset_meta=None, visualizer=None):
+    """How `Inferencer(..., crops=...)` reads its argument: None -> None; a dict with the keys of hip_ops.CROPS (validated
+    and completed by hip_ops.crop_settings: a ValueError names the key; `size` is required) plus `classes`, read as
+    redact_settings reads its own -> dict(settings, classes: the sorted ids or None, select: the [C] uint8 table of
+    hip_ops.crop_detections or None)"""
+    if crops is None:
+        return None
+    if not isinstance(crops, dict):
+        raise ValueError(f"crops must be None or a dict with keys of {sorted(set(hip_ops.CROPS) | {'classes'})}")
+    settings = hip_ops.crop_settings({k: v for k, v in crops.items() if k != "classes"})
+    ids, select = _selected_classes("crops", cfg, crops.get("classes"), dataset_meta, visualizer)
+    return dict(settings=settings, classes=ids, select=select)
+
+
+def crop_region(box, expand, hw=None):
+    """the half-open pixel rectangle (x0, y0, x1, y1) of a cropped row (include/codetr_crops.h, "Region": fp32 with one
+    rounding per operation), clipped to the image hw = (H, W) when given; None when it is empty"""
+    f = np.float32
+    x1, y1, x2, y2 = (np.minimum(np.maximum(f(v), f(-16384.0)), f(16383.0)) for v in box)
+    ex, ey = f(f(expand) * f(x2 - x1)), f(f(expand) * f(y2 - y1))
+    clamp = lambda v: np.minimum(np.maximum(f(v), f(-16384.0)), f(16383.0))  # noqa: E731
+    X1, X2 = int(np.floor(clamp(x1 - ex))), int(np.ceil(clamp(x2 + ex))) - 1
+    Y1, Y2 = int(np.floor(clamp(y1 - ey))), int(np.ceil(clamp(y2 + ey))) - 1
+    if X2 < X1 or Y2 < Y1:
+        return None
+    H, W = hw if hw is not None else (Y2 + 1, X2 + 1)
+    x0, y0, xe, ye = max(X1, 0), max(Y1, 0), min(X2 + 1, W), min(Y2 + 1, H)
+    return (x0, y0, xe, ye) if xe > x0 and ye > y0 else None
+
+
+def cropped_rows(pred, crops, hw=None):
+    """the indices of the rows of a prediction dict that the crop stage takes (include/codetr_crops.h, "Selection"),
+    from the labels, scores and boxes the prediction carries: score >= score_thr in fp32, a selected label, four finite
+    coordinates, a region that is not empty (hw = (H, W): after clipping to the image) -- the first max_per_img in order"""
+    st = crops["settings"]
+    thr = np.float32(st["score_thr"])
+    chosen = None if crops["classes"] is None else set(crops["classes"])
+    boxes = np.asarray(pred["bboxes"], np.float32).reshape(-1, 4)
+    rows = []
+    for j, (s, l) in enumerate(zip(pred["scores"], pred["labels"])):
+        if len(rows) == st["max_per_img"]:
+            break
+        if np.float32(s) >= thr and (chosen is None or l in chosen) and bool(np.isfinite(boxes[j]).all()) and \
+                crop_region(boxes[j], st["expand"], hw) is not None:
+            rows.append(j)
+    return rows
 
 
 VIS_FORMAT_KEYS = ("type", "quality", "subsampling")
@@ -685,7 +753,7 @@ class Inferencer:
     def __init__(self, model, model_file: str, dataset_meta, score_threshold: Optional[float] = None,
                  iou_threshold: Optional[float] = None, nms_type: Optional[str] = None, tta=None, visualizer=None,
                  slicing=None, tracker=None, vis_format=None,
-                 track_association=None, ensemble=None, track_motion=None, track_appearance=None, redact=None):
+                 track_association=None, ensemble=None, track_motion=None, track_appearance=None, redact=None, crops=None):
         self.model = model
         self.dataset_meta = dataset_meta
         self.cfg = Config.fromfile(model_file)
@@ -749,6 +817,8 @@ class Inferencer:
         self._appearance_state = None   # [rows, max_tracks, 128] int16: every track's appearance, on the device
         self.redact = redact_settings(self.cfg, redact, dataset_meta, self.visualizer)
         self._redact_tables = {}   # device -> the class table on it: uploaded on the first redacting call there
+        self.crops = crops_settings(self.cfg, crops, dataset_meta, self.visualizer)
+        self._crop_tables = {}     # device -> the class table on it: uploaded on the first cropping call there
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -1337,6 +1407,40 @@ class Inferencer:
             select = self._redact_tables[key]
         hip_ops.redact_detections(src, rows, self._clamped(dets), self.redact["style"], select)
 
+    def crop_chunk(self, src, rows, dets):
+        """the chunk's detected objects as crops: hip_ops.crop_detections on the buffer the preprocessing read, on the
+        same stream -- behind track_chunk, in front of redact_chunk, draw_chunk and encode_jpeg, so the crops show the
+        original pixels -> (crops [N, M, h, w, 3] uint8, counts [N] int32, the normalised [N, M, 3, h, w] or None), all
+        on the device.  No copy, no synchronisation."""
+        select = self.crops["select"]
+        if select is not None:
+            key = str(src.device)
+            if key not in self._crop_tables:
+                self._crop_tables[key] = select.to(src.device)
+            select = self._crop_tables[key]
+        out = hip_ops.crop_detections(src, rows, self._clamped(dets), self.crops["settings"], select)
+        return out if len(out) == 3 else out + (None,)
+
+    def _crops_of_chunk(self, src, rows, dets, preds, results):
+        """crop_chunk, `crop_rows` into the chunk's predictions and the chunk's crops into results["crops"] (one
+        device-to-host copy of the counts and the slots in use; a count that is not the host's is a RuntimeError) and
+        results["crop_tensors"] (views of the chunk's tensor, on the device)"""
+        st = self.crops["settings"]
+        crops, counts, tensor = self.crop_chunk(src, rows, dets)
+        for pred, (_, H, W) in zip(preds, rows):
+            pred["crop_rows"] = cropped_rows(pred, self.crops, (H, W))
+        ks = [len(pred["crop_rows"]) for pred in preds]
+        if st["download"]:   # the kernel's counts ride in front of the slots in the one copy, and must be the host's
+            top = max(ks + [0])
+            host = torch.cat((counts.view(torch.uint8), crops[:, :top].reshape(-1))).cpu().numpy()
+            got = host[:4 * len(ks)].view(np.int32).tolist()
+            if got != ks:
+                raise RuntimeError(f"crops: the kernel filled {got} slots per image, the predictions select {ks}")
+            host = host[4 * len(ks):].reshape((len(ks), top) + tuple(crops.shape[2:]))
+            results.setdefault("crops", []).extend(host[i, :k].copy() for i, k in enumerate(ks))
+        if tensor is not None:
+            results.setdefault("crop_tensors", []).extend(tensor[i, :k] for i, k in enumerate(ks))
+
     def save_outputs(self, pred, vis, out_dir, no_save_pred, jpeg=None):
         """the files of one image (reference pred2dict :303-341, visualize :214-219): vis/%08d.png from the array `vis`,
         or, with a JPEG vis_format, the reference's vis/%08d.jpg from the encoded file `jpeg`"""
@@ -1382,7 +1486,7 @@ class Inferencer:
         elif streams is not None:
             raise ValueError("streams without a tracker: Inferencer(..., tracker=dict(...)) turns tracking on")
         if (batch_size == 1 and dtype != torch.bfloat16 and not self.soft and self.tta is None and self.slicing is None
-                and not visualise and plain and self.tracker is None):
+                and not visualise and plain and self.tracker is None and self.crops is None):
             for image in images:
                 with torch.no_grad():
                     x, m, meta = self.preprocess(image, device, dtype)
@@ -1422,6 +1526,8 @@ class Inferencer:
                     for pred, row in zip(preds, ids):
                         pred["track_ids"] = row[:len(pred["labels"])].tolist()
                     self._chunk_streams = None
+                if self.crops is not None:   # behind the descriptors, in front of everything that writes the pixels
+                    self._crops_of_chunk(src, rows, dets, preds, results_dict)
                 drawn = [None] * len(chunk)
                 if self.redact is not None:
                     for pred in preds:

@@ -25,6 +25,7 @@
 
 #include "codetr_redact.h"
 #include "box_prims.h"
+#include "box_region.h"
 #include "redact_args.h"
 
 namespace {
@@ -45,19 +46,6 @@ struct Params {
   int fill[3];
   int C;
 };
-
-__device__ __forceinline__ float clamp_coord(float v) { return fminf(fmaxf(v, -16384.f), 16383.f); }
-
-// the region of a redacted row; false when it does not exist
-__device__ __forceinline__ bool region_of(float x1, float y1, float x2, float y2, float expand, int4* r) {
-  x1 = clamp_coord(x1), y1 = clamp_coord(y1), x2 = clamp_coord(x2), y2 = clamp_coord(y2);
-  const float w = x2 - x1, h = y2 - y1;
-  const float ex = expand * w, ey = expand * h;
-  const float a1 = clamp_coord(x1 - ex), a2 = clamp_coord(x2 + ex);
-  const float b1 = clamp_coord(y1 - ey), b2 = clamp_coord(y2 + ey);
-  *r = make_int4((int)floorf(a1), (int)floorf(b1), (int)ceilf(a2) - 1, (int)ceilf(b2) - 1);
-  return r->z >= r->x && r->w >= r->y;
-}
 
 // the first byte of the tile's row `y` of an image and the segment's byte phase inside its first aligned dword
 __device__ __forceinline__ unsigned char* row_segment(unsigned char* img, int y, int W, int tx0, int* phase) {

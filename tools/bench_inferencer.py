@@ -91,6 +91,11 @@ alternating.
     python tools/bench_inferencer.py --track --motion similarity
     python tools/bench_inferencer.py --track --appearance
     python tools/bench_inferencer.py --redact blur
+`--crops` prints only a `crops` record (object crops for a second stage, fp16): crop_detections alone on 8 frames of
+1920x1080 at N = 8, Q = 300 with 20 person-sized boxes per frame -> 128 x 256, uint8 only and with an fp16 tensor (HIP event
+pairs), beside a device-to-device copy of the region bytes and the numpy restatement of one frame; and the Inferencer at
+batch_size 8 with and without `crops=dict(size=(128, 256), score_thr=0.0)` (random weights score near zero):
+    python tools/bench_inferencer.py --crops --images 32
 """
 import argparse
 import csv
@@ -595,6 +600,80 @@ def redact_record(inf, mode, n_images, repeats, bs=8):
     finally:
         shutil.rmtree(root, ignore_errors=True)
     rec["kernels"] = redact_kernel_times(frames[:8])
+    return rec
+
+
+def crops_kernel_times(frames, Q=300, people=20, size=(128, 256), seed=11):
+    """us per hip_ops.crop_detections call (the selection pass and the resampling kernel) on the frames (one buffer)
+    with `people` person-sized boxes of Q rows per frame above the threshold -> size, uint8 only and with an fp16 tensor,
+    beside a device-to-device copy of the bytes the call reads (the regions) and the numpy restatement of one frame on
+    this machine's CPU"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import crops_ref
+
+    from codetr import hip_ops
+
+    N, (H, W) = len(frames), frames[0].shape[:2]
+    rng = np.random.default_rng(seed)
+    c = rng.uniform((0, 0), (W, H), (N, Q, 2))
+    wh = np.stack((rng.uniform(60, 160, (N, Q)), rng.uniform(160, 420, (N, Q))), -1)      # persons: 60-160 x 160-420
+    boxes = np.concatenate((c - wh / 2, c + wh / 2), -1).astype(np.float32)
+    scores = np.full((N, Q), 0.1, np.float32)
+    scores[:, :people] = rng.uniform(0.4, 1.0, (N, people))
+    labels = np.zeros((N, Q), np.int64)
+    buf = torch.from_numpy(np.concatenate([f.reshape(-1) for f in frames])).to(DEV)
+    rows = [(n * H * W * 3, H, W) for n in range(N)]
+    dets = hip_ops.Detections(torch.from_numpy(boxes).half().to(DEV), torch.from_numpy(scores).half().to(DEV),
+                              torch.from_numpy(labels).to(DEV), torch.full((N,), Q, dtype=torch.int32, device=DEV), None)
+    st = dict(size=size, max_per_img=32)
+    half = dict(st, tensor=dict(mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), dtype=torch.float16))
+    b16 = dets.boxes.float().cpu().numpy()
+    regions = [crops_ref.region(b16[n, j], 0.0, H, W) for n in range(N) for j in range(people)]
+    read = sum(3 * (r[2] - r[0]) * (r[3] - r[1]) for r in regions if r is not None)
+    a, b = torch.empty(read, dtype=torch.uint8, device=DEV), torch.empty(read, dtype=torch.uint8, device=DEV)
+    rec = {"frames": N, "frame_wh": [W, H], "Q": Q, "rows_above_threshold_per_frame": people, "size_wh": list(size),
+           "region_bytes_read": read, "launches": 200, "timing": "HIP event pair around each call, median"}
+    calls = [("torch_copy_region_bytes", lambda: b.copy_(a)),
+             ("crop_detections_u8", lambda: hip_ops.crop_detections(buf, rows, dets, st)),
+             ("crop_detections_u8_f16_tensor", lambda: hip_ops.crop_detections(buf, rows, dets, half))]
+    for again in ("", "_again"):
+        for name, call in calls:
+            rec[name + again] = {"us_per_call_median": _event_us_each(call, launches=200, warmup=10)}
+    got, counts = hip_ops.crop_detections(buf, rows, dets, st)
+    t0 = time.perf_counter()
+    ref, kept = crops_ref.crops(frames[0], b16[0], dets.scores[0].float().cpu().numpy(), labels[0], st)
+    rec["numpy_restatement_one_frame_ms"] = round((time.perf_counter() - t0) * 1e3, 1)
+    rec["matches_restatement"] = bool(counts[0].item() == len(kept) and np.array_equal(got[0, :len(kept)].cpu().numpy(), ref))
+    rec["crops_frame_0"] = len(kept)
+    return rec
+
+
+def crops_record(inf, n_images, repeats, bs=8, size=(128, 256)):
+    """the launch pair alone (crops_kernel_times) and images/s of the Inferencer on 1920x1080 frames at batch_size 8, fp16,
+    with and without crops=dict(size=size, score_thr=0.0), alternating.  Random weights score near zero, so the default
+    score_thr of 0.3 would select nothing: the threshold is lowered to 0 and the record says how many rows a frame had
+    cropped."""
+    import bench
+    from codetr.inferencer import Inferencer
+
+    frames = vis_frames(n_images)
+    off = Inferencer(inf.model, bench.CFG, dataset_meta=None)
+    on = Inferencer(inf.model, bench.CFG, dataset_meta=None, crops=dict(size=size, score_thr=0.0))
+    rec = {"batch_size": bs, "images": n_images, "frame_wh": [1920, 1080], "repeats": repeats, "dtype": "fp16",
+           "size_wh": list(size), "score_thr": 0.0}
+    for name, who in (("plain", off), ("crops", on), ("plain_again", off), ("crops_again", on)):
+        with torch.no_grad():
+            who(frames[:bs], device=DEV, dtype=torch.float16, batch_size=bs)   # warm-up
+            times = []
+            for _ in range(repeats):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = who(frames, device=DEV, dtype=torch.float16, batch_size=bs)
+                times.append(time.perf_counter() - t0)
+        rec[name] = {"images_per_s": round(n_images / min(times), 2), "pass_s": [round(t, 4) for t in times]}
+        if who is on:
+            rec["crop_rows_per_image"] = round(sum(len(p["crop_rows"]) for p in out["predictions"]) / n_images, 1)
+    rec["kernels"] = crops_kernel_times(frames[:8], size=size)
     return rec
 
 
@@ -1250,6 +1329,9 @@ def main():
     ap.add_argument("--redact", choices=("pixelate", "blur", "fill"),
                     help="only the redaction record: redact_detections alone per mode, and the Inferencer writing JPEG "
                          "files with and without redact=dict(mode=MODE)")
+    ap.add_argument("--crops", action="store_true",
+                    help="only the object-crop record: crop_detections alone (uint8, and with an fp16 tensor), and the "
+                         "Inferencer with and without crops=dict(size=(128, 256))")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -1275,6 +1357,11 @@ def main():
         print(json.dumps({"metric": "Inferencer redaction of detected regions (Swin-L config, random weights)",
                           "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass; HIP events for the kernels",
                           "redact": redact_record(infs["fp16"], a.redact, a.images, a.repeats)}))
+        return
+    if a.crops:
+        print(json.dumps({"metric": "Inferencer object crops for a second stage (Swin-L config, random weights)",
+                          "device": torch.cuda.get_device_name(0), "timing": "host clock, best pass; HIP events for the kernels",
+                          "crops": crops_record(infs["fp16"], a.images, a.repeats)}))
         return
     if a.track and a.appearance:
         print(json.dumps({"metric": "Inferencer tracking with the appearance cue (Swin-L config, random weights)",
