@@ -462,6 +462,7 @@ from .detection_ops import *  # noqa: E402,F401,F403
 from .image_ops import *  # noqa: E402,F401,F403
 from .track_ops import *  # noqa: E402,F401,F403
 from .crop_ops import *  # noqa: E402,F401,F403
+from .trail_ops import *  # noqa: E402,F401,F403
 
 
 def mask_pyramid(img_masks, shapes):

@@ -180,6 +180,18 @@ per chunk -- the frame is never downloaded.  ``tensor=dict(mean, std, dtype)`` a
 on the device and ``results["crops"]`` out.  Like ``tracker``, ``crops`` keeps a call on the chunk path.
 ``include/codetr_crops.h`` states the rule byte for byte: the filter is Pillow's antialiased BILINEAR, the arithmetic is
 not; nothing is learned, boxes stay axis-aligned, parity with cv2 is unpinned.
+
+``visualizer["tracks"]``: absent, the default, means no new launch and ``codetr_draw_detections_*`` called as ever.
+``tracks=True`` or ``dict(color_by="track", show_id=True, trail=30, trail_width=2, trail_alpha=0.6, anchor="center",
+tentative=False, untracked=True, retain=None, palette=None)`` (``tracks_settings``; it needs a ``tracker``) puts the
+tracker's output on the picture: ``track_chunk`` keeps the chunk's ids on the device and, with ``trail > 0``, one
+``hip_ops.trail_update`` launch follows it on every chunk of a tracked call, visualised or not, so a trail stays continuous;
+the states live beside the track states and ``reset_tracks`` clears both.  ``draw_chunk`` then calls ``hip_ops.draw_tracks``
+(``csrc/draw_tracks.hip``) in place of ``draw_detections``: the trails first, one colour per identity, ``"#<id> "`` in front
+of the label (``~`` while the track is tentative).  The order relative to crops, redaction and the encoder is unchanged:
+trails and ids go over redacted pixels, crops show original ones.  ``include/codetr_draw_tracks.h`` states the rule byte for
+byte.  Limits: trails are integer polylines, not antialiased; the alpha is constant, nothing fades; trail points are not
+moved by ``track_motion``; parity with mmdet's ``TrackLocalVisualizer`` and supervision's ``TraceAnnotator`` is unpinned.
 """
 import collections
 import colorsys
@@ -483,7 +495,7 @@ def generated_palette(n):
     return out
 
 
-VISUALIZER_KEYS = ("line_width", "alpha", "text_color", "font_scale", "draw_labels", "palette", "classes")
+VISUALIZER_KEYS = ("line_width", "alpha", "text_color", "font_scale", "draw_labels", "palette", "classes", "tracks")
 
 
 def _meta(dataset_meta, key):
@@ -512,7 +524,7 @@ def visualizer_settings(cfg, visualizer, dataset_meta=None):
     unknown = set(visualizer) - set(VISUALIZER_KEYS)
     if unknown:
         raise ValueError(f"visualizer: unknown key(s) {sorted(unknown)}; known: {list(VISUALIZER_KEYS)}")
-    style = hip_ops.draw_style({k: v for k, v in visualizer.items() if k not in ("palette", "classes")})
+    style = hip_ops.draw_style({k: v for k, v in visualizer.items() if k not in ("palette", "classes", "tracks")})
     classes = visualizer.get("classes")
     if classes is None:
         classes = _meta(dataset_meta, "classes")
@@ -532,6 +544,32 @@ def visualizer_settings(cfg, visualizer, dataset_meta=None):
         raise ValueError("visualizer: the palette needs one RGB triple in 0..255 per class")
     return dict(style=style, classes=classes, palette=palette, names=hip_ops.draw_names_table(classes),
                 colors=torch.tensor(palette, dtype=torch.uint8).view(-1, 3))
+
+
+def tracks_settings(tracks, tracker):
+    """How `visualizer=dict(..., tracks=...)` reads its value: None / False -> None; True -> the defaults; a dict with the
+    keys of hip_ops.TRAILS (hip_ops.trail_settings: a ValueError names the key) plus `palette`: a list of RGB triples, one
+    per identity modulo its length, None: generated_palette(64).  retain None takes the tracker's num_frames_retain.
+    ValueError without a tracker.  -> dict(style, palette [(r, g, b)], colors: [P, 3] uint8)"""
+    if tracks is None or tracks is False:
+        return None
+    if tracks is not True and not isinstance(tracks, dict):
+        raise ValueError(f"visualizer tracks must be True or a dict with keys of {sorted(set(hip_ops.TRAILS) | {'palette'})}")
+    if tracker is None:
+        raise ValueError("visualizer tracks without a tracker: Inferencer(..., tracker=dict(...)) turns tracking on")
+    given = {} if tracks is True else dict(tracks)
+    palette = given.pop("palette", None)
+    if given.get("retain") is None:
+        given["retain"] = tracker["num_frames_retain"]
+    style = hip_ops.trail_settings(given)
+    if palette is None:
+        palette = generated_palette(64)
+    if not isinstance(palette, (list, tuple)) or not 1 <= len(palette) <= 65536 or \
+            any(not isinstance(c, (list, tuple)) or len(c) != 3 or any(int(v) != v or not 0 <= v <= 255 for v in c)
+                for c in palette):
+        raise ValueError("visualizer tracks: the palette needs 1..65536 RGB triples in 0..255")
+    palette = [tuple(int(v) for v in c) for c in palette]
+    return dict(style=style, palette=palette, colors=torch.tensor(palette, dtype=torch.uint8).view(-1, 3))
 
 
 REDACT_KEYS = ("mode", "classes", "score_thr", "expand", "shape", "cell", "fill")
@@ -806,6 +844,12 @@ class Inferencer:
         self.vis_format = vis_format_settings(vis_format)   # None: PNG files; a dict: JPEG files encoded on the GPU
         self.tracker = tracker_settings(tracker, self.cfg)
         self.track_association = track_association_setting(track_association, self.tracker)
+        # visualizer=dict(..., tracks=...): ids, per-track colours and trails on the picture
+        self.tracks = tracks_settings(visualizer.get("tracks") if isinstance(visualizer, dict) else None, self.tracker)
+        self._track_tables = {}    # device -> the track palette on it: uploaded on the first drawing call there
+        self._trail_state = None   # [rows, trail state bytes] uint8: every track's last positions, on the device
+        self._chunk_ids = None     # the chunk's [N, Q] ids and [N, snapshot bytes] trails on the device: track_chunk -> draw_chunk
+        self._chunk_trails = None
         self._track_state = None   # [rows, state bytes] uint8 on the device of the first tracked call
         self._track_rows = {}      # stream -> its row of _track_state (and of _motion_state)
         self.track_motion = track_motion_settings(track_motion, self.tracker)
@@ -1309,8 +1353,9 @@ class Inferencer:
         appearances of its tracks"""
         if stream is None:
             self._track_state, self._track_rows, self._motion_state, self._appearance_state = None, {}, None, None
+            self._trail_state = None
         elif hip_ops.track_streams(stream, 1)[0] in self._track_rows:
-            for state in (self._track_state, self._motion_state, self._appearance_state):
+            for state in (self._track_state, self._motion_state, self._appearance_state, self._trail_state):
                 if state is not None and self._track_rows[int(stream)] < state.shape[0]:
                     state[self._track_rows[int(stream)]].zero_()
 
@@ -1361,11 +1406,18 @@ class Inferencer:
                 raise RuntimeError("the appearance states and the track states hold different numbers of streams")
             app = dict(appearance=hip_ops.appearance_descriptors(src, src_rows, dets),
                        appearance_state=self._appearance_state, appearance_settings=self.track_appearance)
+        motion = {} if self.track_motion is None else dict(motion=self._chunk_motion)
+        ids = hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association, **motion, **app)
+        if self.tracks is not None:   # the ids stay on the device for draw_chunk; the trails go on, drawn or not
+            self._chunk_ids, self._chunk_trails = ids, None
+            if self.tracks["style"]["trail"] > 0:
+                K = self.tracks["style"]["trail"]
+                self._trail_state = self._stream_state(self._trail_state, lambda n: hip_ops.new_trail_state(n, T, K, dev),
+                                                       streams, dev)
+                self._chunk_trails = hip_ops.trail_update(self._clamped(dets), ids, self._trail_state, rows,
+                                                          self.tracks["style"])
         if self.track_motion is None:
-            return hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association,
-                                        **app).cpu().numpy()
-        ids = hip_ops.track_update(dets, self._track_state, rows, self.tracker, self.track_association,
-                                   motion=self._chunk_motion, **app)
+            return ids.cpu().numpy()
         return ids.cpu().numpy(), self._chunk_motion.cpu().numpy()
 
     # ---- visualisation and files --------------------------------------------------------------------------
@@ -1384,6 +1436,13 @@ class Inferencer:
         if key not in self._vis_tables:
             self._vis_tables[key] = (v["names"].to(src.device), v["colors"].to(src.device))
         names, colors = self._vis_tables[key]
+        if self.tracks is not None:   # ids, per-track colours and trails: hip_ops.draw_tracks in place of draw_detections
+            if key not in self._track_tables:
+                self._track_tables[key] = self.tracks["colors"].to(src.device)
+            hip_ops.draw_tracks(src, rows, self._clamped(dets), self._chunk_ids, self._chunk_trails, names, colors,
+                                self._track_tables[key],
+                                dict(v["style"], score_thr=float(pred_score_thr), **self.tracks["style"]))
+            return self.download_chunk(src, rows) if download else [None] * len(rows)
         hip_ops.draw_detections(src, rows, self._clamped(dets), names, colors,
                                 dict(v["style"], score_thr=float(pred_score_thr)))
         return self.download_chunk(src, rows) if download else [None] * len(rows)

@@ -23,102 +23,12 @@
 
 #include "codetr_hip.h"
 #include "box_prims.h"
-
-// The 5x7 font, authored for this library: ASCII 32..126, 7 bytes per glyph, top row first, bit 4 = the leftmost pixel.
-// One initialiser for the kernel's __constant__ copy and for the host copy that codetr_draw_font hands out.
-#define CODETR_DRAW_FONT_ROWS \
-  0x00,0x00,0x00,0x00,0x00,0x00,0x00,  0x04,0x04,0x04,0x04,0x04,0x00,0x04,  0x0a,0x0a,0x0a,0x00,0x00,0x00,0x00,  0x0a,0x0a,0x1f,0x0a,0x1f,0x0a,0x0a, /* sp ! " # */ \
-  0x04,0x0f,0x14,0x0e,0x05,0x1e,0x04,  0x18,0x19,0x02,0x04,0x08,0x13,0x03,  0x0c,0x12,0x14,0x08,0x15,0x12,0x0d,  0x04,0x04,0x08,0x00,0x00,0x00,0x00, /* $ % & ' */ \
-  0x02,0x04,0x08,0x08,0x08,0x04,0x02,  0x08,0x04,0x02,0x02,0x02,0x04,0x08,  0x00,0x04,0x15,0x0e,0x15,0x04,0x00,  0x00,0x04,0x04,0x1f,0x04,0x04,0x00, /* ( ) * + */ \
-  0x00,0x00,0x00,0x00,0x0c,0x04,0x08,  0x00,0x00,0x00,0x1f,0x00,0x00,0x00,  0x00,0x00,0x00,0x00,0x00,0x0c,0x0c,  0x00,0x01,0x02,0x04,0x08,0x10,0x00, /* , - . / */ \
-  0x0e,0x11,0x13,0x15,0x19,0x11,0x0e,  0x04,0x0c,0x04,0x04,0x04,0x04,0x0e,  0x0e,0x11,0x01,0x02,0x04,0x08,0x1f,  0x1f,0x02,0x04,0x02,0x01,0x11,0x0e, /* 0 1 2 3 */ \
-  0x02,0x06,0x0a,0x12,0x1f,0x02,0x02,  0x1f,0x10,0x1e,0x01,0x01,0x11,0x0e,  0x06,0x08,0x10,0x1e,0x11,0x11,0x0e,  0x1f,0x01,0x02,0x04,0x08,0x08,0x08, /* 4 5 6 7 */ \
-  0x0e,0x11,0x11,0x0e,0x11,0x11,0x0e,  0x0e,0x11,0x11,0x0f,0x01,0x02,0x0c,  0x00,0x0c,0x0c,0x00,0x0c,0x0c,0x00,  0x00,0x0c,0x0c,0x00,0x0c,0x04,0x08, /* 8 9 : ; */ \
-  0x02,0x04,0x08,0x10,0x08,0x04,0x02,  0x00,0x00,0x1f,0x00,0x1f,0x00,0x00,  0x08,0x04,0x02,0x01,0x02,0x04,0x08,  0x0e,0x11,0x01,0x02,0x04,0x00,0x04, /* < = > ? */ \
-  0x0e,0x11,0x01,0x0d,0x15,0x15,0x0e,  0x0e,0x11,0x11,0x11,0x1f,0x11,0x11,  0x1e,0x11,0x11,0x1e,0x11,0x11,0x1e,  0x0e,0x11,0x10,0x10,0x10,0x11,0x0e, /* @ A B C */ \
-  0x1c,0x12,0x11,0x11,0x11,0x12,0x1c,  0x1f,0x10,0x10,0x1e,0x10,0x10,0x1f,  0x1f,0x10,0x10,0x1e,0x10,0x10,0x10,  0x0e,0x11,0x10,0x17,0x11,0x11,0x0f, /* D E F G */ \
-  0x11,0x11,0x11,0x1f,0x11,0x11,0x11,  0x0e,0x04,0x04,0x04,0x04,0x04,0x0e,  0x07,0x02,0x02,0x02,0x02,0x12,0x0c,  0x11,0x12,0x14,0x18,0x14,0x12,0x11, /* H I J K */ \
-  0x10,0x10,0x10,0x10,0x10,0x10,0x1f,  0x11,0x1b,0x15,0x15,0x11,0x11,0x11,  0x11,0x11,0x19,0x15,0x13,0x11,0x11,  0x0e,0x11,0x11,0x11,0x11,0x11,0x0e, /* L M N O */ \
-  0x1e,0x11,0x11,0x1e,0x10,0x10,0x10,  0x0e,0x11,0x11,0x11,0x15,0x12,0x0d,  0x1e,0x11,0x11,0x1e,0x14,0x12,0x11,  0x0f,0x10,0x10,0x0e,0x01,0x01,0x1e, /* P Q R S */ \
-  0x1f,0x04,0x04,0x04,0x04,0x04,0x04,  0x11,0x11,0x11,0x11,0x11,0x11,0x0e,  0x11,0x11,0x11,0x11,0x11,0x0a,0x04,  0x11,0x11,0x11,0x15,0x15,0x15,0x0a, /* T U V W */ \
-  0x11,0x11,0x0a,0x04,0x0a,0x11,0x11,  0x11,0x11,0x11,0x0a,0x04,0x04,0x04,  0x1f,0x01,0x02,0x04,0x08,0x10,0x1f,  0x0e,0x08,0x08,0x08,0x08,0x08,0x0e, /* X Y Z [ */ \
-  0x00,0x10,0x08,0x04,0x02,0x01,0x00,  0x0e,0x02,0x02,0x02,0x02,0x02,0x0e,  0x04,0x0a,0x11,0x00,0x00,0x00,0x00,  0x00,0x00,0x00,0x00,0x00,0x00,0x1f, /* backslash ] ^ _ */ \
-  0x08,0x04,0x02,0x00,0x00,0x00,0x00,  0x00,0x00,0x0e,0x01,0x0f,0x11,0x0f,  0x10,0x10,0x16,0x19,0x11,0x11,0x1e,  0x00,0x00,0x0e,0x10,0x10,0x11,0x0e, /* ` a b c */ \
-  0x01,0x01,0x0d,0x13,0x11,0x11,0x0f,  0x00,0x00,0x0e,0x11,0x1f,0x10,0x0e,  0x06,0x09,0x08,0x1c,0x08,0x08,0x08,  0x00,0x0f,0x11,0x11,0x0f,0x01,0x0e, /* d e f g */ \
-  0x10,0x10,0x16,0x19,0x11,0x11,0x11,  0x04,0x00,0x0c,0x04,0x04,0x04,0x0e,  0x02,0x00,0x06,0x02,0x02,0x12,0x0c,  0x10,0x10,0x12,0x14,0x18,0x14,0x12, /* h i j k */ \
-  0x0c,0x04,0x04,0x04,0x04,0x04,0x0e,  0x00,0x00,0x1a,0x15,0x15,0x11,0x11,  0x00,0x00,0x16,0x19,0x11,0x11,0x11,  0x00,0x00,0x0e,0x11,0x11,0x11,0x0e, /* l m n o */ \
-  0x00,0x1e,0x11,0x11,0x1e,0x10,0x10,  0x00,0x0f,0x11,0x11,0x0f,0x01,0x01,  0x00,0x00,0x16,0x19,0x10,0x10,0x10,  0x00,0x00,0x0f,0x10,0x0e,0x01,0x1e, /* p q r s */ \
-  0x08,0x08,0x1c,0x08,0x08,0x09,0x06,  0x00,0x00,0x11,0x11,0x11,0x13,0x0d,  0x00,0x00,0x11,0x11,0x11,0x0a,0x04,  0x00,0x00,0x11,0x11,0x15,0x15,0x0a, /* t u v w */ \
-  0x00,0x00,0x11,0x0a,0x04,0x0a,0x11,  0x00,0x11,0x11,0x11,0x0f,0x01,0x0e,  0x00,0x00,0x1f,0x02,0x04,0x08,0x1f,  0x02,0x04,0x04,0x08,0x04,0x04,0x02, /* x y z { */ \
-  0x04,0x04,0x04,0x04,0x04,0x04,0x04,  0x08,0x04,0x04,0x02,0x04,0x04,0x08,  0x00,0x00,0x08,0x15,0x02,0x00,0x00, /* | } ~ */ \
+#include "draw_prims.h"
 
 namespace {
 
-constexpr int kTileW = 64, kTileH = 16, kRowsPerThread = 4;
-constexpr int kDrawMaxQ = CODETR_DRAW_MAX_Q;
-constexpr int kNameRow = 24;  // bytes per row of the names table: the length, then up to 23 characters
-static_assert(kDrawMaxQ <= 65536, "the LDS lists hold uint16 indices");
-
 __constant__ unsigned char d_font[CODETR_DRAW_FONT_BYTES] = {CODETR_DRAW_FONT_ROWS};
 const unsigned char h_font[CODETR_DRAW_FONT_BYTES] = {CODETR_DRAW_FONT_ROWS};
-
-struct DrawImage {
-  int64_t offset;
-  int H, W;
-};
-struct DrawTable {  // a kernel argument, like prepost.hip's BatchTable (512 B)
-  DrawImage img[CODETR_PREPROCESS_BATCH_MAX];
-};
-struct DrawStyle {
-  int lw, A, font_scale, draw_labels;
-  float score_thr;
-  int text[3];
-};
-
-// one drawn detection in pixel units
-struct Det {
-  int x1, y1, x2, y2;
-};
-
-__device__ __forceinline__ bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// clamp in fp32 to [-16384, 16383], then (int)floorf(x + 0.5f): one fp32 rounding in the sum
-__device__ __forceinline__ int pixel_coord(float v) {
-#pragma clang fp contract(off)
-  v = fminf(fmaxf(v, -16384.f), 16383.f);
-  return (int)floorf(v + 0.5f);
-}
-
-template <class T>
-__device__ __forceinline__ Det pixel_box(const T* __restrict__ box) {
-  return Det{pixel_coord(to_f32(box[0])), pixel_coord(to_f32(box[1])), pixel_coord(to_f32(box[2])),
-             pixel_coord(to_f32(box[3]))};
-}
-
-// tenths of a percent: score * 1000 + 0.5 with a rounding after each operation, clamped in fp32, truncated
-__device__ __forceinline__ int score_tenths(float s) {
-#pragma clang fp contract(off)
-  const float m = s * 1000.0f;
-  const float v = m + 0.5f;
-  return !(v > 0.f) ? 0 : v >= 1000.f ? 1000 : (int)v;
-}
-__device__ __forceinline__ int int_digits(int tenths) { return tenths >= 1000 ? 3 : tenths >= 100 ? 2 : 1; }
-
-__device__ __forceinline__ int name_length(const unsigned char* __restrict__ names, int label) {
-  const int len = names[(size_t)label * kNameRow];
-  return len > kNameRow - 1 ? kNameRow - 1 : len;
-}
-
-__device__ __forceinline__ int text_scale(Det d, int font_scale) {
-  return font_scale * (1 + ((d.x2 - d.x1) * (d.y2 - d.y1) >= 15400 ? 1 : 0));
-}
-
-__device__ __forceinline__ int blend(int p, int c, int A) { return (p * (256 - A) + c * A + 128) >> 8; }
-
-// how many set bits of a ballot sit below this lane
-__device__ __forceinline__ int lower_lanes(unsigned long long m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
 
 // grid (ceil(Wmax / 64), ceil(Hmax / 16), N)
 template <class T>
