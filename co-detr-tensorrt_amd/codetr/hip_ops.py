@@ -456,13 +456,14 @@ def row_max(x):
         return _cabi.row_max(x.view(-1, x.shape[-1])).view(x.shape[:-1])
 
 
-# The Inferencer-side operators -- pre- and post-processing, merges, draw / redact / JPEG / frames, tracking, crops -- live in
+# The Inferencer-side operators -- pre- and post-processing, merges, draw / redact / JPEG / frames, orientation, tracking, crops -- live in
 # their own modules; every public name of theirs still resolves here
 from .detection_ops import *  # noqa: E402,F401,F403
 from .image_ops import *  # noqa: E402,F401,F403
 from .track_ops import *  # noqa: E402,F401,F403
 from .crop_ops import *  # noqa: E402,F401,F403
 from .trail_ops import *  # noqa: E402,F401,F403
+from .orient_ops import *  # noqa: E402,F401,F403
 
 
 def mask_pyramid(img_masks, shapes):

@@ -9,6 +9,7 @@ import torch
 
 from . import _cabi, _jpeg, _jpeg_dec, _redact
 from . import _operands as _check
+from . import orient_ops as _orient_ops
 from ._operands import _gpu
 
 # the public names (hip_ops re-exports exactly these)
@@ -378,13 +379,17 @@ def jpeg_status_error(status, names):
     return None
 
 
-def decode_jpeg(files, out=None, device="cuda:0"):
+def decode_jpeg(files, out=None, device="cuda:0", orientation=None):
     """Baseline JPEG files -> packed RGB HWC images on the device, decoded on the GPU (csrc/jpeg_dec.hip; the rule and the
     supported files are stated in include/codetr_jpeg_dec.h): only the headers are read on the host, the scans are
     uploaded as they are in the files, in one copy with their tables, and decoded by five launches per
     PREPROCESS_BATCH_MAX files.
       files   each bytes / bytearray / memoryview, a 1-D uint8 array or host tensor, or a path
       out     a flat uint8 device buffer to decode into (at least the returned layout's bytes) instead of a new one
+      orientation  None: the images as they are stored.  "exif": every file turned as its EXIF orientation tag asks
+              (jpeg_orientation); an int 1..8 for every file, or a list with one per file: the decoder writes a scratch
+              buffer and one orient_frames launch per PREPROCESS_BATCH_MAX files writes the upright images (into `out`),
+              whose sizes the returned list then holds
     -> (the flat uint8 buffer, [(offset, H, W)] per image); images start at multiples of 16 bytes, as stage_chunk lays
     them out.  ValueError naming the image and the reason for a bad header, a file outside the supported set, or a scan
     that does not decode."""
@@ -401,6 +406,14 @@ def decode_jpeg(files, out=None, device="cuda:0"):
     for _, info, _ in parsed:
         staged.append((total, int(info[0]), int(info[1])))
         total += _jpeg_dec.output_bytes(info[0], info[1])
+    if orientation is not None:
+        if isinstance(orientation, str) and orientation == "exif":
+            orientation = [_orient_ops.jpeg_orientation(data) for data, _, _ in parsed]
+        elif not isinstance(orientation, (list, tuple)):
+            orientation = [orientation] * len(parsed)
+        if len(orientation) != len(parsed):
+            raise ValueError(f"decode_jpeg: {len(orientation)} orientations for {len(parsed)} files")
+        upright, out = out, None   # the decoder's buffer is a scratch of this call
     if out is None:
         out = torch.empty((total,), dtype=torch.uint8, device=device)
     elif (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or out.dim() != 1 or not out.is_contiguous()
@@ -416,6 +429,8 @@ def decode_jpeg(files, out=None, device="cuda:0"):
     err = jpeg_status_error(status.cpu().numpy(), [f"image {i}" for i in _range(len(parsed))])
     if err is not None:
         raise err
+    if orientation is not None:
+        return _orient_ops.orient_frames(out, [(o, H, W, at, 3 * W) for o, (at, H, W) in zip(orientation, staged)], upright)
     return out, staged
 
 

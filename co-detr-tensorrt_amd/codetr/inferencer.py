@@ -192,6 +192,19 @@ of the label (``~`` while the track is tentative).  The order relative to crops,
 trails and ids go over redacted pixels, crops show original ones.  ``include/codetr_draw_tracks.h`` states the rule byte for
 byte.  Limits: trails are integer polylines, not antialiased; the alpha is constant, nothing fades; trail points are not
 moved by ``track_motion``; parity with mmdet's ``TrackLocalVisualizer`` and supervision's ``TraceAnnotator`` is unpinned.
+
+``orientation`` of ``__call__`` (beyond the reference, whose callers get it from ``cv2.imread``, which honours the EXIF tag):
+``None``, the default, means no launch, no new key and every route as it is.  An int 1..8 (EXIF's orientations: 3 a camera
+mounted upside down, 6 and 8 one mounted in portrait) turns every frame, a list holds one value per image, and ``"exif"``
+-- with ``input_format="jpeg"`` only -- reads each file's own tag (``hip_ops.jpeg_orientation``; a file without one is 1),
+the files the Pillow fallback decodes included.  Such a call takes the chunked path; per chunk ``stage_chunk`` lets the
+conversion / decoder write a scratch buffer and one ``hip_ops.orient_frames`` launch per 32 frames (``csrc/orient.hip``)
+writes the upright images as the chunk's RGB buffer, which is all that the pre-processing, the TTA views, the tiles, the
+motion estimate, the descriptors, crops, redaction, drawing and the JPEG encoder read: boxes and every image that leaves
+the call are those of the upright image, and the TTA / slicing tails are built from the upright sizes.  A chunk whose
+orientations are all 1 launches nothing and allocates no scratch.  Every result dict gains ``"orientation"``, the value
+applied to its image; ``hip_ops.unorient_boxes`` maps boxes back to the stored image for tools that ignore the tag.
+``include/codetr_orient.h`` states the rule byte for byte and which bytes of a file the tag is read from.
 """
 import collections
 import colorsys
@@ -679,6 +692,28 @@ def cropped_rows(pred, crops, hw=None):
     return rows
 
 
+def orientation_settings(orientation, count, input_format="rgb"):
+    """How `__call__(..., orientation=...)` reads its argument for `count` images: None -> None; an int of
+    hip_ops.ORIENTATIONS (EXIF's 1..8) -> that value for every image; a list or tuple of them, one per image -> the list;
+    "exif" -> "exif": every file's own tag, for input_format "jpeg" only.  ValueError for anything else."""
+    if orientation is None:
+        return None
+    if isinstance(orientation, str):
+        if orientation != "exif":
+            raise ValueError(f'orientation must be None, an integer in 1..8, a list of them or "exif", got {orientation!r}')
+        if input_format != "jpeg":
+            raise ValueError(f'orientation="exif" reads the tag of JPEG files: it needs input_format="jpeg", not '
+                             f"{input_format!r}")
+        return "exif"
+    values = list(orientation) if isinstance(orientation, (list, tuple)) else [orientation] * count
+    if len(values) != count:
+        raise ValueError(f"orientation: {len(values)} values for {count} images")
+    for o in values:
+        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or o not in hip_ops.ORIENTATIONS:
+            raise ValueError(f'orientation must be None, an integer in 1..8, a list of them or "exif", got {o!r}')
+    return [int(o) for o in values]
+
+
 VIS_FORMAT_KEYS = ("type", "quality", "subsampling")
 VIS_DOWNLOADS = {"rgb": 0}   # device-to-host copies of a chunk's whole RGB buffer made for the visualisation, this process
 
@@ -863,6 +898,8 @@ class Inferencer:
         self._redact_tables = {}   # device -> the class table on it: uploaded on the first redacting call there
         self.crops = crops_settings(self.cfg, crops, dataset_meta, self.visualizer)
         self._crop_tables = {}     # device -> the class table on it: uploaded on the first cropping call there
+        self._chunk_orient = None    # the orientations of the chunk __call__ is staging: None, "exif" or one int per image
+        self._chunk_applied = None   # the values stage_chunk applied to it
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -892,12 +929,14 @@ class Inferencer:
         return x[None], m[None], meta
 
     def preprocess_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                         color=None):
+                         color=None, orientation=None):
         """RGB uint8 images [H_i, W_i, 3] -> (batch_inputs [N,3,H,W], img_masks [N,H,W], metas): per image the
         arithmetic of `preprocess`, stacked as mmdet's DetDataPreprocessor does (H, W = the largest Pad shape rounded
         up to pad_size_divisor; beyond an image's Pad region pad_value, mask 1).  One host-to-device copy, one launch
         per 32 images; dtype f16, bf16 or f32.  `input_format` / `color`: frames of another format or already on the
-        GPU (`frame_settings`, `stage_chunk`)."""
+        GPU (`frame_settings`, `stage_chunk`).  `orientation`: as `__call__` takes it (`orientation_settings`); the
+        batch and the metas are those of the upright images."""
+        self._chunk_orient = orientation_settings(orientation, len(images), input_format)
         return self._preprocess_chunk(images, device, dtype, frame_settings(input_format, color))[:3]
 
     def _preprocess_chunk(self, images, device, dtype, frames=None):
@@ -1021,7 +1060,7 @@ class Inferencer:
         """whether a chunk is what the reference's Inferencer takes: RGB frames, every one a host numpy array"""
         return (frames is None or frames["format"] == "rgb") and all(isinstance(im, np.ndarray) for im in images)
 
-    def stage_chunk(self, images, device="cuda:0", frames=None, tail=None):
+    def stage_chunk(self, images, device="cuda:0", frames=None, tail=None, orientation=None):
         """The chunk's frames as packed RGB HWC images in one flat uint8 buffer on the device
         -> (the buffer, [(offset, H, W)] per image, `tail` on the device).
         `frames`: `frame_settings(...)`, None for RGB.  `tail`: a small host tensor that rides in the chunk's one
@@ -1038,9 +1077,15 @@ class Inferencer:
           * GPU-resident frames: no upload; one launch per group of frames that share a storage, which read the planes
             where they lie (offsets relative to the storage, pitches from the strides).  With no host frame in the chunk
             the tail is a small copy of its own.
-        Host and GPU frames may be mixed.  The images of a converted chunk start at multiples of 16 bytes."""
+        Host and GPU frames may be mixed.  The images of a converted chunk start at multiples of 16 bytes.
+        `orientation`: None, "exif" (JPEG files) or one int 1..8 per image (`orientation_settings`): whichever route
+        stages the chunk writes a scratch buffer, one `hip_ops.orient_frames` launch per 32 frames writes the upright
+        images as the chunk's buffer, and the returned list -- and a callable `tail` -- hold the upright sizes.  A chunk
+        whose orientations are all 1 is staged as without them."""
         if not len(images):
             raise ValueError("stage_chunk: no images")
+        if orientation is not None:
+            return self._stage_oriented_chunk(images, device, frames, tail, orientation)
         if frames is not None and frames["format"] == "jpeg":
             return self._stage_jpeg_chunk(images, device, frames, tail)
         if self.host_rgb(images, frames):
@@ -1104,6 +1149,30 @@ class Inferencer:
         for flat, rows in groups.values():
             hip_ops.frames_to_rgb(flat, rows, dst_bytes, frames["matrix"], frames["range"], out=src)
         return src, staged, (up[tail_at:].view(tail.dtype).view(tail.shape) if tail is not None else None)
+
+    def _stage_oriented_chunk(self, images, device, frames, tail, orientation):
+        """stage_chunk with orientations: the chunk staged as it is stored, then turned"""
+        if orientation == "exif":   # (the files are read here, once: the decoder takes their bytes)
+            images = [hip_ops.jpeg_file_bytes(item) for item in images]
+            orientation = [hip_ops.jpeg_orientation(data) for data in images]
+        if len(orientation) != len(images):
+            raise ValueError(f"stage_chunk: {len(orientation)} orientations for {len(images)} images")
+        self._chunk_applied = list(orientation)
+        if all(o == 1 for o in orientation):
+            return self.stage_chunk(images, device, frames, tail)
+        rows = []
+
+        def tail_of(stored):   # the stored layout is known: the tail is built from the upright sizes
+            rows.extend((o, H, W, at, 3 * W) for o, (at, H, W) in zip(orientation, stored))
+            upright, at = [], 0
+            for o, H, W, _, _ in rows:
+                upright.append((at,) + hip_ops.oriented_size(o, H, W))
+                at = -(-(at + H * W * 3) // 16) * 16
+            return tail(upright) if callable(tail) else tail
+
+        scratch, _, tail = self.stage_chunk(images, device, frames, tail_of)
+        src, staged = hip_ops.orient_frames(scratch, rows)
+        return src, staged, tail
 
     def _stage_jpeg_chunk(self, images, device, frames, tail):
         """stage_chunk for JPEG files"""
@@ -1194,9 +1263,12 @@ class Inferencer:
             m["batch_input_shape"] = (Hb, Wb)
         return rows, metas, (Hb, Wb)
 
-    def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb", color=None):
+    def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb", color=None,
+                  orientation=None):
         """one chunk through every view and the merge -> one result dict per image (see the module docstring).  The
-        chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor."""
+        chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor.
+        `orientation`: as `__call__` takes it; the boxes are those of the upright images."""
+        self._chunk_orient = orientation_settings(orientation, len(images), input_format)
         return self._tta_chunk(images, device, dtype, frame_settings(input_format, color))[0]
 
     def _tta_chunk(self, images, device, dtype, frames=None):
@@ -1302,9 +1374,11 @@ class Inferencer:
         return rows, metas, [t + [-1] * (V - len(t)) for t in table], (Hb, Wb)
 
     def slice_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                    color=None):
+                    color=None, orientation=None):
         """one chunk through every tile and the merge -> one result dict per image (see the module docstring).  The
-        chunk's one upload carries the images, every row's origin and rescale divisor, the image sizes and the view table."""
+        chunk's one upload carries the images, every row's origin and rescale divisor, the image sizes and the view table.
+        `orientation`: as `__call__` takes it; the tiles are cut from, and the boxes are those of, the upright images."""
+        self._chunk_orient = orientation_settings(orientation, len(images), input_format)
         return self._slice_chunk(images, device, dtype, frame_settings(input_format, color))[0]
 
     def _slice_chunk(self, images, device, dtype, frames=None):
@@ -1376,8 +1450,10 @@ class Inferencer:
     def _stage_call_chunk(self, images, device, frames, tail=None):
         """stage_chunk for a chunk of __call__: with track_motion the camera-motion estimate of the chunk's own images
         (whole frames, not views or tiles) is launched behind the staging -- in front of the forward, and of draw_chunk,
-        which draws into that buffer.  The motion stays on the device for track_chunk."""
-        src, staged, tail = self.stage_chunk(images, device, frames, tail)
+        which draws into that buffer.  The motion stays on the device for track_chunk.  The chunk's orientations
+        (`_chunk_orient`, set by __call__) are taken here, once."""
+        orientation, self._chunk_orient = self._chunk_orient, None
+        src, staged, tail = self.stage_chunk(images, device, frames, tail, orientation)
         self._chunk_motion = None
         if self.track_motion is not None and self._chunk_streams is not None:
             self._motion_state = self._stream_state(self._motion_state, lambda n: hip_ops.new_motion_state(n, src.device),
@@ -1521,14 +1597,16 @@ class Inferencer:
                  no_save_vis: bool = False, draw_pred: bool = True, pred_score_thr: float = 0.3,
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
-                 batch_size: int = 1, input_format: str = "rgb", color=None, streams=None) -> Dict:
+                 batch_size: int = 1, input_format: str = "rgb", color=None, streams=None, orientation=None) -> Dict:
         if show or return_datasamples or (return_vis and self.visualizer is None and self.redact is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
         batch_size = int(batch_size)
         frames = frame_settings(input_format, color)
-        plain = self.host_rgb(images, frames)   # what the reference takes; everything else is staged per chunk
+        orientation = orientation_settings(orientation, len(images), frames["format"])
+        # what the reference takes; everything else, and every frame that is turned, is staged per chunk
+        plain = self.host_rgb(images, frames) and orientation is None
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
         # (with `redact` the images come out without a visualiser too: redacted and undrawn)
@@ -1564,6 +1642,7 @@ class Inferencer:
             chunk = images[start:start + batch_size]
             self._chunk_start = start
             self._chunk_streams = streams[start:start + batch_size] if self.track_motion is not None else None
+            self._chunk_orient = orientation[start:start + batch_size] if isinstance(orientation, list) else orientation
             with torch.no_grad():
                 if self.tta is not None:
                     preds, src, rows, dets = self._tta_chunk(chunk, device, dtype, frames)
@@ -1574,6 +1653,9 @@ class Inferencer:
                     preds, dets = self._postprocess_chunk(self.model(x, m), metas)
                 if frames["format"] == "jpeg":   # (the detections are on the host: the status words cost no wait)
                     self.check_jpeg_status()
+                if orientation is not None:
+                    for pred, o in zip(preds, self._chunk_applied):
+                        pred["orientation"] = o
                 if self.tracker is not None:   # the ids of the rows the predictions kept (a host-side cut included)
                     ids = self.track_chunk(dets, streams[start:start + batch_size], src, rows)
                     if self.track_motion is not None:
