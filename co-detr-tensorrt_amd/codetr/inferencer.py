@@ -205,6 +205,14 @@ the call are those of the upright image, and the TTA / slicing tails are built f
 orientations are all 1 launches nothing and allocates no scratch.  Every result dict gains ``"orientation"``, the value
 applied to its image; ``hip_ops.unorient_boxes`` maps boxes back to the stored image for tools that ignore the tag.
 ``include/codetr_orient.h`` states the rule byte for byte and which bytes of a file the tag is read from.
+
+``input_format="bayer_rggb" | "bayer_grbg" | "bayer_gbrg" | "bayer_bggr"`` with ``raw=dict(bits, black_level, white_level,
+white_balance, method, tone)`` (beyond the reference): raw sensor frames, ``[H, W]`` uint8 or uint16, on the host or
+GPU-resident, uploaded as they are (1 or 2 bytes per pixel in the chunk's one staging copy) and demosaiced by one
+``hip_ops.raw_to_rgb`` launch per 32 frames (``csrc/raw.hip``), which fills the chunk's RGB buffer in the place of
+``frames_to_rgb``; nothing behind that buffer changes, so ``orientation``, ``streams`` and every post-processing mode work
+as for any other format.  ``include/codetr_raw.h`` states the rule in integers.  Limits: no packed 10 / 12-bit containers,
+one black level for all four sites, no colour-correction matrix, no edge-directed demosaicing.
 """
 import collections
 import colorsys
@@ -392,15 +400,23 @@ def tracker_settings(tracker, cfg=None):
 FRAME_COLOR_KEYS = ("matrix", "range")
 
 
-def frame_settings(input_format="rgb", color=None):
-    """How `__call__(..., input_format=..., color=...)` reads its arguments: `input_format` a name of
+def frame_settings(input_format="rgb", color=None, raw=None):
+    """How `__call__(..., input_format=..., color=..., raw=...)` reads its arguments: `input_format` a name of
     hip_ops.FRAME_FORMATS ('rgb', 'bgr', 'rgba', 'bgra', 'gray', 'nv12', 'nv21', 'i420'); `color` None or a dict with any
     of `matrix` ('bt601' | 'bt709') and `range` ('limited' | 'full'), completed from hip_ops.FRAME_COLOR (BT.601,
     limited range: what OpenCV's cvtColor computes) -- only the YUV formats read it.  `input_format` may also be 'jpeg':
     the items are baseline JPEG files (bytes, 1-D uint8 arrays or paths), decoded on the GPU (`hip_ops.decode_jpeg`).
+    Or a name of hip_ops.RAW_FORMATS ('bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr'): raw sensor frames,
+    demosaiced on the GPU (`hip_ops.raw_to_rgb`); only then may `raw` be given, a dict of hip_ops.RAW_DEFAULTS' keys
+    (None: the defaults), and the result holds `raw`, the completed `hip_ops.raw_settings(raw)`.
     -> dict(format, matrix, range)"""
-    if input_format != "jpeg" and (not isinstance(input_format, str) or input_format not in hip_ops.FRAME_FORMATS):
-        raise ValueError(f"input_format must be one of {sorted(hip_ops.FRAME_FORMATS)}, got {input_format!r}")
+    bayer = isinstance(input_format, str) and input_format in hip_ops.RAW_FORMATS
+    if raw is not None and not bayer:
+        raise ValueError(f"raw= describes raw Bayer frames: it needs an input_format of {sorted(hip_ops.RAW_FORMATS)}, "
+                         f"not {input_format!r}")
+    if input_format != "jpeg" and not bayer and (not isinstance(input_format, str) or input_format not in hip_ops.FRAME_FORMATS):
+        raise ValueError(f"input_format must be one of {sorted(hip_ops.FRAME_FORMATS) + sorted(hip_ops.RAW_FORMATS)}, "
+                         f"got {input_format!r}")
     if color is not None and (not isinstance(color, dict) or set(color) - set(FRAME_COLOR_KEYS)):
         raise ValueError(f"color must be None or a dict with keys of {FRAME_COLOR_KEYS}, got {color!r}")
     out = dict(hip_ops.FRAME_COLOR, **(color or {}))
@@ -408,6 +424,8 @@ def frame_settings(input_format="rgb", color=None):
         raise ValueError(f"color matrix must be 'bt601' or 'bt709', got {out['matrix']!r}")
     if out["range"] not in ("limited", "full"):
         raise ValueError(f"color range must be 'limited' or 'full', got {out['range']!r}")
+    if bayer:
+        return dict(format=input_format, matrix=out["matrix"], range=out["range"], raw=hip_ops.raw_settings(raw))
     return dict(format=input_format, matrix=out["matrix"], range=out["range"])
 
 
@@ -419,14 +437,18 @@ _FRAME_SHAPES = dict(rgb="(H, W, 3)", bgr="(H, W, 3)", rgba="(H, W, 4)", bgra="(
                      nv12="(H * 3 / 2, W) with even H and W, or planes (y (H, W), uv (ceil(H / 2), ceil(W / 2), 2))",
                      nv21="(H * 3 / 2, W) with even H and W, or planes (y (H, W), vu (ceil(H / 2), ceil(W / 2), 2))",
                      i420="(H * 3 / 2, W) with even H and W, or planes (y (H, W), u, v (ceil(H / 2), ceil(W / 2)))")
+_FRAME_SHAPES.update({name: "(H, W), of uint16 (or its (H, 2 W) uint8 view) when bits is 9..16" for name in hip_ops.RAW_FORMATS})
 
 
-def parse_frame(item, input_format="rgb"):
+def parse_frame(item, input_format="rgb", bits=8):
     """One chunk item -> Frame.  `item`: a numpy array or a torch tensor, uint8, on the host or on the GPU, of the
     format's shape (_FRAME_SHAPES); for nv12 / nv21 / i420 either the 2-D array decoders hand out or a tuple of planes.
     A host plane may have any strides (it is copied row by row into the staging buffer); a GPU-resident plane is read
     where it lies and needs unit innermost stride and a positive row stride of at least the row's bytes, which becomes
-    its pitch -- a crop of a wider surface, say.  Anything else is a ValueError that names the format."""
+    its pitch -- a crop of a wider surface, say.  Anything else is a ValueError that names the format.
+    A raw Bayer frame (a name of hip_ops.RAW_FORMATS, `bits` from the call's `raw`) is 2-D [H, W]: uint8 when bits is 8,
+    else the little-endian uint16 container -- numpy uint16, torch.uint16 / torch.int16, or the [H, 2 W] uint8 view of
+    it -- whose GPU-resident form needs an even byte address and an even pitch."""
     fmt = input_format
 
     def bad(why):
@@ -455,6 +477,34 @@ def parse_frame(item, input_format="rgb"):
                       f"got strides {tuple(a.stride())} for shape {tuple(a.shape)}")
         return a.as_strided((R, B), (a.stride(0) if R > 1 else B, 1))
 
+    if fmt in hip_ops.RAW_FORMATS:
+        a, wide = item, bits > 8
+        if torch.is_tensor(a) and a.dtype == torch.int16:
+            a = a.view(torch.uint16)
+        if torch.is_tensor(a) and not a.is_cuda:
+            a = a.detach().numpy()
+        if not torch.is_tensor(a) and not isinstance(a, np.ndarray):
+            raise bad(f"got {type(a).__name__}")
+        u8, u16 = (torch.uint8, torch.uint16) if torch.is_tensor(a) else (np.uint8, np.uint16)
+        typed = a.dtype == u16
+        if not (typed and wide) and a.dtype != u8:
+            raise bad(f"got {a.dtype} with bits={bits}")
+        halves = 2 if wide and not typed else 1   # (the byte view of a 16-bit frame)
+        if a.ndim != 2 or min(a.shape) < 1 or a.shape[1] % halves:
+            raise bad(f"got shape {tuple(a.shape)}")
+        H, W = int(a.shape[0]), int(a.shape[1]) // halves
+        if isinstance(a, np.ndarray):
+            planes = [np.ascontiguousarray(a.astype("<u2", copy=False)).view(np.uint8) if typed else a]
+        else:
+            if a.shape[1] > 1 and a.stride(1) != 1:
+                raise bad(f"a GPU-resident frame needs unit innermost stride, got strides {tuple(a.stride())}")
+            if typed:
+                a = a.as_strided(a.shape, (a.stride(0), 1)).view(torch.uint8)
+            planes = [rows2d(a)]
+            if wide and (planes[0].data_ptr() % 2 or planes[0].stride(0) % 2):
+                raise bad(f"a GPU-resident 16-bit frame needs an even byte address and an even pitch, got pitch "
+                          f"{planes[0].stride(0)} at address {planes[0].data_ptr() % 2} mod 2")
+        return Frame(hip_ops.RAW_FORMATS[fmt], H, W, planes, torch.is_tensor(planes[0]))
     if isinstance(item, (tuple, list)):
         if fmt not in ("nv12", "nv21", "i420"):
             raise bad("got a tuple of planes")
@@ -929,15 +979,15 @@ class Inferencer:
         return x[None], m[None], meta
 
     def preprocess_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                         color=None, orientation=None):
+                         color=None, orientation=None, raw=None):
         """RGB uint8 images [H_i, W_i, 3] -> (batch_inputs [N,3,H,W], img_masks [N,H,W], metas): per image the
         arithmetic of `preprocess`, stacked as mmdet's DetDataPreprocessor does (H, W = the largest Pad shape rounded
         up to pad_size_divisor; beyond an image's Pad region pad_value, mask 1).  One host-to-device copy, one launch
         per 32 images; dtype f16, bf16 or f32.  `input_format` / `color`: frames of another format or already on the
         GPU (`frame_settings`, `stage_chunk`).  `orientation`: as `__call__` takes it (`orientation_settings`); the
-        batch and the metas are those of the upright images."""
+        batch and the metas are those of the upright images.  `raw`: the settings of raw Bayer frames (`frame_settings`)."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
-        return self._preprocess_chunk(images, device, dtype, frame_settings(input_format, color))[:3]
+        return self._preprocess_chunk(images, device, dtype, frame_settings(input_format, color, raw))[:3]
 
     def _preprocess_chunk(self, images, device, dtype, frames=None):
         """preprocess_batch + the RGB buffer on the device and every image's (offset, H, W) in it, for the visualisation"""
@@ -1069,7 +1119,8 @@ class Inferencer:
           * host RGB arrays: `upload` -- the images back to back in one pinned staging buffer, one copy, no launch;
           * any other host frame: its raw planes, rows packed, each plane 16-byte aligned, in the one pinned staging
             buffer (1.5 bytes per pixel of NV12 / I420 instead of 3) and one `hip_ops.frames_to_rgb` launch behind the
-            copy;
+            copy -- for raw Bayer frames (`frames["raw"]`) 1 or 2 bytes per pixel and `hip_ops.raw_to_rgb` in its place,
+            here and for resident frames;
           * JPEG files (`frames["format"] == "jpeg"`): only the headers are read on the host; the scans, as they are in
             the files, and their tables ride in the one pinned staging buffer and `hip_ops.jpeg_decode_staged` launches
             the decoder behind the copy.  The status words stay on the device until `check_jpeg_status`.  A file the
@@ -1099,7 +1150,8 @@ class Inferencer:
             src, _, tail = self.upload(images, device, tail(staged) if callable(tail) else tail)
             return src, staged, tail
         frames = frames or frame_settings()
-        items = [parse_frame(im, frames["format"]) for im in images]
+        raw = frames.get("raw")
+        items = [parse_frame(im, frames["format"], raw["bits"]) if raw else parse_frame(im, frames["format"]) for im in images]
         staged, dst_bytes = [], 0
         for it in items:
             staged.append((dst_bytes, it.H, it.W))
@@ -1120,7 +1172,10 @@ class Inferencer:
                     copies.append((pos, plane))
                     cols += [pos, plane.shape[1]]
                     pos += plane.size
-            row = (it.code, H, W) + tuple(cols) + (0,) * (6 - len(cols)) + (dst,)
+            if raw:
+                row = (it.code, raw["bits"], H, W) + tuple(cols) + (dst,)
+            else:
+                row = (it.code, H, W) + tuple(cols) + (0,) * (6 - len(cols)) + (dst,)
             if not it.resident:
                 host_rows.append(row)
                 continue
@@ -1144,10 +1199,16 @@ class Inferencer:
                 staging[tail_at:] = tail_bytes
             up = staging.to(dev, non_blocking=True)
         src = torch.empty((dst_bytes,), dtype=torch.uint8, device=dev)
+        if raw:
+            def to_rgb(flat, rows):
+                hip_ops.raw_to_rgb(flat, rows, dst_bytes, raw, out=src)
+        else:
+            def to_rgb(flat, rows):
+                hip_ops.frames_to_rgb(flat, rows, dst_bytes, frames["matrix"], frames["range"], out=src)
         if host_rows:
-            hip_ops.frames_to_rgb(up[:pos], host_rows, dst_bytes, frames["matrix"], frames["range"], out=src)
+            to_rgb(up[:pos], host_rows)
         for flat, rows in groups.values():
-            hip_ops.frames_to_rgb(flat, rows, dst_bytes, frames["matrix"], frames["range"], out=src)
+            to_rgb(flat, rows)
         return src, staged, (up[tail_at:].view(tail.dtype).view(tail.shape) if tail is not None else None)
 
     def _stage_oriented_chunk(self, images, device, frames, tail, orientation):
@@ -1264,12 +1325,12 @@ class Inferencer:
         return rows, metas, (Hb, Wb)
 
     def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb", color=None,
-                  orientation=None):
+                  orientation=None, raw=None):
         """one chunk through every view and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor.
-        `orientation`: as `__call__` takes it; the boxes are those of the upright images."""
+        `orientation`: as `__call__` takes it; the boxes are those of the upright images.  `raw`: as `frame_settings` takes it."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
-        return self._tta_chunk(images, device, dtype, frame_settings(input_format, color))[0]
+        return self._tta_chunk(images, device, dtype, frame_settings(input_format, color, raw))[0]
 
     def _tta_chunk(self, images, device, dtype, frames=None):
         """tta_batch + the RGB buffer on the device, every image's (offset, H, W) and the merged detections on the device"""
@@ -1374,12 +1435,13 @@ class Inferencer:
         return rows, metas, [t + [-1] * (V - len(t)) for t in table], (Hb, Wb)
 
     def slice_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                    color=None, orientation=None):
+                    color=None, orientation=None, raw=None):
         """one chunk through every tile and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, every row's origin and rescale divisor, the image sizes and the view table.
-        `orientation`: as `__call__` takes it; the tiles are cut from, and the boxes are those of, the upright images."""
+        `orientation`: as `__call__` takes it; the tiles are cut from, and the boxes are those of, the upright images.
+        `raw`: as `frame_settings` takes it."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
-        return self._slice_chunk(images, device, dtype, frame_settings(input_format, color))[0]
+        return self._slice_chunk(images, device, dtype, frame_settings(input_format, color, raw))[0]
 
     def _slice_chunk(self, images, device, dtype, frames=None):
         """slice_batch + the RGB buffer on the device, every image's (offset, H, W) and the merged detections on the device"""
@@ -1597,13 +1659,14 @@ class Inferencer:
                  no_save_vis: bool = False, draw_pred: bool = True, pred_score_thr: float = 0.3,
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
-                 batch_size: int = 1, input_format: str = "rgb", color=None, streams=None, orientation=None) -> Dict:
+                 batch_size: int = 1, input_format: str = "rgb", color=None, streams=None, orientation=None,
+                 raw=None) -> Dict:
         if show or return_datasamples or (return_vis and self.visualizer is None and self.redact is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
             raise ValueError(f"batch_size must be a positive integer, got {batch_size}")
         batch_size = int(batch_size)
-        frames = frame_settings(input_format, color)
+        frames = frame_settings(input_format, color, raw)
         orientation = orientation_settings(orientation, len(images), frames["format"])
         # what the reference takes; everything else, and every frame that is turned, is staged per chunk
         plain = self.host_rgb(images, frames) and orientation is None
