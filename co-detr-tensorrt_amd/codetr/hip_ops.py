@@ -465,6 +465,7 @@ from .crop_ops import *  # noqa: E402,F401,F403
 from .trail_ops import *  # noqa: E402,F401,F403
 from .orient_ops import *  # noqa: E402,F401,F403
 from .raw_ops import *  # noqa: E402,F401,F403
+from .undistort_ops import *  # noqa: E402,F401,F403
 
 
 def mask_pyramid(img_masks, shapes):

@@ -213,6 +213,16 @@ GPU-resident, uploaded as they are (1 or 2 bytes per pixel in the chunk's one st
 ``frames_to_rgb``; nothing behind that buffer changes, so ``orientation``, ``streams`` and every post-processing mode work
 as for any other format.  ``include/codetr_raw.h`` states the rule in integers.  Limits: no packed 10 / 12-bit containers,
 one black level for all four sites, no colour-correction matrix, no edge-directed demosaicing.
+
+``undistort`` of ``__call__`` (beyond the reference, whose callers run ``cv2.undistort`` first): ``None``, the default,
+means no launch, no new key and every route as it is.  A dict of ``hip_ops.UNDISTORT_DEFAULTS``' keys (``model="brown" |
+"fisheye"``, ``camera_matrix``, ``dist_coeffs``, ``new_camera_matrix``, ``size``, ``fill``) rectifies every frame, a list
+holds one dict per image -- cameras differ, and a call may mix them.  Such a call takes the chunked path; per chunk
+``stage_chunk`` lets the conversion / decoder write a scratch buffer and one ``hip_ops.undistort_frames`` launch per 32 frames
+(``csrc/undistort.hip``) writes the rectified images as the chunk's RGB buffer; with ``orientation`` as well the lens comes
+first (the calibration is in sensor coordinates): stored frame -> rectified -> turned.  Sizes, boxes and every image that
+leaves the call are the rectified image's, each result dict gains ``"undistorted": True``, and ``hip_ops.distort_points``
+maps points back to the stored frame.  ``include/codetr_undistort.h`` states the rule byte for byte.
 """
 import collections
 import colorsys
@@ -764,6 +774,19 @@ def orientation_settings(orientation, count, input_format="rgb"):
     return [int(o) for o in values]
 
 
+def undistort_call_settings(undistort, count):
+    """How `__call__(..., undistort=...)` reads its argument for `count` images: None -> None; a dict of
+    hip_ops.UNDISTORT_DEFAULTS' keys -> that calibration for every image; a list or tuple of dicts, one per image -> the list.
+    Every dict is completed by `hip_ops.undistort_settings` (the rectified size still None where it is the frame's own).
+    ValueError for anything else."""
+    if undistort is None:
+        return None
+    values = list(undistort) if isinstance(undistort, (list, tuple)) else [undistort] * count
+    if len(values) != count:
+        raise ValueError(f"undistort: {len(values)} values for {count} images")
+    return [hip_ops.undistort_settings(u) for u in values]
+
+
 VIS_FORMAT_KEYS = ("type", "quality", "subsampling")
 VIS_DOWNLOADS = {"rgb": 0}   # device-to-host copies of a chunk's whole RGB buffer made for the visualisation, this process
 
@@ -950,6 +973,7 @@ class Inferencer:
         self._crop_tables = {}     # device -> the class table on it: uploaded on the first cropping call there
         self._chunk_orient = None    # the orientations of the chunk __call__ is staging: None, "exif" or one int per image
         self._chunk_applied = None   # the values stage_chunk applied to it
+        self._chunk_undistort = None   # the lens calibrations of the chunk __call__ is staging: None or one dict per image
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -979,14 +1003,16 @@ class Inferencer:
         return x[None], m[None], meta
 
     def preprocess_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                         color=None, orientation=None, raw=None):
+                         color=None, orientation=None, raw=None, undistort=None):
         """RGB uint8 images [H_i, W_i, 3] -> (batch_inputs [N,3,H,W], img_masks [N,H,W], metas): per image the
         arithmetic of `preprocess`, stacked as mmdet's DetDataPreprocessor does (H, W = the largest Pad shape rounded
         up to pad_size_divisor; beyond an image's Pad region pad_value, mask 1).  One host-to-device copy, one launch
         per 32 images; dtype f16, bf16 or f32.  `input_format` / `color`: frames of another format or already on the
         GPU (`frame_settings`, `stage_chunk`).  `orientation`: as `__call__` takes it (`orientation_settings`); the
-        batch and the metas are those of the upright images.  `raw`: the settings of raw Bayer frames (`frame_settings`)."""
+        batch and the metas are those of the upright images.  `raw`: the settings of raw Bayer frames (`frame_settings`).
+        `undistort`: as `__call__` takes it (`undistort_call_settings`); the batch and the metas are the rectified images'."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
+        self._chunk_undistort = undistort_call_settings(undistort, len(images))
         return self._preprocess_chunk(images, device, dtype, frame_settings(input_format, color, raw))[:3]
 
     def _preprocess_chunk(self, images, device, dtype, frames=None):
@@ -1110,7 +1136,7 @@ class Inferencer:
         """whether a chunk is what the reference's Inferencer takes: RGB frames, every one a host numpy array"""
         return (frames is None or frames["format"] == "rgb") and all(isinstance(im, np.ndarray) for im in images)
 
-    def stage_chunk(self, images, device="cuda:0", frames=None, tail=None, orientation=None):
+    def stage_chunk(self, images, device="cuda:0", frames=None, tail=None, orientation=None, undistort=None):
         """The chunk's frames as packed RGB HWC images in one flat uint8 buffer on the device
         -> (the buffer, [(offset, H, W)] per image, `tail` on the device).
         `frames`: `frame_settings(...)`, None for RGB.  `tail`: a small host tensor that rides in the chunk's one
@@ -1132,9 +1158,14 @@ class Inferencer:
         `orientation`: None, "exif" (JPEG files) or one int 1..8 per image (`orientation_settings`): whichever route
         stages the chunk writes a scratch buffer, one `hip_ops.orient_frames` launch per 32 frames writes the upright
         images as the chunk's buffer, and the returned list -- and a callable `tail` -- hold the upright sizes.  A chunk
-        whose orientations are all 1 is staged as without them."""
+        whose orientations are all 1 is staged as without them.
+        `undistort`: None or one completed dict per image (`undistort_call_settings`): the chunk is staged into a scratch
+        buffer as it is stored, one `hip_ops.undistort_frames` launch per 32 frames writes the rectified images, and the
+        orientations, if any, turn those; the returned list and a callable `tail` hold the final sizes."""
         if not len(images):
             raise ValueError("stage_chunk: no images")
+        if undistort is not None:
+            return self._stage_undistorted_chunk(images, device, frames, tail, orientation, undistort)
         if orientation is not None:
             return self._stage_oriented_chunk(images, device, frames, tail, orientation)
         if frames is not None and frames["format"] == "jpeg":
@@ -1235,6 +1266,42 @@ class Inferencer:
         src, staged = hip_ops.orient_frames(scratch, rows)
         return src, staged, tail
 
+    def _stage_undistorted_chunk(self, images, device, frames, tail, orientation, undistort):
+        """stage_chunk with lens calibrations: the chunk staged as it is stored, rectified, then -- with orientations --
+        turned (the calibration is in sensor coordinates, so the lens comes first)"""
+        if orientation == "exif":   # (the files are read here, once: the decoder takes their bytes)
+            images = [hip_ops.jpeg_file_bytes(item) for item in images]
+            orientation = [hip_ops.jpeg_orientation(data) for data in images]
+        if len(undistort) != len(images) or (orientation is not None and len(orientation) != len(images)):
+            raise ValueError(f"stage_chunk: {len(undistort)} calibrations and "
+                             f"{'no' if orientation is None else len(orientation)} orientations for {len(images)} images")
+        if orientation is not None:
+            self._chunk_applied = list(orientation)
+        rows, settings, turns = [], [], []
+
+        def layout(sizes):   # images at multiples of 16 bytes, as undistort_frames and orient_frames lay them out
+            out, at = [], 0
+            for H, W in sizes:
+                out.append((at, H, W))
+                at = -(-(at + H * W * 3) // 16) * 16
+            return out
+
+        def tail_of(stored):   # the stored layout is known: the tail is built from the final sizes
+            for u, (at, H, W) in zip(undistort, stored):
+                rows.append((H, W, at, 3 * W))
+                settings.append(hip_ops.undistort_settings(u, H, W))
+            final = layout([s["size"] for s in settings])
+            if orientation is not None and any(o != 1 for o in orientation):
+                turns.extend((o, H, W, at, 3 * W) for o, (at, H, W) in zip(orientation, final))
+                final = layout([hip_ops.oriented_size(o, H, W) for o, H, W, _, _ in turns])
+            return tail(final) if callable(tail) else tail
+
+        scratch, _, tail = self.stage_chunk(images, device, frames, tail_of)
+        src, staged = hip_ops.undistort_frames(scratch, rows, settings)
+        if turns:
+            src, staged = hip_ops.orient_frames(src, turns)
+        return src, staged, tail
+
     def _stage_jpeg_chunk(self, images, device, frames, tail):
         """stage_chunk for JPEG files"""
         dev = torch.device(device)
@@ -1325,11 +1392,13 @@ class Inferencer:
         return rows, metas, (Hb, Wb)
 
     def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb", color=None,
-                  orientation=None, raw=None):
+                  orientation=None, raw=None, undistort=None):
         """one chunk through every view and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor.
-        `orientation`: as `__call__` takes it; the boxes are those of the upright images.  `raw`: as `frame_settings` takes it."""
+        `orientation`: as `__call__` takes it; the boxes are those of the upright images.  `raw`: as `frame_settings` takes it.
+        `undistort`: as `__call__` takes it; the boxes are those of the rectified images."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
+        self._chunk_undistort = undistort_call_settings(undistort, len(images))
         return self._tta_chunk(images, device, dtype, frame_settings(input_format, color, raw))[0]
 
     def _tta_chunk(self, images, device, dtype, frames=None):
@@ -1435,12 +1504,13 @@ class Inferencer:
         return rows, metas, [t + [-1] * (V - len(t)) for t in table], (Hb, Wb)
 
     def slice_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                    color=None, orientation=None, raw=None):
+                    color=None, orientation=None, raw=None, undistort=None):
         """one chunk through every tile and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, every row's origin and rescale divisor, the image sizes and the view table.
         `orientation`: as `__call__` takes it; the tiles are cut from, and the boxes are those of, the upright images.
-        `raw`: as `frame_settings` takes it."""
+        `raw`: as `frame_settings` takes it.  `undistort`: as `__call__` takes it; the tiles are cut from the rectified images."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
+        self._chunk_undistort = undistort_call_settings(undistort, len(images))
         return self._slice_chunk(images, device, dtype, frame_settings(input_format, color, raw))[0]
 
     def _slice_chunk(self, images, device, dtype, frames=None):
@@ -1513,9 +1583,10 @@ class Inferencer:
         """stage_chunk for a chunk of __call__: with track_motion the camera-motion estimate of the chunk's own images
         (whole frames, not views or tiles) is launched behind the staging -- in front of the forward, and of draw_chunk,
         which draws into that buffer.  The motion stays on the device for track_chunk.  The chunk's orientations
-        (`_chunk_orient`, set by __call__) are taken here, once."""
+        (`_chunk_orient`, set by __call__) and lens calibrations (`_chunk_undistort`) are taken here, once."""
         orientation, self._chunk_orient = self._chunk_orient, None
-        src, staged, tail = self.stage_chunk(images, device, frames, tail, orientation)
+        undistort, self._chunk_undistort = self._chunk_undistort, None
+        src, staged, tail = self.stage_chunk(images, device, frames, tail, orientation, undistort)
         self._chunk_motion = None
         if self.track_motion is not None and self._chunk_streams is not None:
             self._motion_state = self._stream_state(self._motion_state, lambda n: hip_ops.new_motion_state(n, src.device),
@@ -1660,7 +1731,7 @@ class Inferencer:
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
                  batch_size: int = 1, input_format: str = "rgb", color=None, streams=None, orientation=None,
-                 raw=None) -> Dict:
+                 raw=None, undistort=None) -> Dict:
         if show or return_datasamples or (return_vis and self.visualizer is None and self.redact is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
@@ -1668,8 +1739,9 @@ class Inferencer:
         batch_size = int(batch_size)
         frames = frame_settings(input_format, color, raw)
         orientation = orientation_settings(orientation, len(images), frames["format"])
-        # what the reference takes; everything else, and every frame that is turned, is staged per chunk
-        plain = self.host_rgb(images, frames) and orientation is None
+        undistort = undistort_call_settings(undistort, len(images))
+        # what the reference takes; everything else, and every frame that is turned or rectified, is staged per chunk
+        plain = self.host_rgb(images, frames) and orientation is None and undistort is None
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
         # (with `redact` the images come out without a visualiser too: redacted and undrawn)
@@ -1706,6 +1778,7 @@ class Inferencer:
             self._chunk_start = start
             self._chunk_streams = streams[start:start + batch_size] if self.track_motion is not None else None
             self._chunk_orient = orientation[start:start + batch_size] if isinstance(orientation, list) else orientation
+            self._chunk_undistort = undistort[start:start + batch_size] if undistort is not None else None
             with torch.no_grad():
                 if self.tta is not None:
                     preds, src, rows, dets = self._tta_chunk(chunk, device, dtype, frames)
@@ -1719,6 +1792,9 @@ class Inferencer:
                 if orientation is not None:
                     for pred, o in zip(preds, self._chunk_applied):
                         pred["orientation"] = o
+                if undistort is not None:
+                    for pred in preds:
+                        pred["undistorted"] = True
                 if self.tracker is not None:   # the ids of the rows the predictions kept (a host-side cut included)
                     ids = self.track_chunk(dets, streams[start:start + batch_size], src, rows)
                     if self.track_motion is not None:
