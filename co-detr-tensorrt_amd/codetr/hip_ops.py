@@ -466,6 +466,7 @@ from .trail_ops import *  # noqa: E402,F401,F403
 from .orient_ops import *  # noqa: E402,F401,F403
 from .raw_ops import *  # noqa: E402,F401,F403
 from .undistort_ops import *  # noqa: E402,F401,F403
+from .enhance_ops import *  # noqa: E402,F401,F403
 
 
 def mask_pyramid(img_masks, shapes):

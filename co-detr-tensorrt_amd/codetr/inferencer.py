@@ -223,6 +223,15 @@ holds one dict per image -- cameras differ, and a call may mix them.  Such a cal
 first (the calibration is in sensor coordinates): stored frame -> rectified -> turned.  Sizes, boxes and every image that
 leaves the call are the rectified image's, each result dict gains ``"undistorted": True``, and ``hip_ops.distort_points``
 maps points back to the stored frame.  ``include/codetr_undistort.h`` states the rule byte for byte.
+
+``enhance`` of ``__call__`` (beyond the reference, whose callers run ``cv2.createCLAHE(...).apply(...)`` first): ``None``,
+the default, means no launch, no new key, no allocation and every route as it is.  A dict of ``hip_ops.ENHANCE_DEFAULTS``'
+keys (``grid=(8, 8)``, ``clip_limit=2.0``; ``None`` for no clipping) equalises the luma of every frame per tile with a
+clipped histogram (CLAHE), a list holds one dict per image.  Such a call takes the chunked path; per chunk ``stage_chunk``
+runs the stage last -- conversion / decoder / raw, then ``undistort``, then ``orientation``, then ``enhance`` -- and in place
+on the chunk's RGB buffer: ``hip_ops.enhance_frames``, two launches per 32 frames (``csrc/enhance.hip``), its scratch kept
+per device.  The model, the tracker's descriptors, crops, redaction, drawing and JPEG output all see the enhanced pixels,
+and each result dict gains ``"enhanced": True``.  ``include/codetr_enhance.h`` states the rule in integers.
 """
 import collections
 import colorsys
@@ -787,6 +796,19 @@ def undistort_call_settings(undistort, count):
     return [hip_ops.undistort_settings(u) for u in values]
 
 
+def enhance_call_settings(enhance, count):
+    """How `__call__(..., enhance=...)` reads its argument for `count` images: None -> None; a dict of
+    hip_ops.ENHANCE_DEFAULTS' keys -> those settings for every image; a list or tuple of dicts, one per image -> the list.
+    Every dict is completed by `hip_ops.enhance_settings` (what depends on the frame's size is checked when the chunk is
+    staged).  ValueError for anything else."""
+    if enhance is None:
+        return None
+    values = list(enhance) if isinstance(enhance, (list, tuple)) else [enhance] * count
+    if len(values) != count:
+        raise ValueError(f"enhance: {len(values)} values for {count} images")
+    return [hip_ops.enhance_settings(e) for e in values]
+
+
 VIS_FORMAT_KEYS = ("type", "quality", "subsampling")
 VIS_DOWNLOADS = {"rgb": 0}   # device-to-host copies of a chunk's whole RGB buffer made for the visualisation, this process
 
@@ -974,6 +996,8 @@ class Inferencer:
         self._chunk_orient = None    # the orientations of the chunk __call__ is staging: None, "exif" or one int per image
         self._chunk_applied = None   # the values stage_chunk applied to it
         self._chunk_undistort = None   # the lens calibrations of the chunk __call__ is staging: None or one dict per image
+        self._chunk_enhance = None     # its contrast settings: None or one dict per image
+        self._enhance_scratch = {}     # device -> the scratch of hip_ops.enhance_frames: allocated on the first enhancing call there
         self.num_predicted_imgs = 0
         self.num_visualized_imgs = 0
 
@@ -1003,16 +1027,18 @@ class Inferencer:
         return x[None], m[None], meta
 
     def preprocess_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                         color=None, orientation=None, raw=None, undistort=None):
+                         color=None, orientation=None, raw=None, undistort=None, enhance=None):
         """RGB uint8 images [H_i, W_i, 3] -> (batch_inputs [N,3,H,W], img_masks [N,H,W], metas): per image the
         arithmetic of `preprocess`, stacked as mmdet's DetDataPreprocessor does (H, W = the largest Pad shape rounded
         up to pad_size_divisor; beyond an image's Pad region pad_value, mask 1).  One host-to-device copy, one launch
         per 32 images; dtype f16, bf16 or f32.  `input_format` / `color`: frames of another format or already on the
         GPU (`frame_settings`, `stage_chunk`).  `orientation`: as `__call__` takes it (`orientation_settings`); the
         batch and the metas are those of the upright images.  `raw`: the settings of raw Bayer frames (`frame_settings`).
-        `undistort`: as `__call__` takes it (`undistort_call_settings`); the batch and the metas are the rectified images'."""
+        `undistort`: as `__call__` takes it (`undistort_call_settings`); the batch and the metas are the rectified images'.
+        `enhance`: as `__call__` takes it (`enhance_call_settings`); the batch is made of the enhanced pixels."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
         self._chunk_undistort = undistort_call_settings(undistort, len(images))
+        self._chunk_enhance = enhance_call_settings(enhance, len(images))
         return self._preprocess_chunk(images, device, dtype, frame_settings(input_format, color, raw))[:3]
 
     def _preprocess_chunk(self, images, device, dtype, frames=None):
@@ -1136,7 +1162,7 @@ class Inferencer:
         """whether a chunk is what the reference's Inferencer takes: RGB frames, every one a host numpy array"""
         return (frames is None or frames["format"] == "rgb") and all(isinstance(im, np.ndarray) for im in images)
 
-    def stage_chunk(self, images, device="cuda:0", frames=None, tail=None, orientation=None, undistort=None):
+    def stage_chunk(self, images, device="cuda:0", frames=None, tail=None, orientation=None, undistort=None, enhance=None):
         """The chunk's frames as packed RGB HWC images in one flat uint8 buffer on the device
         -> (the buffer, [(offset, H, W)] per image, `tail` on the device).
         `frames`: `frame_settings(...)`, None for RGB.  `tail`: a small host tensor that rides in the chunk's one
@@ -1161,9 +1187,19 @@ class Inferencer:
         whose orientations are all 1 is staged as without them.
         `undistort`: None or one completed dict per image (`undistort_call_settings`): the chunk is staged into a scratch
         buffer as it is stored, one `hip_ops.undistort_frames` launch per 32 frames writes the rectified images, and the
-        orientations, if any, turn those; the returned list and a callable `tail` hold the final sizes."""
+        orientations, if any, turn those; the returned list and a callable `tail` hold the final sizes.
+        `enhance`: None or one completed dict per image (`enhance_call_settings`): the last stage, `hip_ops.enhance_frames`
+        in place on the buffer the stages in front of it produced -- always one this call allocated (an upload, a
+        conversion's, a decoder's or a kernel's output), never a caller's GPU-resident frame."""
         if not len(images):
             raise ValueError("stage_chunk: no images")
+        if enhance is not None:
+            if len(enhance) != len(images):
+                raise ValueError(f"stage_chunk: {len(enhance)} enhance settings for {len(images)} images")
+            src, staged, tail = self.stage_chunk(images, device, frames, tail, orientation, undistort)
+            hip_ops.enhance_frames(src, [(H, W, at, 3 * W) for at, H, W in staged], enhance, out=src,
+                                   workspace=self._enhance_scratch)
+            return src, staged, tail
         if undistort is not None:
             return self._stage_undistorted_chunk(images, device, frames, tail, orientation, undistort)
         if orientation is not None:
@@ -1392,13 +1428,14 @@ class Inferencer:
         return rows, metas, (Hb, Wb)
 
     def tta_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb", color=None,
-                  orientation=None, raw=None, undistort=None):
+                  orientation=None, raw=None, undistort=None, enhance=None):
         """one chunk through every view and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, their widths (fp32, for the un-flip) and every view's rescale divisor.
         `orientation`: as `__call__` takes it; the boxes are those of the upright images.  `raw`: as `frame_settings` takes it.
-        `undistort`: as `__call__` takes it; the boxes are those of the rectified images."""
+        `undistort`: as `__call__` takes it; the boxes are those of the rectified images.  `enhance`: as `__call__` takes it."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
         self._chunk_undistort = undistort_call_settings(undistort, len(images))
+        self._chunk_enhance = enhance_call_settings(enhance, len(images))
         return self._tta_chunk(images, device, dtype, frame_settings(input_format, color, raw))[0]
 
     def _tta_chunk(self, images, device, dtype, frames=None):
@@ -1504,13 +1541,15 @@ class Inferencer:
         return rows, metas, [t + [-1] * (V - len(t)) for t in table], (Hb, Wb)
 
     def slice_batch(self, images: List[np.ndarray], device="cuda:0", dtype=torch.float32, input_format="rgb",
-                    color=None, orientation=None, raw=None, undistort=None):
+                    color=None, orientation=None, raw=None, undistort=None, enhance=None):
         """one chunk through every tile and the merge -> one result dict per image (see the module docstring).  The
         chunk's one upload carries the images, every row's origin and rescale divisor, the image sizes and the view table.
         `orientation`: as `__call__` takes it; the tiles are cut from, and the boxes are those of, the upright images.
-        `raw`: as `frame_settings` takes it.  `undistort`: as `__call__` takes it; the tiles are cut from the rectified images."""
+        `raw`: as `frame_settings` takes it.  `undistort`: as `__call__` takes it; the tiles are cut from the rectified images.
+        `enhance`: as `__call__` takes it; the tiles are cut from the enhanced images."""
         self._chunk_orient = orientation_settings(orientation, len(images), input_format)
         self._chunk_undistort = undistort_call_settings(undistort, len(images))
+        self._chunk_enhance = enhance_call_settings(enhance, len(images))
         return self._slice_chunk(images, device, dtype, frame_settings(input_format, color, raw))[0]
 
     def _slice_chunk(self, images, device, dtype, frames=None):
@@ -1583,10 +1622,12 @@ class Inferencer:
         """stage_chunk for a chunk of __call__: with track_motion the camera-motion estimate of the chunk's own images
         (whole frames, not views or tiles) is launched behind the staging -- in front of the forward, and of draw_chunk,
         which draws into that buffer.  The motion stays on the device for track_chunk.  The chunk's orientations
-        (`_chunk_orient`, set by __call__) and lens calibrations (`_chunk_undistort`) are taken here, once."""
+        (`_chunk_orient`, set by __call__), lens calibrations (`_chunk_undistort`) and contrast settings (`_chunk_enhance`)
+        are taken here, once."""
         orientation, self._chunk_orient = self._chunk_orient, None
         undistort, self._chunk_undistort = self._chunk_undistort, None
-        src, staged, tail = self.stage_chunk(images, device, frames, tail, orientation, undistort)
+        enhance, self._chunk_enhance = self._chunk_enhance, None
+        src, staged, tail = self.stage_chunk(images, device, frames, tail, orientation, undistort, enhance)
         self._chunk_motion = None
         if self.track_motion is not None and self._chunk_streams is not None:
             self._motion_state = self._stream_state(self._motion_state, lambda n: hip_ops.new_motion_state(n, src.device),
@@ -1731,7 +1772,7 @@ class Inferencer:
                  return_datasamples: bool = False, print_result: bool = False, no_save_pred: bool = True,
                  out_dir: str = "", device: str = "cuda:0", dtype: torch.dtype = torch.float32,
                  batch_size: int = 1, input_format: str = "rgb", color=None, streams=None, orientation=None,
-                 raw=None, undistort=None) -> Dict:
+                 raw=None, undistort=None, enhance=None) -> Dict:
         if show or return_datasamples or (return_vis and self.visualizer is None and self.redact is None):
             raise NotImplementedError("visualisation / DetDataSample / file output need mmengine + cv2: not part of this build")
         if int(batch_size) != batch_size or batch_size < 1:
@@ -1740,8 +1781,9 @@ class Inferencer:
         frames = frame_settings(input_format, color, raw)
         orientation = orientation_settings(orientation, len(images), frames["format"])
         undistort = undistort_call_settings(undistort, len(images))
-        # what the reference takes; everything else, and every frame that is turned or rectified, is staged per chunk
-        plain = self.host_rgb(images, frames) and orientation is None and undistort is None
+        enhance = enhance_call_settings(enhance, len(images))
+        # what the reference takes; everything else, and every frame that is turned, rectified or enhanced, is staged per chunk
+        plain = self.host_rgb(images, frames) and orientation is None and undistort is None and enhance is None
         results_dict = {"predictions": [], "visualization": []}
         save_vis = out_dir != "" and not no_save_vis
         # (with `redact` the images come out without a visualiser too: redacted and undrawn)
@@ -1779,6 +1821,7 @@ class Inferencer:
             self._chunk_streams = streams[start:start + batch_size] if self.track_motion is not None else None
             self._chunk_orient = orientation[start:start + batch_size] if isinstance(orientation, list) else orientation
             self._chunk_undistort = undistort[start:start + batch_size] if undistort is not None else None
+            self._chunk_enhance = enhance[start:start + batch_size] if enhance is not None else None
             with torch.no_grad():
                 if self.tta is not None:
                     preds, src, rows, dets = self._tta_chunk(chunk, device, dtype, frames)
@@ -1795,6 +1838,9 @@ class Inferencer:
                 if undistort is not None:
                     for pred in preds:
                         pred["undistorted"] = True
+                if enhance is not None:
+                    for pred in preds:
+                        pred["enhanced"] = True
                 if self.tracker is not None:   # the ids of the rows the predictions kept (a host-side cut included)
                     ids = self.track_chunk(dets, streams[start:start + batch_size], src, rows)
                     if self.track_motion is not None:
